@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: 3D hex BwdTrans sum-factorisation, fp64, nq = 8, on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path (one sf_bwdtrans_hex_f64 launch) over this rank's batch of
@@ -16,18 +16,27 @@ exits with the child's code; it refuses when the box has fewer than N GPUs.  `n_
 is the number of ranks the collectives actually reduced over, never the flag.
 
 Workload.  N = 1: 1 048 576 elements (BASELINE configs[2], the config the metric's target is quoted
-on).  N > 1: BASELINE configs[4], a 10 000 000-element batch sharded over the ranks ("strong"); rank 0
-then times the SAME batch alone on its GPU (it fits: 68 GB) for `speedup_vs_1gpu_same_batch`.
+on).  N > 1: BASELINE configs[4], a 10 000 000-element batch sharded over the ranks ("strong"); with
+`--full` rank 0 then times the SAME batch alone on its GPU (it fits: 68 GB) for `speedup_vs_1gpu_same_batch`.
 `--elements-per-gpu` selects weak scaling instead.
 
 Metric (BASELINE.json): GDOF/s = 1e-9 * nelmt * nm^3 / t   (benchmark05/benchmark05.cc:1408; DOF =
 input modes).  Roofline: HBM, algorithmic bytes 8*(nm^3 + nq^3) per element.
 
-Rank 0 prints ONE JSON line.  Extra keys: "roofline", "cpu_baseline" (oracle port timed on this
-box's host cores by rank 0 after the timed region, every N) and "extra" (nq sweep 2..10 and the 2D quad
-orders, N=1 only).  One protocol per number: `value` / `ms_per_step` / `roofline.frac` = mean of the timed
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes its outputs
+(`--dump-outputs`) and prints the line: the headline keys, "roofline" and "checksum_norm".  `--full` adds
+what takes runs of its own, after the timed region: "cpu_baseline" (oracle port timed on the host's cores
+by rank 0, every N), the graph-replayed group timings and the golden-norm check (N=1), "extra" (nq sweep
+2..10 and the 2D quad orders, N=1 only; `--no-extra` drops it) and the single-GPU run of the same batch
+(N>1, strong).  One protocol per number: `value` / `ms_per_step` / `roofline.frac` = mean of the timed
 steps by wall clock; `roofline.kernel_ms` = the same launches between HIP events; `ms_min_of_40` and every
 `*_min` = the fastest of 40 graph-replayed groups; `frac` / `*_mean` in the sweeps = the mean over them.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last step computed on rank 0: `DIR/hex_out.npy`,
+float64, shape (S, nq^3) = the output rows of S elements of rank 0's batch ([k][j][i] within a row), and
+`DIR/hex_out_elements.npy`, float64, the element indices of those rows.  S covers the whole batch when it fits
+DUMP_BYTES, else the first and last DUMP_EDGE elements plus a fixed seeded sample of the rest.  Inputs are
+seeded, so the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -47,6 +56,9 @@ NQ = 8
 GOLDEN_NORM_1M = 17134.76235  # benchmark05/nq8x8x8.log:45 (nelmt 1 048 576, sin/cos data)
 CONFIG4_ELEMENTS = 10_000_000  # BASELINE.json configs[4]
 QUAD_ORDERS = (2, 4, 6, 8, 10, 12, 14, 16, 20, 24, 26, 28, 30, 32)  # benchmark04/run.sh:5-6 + 20 / 24 / 26 / 28 / 30
+DUMP_BYTES = 32 << 20   # --dump-outputs: at most this many bytes of output rows
+DUMP_EDGE = 512         # elements always dumped at each end of the batch (chunk / dispatch seams)
+DUMP_SEED = 20260401    # seeds the sample of the interior elements
 
 
 def parse(argv=None):
@@ -61,12 +73,41 @@ def parse(argv=None):
                     help="strong scaling: shard this many elements over the ranks "
                          "(N > 1 default: 10 000 000 = BASELINE config 4)")
     ap.add_argument("--nq", type=int, default=NQ)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the order sweeps, the group timings, the golden-norm check "
+                         "and (N > 1) the single-GPU run of the same batch")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the order sweeps")
     ap.add_argument("--no-single-gpu-reference", action="store_true",
-                    help="N > 1, strong scaling: skip rank 0's solo run of the same batch")
+                    help="with --full, N > 1, strong scaling: skip rank 0's solo run of the same batch")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     return ap.parse_args(argv)
+
+
+def dump_elements(nelmt, nq):
+    """Element indices (sorted, unique) whose output rows --dump-outputs writes: all of them when they fit
+    DUMP_BYTES, else the first and last DUMP_EDGE plus a sample of the rest drawn with DUMP_SEED."""
+    import numpy as np
+    cap = max(1, DUMP_BYTES // (8 * nq ** 3))
+    if nelmt <= cap:
+        return np.arange(nelmt, dtype=np.int64)
+    edge = min(DUMP_EDGE, cap // 4)
+    rng = np.random.default_rng(DUMP_SEED)
+    mid = edge + rng.choice(nelmt - 2 * edge, size=cap - 2 * edge, replace=False)
+    return np.unique(np.concatenate([np.arange(edge), mid, np.arange(nelmt - edge, nelmt)])).astype(np.int64)
+
+
+def dump_outputs(path, out, nelmt, nq, torch):
+    """Rows of the output buffer (this rank's batch, as the last step left it) -> path/hex_out.npy and the
+    element index of every row -> path/hex_out_elements.npy."""
+    import numpy as np
+    idx = dump_elements(nelmt, nq)
+    rows = out.view(nelmt, nq ** 3).index_select(0, torch.from_numpy(idx).to(out.device))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "hex_out.npy"), rows.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "hex_out_elements.npy"), idx.astype(np.float64))
 
 
 def resolve_world(args, environ):
@@ -375,6 +416,8 @@ def main():
     if ranks_reduced != world or elements_reduced != total:
         raise SystemExit(f"bench.py: collectives reduced over {ranks_reduced} ranks / {elements_reduced} "
                          f"elements, expected {world} / {total}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, nelmt, nq, torch)
     result = None
     bytes_per_elmt = 8 * (nm ** 3 + nq ** 3)
     if rank == 0:
@@ -391,7 +434,8 @@ def main():
         result = {
             "metric": "GDOF/s for 3D hex sum-factorisation, fp64, nq=2..10 sweep",
             "metric_detail": f"value = the nq={nq} order (the one north_star's target is quoted on); the "
-                             "per-order sweep 2..10 is in extra.hex_sweep, its min / geomean in roofline",
+                             "per-order sweep 2..10 is in extra.hex_sweep, its min / geomean in roofline "
+                             "(bench.py --full)",
             "value": round(1e-9 * dof * args.steps / wall_max, 3),
             "unit": "GDOF/s",
             "n_gpus": ranks_reduced, "steps": args.steps, "warmup": args.warmup,
@@ -430,7 +474,7 @@ def main():
             if backend != "nccl":
                 result["rehearsal"] = f"backend {backend}: ranks may share a GPU; not a scaling measurement"
 
-    if world > 1 and scaling == "strong" and not args.no_single_gpu_reference:
+    if args.full and world > 1 and scaling == "strong" and not args.no_single_gpu_reference:
         # rank 0 alone over the same batch, the others wait (asleep on the rendezvous store, then at the barrier)
         if rank != 0:
             wait_for_rank0(dist, "solo_done")
@@ -444,7 +488,7 @@ def main():
             release_ranks(dist, "solo_done")
         dist.barrier()
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # the same launches under the sweep's protocol (groups of 8 replayed from a HIP graph, HIP events):
         # mean and minimum over 40 groups next to the eager wall-clock mean that `value` is
         mean_ms, min_ms, _ = grouped_ms(torch, step)
@@ -474,7 +518,7 @@ def main():
             result["roofline"]["measured_stream_gb_s"] = round(stream, 1)
             result["roofline"]["frac_of_measured_stream"] = round(
                 result["roofline"]["achieved"] / stream, 4)
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # the oracle on this box's host cores, in the same run (north_star), AFTER the timed region; for N > 1 the
         # other ranks wait at the barrier as they do for rank 0's solo run
         if use_dist and rank != 0:

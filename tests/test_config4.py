@@ -65,6 +65,20 @@ def test_default_workloads():
         b.pick_workload(b.parse(["--total-elements", "7", "--elements-per-gpu", "7"]), 2)
 
 
+def test_plain_run_options_and_dump_sample():
+    """A plain run leaves the --full measurements off; the --dump-outputs sample is fixed, sorted, inside the
+    batch, holds both ends and stays within its byte budget."""
+    b = _bench()
+    a = b.parse(["--steps", "3"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 3
+    assert b.parse(["--full", "--dump-outputs", "d"]).full is True
+    for nelmt, nq in ((1, 8), (5000, 8), (1 << 20, 8), (TOTAL // WORLD + 1, 8), (131072, 16), (333, 2)):
+        idx = b.dump_elements(nelmt, nq)
+        assert np.array_equal(idx, b.dump_elements(nelmt, nq))
+        assert idx[0] == 0 and idx[-1] == nelmt - 1 and np.all(np.diff(idx) > 0)
+        assert idx.size * 8 * nq ** 3 <= b.DUMP_BYTES and idx.size == min(nelmt, b.DUMP_BYTES // (8 * nq ** 3))
+
+
 def test_mismatched_launch_exits_nonzero_without_touching_a_gpu():
     env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8"], env=env,
@@ -218,12 +232,12 @@ def test_spawning_parent_holds_no_gpu_device_file(sf):
 
 @pytest.mark.gpu
 def test_bench_spawns_its_own_ranks_config4(sf):
-    """`python bench.py --gpus 2` with no launcher starts 2 ranks itself (gloo rehearsal: the ranks share this
-    box's GPU), defaults to the 10 M-element strong-scaling batch and reports the ranks actually reduced over."""
+    """`python bench.py --gpus 2 --full` with no launcher starts 2 ranks itself (gloo rehearsal: the ranks share
+    this box's GPU), defaults to the 10 M-element strong-scaling batch and reports the ranks actually reduced over."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["SF_BENCH_BACKEND"] = "gloo"
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-                          "--warmup", "1"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--warmup", "1", "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1

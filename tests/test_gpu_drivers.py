@@ -120,11 +120,11 @@ def test_benchmark01_default_problem_size(pkg, golden):
 
 
 def test_bench_contract_single_gpu(pkg):
-    """`python bench.py` (N = 1): one JSON line with the contract keys, the roofline and cpu_baseline
+    """`python bench.py --full` (N = 1): one JSON line with the contract keys, the roofline and cpu_baseline
     objects, the golden-norm self check, and a loose performance floor (reference's best: 26.4)."""
     import sys
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3",
-                          "--cpu-seconds", "2"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--cpu-seconds", "2", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines                       # exactly ONE line on stdout
@@ -148,6 +148,48 @@ def test_bench_contract_single_gpu(pkg):
     assert rec["value"] > 150.0 and rl["frac"] > 0.35   # measured 280-300 / 0.70-0.74
 
 
+def test_bench_plain_run_and_dumped_outputs(pkg, oracle, tmp_path):
+    """`python bench.py` without --full: exactly --steps timed steps, the headline keys and none of what --full
+    adds; `--dump-outputs` writes the last step's output rows, which match the oracle on the same seeded inputs
+    and come out bit-identical from a second run."""
+    import math
+    import sys
+    import numpy as np
+    recs, dumps = [], []
+    for run in ("a", "b"):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7",
+                              "--warmup", "2", "--dump-outputs", str(tmp_path / run)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        recs.append(json.loads(lines[0]))
+        dumps.append({name: np.load(tmp_path / run / f"{name}.npy") for name in ("hex_out", "hex_out_elements")})
+        assert sorted(os.listdir(tmp_path / run)) == ["hex_out.npy", "hex_out_elements.npy"]
+    rec = recs[0]
+    nelmt, nq, nm = 1 << 20, 8, 7
+    assert rec["metric"].startswith("GDOF/s for 3D hex") and rec["unit"] == "GDOF/s" and rec["dtype"] == "f64"
+    assert rec["higher_is_better"] is True and rec["n_gpus"] == 1 and rec["steps"] == 7 and rec["warmup"] == 2
+    assert abs(rec["value"] - 1e-9 * nelmt * nm ** 3 / (rec["ms_per_step"] * 1e-3)) <= 1e-3 * rec["value"]
+    for key in ("cpu_baseline", "extra", "golden_norm_check", "ms_min_of_40", "vs_reference_published"):
+        assert key not in rec, key
+    out, idx = dumps[0]["hex_out"], dumps[0]["hex_out_elements"]
+    assert out.dtype == np.float64 and idx.dtype == np.float64 and out.shape == (idx.size, nq ** 3)
+    assert out.nbytes + idx.nbytes <= 64 << 20 and idx.size >= 1024
+    elems = idx.astype(np.int64)
+    assert np.array_equal(elems, idx) and elems[0] == 0 and elems[-1] == nelmt - 1
+    assert np.all(np.diff(elems) > 0)
+    b = oracle.fill_basis(nm, nq)
+    x = np.concatenate([oracle.fill_random(nm ** 3, 0x5F3759DF, int(e) * nm ** 3) for e in elems])
+    ref = oracle.bwdtrans_hex((nq,) * 3, elems.size, b, b, b, x)
+    assert oracle.rel_err(out.ravel(), ref) <= 1e-12
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+    norm = math.sqrt(float(pkg.sumsq(pkg.bwdtrans_hex((nq,) * 3, *(pkg.fill_basis(nm, nq),) * 3,
+                                                      pkg.fill_random(nelmt * nm ** 3, 0x5F3759DF, 0)))))
+    assert abs(rec["checksum_norm"] - norm) <= 1e-12 * norm
+
+
 def test_bench_two_ranks_rehearsal(pkg, tmp_path):
     """bench.py's N>1 path on real hardware: 2 ranks share the one GPU of this box, scalar reductions
     over gloo (SF_BENCH_BACKEND); checks the contract keys and that the shards add up."""
@@ -155,7 +197,8 @@ def test_bench_two_ranks_rehearsal(pkg, tmp_path):
     env = dict(os.environ, SF_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "5", "--warmup", "1", "--total-elements", "200001", "--cpu-seconds", "2"]
+           "--gpus", "2", "--steps", "5", "--warmup", "1", "--total-elements", "200001", "--cpu-seconds", "2",
+           "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]
