@@ -132,6 +132,69 @@ def bwdtrans_quad(nq, basis0, basis1, inp, out=None, variant="auto", wsp=None, s
     return out
 
 
+def _spec_args(nq, dtype):
+    nq = tuple(int(x) for x in nq)
+    if len(nq) not in (2, 3):
+        raise ValueError("nq must hold 2 (quad) or 3 (hex) extents")
+    if dtype not in (torch.float64, torch.float32):
+        raise TypeError("dtype must be torch.float64 or torch.float32")
+    return (len(nq),) + nq + (0,) * (3 - len(nq)) + (8 if dtype == torch.float64 else 4,)
+
+
+def specialise(nq, dtype=torch.float64, device=None):
+    """Compile (once per process) and load (once per device) the wave-per-chunk kernel for extents `nq` (2 or 3 of
+    them) on `device` (default: the current device).  Returns SF_OK, or SF_ECOMPILE when the shape cannot be
+    specialised (hiprtc missing, compile failed, it would spill): AUTO then keeps its usual route.  AUTO calls of
+    bwdtrans_hex / bwdtrans_quad launch a ready specialisation for shapes the compiled tables miss."""
+    args = _spec_args(nq, dtype)
+    with torch.cuda.device(device if device is not None else torch.cuda.current_device()):
+        rc = capi.lib().sf_specialise(*args)
+    if rc not in (capi.SF_OK, capi.SF_ECOMPILE):
+        capi.check(rc, "sf_specialise")
+    return rc
+
+
+def specialisation_state(nq, dtype=torch.float64, device=None):
+    """(state, launches) of the specialisation of `nq` on `device`: state 0 none, 1 ready, SF_ECOMPILE failed."""
+    n = ctypes.c_uint64(0)
+    with torch.cuda.device(device if device is not None else torch.cuda.current_device()):
+        rc = capi.lib().sf_specialisation_state(*_spec_args(nq, dtype), ctypes.byref(n))
+    if rc not in (0, 1, capi.SF_ECOMPILE):
+        capi.check(rc, "sf_specialisation_state")
+    return rc, n.value
+
+
+def specialise_log():
+    """This thread's last specialise() log (compile number, seconds, instantiation, compiler remarks)."""
+    return capi.lib().sf_last_specialise_log().decode()
+
+
+def bwdtrans_specialised(nq, *bases, inp, out=None, stream=None):
+    """Launch only the specialised kernel of `nq` (ready after specialise()); same layouts as bwdtrans_hex / _quad.
+    Raises SumfactError SF_ENOTBUILT when it is not ready, SF_EALIGN unless inp / out are 16-byte aligned."""
+    args = _spec_args(nq, inp.dtype)
+    dim, ext = args[0], args[1:1 + len(nq)]
+    if len(bases) != dim:
+        raise ValueError(f"{dim} extents need {dim} bases")
+    nmt, nqt = 1, 1
+    for q in ext:
+        nmt, nqt = nmt * (q - 1), nqt * q
+    nelmt = inp.numel() // nmt
+    if nelmt * nmt != inp.numel():
+        raise ValueError("in.numel() is not a multiple of the modes per element")
+    if out is None:
+        out = torch.empty(nelmt * nqt, dtype=inp.dtype, device=inp.device)
+    elif out.numel() != nelmt * nqt:
+        raise ValueError("out has the wrong size")
+    _check_sizes("bwdtrans_specialised", bases, ext, None, 0)
+    ptrs = [_dev_f64(b, f"basis{d}", inp.dtype) for d, b in enumerate(bases)] + [None] * (3 - dim)
+    with torch.cuda.device(inp.device):
+        rc = capi.lib().sf_bwdtrans_specialised(*args, nelmt, *ptrs, _dev_f64(inp, "in", inp.dtype),
+                                                _dev_f64(out, "out", inp.dtype), _stream(stream, inp.device))
+    capi.check(rc, "sf_bwdtrans_specialised")
+    return out
+
+
 def interleave64(src, nelmt, n, inverse=False, stream=None):
     """[e][n] -> [(e/64)][n][e%64] (padded to whole groups of 64 elements), or back."""
     padded = (nelmt + 63) // 64 * 64

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsumfact.so")
 
-SF_OK, SF_EINVAL, SF_EALIGN, SF_ENOTBUILT, SF_ENOMEM = 0, -1, -2, -3, -4
+SF_OK, SF_EINVAL, SF_EALIGN, SF_ENOTBUILT, SF_ENOMEM, SF_ECOMPILE = 0, -1, -2, -3, -4, -5
 
 # every symbol include/sumfact.h declares: name -> (restype, argtypes)
 _vp, _sz, _u, _u64, _i = (ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint64,
@@ -44,6 +44,10 @@ SYMBOLS = {
     "sf_fill_matvec_f64": (_i, [_vp, _vp, _u, _u, _vp]),
     "sf_set_launch_hint": (_i, [_u, _u]),
     "sf_device_info": (_i, [ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.c_char_p, _sz]),
+    "sf_specialise": (_i, [_i, _u, _u, _u, _i]),
+    "sf_specialisation_state": (_i, [_i, _u, _u, _u, _i, ctypes.POINTER(_u64)]),
+    "sf_bwdtrans_specialised": (_i, [_i, _u, _u, _u, _i, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sf_last_specialise_log": (ctypes.c_char_p, []),
     "sf_shutdown": (_i, []),
 }
 

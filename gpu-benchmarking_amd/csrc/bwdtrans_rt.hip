@@ -3,6 +3,7 @@
 // benchmark05/benchmark05.cc:291-297, 1425-1429).
 #include "bwdtrans_rt.h"
 #include "bwdtrans_wave3.h"
+#include "rtc_config.h"
 #include "sf_dispatch.h"
 
 #include <cstdlib>
@@ -62,6 +63,19 @@ template <int NQ0, int NQ1, int NQ2> static int go3(const HexArgs &a, hipStream_
     X(10, 8, 6) X(6, 10, 8) X(6, 8, 10) X(8, 10, 6) X(8, 6, 10) X(8, 8, 6) X(8, 6, 8) X(6, 8, 8) X(6, 6, 8) X(6, 8, 6)       \
     X(8, 6, 6) X(8, 8, 10) X(8, 10, 8) X(10, 8, 8) X(10, 10, 8) X(10, 8, 10) X(8, 10, 10) X(6, 6, 4) X(6, 4, 6) X(4, 6, 6)   \
     X(4, 4, 6) X(4, 6, 4) X(6, 4, 4)
+
+// the run-time specialisation's host-side configuration (rtc_config.h) restates Cfg3 and the slab of WaveGeom3: pinned
+// here to the template's own values for every compile-time triple
+template <int A, int B, int C> constexpr bool rtc_matches_cfg3()
+{
+    constexpr RtcCfg r = rtc_cfg(3, A, B, C, 8);
+    using C3           = Cfg3<A, B, C>;
+    return r.ec == C3::EC && r.bmode == C3::BM && r.wpb == 4 && r.minw == 2 && r.xg == 64 &&
+           r.slab == WaveGeom3<A, B, C, C3::EC>::SLAB_OUT && r.lds == wave3_lds_bytes<A, B, C, C3::EC, 4>();
+}
+#define SF_PIN3(A, B, C) static_assert(rtc_matches_cfg3<A, B, C>(), "rtc_config.h disagrees with Cfg3 / WaveGeom3");
+SF_TRIPLES(SF_PIN3)
+#undef SF_PIN3
 
 // SF_ENOTBUILT: the shape is not in the table (the caller then takes the run-time-extent kernel)
 int launch_hex_wave3(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, hipStream_t s)

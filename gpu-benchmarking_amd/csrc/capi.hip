@@ -30,6 +30,7 @@ const char *sf_error_string(int rc)
     case SF_EALIGN: return "pointer not sufficiently aligned";
     case SF_ENOTBUILT: return "variant not instantiated for these extents";
     case SF_ENOMEM: return "internal workspace allocation failed";
+    case SF_ECOMPILE: return "run-time specialisation unavailable (hiprtc missing, compile failed, or it would spill)";
     default: return rc > 0 ? hipGetErrorString((hipError_t)rc) : "unknown sumfact error";
     }
 }
@@ -76,6 +77,8 @@ int sf_bwdtrans_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigne
         // anisotropic extents, or buffers that are only 8-byte aligned: the compile-time triples of bwdtrans_rt.hip, then
         // the run-time-extent wave kernel (bwdtrans_rt.h), then the barrier-per-sweep block kernel
         int rc = (!iso && vec_ok) ? launch_hex_wave3(nq0, nq1, nq2, a, s) : SF_ENOTBUILT; // compile-time triples
+        if (rc == SF_ENOTBUILT && vec_ok) // a specialisation the caller made ready (sf_specialise)
+            rc = launch_specialised(3, nq0, nq1, nq2, 8, basis0, basis1, basis2, in, out, a.nelmt, s);
         // the run-time-extent kernel is ahead of the block kernel up to nq = 8 per direction (0.39-0.52 of the roofline
         // against 0.28-0.34; above that its unrolled-to-the-bound loops lose: profiles/r03/anisotropic_shapes.log)
         if (rc == SF_ENOTBUILT && nq0 <= 8 && nq1 <= 8 && nq2 <= 8)
@@ -151,6 +154,12 @@ int sf_bwdtrans_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t
                 rc = launch_quad_wave_nq(nq0, a, s);
             if (rc == SF_ENOTBUILT)
                 rc = launch_quad_mfma_nq(nq0, a, s);
+            if (rc != SF_ENOTBUILT)
+                return rc;
+        }
+        if (vec_ok) // a specialisation the caller made ready (sf_specialise)
+        {
+            const int rc = launch_specialised(2, nq0, nq1, 0, 8, basis0, basis1, nullptr, in, out, a.nelmt, s);
             if (rc != SF_ENOTBUILT)
                 return rc;
         }
@@ -238,6 +247,12 @@ int sf_bwdtrans_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, 
         if (rc != SF_ENOTBUILT)
             return rc;
     }
+    if (aligned(in, 16) && aligned(out, 16)) // a specialisation the caller made ready (sf_specialise)
+    {
+        const int rc = launch_specialised(3, nq0, nq1, nq2, 4, basis0, basis1, basis2, in, out, a.nelmt, s);
+        if (rc != SF_ENOTBUILT)
+            return rc;
+    }
     return launch_hex_generic_f32(SF_VARIANT_GENERIC, nq0, nq1, nq2, a, s);
 }
 
@@ -257,6 +272,12 @@ int sf_bwdtrans_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *
     if (nq0 == nq1 && aligned(in, 16) && aligned(out, 16))
     {
         int rc = launch_quad_wave_f32_nq(nq0, a, s);
+        if (rc != SF_ENOTBUILT)
+            return rc;
+    }
+    if (aligned(in, 16) && aligned(out, 16)) // a specialisation the caller made ready (sf_specialise)
+    {
+        const int rc = launch_specialised(2, nq0, nq1, 0, 4, basis0, basis1, nullptr, in, out, a.nelmt, s);
         if (rc != SF_ENOTBUILT)
             return rc;
     }
@@ -412,10 +433,47 @@ int sf_device_info(int *num_cu, int *wave_size, char *name, size_t name_len)
     return SF_OK;
 }
 
+// ---- run-time specialisation (rtc.hip) -------------------------------------------------------------------------
+int sf_specialise(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes)
+{
+    return rtc_specialise(dim, nq0, nq1, nq2, scalar_bytes);
+}
+
+int sf_specialisation_state(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes, uint64_t *launches)
+{
+    return rtc_state(dim, nq0, nq1, nq2, scalar_bytes, launches);
+}
+
+int sf_bwdtrans_specialised(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes, size_t nelmt,
+                            const void *basis0, const void *basis1, const void *basis2, const void *in, void *out,
+                            void *stream)
+{
+    const unsigned mx = dim == 3 ? 16u : 24u;
+    if ((dim != 2 && dim != 3) || (scalar_bytes != 4 && scalar_bytes != 8) || nq0 < 2 || nq1 < 2 || nq0 > mx ||
+        nq1 > mx || (dim == 3 && (nq2 < 2 || nq2 > mx)))
+        return SF_EINVAL;
+    if (nelmt == 0)
+        return SF_OK;
+    if (!basis0 || !basis1 || (dim == 3 && !basis2) || !in || !out)
+        return SF_EINVAL;
+    if (!aligned(in, 16) || !aligned(out, 16) || !aligned(basis0, scalar_bytes) || !aligned(basis1, scalar_bytes) ||
+        (dim == 3 && !aligned(basis2, scalar_bytes)))
+        return SF_EALIGN;
+    return launch_specialised(dim, nq0, nq1, dim == 3 ? nq2 : 0, scalar_bytes, basis0, basis1, basis2, in, out,
+                              (uint64_t)nelmt, (hipStream_t)stream);
+}
+
+const char *sf_last_specialise_log(void)
+{
+    return rtc_last_log();
+}
+
 int sf_shutdown(void)
 {
+    const int rtc = rtc_release();
     (void)release_counters();
-    return release_workspaces();
+    const int rc = release_workspaces();
+    return rc != SF_OK ? rc : rtc;
 }
 
 } // extern "C"

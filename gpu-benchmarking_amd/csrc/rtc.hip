@@ -1,0 +1,236 @@
+// rtc.hip -- load / launch half of the run-time specialisation: sf_specialise() compiles (once per process, through
+// rtc_compile.cc) and loads (once per device) the wave-per-chunk kernel of bwdtrans_wave3.h / bwdtrans_wave2.h for the
+// extents a caller names; AUTO then launches it for shapes the compiled tables miss.  Nothing here compiles or loads
+// behind a launch: a launch only finds what sf_specialise() made ready.
+#include "bwdtrans_wave2.h"
+#include "bwdtrans_wave3.h"
+#include "rtc_compile.h"
+#include "sf_dispatch.h"
+
+#include <atomic>
+#include <cstdio>
+#include <map>
+#include <memory>
+#include <mutex>
+
+namespace sf
+{
+
+// the host's launch configuration against the templates' own geometry, 2D and odd 3D shapes (the 33 compile-time
+// triples are pinned in bwdtrans_rt.hip)
+template <int A, int B, int S> constexpr bool rtc_pins2()
+{
+    constexpr RtcCfg c = rtc_cfg(2, A, B, 0, S);
+    using T            = typename std::conditional<S == 8, double, float>::type;
+    return c.slab == WaveGeom2<A, B, c.ec, T>::SLAB_OUT && c.lds == wave2_lds_bytes<A, B, c.ec, c.wpb, T>();
+}
+template <int A, int B, int C, int S> constexpr bool rtc_pins3()
+{
+    constexpr RtcCfg c = rtc_cfg(3, A, B, C, S);
+    using T            = typename std::conditional<S == 8, double, float>::type;
+    return c.slab == WaveGeom3<A, B, C, c.ec, T>::SLAB_OUT && c.lds == wave3_lds_bytes<A, B, C, c.ec, c.wpb, T>();
+}
+static_assert(kRtcBasisSmem == BASIS_SMEM && kRtcBasisCols == BASIS_SMEM_COLS, "basis modes");
+static_assert(rtc_pins2<4, 9, 8>() && rtc_pins2<16, 3, 8>() && rtc_pins2<12, 20, 8>() && rtc_pins2<23, 5, 8>() &&
+                  rtc_pins2<2, 24, 8>() && rtc_pins2<24, 24, 8>() && rtc_pins2<4, 9, 4>() && rtc_pins2<7, 2, 4>(),
+              "2D launch configuration");
+static_assert(rtc_pins3<6, 6, 12, 8>() && rtc_pins3<12, 10, 8, 8>() && rtc_pins3<5, 9, 7, 8>() &&
+                  rtc_pins3<3, 5, 4, 8>() && rtc_pins3<2, 3, 2, 8>() && rtc_pins3<16, 12, 14, 8>() &&
+                  rtc_pins3<3, 5, 4, 4>() && rtc_pins3<6, 6, 12, 4>(),
+              "3D launch configuration");
+
+namespace
+{
+
+struct Compiled // one code object per (arch, shape)
+{
+    int rc;
+    RtcCode code;
+    unsigned serial; // n-th compile of the process
+};
+
+struct Loaded // one module per (device, shape)
+{
+    int state = 0; // 1 ready, SF_ECOMPILE failed
+    hipModule_t mod = nullptr;
+    hipFunction_t fn = nullptr;
+    RtcCfg cfg{};
+    std::atomic<uint64_t> launches{0};
+};
+
+struct DevKey
+{
+    int dev;
+    RtcKey k;
+    bool operator<(const DevKey &o) const
+    {
+        return dev != o.dev ? dev < o.dev : k < o.k;
+    }
+};
+
+std::mutex g_mu; // covers compile and load
+std::atomic<int> g_ready{0}; // modules ready on any device: AUTO's only cost while it is 0
+std::map<std::pair<std::string, RtcKey>, std::unique_ptr<Compiled>> g_code;
+std::map<DevKey, std::unique_ptr<Loaded>> g_loaded;
+unsigned g_compiles = 0;
+thread_local std::string t_log;
+
+// the ready module of `k` on the current device, or nullptr
+Loaded *ready(const RtcKey &k)
+{
+    if (g_ready.load(std::memory_order_relaxed) == 0)
+        return nullptr;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess)
+        return nullptr;
+    std::lock_guard<std::mutex> g(g_mu);
+    auto it = g_loaded.find(DevKey{dev, k});
+    return (it != g_loaded.end() && it->second->state == 1) ? it->second.get() : nullptr;
+}
+
+int launch(Loaded &L, int dim, const void *b0, const void *b1, const void *b2, const void *in, void *out,
+           uint64_t nelmt, hipStream_t s)
+{
+    if (nelmt == 0)
+        return SF_OK;
+    const uint64_t nchunk = (nelmt + L.cfg.ec - 1) / L.cfg.ec;
+    const uint64_t grid   = (nchunk + L.cfg.wpb - 1) / L.cfg.wpb;
+    if (grid > 0x7fffffffull)
+        return SF_EINVAL;
+    void *args3[] = {&b0, &b1, &b2, &in, &out, &nelmt};
+    void *args2[] = {&b0, &b1, &in, &out, &nelmt};
+    hipError_t e  = hipModuleLaunchKernel(L.fn, (unsigned)grid, 1, 1, kWave * L.cfg.wpb, 1, 1, (unsigned)L.cfg.lds, s,
+                                          dim == 3 ? args3 : args2, nullptr);
+    if (e != hipSuccess)
+        return (int)e;
+    L.launches.fetch_add(1, std::memory_order_relaxed);
+    return SF_OK;
+}
+
+} // namespace
+
+int rtc_specialise(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes)
+{
+    RtcKey k;
+    if (rtc_key(dim, nq0, nq1, nq2, scalar_bytes, &k) != SF_OK)
+        return SF_EINVAL;
+    int dev      = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess)
+        return (int)e;
+    hipDeviceProp_t p;
+    if ((e = hipGetDeviceProperties(&p, dev)) != hipSuccess)
+        return (int)e;
+    const std::string arch = p.gcnArchName; // verbatim, e.g. gfx950:sramecc+:xnack-
+
+    std::lock_guard<std::mutex> g(g_mu);
+    std::unique_ptr<Compiled> &cc = g_code[{arch, k}];
+    if (!cc)
+    {
+        cc.reset(new Compiled);
+        cc->rc     = rtc_compile(k, arch, &cc->code);
+        cc->serial = ++g_compiles;
+    }
+    char head[256];
+    std::snprintf(head, sizeof head, "sf_specialise %s, device %d (%s): compile #%u, %.3f s\n%s\n",
+                  rtc_describe(k).c_str(), dev, arch.c_str(), cc->serial, cc->code.seconds,
+                  rtc_name_expression(k).c_str());
+    t_log = head + cc->code.log;
+
+    auto it = g_loaded.find(DevKey{dev, k});
+    if (it != g_loaded.end())
+        return it->second->state == 1 ? SF_OK : SF_ECOMPILE;
+    std::unique_ptr<Loaded> L(new Loaded);
+    L->cfg = rtc_cfg_of(k);
+    if (cc->rc != SF_OK)
+    {
+        L->state = SF_ECOMPILE;
+        g_loaded[DevKey{dev, k}] = std::move(L);
+        return SF_ECOMPILE;
+    }
+    if ((e = hipModuleLoadData(&L->mod, cc->code.code.data())) != hipSuccess)
+        return (int)e; // nothing cached: a later call may try again
+    if ((e = hipModuleGetFunction(&L->fn, L->mod, cc->code.lowered_name.c_str())) != hipSuccess)
+    {
+        (void)hipModuleUnload(L->mod);
+        return (int)e;
+    }
+    // spill guard: a specialisation that needs scratch is refused (AUTO keeps today's route)
+    int scratch = 0;
+    if ((e = hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, L->fn)) != hipSuccess || scratch > 0 ||
+        cc->code.scratch > 0)
+    {
+        scratch = scratch > 0 ? scratch : (int)cc->code.scratch;
+        (void)hipModuleUnload(L->mod);
+        L->mod = nullptr, L->fn = nullptr;
+        if (e != hipSuccess)
+            return (int)e;
+        char why[96];
+        std::snprintf(why, sizeof why, "refused: the kernel spills (%d bytes of scratch per lane)\n", scratch);
+        t_log += why;
+        L->state = SF_ECOMPILE;
+        g_loaded[DevKey{dev, k}] = std::move(L);
+        return SF_ECOMPILE;
+    }
+    L->state = 1;
+    g_loaded[DevKey{dev, k}] = std::move(L);
+    g_ready.fetch_add(1, std::memory_order_relaxed);
+    return SF_OK;
+}
+
+int rtc_state(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes, uint64_t *launches)
+{
+    RtcKey k;
+    if (rtc_key(dim, nq0, nq1, nq2, scalar_bytes, &k) != SF_OK)
+        return SF_EINVAL;
+    int dev      = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess)
+        return (int)e;
+    std::lock_guard<std::mutex> g(g_mu);
+    auto it = g_loaded.find(DevKey{dev, k});
+    if (launches)
+        *launches = it == g_loaded.end() ? 0 : it->second->launches.load(std::memory_order_relaxed);
+    return it == g_loaded.end() ? 0 : it->second->state;
+}
+
+int launch_specialised(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes, const void *b0,
+                       const void *b1, const void *b2, const void *in, void *out, uint64_t nelmt, hipStream_t s)
+{
+    if (g_ready.load(std::memory_order_relaxed) == 0) // the common case: one relaxed load
+        return SF_ENOTBUILT;
+    RtcKey k;
+    if (rtc_key(dim, nq0, nq1, nq2, scalar_bytes, &k) != SF_OK)
+        return SF_ENOTBUILT;
+    Loaded *L = ready(k);
+    return L ? launch(*L, dim, b0, b1, b2, in, out, nelmt, s) : SF_ENOTBUILT;
+}
+
+const char *rtc_last_log()
+{
+    return t_log.c_str();
+}
+
+int rtc_release()
+{
+    std::lock_guard<std::mutex> g(g_mu);
+    int cur = 0;
+    const bool have = hipGetDevice(&cur) == hipSuccess;
+    int rc          = SF_OK;
+    for (auto &kv : g_loaded)
+        if (kv.second->mod)
+        {
+            hipError_t e = hipSetDevice(kv.first.dev);
+            if (e == hipSuccess)
+                e = hipModuleUnload(kv.second->mod);
+            if (e != hipSuccess && rc == SF_OK)
+                rc = (int)e;
+        }
+    if (have && !g_loaded.empty())
+        (void)hipSetDevice(cur);
+    g_loaded.clear();
+    g_ready.store(0, std::memory_order_relaxed);
+    return rc;
+}
+
+} // namespace sf

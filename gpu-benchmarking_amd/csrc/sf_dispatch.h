@@ -55,6 +55,14 @@ int launch_hex_generic_f32(int variant, unsigned nq0, unsigned nq1, unsigned nq2
                            const HexArgsT<float> &a, hipStream_t s);
 int launch_quad_generic_f32(int variant, unsigned nq0, unsigned nq1, const QuadArgsT<float> &a,
                             hipStream_t s);
+// run-time specialisation (rtc.hip): sf_specialise / sf_specialisation_state / the launch of a ready module (SF_ENOTBUILT
+// unless one of the shape is ready on the current device) / the calling thread's last compile log / sf_shutdown's part
+int rtc_specialise(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes);
+int rtc_state(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes, uint64_t *launches);
+int launch_specialised(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes, const void *b0,
+                       const void *b1, const void *b2, const void *in, void *out, uint64_t nelmt, hipStream_t s);
+const char *rtc_last_log();
+int rtc_release();
 int sumsq_f32_blocking(const float *x, size_t n, double *result_host, hipStream_t s);
 int fill_sincos_f32(float *in, size_t nelmt, size_t nm_tot, hipStream_t s);
 int fill_basis_f32(float *b, size_t nm, size_t nq, hipStream_t s);

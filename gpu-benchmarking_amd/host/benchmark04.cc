@@ -172,6 +172,8 @@ int main(int argc, char **argv)
         return 4;
     }
     const bool f32 = (g_opt.precision == "f32");
+    const std::string spec =
+        g_opt.specialise ? specialise_devices(2, nq0, nq1, 0, f32 ? 4 : 8, g_opt.ngpus) : std::string();
     if (g_opt.nelmt > 0)
     {
         if (f32)
@@ -189,7 +191,7 @@ int main(int argc, char **argv)
             else
                 run_test<double>(size, nq0, nq1, threads, elblocks);
         }
-    g_json.write(g_opt.json, device_header() + ", \"benchmark\": \"benchmark04\"");
+    g_json.write(g_opt.json, device_header() + ", \"benchmark\": \"benchmark04\"" + spec);
     (void)sf_shutdown();
     return 0;
 }

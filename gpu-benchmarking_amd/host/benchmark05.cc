@@ -253,6 +253,8 @@ int main(int argc, char **argv)
         return 4;
     }
     const bool f32 = (g_opt.precision == "f32");
+    const std::string spec =
+        g_opt.specialise ? specialise_devices(3, nq0, nq1, nq2, f32 ? 4 : 8, g_opt.ngpus) : std::string();
     if (g_opt.ngpus > 1 || getenv("SF_FORCE_MULTIGPU_PATH"))
     {
         int ndev = 0;
@@ -280,7 +282,7 @@ int main(int argc, char **argv)
                 run_test_multi(size, nq0, nq1, nq2);
             }
         g_json.write(g_opt.json, device_header() + ", \"benchmark\": \"benchmark05\", \"ngpus\": " +
-                                     std::to_string(g_opt.ngpus));
+                                     std::to_string(g_opt.ngpus) + spec);
         g_multi.reset();
         (void)sf_shutdown();
         return 0;
@@ -302,7 +304,7 @@ int main(int argc, char **argv)
             else
                 run_test<double>(size, nq0, nq1, nq2, threads, elblocks);
         }
-    g_json.write(g_opt.json, device_header() + ", \"benchmark\": \"benchmark05\"");
+    g_json.write(g_opt.json, device_header() + ", \"benchmark\": \"benchmark05\"" + spec);
     (void)sf_shutdown();
     return 0;
 }

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -138,6 +139,7 @@ struct Options
     unsigned seed     = 0x5F3759DFu;
     std::string precision = "f64"; // --precision f64|f32
     int ngpus = 1;               // --ngpus N : benchmark05's aggregate row over N devices of this node (multigpu.h)
+    bool specialise = false;     // --specialise : sf_specialise() the run's shape on every device before timing
 };
 
 inline Options parse(int argc, char **argv)
@@ -165,6 +167,8 @@ inline Options parse(int argc, char **argv)
             o.json = next("--json");
         else if (s == "--seed")
             o.seed = (unsigned)std::strtoul(next("--seed").c_str(), nullptr, 0);
+        else if (s == "--specialise")
+            o.specialise = true;
         else if (s == "--no-baselines")
             o.baselines = false;
         else if (s == "--precision")
@@ -366,6 +370,40 @@ struct RocblasColumn
     }
 };
 #endif
+
+// --specialise: compile / load the run-time specialised wave kernel of the run's shape on devices 0 .. ngpus-1 before
+// any timed launch (AUTO, the flagship column, then takes it where the compiled tables miss the shape).  Returns the
+// --json header fragment: per device the state (1 ready, SF_ECOMPILE refused) and the wall seconds of the call, and
+// the compile seconds from the library's log.  Nothing goes to stdout (the reference's grammar stays as it is).
+inline std::string specialise_devices(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes, int ngpus)
+{
+    std::ostringstream st, wall;
+    double compile_s = -1;
+    int ndev         = 0;
+    HIP_CHECK(hipGetDeviceCount(&ndev));
+    for (int d = 0; d < ngpus && d < ndev; ++d) // the drivers refuse an --ngpus above the device count themselves
+    {
+        HIP_CHECK(hipSetDevice(d));
+        const auto t0 = std::chrono::steady_clock::now();
+        const int rc  = sf_specialise(dim, nq0, nq1, nq2, scalar_bytes);
+        const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        const int state = sf_specialisation_state(dim, nq0, nq1, nq2, scalar_bytes, nullptr);
+        const char *log = sf_last_specialise_log();
+        const char *c   = log ? std::strstr(log, "compile #") : nullptr;
+        unsigned serial = 0;
+        if (d == 0 && c)
+            (void)std::sscanf(c, "compile #%u, %lf s", &serial, &compile_s);
+        st << (d ? ", " : "") << state;
+        wall << (d ? ", " : "") << s;
+        std::cerr << "specialise device " << d << ": rc " << rc << " (" << sf_error_string(rc) << "), state " << state
+                  << ", " << s << " s" << std::endl;
+    }
+    HIP_CHECK(hipSetDevice(0));
+    std::ostringstream j;
+    j << std::setprecision(6) << ", \"specialise\": {\"state\": [" << st.str() << "], \"wall_s\": [" << wall.str()
+      << "], \"compile_s\": " << compile_s << "}";
+    return j.str();
+}
 
 inline std::string device_header()
 {

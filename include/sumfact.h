@@ -48,7 +48,8 @@ enum
     SF_EINVAL    = -1, /* nq < 2, null pointer with nelmt > 0, unknown variant */
     SF_EALIGN    = -2, /* in/out not 8-byte aligned */
     SF_ENOTBUILT = -3, /* requested variant has no instantiation for this nq */
-    SF_ENOMEM    = -4  /* internal workspace allocation failed */
+    SF_ENOMEM    = -4, /* internal workspace allocation failed */
+    SF_ECOMPILE  = -5  /* run-time specialisation unavailable: hiprtc missing, compile failed, or it would spill */
 };
 
 /* Kernel strategies (benchmark columns / tuning).  SF_VARIANT_AUTO picks the fastest measured: 3D isotropic nq 2..11
@@ -195,7 +196,37 @@ int sf_set_launch_hint(unsigned threads, unsigned elblocks);
 /* Number of compute units / device name of the current device (for logs). */
 int sf_device_info(int *num_cu, int *wave_size, char *name, size_t name_len);
 
-/* Free internal workspaces of the current device (optional; called at exit otherwise never). */
+/*
+ * Run-time specialisation.  The flagship wave-per-chunk kernels are compiled ahead of time for a table of shapes (3D
+ * isotropic, 33 anisotropic triples, 2D isotropic); sf_specialise() compiles the same kernel for any other extents
+ * with hiprtc (loaded with dlopen on first use; never linked), once per process, and loads it once per device.
+ * SF_VARIANT_AUTO of sf_bwdtrans_{hex,quad}_f64 and sf_bwdtrans_{hex,quad}_f32 then launches a READY specialisation
+ * for a shape the compiled tables miss when in / out are 16-byte aligned (order: table, specialisation, the fallbacks
+ * above).  AUTO never compiles on its own; the other variants are unaffected.  sf_shutdown() unloads every module.
+ */
+
+/* Compile (once per process) and load (once per device) the wave-per-chunk kernel specialised for these extents on
+ * the current device.  dim 2 ignores nq2; scalar_bytes 8 (fp64) or 4 (fp32).  3D extents 2..16, 2D 2..24.
+ * Not inside a stream capture.  Shapes already in a compiled table also specialise (for comparison); AUTO keeps
+ * preferring the table for those.  SF_ECOMPILE: hiprtc missing, compile failed, the device is not gfx950 (xnack-),
+ * one wave's LDS would exceed 64 KiB, or the kernel spills; the failure is remembered for the device. */
+int sf_specialise(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes);
+
+/* State on the current device: 0 none, 1 ready, SF_ECOMPILE failed; *launches (may be NULL) counts launches of it. */
+int sf_specialisation_state(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes, uint64_t *launches);
+
+/* Launch only the specialised kernel: SF_ENOTBUILT if it is not ready, SF_EALIGN unless in/out are 16-byte aligned. */
+int sf_bwdtrans_specialised(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes, size_t nelmt,
+                            const void *basis0, const void *basis1, const void *basis2, const void *in, void *out,
+                            void *stream);
+
+/* The calling thread's last sf_specialise() log: one line with the shape, device, target, the process's compile
+ * number and its seconds, the instantiation, then the compiler's log (resource-usage remarks included).  "" before
+ * the first call; valid until the thread's next sf_specialise(). */
+const char *sf_last_specialise_log(void);
+
+/* Free internal workspaces of the current device and unload every specialisation (optional; called at exit otherwise
+ * never). */
 int sf_shutdown(void);
 
 #ifdef __cplusplus

@@ -1,0 +1,116 @@
+"""CPU-side checks of the run-time specialisation (csrc/rtc.hip, csrc/rtc_compile.cc): the C exports, argument
+validation before any device call, and the compile half through bin/sf_rtc_check -- the library's own embedded
+headers, options and launch configuration, compiled for gfx950 on a machine without a GPU."""
+import ctypes
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "gpu-benchmarking_amd")
+CHECK = os.path.join(PKG, "bin", "sf_rtc_check")
+
+SHAPES_3D = ["6x6x12", "12x10x8", "5x9x7", "3x5x4", "2x3x2"]
+SHAPES_2D = ["4x9", "16x3", "12x20", "23x5", "2x24"]
+SHAPES_F32 = ["3x5x4:f32", "4x9:f32"]
+
+ROW = re.compile(r"^(fp64|fp32) ([23])D (\S+)\s+vgpr\s+(\d+) agpr\s+(\d+) sgpr\s+(\d+) scratch\s+(\d+) "
+                 r"spill v(\d+)/s(\d+) occ (\d+) lds\s+(\d+) wpb (\d) ec\s+(\d+)\s+compile ([\d.]+) s\s+(ok|SPILLS)$")
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    import __graft_entry__ as ge
+    if not (os.path.exists(os.path.join(PKG, "lib", "libsumfact.so")) and os.path.exists(CHECK)):
+        ge.build()
+    return ge.load_package()
+
+
+def _run_check(*shapes):
+    r = subprocess.run([CHECK, *shapes], capture_output=True, text=True, timeout=600)
+    lines = r.stdout.splitlines()
+    rows = {}
+    for ln in lines[1:]:
+        m = ROW.match(ln)
+        assert m, f"unparsed sf_rtc_check line: {ln!r}\n{r.stdout}\n{r.stderr}"
+        key = m.group(3) + (":f32" if m.group(1) == "fp32" else "")
+        rows[key] = {"vgpr": int(m.group(4)), "sgpr": int(m.group(6)), "scratch": int(m.group(7)),
+                     "spill_v": int(m.group(8)), "lds": int(m.group(11)), "seconds": float(m.group(14)),
+                     "status": m.group(15)}
+    return r.returncode, lines, rows
+
+
+def test_specialisation_exports(pkg):
+    lib = pkg.capi.lib()
+    for name in ("sf_specialise", "sf_specialisation_state", "sf_bwdtrans_specialised", "sf_last_specialise_log"):
+        assert hasattr(lib, name), name
+        assert name in pkg.capi.SYMBOLS, name
+    assert pkg.capi.SF_ECOMPILE == -5
+    assert b"specialisation" in lib.sf_error_string(-5)
+    assert isinstance(lib.sf_last_specialise_log(), bytes)
+
+
+def test_specialisation_argument_validation_without_gpu(pkg):
+    """Every malformed request is SF_EINVAL before any HIP call."""
+    lib = pkg.capi.lib()
+    n = ctypes.c_uint64(7)
+    bad = [(1, 4, 4, 4, 8), (4, 4, 4, 4, 8), (3, 1, 4, 4, 8), (3, 4, 4, 1, 8), (2, 4, 1, 0, 8),
+           (3, 17, 4, 4, 8), (3, 4, 4, 17, 8), (2, 25, 4, 0, 8), (2, 4, 25, 0, 8), (3, 4, 4, 4, 2), (2, 4, 9, 0, 16)]
+    for args in bad:
+        assert lib.sf_specialise(*args) == -1, args
+        assert lib.sf_specialisation_state(*args, None) == -1, args
+        assert lib.sf_specialisation_state(*args, ctypes.byref(n)) == -1, args
+        assert lib.sf_bwdtrans_specialised(*args, 10, None, None, None, None, None, None) == -1, args
+    # well-formed but empty: nothing to do, no device touched
+    assert lib.sf_bwdtrans_specialised(3, 6, 6, 12, 8, 0, None, None, None, None, None, None) == 0
+    # null pointers / misalignment are caught before the device lookup
+    assert lib.sf_bwdtrans_specialised(3, 6, 6, 12, 8, 10, None, None, None, None, None, None) == -1
+    assert lib.sf_bwdtrans_specialised(2, 4, 9, 0, 8, 10, 0x1000, 0x1000, None, 0x1008, 0x2000, None) == -2
+    assert lib.sf_bwdtrans_specialised(3, 6, 6, 12, 4, 10, 0x1000, 0x1000, 0x1000, 0x1000, 0x2004, None) == -2
+
+
+def test_rtc_check_compiles_every_listed_shape_without_spilling(pkg):
+    shapes = SHAPES_3D + SHAPES_2D + SHAPES_F32
+    rc, lines, rows = _run_check(*shapes)
+    assert rc == 0, "\n".join(lines)
+    assert sorted(rows) == sorted(shapes)
+    for s, r in rows.items():
+        assert r["scratch"] == 0 and r["spill_v"] == 0 and r["status"] == "ok", (s, r)
+        assert 0 < r["vgpr"] <= 256 and 0 < r["lds"] <= 64 * 1024, (s, r)
+
+
+def test_rtc_check_reports_the_spilling_shape(pkg):
+    rc, lines, rows = _run_check("16x16x14")
+    assert rc == 0, "\n".join(lines)
+    r = rows["16x16x14"]
+    assert r["status"] == "SPILLS" and r["scratch"] > 0, r
+
+
+def test_rtc_check_matches_the_aot_instantiation(pkg):
+    """8x8x4 is one of the compile-time triples: hiprtc and hipcc must give its kernel the same resources."""
+    _, lines, rows = _run_check("8x8x4")
+    aot = subprocess.run(["python3", os.path.join(PKG, "tools", "kernel_resources.py"),
+                          os.path.join(PKG, "csrc", "bwdtrans_rt.hip"), "hex_wave3_kernel<8, 8, 4,"],
+                         capture_output=True, text=True, cwd=PKG, timeout=900).stdout
+    m = re.search(r"vgpr\s+(\d+) agpr\s+\d+ sgpr\s+(\d+) scratch\s+(\d+)", aot)
+    assert m, aot
+    r = rows["8x8x4"]
+    assert (r["vgpr"], r["sgpr"], r["scratch"]) == (int(m.group(1)), int(m.group(2)), int(m.group(3))), (r, aot)
+    assert (r["vgpr"], r["sgpr"], r["scratch"]) == (36, 70, 0)
+
+
+def test_rtc_source_hash_is_the_hash_of_the_current_headers(pkg):
+    """The library embeds the kernel headers at build time; the hash it prints must be that of the files as they are."""
+    files = [("sf_common.h", "csrc/sf_common.h"), ("bwdtrans_wave.h", "csrc/bwdtrans_wave.h"),
+             ("bwdtrans_wave3.h", "csrc/bwdtrans_wave3.h"), ("bwdtrans_wave2.h", "csrc/bwdtrans_wave2.h"),
+             ("../../include/sumfact.h", "../include/sumfact.h")]
+    x = 0xcbf29ce484222325
+    for name, path in files:
+        with open(os.path.join(PKG, path), "rb") as f:
+            text = f.read()
+        for byte in name.encode() + b"\0" + text + b"\0":
+            x = ((x ^ byte) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
+    out = subprocess.run([CHECK, "2x3x2"], capture_output=True, text=True, timeout=300).stdout
+    assert out.splitlines()[0] == f"source-hash {x:016x}", out
