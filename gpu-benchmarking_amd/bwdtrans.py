@@ -132,6 +132,78 @@ def bwdtrans_quad(nq, basis0, basis1, inp, out=None, variant="auto", wsp=None, s
     return out
 
 
+def _iprod_call(what, nq, bases, inp, out, variant, stream):
+    """Shared body of iproduct_hex / iproduct_quad: sizes checked here, pointers and alignment in the C ABI."""
+    nq = tuple(int(x) for x in nq)
+    nmt, nqt = 1, 1
+    for q in nq:
+        nmt, nqt = nmt * (q - 1), nqt * q
+    if nmt <= 0:
+        raise capi.SumfactError(capi.SF_EINVAL, what)
+    nelmt = inp.numel() // nqt
+    if nelmt * nqt != inp.numel():
+        raise ValueError(f"{what}: in.numel() is not a multiple of the points per element ({nqt})")
+    if out is None:
+        out = torch.empty(nelmt * nmt, dtype=inp.dtype, device=inp.device)
+    elif out.numel() != nelmt * nmt:
+        raise ValueError(f"{what}: out has the wrong size")
+    _check_sizes(what, bases, nq, None, 0)
+    v = _variant(variant)
+    if inp.dtype == torch.float32:
+        if v != VARIANTS["auto"]:
+            raise ValueError(f"{what}: float32 has the AUTO route only")
+        fn, ptr = getattr(capi.lib(), f"sf_iproduct_{'hex' if len(nq) == 3 else 'quad'}_f32"), _dev_f32
+        head = ()
+    else:
+        fn, ptr = getattr(capi.lib(), f"sf_iproduct_{'hex' if len(nq) == 3 else 'quad'}_f64_variant"), _dev_f64
+        head = (v,)
+    with torch.cuda.device(inp.device):
+        rc = fn(*head, *nq, nelmt, *[ptr(b, f"basis{d}") for d, b in enumerate(bases)], ptr(inp, "in"),
+                ptr(out, "out"), _stream(stream, inp.device))
+    capi.check(rc, what)
+    return out
+
+
+def iproduct_hex(nq, basis0, basis1, basis2, inp, out=None, variant="auto", stream=None):
+    """IProductWRTBase, the transpose of bwdtrans_hex: out[e][r][q][p] = sum_kji in[e][k][j][i] B0[p][i] B1[q][j]
+    B2[r][k] on inp's device.  Same bases as bwdtrans_hex; inp holds nq0*nq1*nq2 values per element, out nm0*nm1*nm2.
+    float64 takes variant "auto", "wave" or "generic"; float32 the AUTO route."""
+    return _iprod_call("iproduct_hex", nq, (basis0, basis1, basis2), inp, out, variant, stream)
+
+
+def iproduct_quad(nq, basis0, basis1, inp, out=None, variant="auto", stream=None):
+    """IProductWRTBase, the transpose of bwdtrans_quad: out[e][q][p] = sum_ji in[e][j][i] B0[p][i] B1[q][j]."""
+    return _iprod_call("iproduct_quad", nq, (basis0, basis1), inp, out, variant, stream)
+
+
+class _BwdTrans(torch.autograd.Function):
+    """AUTO BwdTrans forward; its input gradient is IProductWRTBase of the output gradient (the exact transpose)."""
+
+    @staticmethod
+    def forward(ctx, inp, nq, *bases):
+        ctx.nq, ctx.shape = nq, inp.shape
+        ctx.save_for_backward(*bases)
+        x = inp.contiguous()
+        return bwdtrans_hex(nq, *bases, x) if len(nq) == 3 else bwdtrans_quad(nq, *bases, x)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        bases, g = ctx.saved_tensors, grad_out.contiguous()
+        gin = iproduct_hex(ctx.nq, *bases, g) if len(ctx.nq) == 3 else iproduct_quad(ctx.nq, *bases, g)
+        return (gin.reshape(ctx.shape), None) + (None,) * len(bases)
+
+
+def bwdtrans_autograd(nq, bases, inp):
+    """BwdTrans (AUTO) with a backward pass: the gradient with respect to `inp` is iproduct_*(grad_out), enqueued on
+    the current stream.  The bases are constants: a basis that requires grad is refused.  Returns the flat output."""
+    nq, bases = tuple(int(x) for x in nq), tuple(bases)
+    if len(nq) not in (2, 3) or len(bases) != len(nq):
+        raise ValueError("bwdtrans_autograd: 2 or 3 extents, one basis per extent")
+    if any(b.requires_grad for b in bases):
+        raise ValueError("bwdtrans_autograd: the bases are constants; detach them (no gradient flows to a basis)")
+    return _BwdTrans.apply(inp, nq, *bases)
+
+
 def _spec_args(nq, dtype):
     nq = tuple(int(x) for x in nq)
     if len(nq) not in (2, 3):

@@ -1,6 +1,6 @@
 // capi.hip -- the extern "C" boundary of libsumfact.so (declared in include/sumfact.h).
 // Validation + dispatch only; kernels live in bwdtrans_hex.hip / bwdtrans_quad.hip /
-// bwdtrans_generic.hip / aux_kernels.hip.
+// bwdtrans_generic.hip / aux_kernels.hip, IProductWRTBase in iproduct.hip / iproduct_generic.hip.
 #include "sf_dispatch.h"
 
 #include <cstdio>
@@ -12,6 +12,78 @@ using namespace sf;
 static inline bool aligned(const void *p, size_t a)
 {
     return ((uintptr_t)p & (a - 1)) == 0;
+}
+
+// ---- IProductWRTBase: one validation and routing for both dimensions and both scalar types ---------------------------
+static int iprod_wave(unsigned nq, const HexArgs &a, hipStream_t s)
+{
+    return launch_hex_iprod_wave_nq(nq, a, s);
+}
+static int iprod_wave(unsigned nq, const HexArgsT<float> &a, hipStream_t s)
+{
+    return launch_hex_iprod_wave_f32_nq(nq, a, s);
+}
+static int iprod_wave(unsigned nq, const QuadArgs &a, hipStream_t s)
+{
+    return launch_quad_iprod_wave_nq(nq, a, s);
+}
+static int iprod_wave(unsigned nq, const QuadArgsT<float> &a, hipStream_t s)
+{
+    return launch_quad_iprod_wave_f32_nq(nq, a, s);
+}
+static int iprod_generic(const unsigned (&nq)[3], const HexArgs &a, hipStream_t s)
+{
+    return launch_hex_iprod_generic(nq[0], nq[1], nq[2], a, s);
+}
+static int iprod_generic(const unsigned (&nq)[3], const HexArgsT<float> &a, hipStream_t s)
+{
+    return launch_hex_iprod_generic_f32(nq[0], nq[1], nq[2], a, s);
+}
+static int iprod_generic(const unsigned (&nq)[3], const QuadArgs &a, hipStream_t s)
+{
+    return launch_quad_iprod_generic(nq[0], nq[1], a, s);
+}
+static int iprod_generic(const unsigned (&nq)[3], const QuadArgsT<float> &a, hipStream_t s)
+{
+    return launch_quad_iprod_generic_f32(nq[0], nq[1], a, s);
+}
+
+// Validation before any HIP call, in the order of sf_bwdtrans_*; then AUTO takes the wave kernel for an isotropic order
+// of its table when in / out are 16-byte aligned, and the any-extent kernel otherwise.
+template <int DIM, class Args, typename T>
+static int iprod(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *in, T *out,
+                 void *stream)
+{
+    if (nq[0] < 2 || nq[1] < 2 || (DIM == 3 && nq[2] < 2) || variant < 0 || variant >= SF_NUM_VARIANTS)
+        return SF_EINVAL;
+    if (nelmt == 0)
+        return SF_OK;
+    if (!b[0] || !b[1] || (DIM == 3 && !b[2]) || !in || !out)
+        return SF_EINVAL;
+    if (!aligned(in, sizeof(T)) || !aligned(out, sizeof(T)) || !aligned(b[0], sizeof(T)) || !aligned(b[1], sizeof(T)) ||
+        (DIM == 3 && !aligned(b[2], sizeof(T))))
+        return SF_EALIGN;
+    if (!iprod_generic_built(DIM, nq[0], nq[1], nq[2]))
+        return SF_ENOTBUILT;
+    if (variant != SF_VARIANT_AUTO && variant != SF_VARIANT_WAVE && variant != SF_VARIANT_GENERIC)
+        return SF_ENOTBUILT;
+    const hipStream_t s = (hipStream_t)stream;
+    Args a{};
+    if constexpr (DIM == 3)
+        a = Args{b[0], b[1], b[2], in, nullptr, out, (uint64_t)nelmt};
+    else
+        a = Args{b[0], b[1], in, nullptr, out, (uint64_t)nelmt};
+    const bool wave_ok = nq[0] == nq[1] && (DIM == 2 || nq[1] == nq[2]) && iprod_wave_built(DIM, nq[0]);
+    const bool vec_ok  = aligned(in, 16) && aligned(out, 16);
+    if (variant == SF_VARIANT_WAVE)
+    {
+        if (!wave_ok)
+            return SF_ENOTBUILT;
+        return vec_ok ? iprod_wave(nq[0], a, s) : SF_EALIGN;
+    }
+    if (variant == SF_VARIANT_AUTO && wave_ok && vec_ok)
+        return iprod_wave(nq[0], a, s);
+    return iprod_generic(nq, a, s);
 }
 
 extern "C" {
@@ -282,6 +354,46 @@ int sf_bwdtrans_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *
             return rc;
     }
     return launch_quad_generic_f32(SF_VARIANT_GENERIC, nq0, nq1, a, s);
+}
+
+// ---- IProductWRTBase, the transpose of BwdTrans ----------------------------------------------------------------------
+int sf_iproduct_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                                const double *basis0, const double *basis1, const double *basis2, const double *in,
+                                double *out, void *stream)
+{
+    return iprod<3, HexArgs, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, out, stream);
+}
+
+int sf_iproduct_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
+                        const double *basis1, const double *basis2, const double *in, double *out, void *stream)
+{
+    return iprod<3, HexArgs, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, out, stream);
+}
+
+int sf_iproduct_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                                 const double *basis1, const double *in, double *out, void *stream)
+{
+    return iprod<2, QuadArgs, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, out, stream);
+}
+
+int sf_iproduct_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                         const double *in, double *out, void *stream)
+{
+    return iprod<2, QuadArgs, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, out, stream);
+}
+
+int sf_iproduct_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
+                        const float *basis1, const float *basis2, const float *in, float *out, void *stream)
+{
+    return iprod<3, HexArgsT<float>, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, out,
+                                     stream);
+}
+
+int sf_iproduct_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
+                         const float *in, float *out, void *stream)
+{
+    return iprod<2, QuadArgsT<float>, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, out,
+                                      stream);
 }
 
 int sf_sumsq_f32(const float *x, size_t n, double *result_host, void *stream)

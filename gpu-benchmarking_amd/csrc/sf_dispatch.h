@@ -63,6 +63,18 @@ int launch_specialised(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int sc
                        const void *b1, const void *b2, const void *in, void *out, uint64_t nelmt, hipStream_t s);
 const char *rtc_last_log();
 int rtc_release();
+// IProductWRTBase (iproduct.hip: the wave kernels, SF_ENOTBUILT off their table -- 3D isotropic nq 2..11, 2D 2..16;
+// iproduct_generic.hip: any extents up to 16 per direction in 3D and 32 in 2D, SF_ENOTBUILT beyond)
+int launch_hex_iprod_wave_nq(unsigned nq, const HexArgs &a, hipStream_t s);
+int launch_hex_iprod_wave_f32_nq(unsigned nq, const HexArgsT<float> &a, hipStream_t s);
+int launch_quad_iprod_wave_nq(unsigned nq, const QuadArgs &a, hipStream_t s);
+int launch_quad_iprod_wave_f32_nq(unsigned nq, const QuadArgsT<float> &a, hipStream_t s);
+bool iprod_wave_built(int dim, unsigned nq);
+int launch_hex_iprod_generic(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, hipStream_t s);
+int launch_hex_iprod_generic_f32(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgsT<float> &a, hipStream_t s);
+int launch_quad_iprod_generic(unsigned nq0, unsigned nq1, const QuadArgs &a, hipStream_t s);
+int launch_quad_iprod_generic_f32(unsigned nq0, unsigned nq1, const QuadArgsT<float> &a, hipStream_t s);
+bool iprod_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
 int sumsq_f32_blocking(const float *x, size_t n, double *result_host, hipStream_t s);
 int fill_sincos_f32(float *in, size_t nelmt, size_t nm_tot, hipStream_t s);
 int fill_basis_f32(float *b, size_t nm, size_t nq, hipStream_t s);

@@ -1,6 +1,7 @@
 // wave_table.h -- the tuned configuration of the wave-per-chunk kernels, one row per isotropic nq.
 // Shared by the dispatchers (bwdtrans_hex.hip, bwdtrans_quad.hip) and tools/sf_tune_table.hip, which
-// re-measures every row (and its memory-flag alternatives) on the device.
+// re-measures every row (and its memory-flag alternatives) on the device.  The IProductWRTBase kernels (iproduct.hip) run
+// the same rows with OUT_LDS and MEMF bit 3 forced; a re-tuned row changes them too (tools/iprod_bench.py re-measures).
 #pragma once
 #include "bwdtrans_wave.h"
 

@@ -170,6 +170,39 @@ int sf_fill_basis_f32(float *basis, size_t nm, size_t nq, void *stream);
 int sf_fill_random_f32(float *x, size_t n, uint64_t seed, uint64_t first_idx, void *stream);
 
 /*
+ * IProductWRTBase, the inner product with respect to the basis: the exact transpose of BwdTrans.
+ *   3D: out[e][r][q][p] = sum_k sum_j sum_i in[e][k][j][i] B0[p][i] B1[q][j] B2[r][k]
+ *   2D: out[e][q][p]    = sum_j sum_i       in[e][j][i]    B0[p][i] B1[q][j]
+ * `in` holds nq0*nq1[*nq2] values per element at the quadrature points (i fastest), `out` nm0*nm1[*nm2] modes per
+ * element (p fastest).  The bases are the BwdTrans bases, unchanged: basis[p*nq + i], row-major nm x nq.  Sweeps i -> p,
+ * j -> q, k -> r, each sum in ascending index.  Quadrature weights of tensor-product form fold into the bases
+ * (B_d'[p][i] = B_d[p][i] * w_d[i]), so the kernels carry no weight array.  Chain BwdTrans -> pointwise weight ->
+ * IProductWRTBase for a mass or Helmholtz operator; this is also the gradient of BwdTrans with respect to its input.
+ * Variants: SF_VARIANT_AUTO (the wave kernel for the isotropic orders of its table -- 3D nq 2..11, 2D nq 2..16 -- when
+ * in / out are 16-byte aligned, else GENERIC), SF_VARIANT_WAVE (SF_ENOTBUILT off that table, SF_EALIGN unless 16-byte
+ * aligned), SF_VARIANT_GENERIC (one workgroup per element, any extents up to 16 per direction in 3D and 32 in 2D);
+ * any other variant SF_ENOTBUILT, extents beyond those bounds SF_ENOTBUILT.  Validation as sf_bwdtrans_*, before any
+ * HIP call.  No internal workspace: every call is capture-safe from the first one.
+ */
+int sf_iproduct_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                        const double *basis0, const double *basis1, const double *basis2,
+                        const double *in, double *out, void *stream);
+int sf_iproduct_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                                const double *basis0, const double *basis1, const double *basis2,
+                                const double *in, double *out, void *stream);
+int sf_iproduct_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                         const double *basis1, const double *in, double *out, void *stream);
+int sf_iproduct_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt,
+                                 const double *basis0, const double *basis1, const double *in,
+                                 double *out, void *stream);
+/* T = float (AUTO route; in / out / bases 4-byte aligned) */
+int sf_iproduct_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
+                        const float *basis1, const float *basis2, const float *in, float *out,
+                        void *stream);
+int sf_iproduct_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0,
+                         const float *basis1, const float *in, float *out, void *stream);
+
+/*
  * benchmark02: x[i] += y[i]  -- replaces add_vector<T,vl><<<>>>
  * (benchmark02/benchmark02.cc:16-58); 24 bytes of HBM traffic per element (:255), so its GB/s is the
  * measured stream rate used as the second roofline denominator.  fill: data1/data2 of :84-85.
