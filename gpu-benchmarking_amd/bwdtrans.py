@@ -176,6 +176,55 @@ def iproduct_quad(nq, basis0, basis1, inp, out=None, variant="auto", stream=None
     return _iprod_call("iproduct_quad", nq, (basis0, basis1), inp, out, variant, stream)
 
 
+def _mass_call(what, nq, bases, w, inp, out, variant, stream):
+    """Shared body of mass_hex / mass_quad: sizes checked here, pointers, alignment and overlap in the C ABI."""
+    nq = tuple(int(x) for x in nq)
+    nmt, nqt = 1, 1
+    for q in nq:
+        nmt, nqt = nmt * (q - 1), nqt * q
+    if nmt <= 0:
+        raise capi.SumfactError(capi.SF_EINVAL, what)
+    nelmt = inp.numel() // nmt
+    if nelmt * nmt != inp.numel():
+        raise ValueError(f"{what}: in.numel() is not a multiple of the modes per element ({nmt})")
+    if w.numel() != nelmt * nqt:
+        raise ValueError(f"{what}: w has {w.numel()} values, nelmt * points per element = {nelmt * nqt}")
+    if w.dtype != inp.dtype:
+        raise ValueError(f"{what}: w is {w.dtype}, in is {inp.dtype}")
+    if out is None:
+        out = torch.empty(nelmt * nmt, dtype=inp.dtype, device=inp.device)
+    elif out.numel() != nelmt * nmt:
+        raise ValueError(f"{what}: out has the wrong size")
+    _check_sizes(what, bases, nq, None, 0)
+    v = _variant(variant)
+    shape = "hex" if len(nq) == 3 else "quad"
+    if inp.dtype == torch.float32:
+        if v != VARIANTS["auto"]:
+            raise ValueError(f"{what}: float32 has the AUTO route only")
+        fn, ptr, head = getattr(capi.lib(), f"sf_mass_{shape}_f32"), _dev_f32, ()
+    else:
+        fn, ptr, head = getattr(capi.lib(), f"sf_mass_{shape}_f64_variant"), _dev_f64, (v,)
+    with torch.cuda.device(inp.device):
+        rc = fn(*head, *nq, nelmt, *[ptr(b, f"basis{d}") for d, b in enumerate(bases)], ptr(w, "w"), ptr(inp, "in"),
+                ptr(out, "out"), _stream(stream, inp.device))
+    capi.check(rc, what)
+    return out
+
+
+def mass_hex(nq, basis0, basis1, basis2, w, inp, out=None, variant="auto", stream=None):
+    """The fused mass operator B^T diag(w) B in one kernel: out[e][r'][q'][p'] = sum_kji B0[p'][i] B1[q'][j] B2[r'][k]
+    w[e][k][j][i] (sum_rqp in[e][r][q][p] B0[p][i] B1[q][j] B2[r][k]) on inp's device.  The bases of bwdtrans_hex; inp and
+    out hold nm0*nm1*nm2 modes per element, w nq0*nq1*nq2 weights per element.  out may not overlap inp or w.  float64
+    takes variant "auto", "wave" or "generic"; float32 the AUTO route.  A plain function: no autograd."""
+    return _mass_call("mass_hex", nq, (basis0, basis1, basis2), w, inp, out, variant, stream)
+
+
+def mass_quad(nq, basis0, basis1, w, inp, out=None, variant="auto", stream=None):
+    """The fused mass operator in 2D: out[e][q'][p'] = sum_ji B0[p'][i] B1[q'][j] w[e][j][i] (sum_qp in[e][q][p] B0[p][i]
+    B1[q][j])."""
+    return _mass_call("mass_quad", nq, (basis0, basis1), w, inp, out, variant, stream)
+
+
 class _BwdTrans(torch.autograd.Function):
     """AUTO BwdTrans forward; its input gradient is IProductWRTBase of the output gradient (the exact transpose)."""
 

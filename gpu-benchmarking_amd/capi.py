@@ -44,6 +44,12 @@ SYMBOLS = {
     "sf_iproduct_quad_f64_variant": (_i, [_i, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp]),
     "sf_iproduct_hex_f32": (_i, [_u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sf_iproduct_quad_f32": (_i, [_u, _u, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "sf_mass_hex_f64": (_i, [_u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sf_mass_hex_f64_variant": (_i, [_i, _u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sf_mass_quad_f64": (_i, [_u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sf_mass_quad_f64_variant": (_i, [_i, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sf_mass_hex_f32": (_i, [_u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sf_mass_quad_f32": (_i, [_u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sf_vector_add_f64": (_i, [_vp, _vp, _sz, _vp]),
     "sf_fill_vecadd_f64": (_i, [_vp, _vp, _sz, _vp]),
     "sf_matvec_f64": (_i, [_u, _u, _vp, _vp, _vp, _vp]),

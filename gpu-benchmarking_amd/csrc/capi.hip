@@ -1,6 +1,7 @@
 // capi.hip -- the extern "C" boundary of libsumfact.so (declared in include/sumfact.h).
 // Validation + dispatch only; kernels live in bwdtrans_hex.hip / bwdtrans_quad.hip /
-// bwdtrans_generic.hip / aux_kernels.hip, IProductWRTBase in iproduct.hip / iproduct_generic.hip.
+// bwdtrans_generic.hip / aux_kernels.hip, IProductWRTBase in iproduct.hip / iproduct_generic.hip, the fused mass
+// operator in mass.hip / mass_f32.hip / mass_generic.hip.
 #include "sf_dispatch.h"
 
 #include <cstdio>
@@ -84,6 +85,91 @@ static int iprod(int variant, const unsigned (&nq)[3], size_t nelmt, const T *co
     if (variant == SF_VARIANT_AUTO && wave_ok && vec_ok)
         return iprod_wave(nq[0], a, s);
     return iprod_generic(nq, a, s);
+}
+
+// ---- the fused mass operator B^T diag(w) B: one validation and routing for both dimensions and both scalar types ----
+static int mass_wave(unsigned nq, const HexArgs &a, const double *w, hipStream_t s)
+{
+    return launch_hex_mass_wave_nq(nq, a, w, s);
+}
+static int mass_wave(unsigned nq, const HexArgsT<float> &a, const float *w, hipStream_t s)
+{
+    return launch_hex_mass_wave_f32_nq(nq, a, w, s);
+}
+static int mass_wave(unsigned nq, const QuadArgs &a, const double *w, hipStream_t s)
+{
+    return launch_quad_mass_wave_nq(nq, a, w, s);
+}
+static int mass_wave(unsigned nq, const QuadArgsT<float> &a, const float *w, hipStream_t s)
+{
+    return launch_quad_mass_wave_f32_nq(nq, a, w, s);
+}
+static int mass_generic(const unsigned (&nq)[3], const HexArgs &a, const double *w, hipStream_t s)
+{
+    return launch_hex_mass_generic(nq[0], nq[1], nq[2], a, w, s);
+}
+static int mass_generic(const unsigned (&nq)[3], const HexArgsT<float> &a, const float *w, hipStream_t s)
+{
+    return launch_hex_mass_generic_f32(nq[0], nq[1], nq[2], a, w, s);
+}
+static int mass_generic(const unsigned (&nq)[3], const QuadArgs &a, const double *w, hipStream_t s)
+{
+    return launch_quad_mass_generic(nq[0], nq[1], a, w, s);
+}
+static int mass_generic(const unsigned (&nq)[3], const QuadArgsT<float> &a, const float *w, hipStream_t s)
+{
+    return launch_quad_mass_generic_f32(nq[0], nq[1], a, w, s);
+}
+
+// byte ranges [p, p + np) and [q, q + nq) share a byte
+static inline bool overlaps(const void *p, size_t np, const void *q, size_t nq)
+{
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + nq && b < a + np;
+}
+
+// Validation before any HIP call, in the order documented in include/sumfact.h; then AUTO takes the wave kernel for an
+// isotropic order of its table when in / out are 16-byte aligned, and the any-extent kernel otherwise.
+template <int DIM, class Args, typename T>
+static int mass(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *w, const T *in,
+                T *out, void *stream)
+{
+    if (nq[0] < 2 || nq[1] < 2 || (DIM == 3 && nq[2] < 2) || variant < 0 || variant >= SF_NUM_VARIANTS)
+        return SF_EINVAL;
+    if (nelmt == 0)
+        return SF_OK;
+    if (!b[0] || !b[1] || (DIM == 3 && !b[2]) || !w || !in || !out)
+        return SF_EINVAL;
+    if (!aligned(in, sizeof(T)) || !aligned(out, sizeof(T)) || !aligned(w, sizeof(T)) || !aligned(b[0], sizeof(T)) ||
+        !aligned(b[1], sizeof(T)) || (DIM == 3 && !aligned(b[2], sizeof(T))))
+        return SF_EALIGN;
+    // not in-place safe (the word-grid loads of a chunk read 16-byte words that straddle the neighbouring element)
+    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
+    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
+    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
+    if (overlaps(out, modes_bytes, in, modes_bytes) || overlaps(out, modes_bytes, w, points_bytes))
+        return SF_EINVAL;
+    if (!mass_generic_built(DIM, nq[0], nq[1], nq[2]))
+        return SF_ENOTBUILT;
+    if (variant != SF_VARIANT_AUTO && variant != SF_VARIANT_WAVE && variant != SF_VARIANT_GENERIC)
+        return SF_ENOTBUILT;
+    const hipStream_t s = (hipStream_t)stream;
+    Args a{};
+    if constexpr (DIM == 3)
+        a = Args{b[0], b[1], b[2], in, nullptr, out, (uint64_t)nelmt};
+    else
+        a = Args{b[0], b[1], in, nullptr, out, (uint64_t)nelmt};
+    const bool wave_ok = nq[0] == nq[1] && (DIM == 2 || nq[1] == nq[2]) && mass_wave_built(DIM, nq[0]);
+    const bool vec_ok  = aligned(in, 16) && aligned(out, 16);
+    if (variant == SF_VARIANT_WAVE)
+    {
+        if (!wave_ok)
+            return SF_ENOTBUILT;
+        return vec_ok ? mass_wave(nq[0], a, w, s) : SF_EALIGN;
+    }
+    if (variant == SF_VARIANT_AUTO && wave_ok && vec_ok)
+        return mass_wave(nq[0], a, w, s);
+    return mass_generic(nq, a, w, s);
 }
 
 extern "C" {
@@ -394,6 +480,46 @@ int sf_iproduct_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *
 {
     return iprod<2, QuadArgsT<float>, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, out,
                                       stream);
+}
+
+// ---- the fused mass operator: BwdTrans, pointwise weight, IProductWRTBase in one kernel -------------------------------
+int sf_mass_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
+                            const double *basis1, const double *basis2, const double *w, const double *in, double *out,
+                            void *stream)
+{
+    return mass<3, HexArgs, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, w, in, out, stream);
+}
+
+int sf_mass_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0, const double *basis1,
+                    const double *basis2, const double *w, const double *in, double *out, void *stream)
+{
+    return mass<3, HexArgs, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, w, in, out, stream);
+}
+
+int sf_mass_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                             const double *basis1, const double *w, const double *in, double *out, void *stream)
+{
+    return mass<2, QuadArgs, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, w, in, out, stream);
+}
+
+int sf_mass_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                     const double *w, const double *in, double *out, void *stream)
+{
+    return mass<2, QuadArgs, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, w, in, out, stream);
+}
+
+int sf_mass_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
+                    const float *basis2, const float *w, const float *in, float *out, void *stream)
+{
+    return mass<3, HexArgsT<float>, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, w, in, out,
+                                           stream);
+}
+
+int sf_mass_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1, const float *w,
+                     const float *in, float *out, void *stream)
+{
+    return mass<2, QuadArgsT<float>, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, w, in, out,
+                                            stream);
 }
 
 int sf_sumsq_f32(const float *x, size_t n, double *result_host, void *stream)

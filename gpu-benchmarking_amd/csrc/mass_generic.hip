@@ -1,0 +1,213 @@
+// mass_generic.hip -- the fused mass operator B^T diag(w) B for any extents: the fallback of the wave kernels of
+// mass_wave.h.
+//
+// One workgroup per element (a grid-stride loop over elements), every image in static LDS, one thread per output value
+// of a sweep, each sum in ascending index.  Sweep order of the wave kernels: forward p -> i, q -> j, r -> k, one
+// multiply by the weight per point, then transposed k -> r', j -> q', i -> p'.  The images ping-pong between two LDS
+// regions A and B:
+//   3D: in (B) -> w1 (A) -> w2 (B) -> weighted points (A) -> t1 (B) -> t2 (A) -> out (HBM)
+//   2D: in (A) -> w1 (B) -> weighted points (A) -> t1 (B) -> out (HBM)
+// A holds nq0*nq1[*nq2] scalars (the point image is the largest it sees), B nq0*nq1*nm2 in 3D and nq0*nm1 in 2D; the
+// launcher derives both from the extents and refuses what does not fit the large class.  `in`, `w` and the bases are
+// read from global memory with scalar loads, `out` is written with scalar stores: buffers that are only 8-byte
+// (fp32: 4-byte) aligned are fine.  No workspace: every launch is a single kernel node, capture-safe from the first
+// call.  Latency-bound (a barrier per sweep, one element per workgroup), not a roofline target.  Extents up to 16 per
+// direction in 3D and 32 in 2D; beyond, SF_ENOTBUILT.
+#include "sf_dispatch.h"
+
+namespace sf
+{
+
+// LDS classes in scalars (those of iproduct_generic.hip).  3D 16^3: 4096 + 3840 = 7936; 2D 32^2: 1024 + 992.
+constexpr int kMassSmallCap = 2048, kMassLargeCap = 7936;
+constexpr unsigned kMassMax3D = 16, kMassMax2D = 32;
+
+__device__ __forceinline__ double mfma_s(double a, double b, double c)
+{
+    return __builtin_fma(a, b, c);
+}
+__device__ __forceinline__ float mfma_s(float a, float b, float c)
+{
+    return __builtin_fmaf(a, b, c);
+}
+
+// a = sum_{m < n} u[m*us] * b[m*bs], ascending m, the first product a multiply
+template <typename T> __device__ __forceinline__ T dot_strided(const T *u, int us, const T *b, int bs, int n)
+{
+    T a = u[0] * b[0];
+    for (int m = 1; m < n; ++m)
+        a = mfma_s(u[m * us], b[m * bs], a);
+    return a;
+}
+
+template <typename T, int DIM, int CAP, int NT>
+__global__ __launch_bounds__(NT) void mass_generic_kernel(const T *__restrict__ b0, const T *__restrict__ b1,
+                                                          const T *__restrict__ b2, const T *__restrict__ w,
+                                                          const T *__restrict__ in, T *__restrict__ out, uint64_t nelmt,
+                                                          int nq0, int nq1, int nq2, int sizeA)
+{
+    __shared__ T lds[CAP];
+    const int nm0 = nq0 - 1, nm1 = nq1 - 1, nm2 = DIM == 3 ? nq2 - 1 : 1;
+    const int nz  = DIM == 3 ? nq2 : 1;
+    const int nqt = nq0 * nq1 * nz;  // points per element
+    const int nmt = nm0 * nm1 * nm2; // modes per element
+    T *A = lds, *B = lds + sizeA;
+    const int tid = threadIdx.x;
+    for (uint64_t e = blockIdx.x; e < nelmt; e += gridDim.x)
+    {
+        const T *src = in + e * (uint64_t)nmt;
+        const T *wt  = w + e * (uint64_t)nqt;
+        T *dst       = out + e * (uint64_t)nmt;
+        if constexpr (DIM == 2)
+        {
+            for (int x = tid; x < nmt; x += NT)
+                A[x] = src[x];
+            __syncthreads();
+            // forward 0: w1[q][i] = sum_p in[q][p] * B0[p][i]
+            for (int x = tid; x < nm1 * nq0; x += NT)
+            {
+                const int i = x % nq0, q = x / nq0;
+                B[x] = dot_strided(A + q * nm0, 1, b0 + i, nq0, nm0);
+            }
+            __syncthreads();
+            // forward 1 and weight: v[j][i] = w[j][i] * sum_q w1[q][i] * B1[q][j]
+            for (int x = tid; x < nqt; x += NT)
+            {
+                const int i = x % nq0, j = x / nq0;
+                A[x] = dot_strided(B + i, nq0, b1 + j, nq1, nm1) * wt[x];
+            }
+            __syncthreads();
+            // transposed 1: t1[q'][i] = sum_j v[j][i] * B1[q'][j]
+            for (int x = tid; x < nm1 * nq0; x += NT)
+            {
+                const int i = x % nq0, q = x / nq0;
+                B[x] = dot_strided(A + i, nq0, b1 + q * nq1, 1, nq1);
+            }
+            __syncthreads();
+            // transposed 0: out[q'][p'] = sum_i t1[q'][i] * B0[p'][i]
+            for (int x = tid; x < nmt; x += NT)
+            {
+                const int p = x % nm0, q = x / nm0;
+                dst[x] = dot_strided(B + q * nq0, 1, b0 + p * nq0, 1, nq0);
+            }
+        }
+        else
+        {
+            const int n01 = nq0 * nq1;
+            for (int x = tid; x < nmt; x += NT)
+                B[x] = src[x];
+            __syncthreads();
+            // forward 0: w1[r][q][i] = sum_p in[r][q][p] * B0[p][i]
+            for (int x = tid; x < nq0 * nm1 * nm2; x += NT)
+            {
+                const int i = x % nq0, rq = x / nq0;
+                A[x] = dot_strided(B + rq * nm0, 1, b0 + i, nq0, nm0);
+            }
+            __syncthreads();
+            // forward 1: w2[r][j][i] = sum_q w1[r][q][i] * B1[q][j]
+            for (int x = tid; x < n01 * nm2; x += NT)
+            {
+                const int i = x % nq0, rj = x / nq0, j = rj % nq1, r = rj / nq1;
+                B[x] = dot_strided(A + r * nm1 * nq0 + i, nq0, b1 + j, nq1, nm1);
+            }
+            __syncthreads();
+            // forward 2 and weight: v[k][j][i] = w[k][j][i] * sum_r w2[r][j][i] * B2[r][k]
+            for (int x = tid; x < nqt; x += NT)
+            {
+                const int ji = x % n01, k = x / n01;
+                A[x] = dot_strided(B + ji, n01, b2 + k, nq2, nm2) * wt[x];
+            }
+            __syncthreads();
+            // transposed 2: t1[r'][j][i] = sum_k v[k][j][i] * B2[r'][k]
+            for (int x = tid; x < n01 * nm2; x += NT)
+            {
+                const int ji = x % n01, r = x / n01;
+                B[x] = dot_strided(A + ji, n01, b2 + r * nq2, 1, nq2);
+            }
+            __syncthreads();
+            // transposed 1: t2[r'][q'][i] = sum_j t1[r'][j][i] * B1[q'][j]
+            for (int x = tid; x < nq0 * nm1 * nm2; x += NT)
+            {
+                const int i = x % nq0, rq = x / nq0, q = rq % nm1, r = rq / nm1;
+                A[x] = dot_strided(B + r * n01 + i, nq0, b1 + q * nq1, 1, nq1);
+            }
+            __syncthreads();
+            // transposed 0: out[r'][q'][p'] = sum_i t2[r'][q'][i] * B0[p'][i]
+            for (int x = tid; x < nmt; x += NT)
+            {
+                const int p = x % nm0, rq = x / nm0;
+                dst[x] = dot_strided(A + rq * nq0, 1, b0 + p * nq0, 1, nq0);
+            }
+        }
+        __syncthreads(); // the next element overwrites the images
+    }
+}
+
+// region sizes in scalars: A the point image, B the larger of the images that alternate with it
+static void mass_regions(int dim, unsigned nq0, unsigned nq1, unsigned nq2, unsigned &sizeA, unsigned &sizeB)
+{
+    if (dim == 3)
+    {
+        sizeA = nq0 * nq1 * nq2;       // >= w1 (nq0 nm1 nm2), t2 (nq0 nm1 nm2)
+        sizeB = nq0 * nq1 * (nq2 - 1); // >= in (nm0 nm1 nm2); w2 and t1 have exactly this size
+    }
+    else
+    {
+        sizeA = nq0 * nq1;       // >= in (nm0 nm1)
+        sizeB = nq0 * (nq1 - 1); // w1 and t1
+    }
+}
+
+template <typename T, int DIM>
+static int launch_mass_generic(unsigned nq0, unsigned nq1, unsigned nq2, const T *b0, const T *b1, const T *b2,
+                               const T *w, const T *in, T *out, uint64_t nelmt, hipStream_t s)
+{
+    if (!mass_generic_built(DIM, nq0, nq1, nq2))
+        return SF_ENOTBUILT;
+    if (nelmt == 0)
+        return SF_OK;
+    unsigned sizeA, sizeB;
+    mass_regions(DIM, nq0, nq1, nq2, sizeA, sizeB);
+    const unsigned need = sizeA + sizeB;
+    const unsigned grid = nelmt < (1ull << 22) ? (unsigned)nelmt : (1u << 22);
+    if (need <= (unsigned)kMassSmallCap)
+        mass_generic_kernel<T, DIM, kMassSmallCap, 64>
+            <<<grid, 64, 0, s>>>(b0, b1, b2, w, in, out, nelmt, (int)nq0, (int)nq1, (int)nq2, (int)sizeA);
+    else
+        mass_generic_kernel<T, DIM, kMassLargeCap, 256>
+            <<<grid, 256, 0, s>>>(b0, b1, b2, w, in, out, nelmt, (int)nq0, (int)nq1, (int)nq2, (int)sizeA);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SF_OK : (int)e;
+}
+
+int launch_hex_mass_generic(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, const double *w, hipStream_t s)
+{
+    return launch_mass_generic<double, 3>(nq0, nq1, nq2, a.b0, a.b1, a.b2, w, a.in, a.out, a.nelmt, s);
+}
+int launch_hex_mass_generic_f32(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgsT<float> &a, const float *w,
+                                hipStream_t s)
+{
+    return launch_mass_generic<float, 3>(nq0, nq1, nq2, a.b0, a.b1, a.b2, w, a.in, a.out, a.nelmt, s);
+}
+int launch_quad_mass_generic(unsigned nq0, unsigned nq1, const QuadArgs &a, const double *w, hipStream_t s)
+{
+    return launch_mass_generic<double, 2>(nq0, nq1, 0, a.b0, a.b1, nullptr, w, a.in, a.out, a.nelmt, s);
+}
+int launch_quad_mass_generic_f32(unsigned nq0, unsigned nq1, const QuadArgsT<float> &a, const float *w, hipStream_t s)
+{
+    return launch_mass_generic<float, 2>(nq0, nq1, 0, a.b0, a.b1, nullptr, w, a.in, a.out, a.nelmt, s);
+}
+
+// within the extent bounds AND the two regions fit the large LDS class (true for every extent within the bounds:
+// 3D 16^3 needs 4096 + 3840, 2D 32^2 1024 + 992; derived all the same, not assumed)
+bool mass_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2)
+{
+    const unsigned mx = dim == 3 ? kMassMax3D : kMassMax2D;
+    if (nq0 < 2 || nq1 < 2 || (dim == 3 && nq2 < 2) || nq0 > mx || nq1 > mx || (dim == 3 && nq2 > mx))
+        return false;
+    unsigned sizeA, sizeB;
+    mass_regions(dim, nq0, nq1, dim == 3 ? nq2 : 0, sizeA, sizeB);
+    return sizeA + sizeB <= (unsigned)kMassLargeCap;
+}
+
+} // namespace sf

@@ -1,0 +1,379 @@
+// mass_wave.h -- the fused mass operator y_e = B^T diag(w_e) B x_e as wave-per-chunk kernels for gfx950.
+//
+//   3D: out[e][r'][q'][p'] = sum_kji B0[p'][i] B1[q'][j] B2[r'][k] * w[e][k][j][i] * (sum_rqp in[e][r][q][p] B0[p][i] B1[q][j] B2[r][k])
+//   2D: out[e][q'][p']     = sum_ji  B0[p'][i] B1[q'][j]           * w[e][j][i]    * (sum_qp  in[e][q][p]    B0[p][i] B1[q][j])
+//
+// BwdTrans (bwdtrans_wave.h), a pointwise weight and IProductWRTBase (iproduct_wave.h) in ONE kernel: the quadrature-space
+// image (nq^d values per element) never exists in HBM, and in 3D not even in LDS.  `in` and `out` hold nm^d modes per
+// element (p fastest, the BwdTrans input layout), `w` nq^d values per element (i fastest, the BwdTrans output layout).
+// Same bases (row-major nm x nq), same machinery as the two halves, reused by inclusion: one wavefront owns a chunk of
+// EC elements, no workgroup barrier, the chunk's input is fetched one chunk ahead (chunk_fetch / chunk_stage), every
+// sweep is "lane owns a pencil", the basis rows go through the SGPR ring of contract() / contract_dot(), and the nm^d
+// output image leaves through the slab as one flat 16-byte-per-lane stream (chunk_flush).
+//
+// Sweep order (it defines the rounding; every sum in ascending index, the first product a multiply, then FMAs):
+//   forward     p -> i (B0), q -> j (B1), r -> k (B2)        -- the BwdTrans order
+//   weight      one multiply per point
+//   transposed  k -> r' (B2), j -> q' (B1), i -> p' (B0)     -- the reverse of the forward order
+// After the last forward sweep lane t = (e, j, i) holds the k-pencil of its point column in registers; the weights are
+// multiplied in there and the first transposed sweep (k -> r') contracts the same registers: no LDS round trip at the
+// hand-over.  (2D: lane (e, i) holds the j-pencil; the first transposed sweep is j -> q'.)
+//
+// Weights: lane (e, j, i) loads w[e][k][j][i], k = 0 .. nq-1, straight from global memory into registers at the top of
+// the chunk, right after the input is staged (non-temporal: w is streamed once), so the latency hides behind the
+// forward sweeps.  Consecutive lanes read consecutive scalars (runs of nq^2 in 3D -- the whole wave at one element per
+// chunk -- and of nq in 2D), every line is fetched from HBM once.  `w` needs only scalar alignment and never touches
+// LDS.  Lanes without a point column (t >= P2) or whose element lies beyond the batch (e >= evalid, last chunk) issue
+// NO load: w ends where the batch ends.
+//
+// LDS per chunk, 3D: 6 images (input, two forward intermediates, two transposed intermediates, output) against the 8 of
+// the two separate kernels.  The slab is the maximum over them and never exceeds the IProductWRTBase slab of the order.
+#pragma once
+
+#include "iproduct_wave.h"
+
+namespace sf
+{
+
+template <int NQ, int EC, int DIM, typename T = double> struct MassGeom
+{
+    using F      = WaveGeom<NQ, EC, DIM, T>; // the forward half: input image and forward intermediates
+    using Scalar = T;
+    using Vec    = typename VecOf<T>::type;
+    static constexpr int VW  = VecOf<T>::W;
+    static constexpr int NM  = NQ - 1;
+    static constexpr int NQP = NQ | 1; // padded pencil stride of the transposed intermediates (odd number of scalars)
+    static constexpr int NMT = F::NMT, NQT = F::NQT;
+    // pencils per chunk of the transposed sweeps: 3D (e,j,i) -> (e,r',i) -> (e,r',q'); 2D (e,i) -> (e,q')
+    static constexpr int PT2 = (DIM == 3) ? EC * NM * NQ : 0;       // pencils over j, read by the sweep j -> q' (3D only)
+    static constexpr int PT1 = (DIM == 3) ? EC * NM * NM : EC * NM; // pencils over i, read by the sweep i -> p'
+    static constexpr int PASST2 = cdiv(PT2 > 0 ? PT2 : 1, kWave);
+    static constexpr int PASST1 = cdiv(PT1, kWave);
+    static constexpr int SLAB_T = CMax<PT2, PT1>::value * NQP;
+    static constexpr int OUT_DBL = EC * NMT; // scalars per chunk written to HBM
+    static constexpr int SLAB =
+        (CMax<CMax<F::SLAB0, SLAB_T>::value, OUT_DBL>::value + VW - 1) / VW * VW;
+    static_assert(SLAB <= IprodGeom<NQ, EC, DIM, T>::SLAB, "the fused slab stays within the IProductWRTBase slab");
+};
+
+// The view that the chunk I/O of bwdtrans_wave.h takes of the geometry: the input side of BwdTrans on both ends.
+template <class G> struct MassIo
+{
+    using F      = typename G::F;
+    using Scalar = typename G::Scalar;
+    using Vec    = typename G::Vec;
+    static constexpr int VW = G::VW, NM = G::NM, NMT = G::NMT, IN_DBL = F::IN_DBL, IN_STRIDE = F::IN_STRIDE;
+    static constexpr int NLD = F::NLD, OUT_DBL = G::OUT_DBL;
+    static constexpr bool VEC2 = F::VEC2, ALIGN_OK = F::ALIGN_OK;
+};
+
+template <int NQ, int EC, int DIM, int WPB, typename T = double> constexpr size_t mass_lds_bytes()
+{
+    return sizeof(T) * (size_t)WPB * MassGeom<NQ, EC, DIM, T>::SLAB;
+}
+
+// Weights of this lane's point columns: wv[s][n] = w[e][n][pl] for column t = s*64 + lane = (e, pl), pl < PLANE, the n
+// of one lane PLANE scalars apart.  Lanes with t >= NP or e >= evalid load nothing and hold zeros.
+template <int NQ, int NPASS, int NP, int PLANE, typename T>
+__device__ __forceinline__ void load_weights(T (&wv)[NPASS][NQ], const T *__restrict__ wc, int evalid, int lane)
+{
+#pragma unroll
+    for (int s = 0; s < NPASS; ++s)
+    {
+        const int t = s * kWave + lane;
+        const int e = t / PLANE, pl = t - e * PLANE;
+#pragma unroll
+        for (int n = 0; n < NQ; ++n)
+            wv[s][n] = T(0);
+        if (((s + 1) * kWave <= NP || t < NP) && e < evalid)
+        {
+            const T *src = wc + e * (NQ * PLANE) + pl;
+#pragma unroll
+            for (int n = 0; n < NQ; ++n)
+                wv[s][n] = __builtin_nontemporal_load(src + n * PLANE);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// 3D hex
+// ------------------------------------------------------------------------------------------------
+template <int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP, int OUTM, int MEMF = 0, typename T = double>
+__global__ __launch_bounds__(kWave *WPB, MINW) void hex_mass_wave_kernel(
+    const T *__restrict__ b0, const T *__restrict__ b1, const T *__restrict__ b2, const T *__restrict__ w,
+    const T *__restrict__ in, T *__restrict__ out, uint64_t nelmt)
+{
+    using G          = MassGeom<NQ, EC, 3, T>;
+    using F          = typename G::F;
+    using IO         = MassIo<G>;
+    constexpr int NM = G::NM, NMP = F::NMP, NQP = G::NQP, NM2 = NM * NM, NQ2 = NQ * NQ;
+    static_assert(OUTM == OUT_LDS, "the output (nm^3 per element) leaves through the LDS stream");
+    static_assert(KMAP > 0, "short-lived waves only");
+
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wib  = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    T *slab        = reinterpret_cast<T *>(lds_raw) + wib * G::SLAB;
+
+    const uint64_t nchunk = (nelmt + EC - 1) / EC;
+    const ChunkIter it    = chunk_iter<KMAP, WPB, ((MEMF >> 4) & 0xfff)>(nchunk, wib);
+    if (it.count == 0)
+        return;
+
+    constexpr bool AL = (MEMF & 4) && IO::ALIGN_OK;
+    typename IO::Vec st[IO::NLD];
+    chunk_fetch<IO, EC, !(MEMF & 1), AL>(st, in, it.first, nelmt, lane);
+
+    uint64_t c = it.first;
+    for (uint64_t n = 0; n < it.count; ++n, c += it.step)
+    {
+        const uint64_t left = nelmt - c * EC;
+        const int evalid    = left >= EC ? EC : (int)left;
+
+        chunk_stage<IO, AL>(st, slab, lane,
+                            IO::VEC2 ? (AL ? align_shift(in + c * IO::IN_DBL) : 0) : line_offset<T>(in + c * IO::IN_DBL));
+        wave_lds_fence();
+        // This chunk's weights, requested as soon as the staging registers are consumed: in flight under the three
+        // forward sweeps.  (Requested above chunk_stage they would be waited for there: behind the conditional loads
+        // hipcc no longer counts and emits s_waitcnt vmcnt(0) for the staging registers.)
+        T wv[F::PASS2][NQ];
+        load_weights<NQ, F::PASS2, F::P2, NQ2>(wv, w + c * (uint64_t)(EC * G::NQT), evalid, lane);
+        if (n + 1 < it.count)
+            chunk_fetch<IO, EC, !(MEMF & 1), AL>(st, in, c + it.step, nelmt, lane);
+
+        // ---- forward 0: w1[(e,i,r)][q] = sum_p in[(e,r,q)][p] * B0[p][i] ---------------------------
+        {
+            T u[F::PASS0][NM], acc[F::PASS0][NQ];
+            read_pencils<NM, F::PASS0, F::P0, F::IN_STRIDE>(u, slab, lane);
+            contract<NM, NQ, F::PASS0, BMODE>(u, acc, b0);
+            wave_lds_fence();
+#pragma unroll
+            for (int s = 0; s < F::PASS0; ++s)
+            {
+                const int t = s * kWave + lane;
+                if ((s + 1) * kWave <= F::P0 || t < F::P0)
+                {
+                    const int e = t / NM2, rq = t - e * NM2, r = rq / NM, q = rq - r * NM;
+                    T *dst = slab + (e * NQ * NM + r) * NMP + q;
+#pragma unroll
+                    for (int i = 0; i < NQ; ++i)
+                        dst[i * NM * NMP] = acc[s][i];
+                }
+            }
+            wave_lds_fence();
+        }
+        // ---- forward 1: w2[(e,j,i)][r] = sum_q w1[(e,i,r)][q] * B1[q][j] ---------------------------
+        {
+            T u[F::PASS1][NM], acc[F::PASS1][NQ];
+            read_pencils<NM, F::PASS1, F::P1, NMP>(u, slab, lane);
+            contract<NM, NQ, F::PASS1, BMODE>(u, acc, b1);
+            wave_lds_fence();
+#pragma unroll
+            for (int s = 0; s < F::PASS1; ++s)
+            {
+                const int t = s * kWave + lane;
+                if ((s + 1) * kWave <= F::P1 || t < F::P1)
+                {
+                    const int e = t / (NQ * NM), ir = t - e * (NQ * NM), i = ir / NM, r = ir - i * NM;
+                    T *dst = slab + (e * NQ2 + i) * NMP + r;
+#pragma unroll
+                    for (int j = 0; j < NQ; ++j)
+                        dst[j * NQ * NMP] = acc[s][j];
+                }
+            }
+            wave_lds_fence();
+        }
+        // ---- forward 2, weight, transposed 2: lane (e,j,i) keeps its k-pencil in registers ---------
+        //      v[k] = w[e][k][j][i] * sum_r w2[(e,j,i)][r] * B2[r][k];  t2[(e,r',i)][j] = sum_k v[k] * B2[r'][k]
+        {
+            T u[F::PASS2][NM], v[F::PASS2][NQ], acc[F::PASS2][NM];
+            read_pencils<NM, F::PASS2, F::P2, NMP>(u, slab, lane);
+            contract<NM, NQ, F::PASS2, BMODE>(u, v, b2);
+#pragma unroll
+            for (int s = 0; s < F::PASS2; ++s)
+#pragma unroll
+                for (int k = 0; k < NQ; ++k)
+                    v[s][k] *= wv[s][k];
+            contract_dot<NQ, NM, F::PASS2, BMODE>(v, acc, b2);
+            wave_lds_fence();
+#pragma unroll
+            for (int s = 0; s < F::PASS2; ++s)
+            {
+                const int t = s * kWave + lane;
+                if ((s + 1) * kWave <= F::P2 || t < F::P2)
+                {
+                    const int e = t / NQ2, ji = t - e * NQ2, j = ji / NQ, i = ji - j * NQ;
+                    T *dst = slab + (e * NM * NQ + i) * NQP + j;
+#pragma unroll
+                    for (int r = 0; r < NM; ++r)
+                        dst[r * NQ * NQP] = acc[s][r];
+                }
+            }
+            wave_lds_fence();
+        }
+        // ---- transposed 1: t1[(e,r',q')][i] = sum_j t2[(e,r',i)][j] * B1[q'][j] --------------------
+        {
+            T u[G::PASST2][NQ], acc[G::PASST2][NM];
+            read_pencils<NQ, G::PASST2, G::PT2, NQP>(u, slab, lane);
+            contract_dot<NQ, NM, G::PASST2, BMODE>(u, acc, b1);
+            wave_lds_fence();
+#pragma unroll
+            for (int s = 0; s < G::PASST2; ++s)
+            {
+                const int t = s * kWave + lane;
+                if ((s + 1) * kWave <= G::PT2 || t < G::PT2)
+                {
+                    const int er = t / NQ, i = t - er * NQ; // er = e*NM + r'
+                    T *dst = slab + er * NM * NQP + i;
+#pragma unroll
+                    for (int q = 0; q < NM; ++q)
+                        dst[q * NQP] = acc[s][q];
+                }
+            }
+            wave_lds_fence();
+        }
+        // ---- transposed 0: out[e][r'][q'][p'] = sum_i t1[(e,r',q')][i] * B0[p'][i] -----------------
+        {
+            T u[G::PASST1][NQ], acc[G::PASST1][NM];
+            read_pencils<NQ, G::PASST1, G::PT1, NQP>(u, slab, lane);
+            contract_dot<NQ, NM, G::PASST1, BMODE>(u, acc, b0);
+            wave_lds_fence();
+#pragma unroll
+            for (int s = 0; s < G::PASST1; ++s)
+            {
+                const int t = s * kWave + lane;
+                if ((s + 1) * kWave <= G::PT1 || t < G::PT1)
+                {
+                    T *dst = slab + t * NM; // t = (e*NM + r')*NM + q'
+#pragma unroll
+                    for (int p = 0; p < NM; ++p)
+                        dst[p] = acc[s][p];
+                }
+            }
+            wave_lds_fence();
+            chunk_flush<IO, !(MEMF & 2), (MEMF & 8) != 0>(slab, out + c * (uint64_t)G::OUT_DBL, evalid * G::NMT, lane);
+            wave_lds_fence(); // slab is rewritten by the next chunk's staging
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// 2D quad
+// ------------------------------------------------------------------------------------------------
+template <int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP, int OUTM, int MEMF = 0, typename T = double>
+__global__ __launch_bounds__(kWave *WPB, MINW) void quad_mass_wave_kernel(
+    const T *__restrict__ b0, const T *__restrict__ b1, const T *__restrict__ w, const T *__restrict__ in,
+    T *__restrict__ out, uint64_t nelmt)
+{
+    using G          = MassGeom<NQ, EC, 2, T>;
+    using F          = typename G::F;
+    using IO         = MassIo<G>;
+    constexpr int NM = G::NM, NMP = F::NMP, NQP = G::NQP;
+    static_assert(OUTM == OUT_LDS, "the output (nm^2 per element) leaves through the LDS stream");
+    static_assert(KMAP > 0, "short-lived waves only");
+
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wib  = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    T *slab        = reinterpret_cast<T *>(lds_raw) + wib * G::SLAB;
+
+    const uint64_t nchunk = (nelmt + EC - 1) / EC;
+    const ChunkIter it    = chunk_iter<KMAP, WPB, ((MEMF >> 4) & 0xfff)>(nchunk, wib);
+    if (it.count == 0)
+        return;
+
+    constexpr bool AL = (MEMF & 4) && IO::ALIGN_OK;
+    typename IO::Vec st[IO::NLD];
+    chunk_fetch<IO, EC, !(MEMF & 1), AL>(st, in, it.first, nelmt, lane);
+
+    uint64_t c = it.first;
+    for (uint64_t n = 0; n < it.count; ++n, c += it.step)
+    {
+        const uint64_t left = nelmt - c * EC;
+        const int evalid    = left >= EC ? EC : (int)left;
+
+        chunk_stage<IO, AL>(st, slab, lane,
+                            IO::VEC2 ? (AL ? align_shift(in + c * IO::IN_DBL) : 0) : line_offset<T>(in + c * IO::IN_DBL));
+        wave_lds_fence();
+        // this chunk's weights (after the staging registers are consumed, see the 3D kernel): lane (e,i) takes
+        // w[e][j][i], j = 0 .. nq-1
+        T wv[F::PASS1][NQ];
+        load_weights<NQ, F::PASS1, F::P1, NQ>(wv, w + c * (uint64_t)(EC * G::NQT), evalid, lane);
+        if (n + 1 < it.count)
+            chunk_fetch<IO, EC, !(MEMF & 1), AL>(st, in, c + it.step, nelmt, lane);
+
+        // ---- forward 0: w1[(e,i)][q] = sum_p in[(e,q)][p] * B0[p][i] -------------------------------
+        {
+            T u[F::PASS0][NM], acc[F::PASS0][NQ];
+            read_pencils<NM, F::PASS0, F::P0, F::IN_STRIDE>(u, slab, lane);
+            contract<NM, NQ, F::PASS0, BMODE>(u, acc, b0);
+            wave_lds_fence();
+#pragma unroll
+            for (int s = 0; s < F::PASS0; ++s)
+            {
+                const int t = s * kWave + lane;
+                if ((s + 1) * kWave <= F::P0 || t < F::P0)
+                {
+                    const int e = t / NM, q = t - e * NM;
+                    T *dst = slab + e * NQ * NMP + q;
+#pragma unroll
+                    for (int i = 0; i < NQ; ++i)
+                        dst[i * NMP] = acc[s][i];
+                }
+            }
+            wave_lds_fence();
+        }
+        // ---- forward 1, weight, transposed 1: lane (e,i) keeps its j-pencil in registers -----------
+        //      v[j] = w[e][j][i] * sum_q w1[(e,i)][q] * B1[q][j];  t1[(e,q')][i] = sum_j v[j] * B1[q'][j]
+        {
+            T u[F::PASS1][NM], v[F::PASS1][NQ], acc[F::PASS1][NM];
+            read_pencils<NM, F::PASS1, F::P1, NMP>(u, slab, lane);
+            contract<NM, NQ, F::PASS1, BMODE>(u, v, b1);
+#pragma unroll
+            for (int s = 0; s < F::PASS1; ++s)
+#pragma unroll
+                for (int j = 0; j < NQ; ++j)
+                    v[s][j] *= wv[s][j];
+            contract_dot<NQ, NM, F::PASS1, BMODE>(v, acc, b1);
+            wave_lds_fence();
+#pragma unroll
+            for (int s = 0; s < F::PASS1; ++s)
+            {
+                const int t = s * kWave + lane;
+                if ((s + 1) * kWave <= F::P1 || t < F::P1)
+                {
+                    const int e = t / NQ, i = t - e * NQ;
+                    T *dst = slab + e * NM * NQP + i;
+#pragma unroll
+                    for (int q = 0; q < NM; ++q)
+                        dst[q * NQP] = acc[s][q];
+                }
+            }
+            wave_lds_fence();
+        }
+        // ---- transposed 0: out[e][q'][p'] = sum_i t1[(e,q')][i] * B0[p'][i] ------------------------
+        {
+            T u[G::PASST1][NQ], acc[G::PASST1][NM];
+            read_pencils<NQ, G::PASST1, G::PT1, NQP>(u, slab, lane);
+            contract_dot<NQ, NM, G::PASST1, BMODE>(u, acc, b0);
+            wave_lds_fence();
+#pragma unroll
+            for (int s = 0; s < G::PASST1; ++s)
+            {
+                const int t = s * kWave + lane;
+                if ((s + 1) * kWave <= G::PT1 || t < G::PT1)
+                {
+                    T *dst = slab + t * NM; // t = e*NM + q'
+#pragma unroll
+                    for (int p = 0; p < NM; ++p)
+                        dst[p] = acc[s][p];
+                }
+            }
+            wave_lds_fence();
+            chunk_flush<IO, !(MEMF & 2), (MEMF & 8) != 0>(slab, out + c * (uint64_t)G::OUT_DBL, evalid * G::NMT, lane);
+            wave_lds_fence();
+        }
+    }
+}
+
+} // namespace sf

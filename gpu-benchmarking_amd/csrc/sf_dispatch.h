@@ -75,6 +75,20 @@ int launch_hex_iprod_generic_f32(unsigned nq0, unsigned nq1, unsigned nq2, const
 int launch_quad_iprod_generic(unsigned nq0, unsigned nq1, const QuadArgs &a, hipStream_t s);
 int launch_quad_iprod_generic_f32(unsigned nq0, unsigned nq1, const QuadArgsT<float> &a, hipStream_t s);
 bool iprod_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
+// The fused mass operator B^T diag(w) B (mass.hip / mass_f32.hip: the wave kernels of mass_wave.h, SF_ENOTBUILT off their
+// table -- 3D isotropic nq 2..11, 2D 2..16; mass_generic.hip: any extents up to 16 per direction in 3D and 32 in 2D,
+// SF_ENOTBUILT beyond).  `w`: one weight per quadrature point per element; a.wsp is not used.
+int launch_hex_mass_wave_nq(unsigned nq, const HexArgs &a, const double *w, hipStream_t s);
+int launch_hex_mass_wave_f32_nq(unsigned nq, const HexArgsT<float> &a, const float *w, hipStream_t s);
+int launch_quad_mass_wave_nq(unsigned nq, const QuadArgs &a, const double *w, hipStream_t s);
+int launch_quad_mass_wave_f32_nq(unsigned nq, const QuadArgsT<float> &a, const float *w, hipStream_t s);
+bool mass_wave_built(int dim, unsigned nq);
+int launch_hex_mass_generic(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, const double *w, hipStream_t s);
+int launch_hex_mass_generic_f32(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgsT<float> &a, const float *w,
+                                hipStream_t s);
+int launch_quad_mass_generic(unsigned nq0, unsigned nq1, const QuadArgs &a, const double *w, hipStream_t s);
+int launch_quad_mass_generic_f32(unsigned nq0, unsigned nq1, const QuadArgsT<float> &a, const float *w, hipStream_t s);
+bool mass_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
 int sumsq_f32_blocking(const float *x, size_t n, double *result_host, hipStream_t s);
 int fill_sincos_f32(float *in, size_t nelmt, size_t nm_tot, hipStream_t s);
 int fill_basis_f32(float *b, size_t nm, size_t nq, hipStream_t s);

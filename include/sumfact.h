@@ -176,8 +176,10 @@ int sf_fill_random_f32(float *x, size_t n, uint64_t seed, uint64_t first_idx, vo
  * `in` holds nq0*nq1[*nq2] values per element at the quadrature points (i fastest), `out` nm0*nm1[*nm2] modes per
  * element (p fastest).  The bases are the BwdTrans bases, unchanged: basis[p*nq + i], row-major nm x nq.  Sweeps i -> p,
  * j -> q, k -> r, each sum in ascending index.  Quadrature weights of tensor-product form fold into the bases
- * (B_d'[p][i] = B_d[p][i] * w_d[i]), so the kernels carry no weight array.  Chain BwdTrans -> pointwise weight ->
- * IProductWRTBase for a mass or Helmholtz operator; this is also the gradient of BwdTrans with respect to its input.
+ * (B_d'[p][i] = B_d[p][i] * w_d[i]), so the kernels carry no weight array.  BwdTrans -> pointwise weight ->
+ * IProductWRTBase is a mass operator: sf_mass_* below runs that chain as ONE kernel (chain the three calls yourself
+ * only for what it does not cover, e.g. a Helmholtz operator); this is also the gradient of BwdTrans with respect to
+ * its input.
  * Variants: SF_VARIANT_AUTO (the wave kernel for the isotropic orders of its table -- 3D nq 2..11, 2D nq 2..16 -- when
  * in / out are 16-byte aligned, else GENERIC), SF_VARIANT_WAVE (SF_ENOTBUILT off that table, SF_EALIGN unless 16-byte
  * aligned), SF_VARIANT_GENERIC (one workgroup per element, any extents up to 16 per direction in 3D and 32 in 2D);
@@ -201,6 +203,51 @@ int sf_iproduct_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, 
                         void *stream);
 int sf_iproduct_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0,
                          const float *basis1, const float *in, float *out, void *stream);
+
+/*
+ * The fused mass operator y_e = B^T diag(w_e) B x_e: BwdTrans, a pointwise weight and IProductWRTBase in one kernel.
+ *   3D: out[e][r'][q'][p'] = sum_kji B0[p'][i] B1[q'][j] B2[r'][k] * w[e][k][j][i] * (sum_rqp in[e][r][q][p] B0[p][i] B1[q][j] B2[r][k])
+ *   2D: out[e][q'][p']     = sum_ji  B0[p'][i] B1[q'][j]           * w[e][j][i]    * (sum_qp  in[e][q][p]    B0[p][i] B1[q][j])
+ * `in` and `out` hold nm0*nm1[*nm2] modes per element (p fastest, the BwdTrans input layout); `w` holds nq0*nq1[*nq2]
+ * values per element (i fastest, the BwdTrans output layout): one weight per quadrature point per element -- Jacobian
+ * determinant times quadrature weights -- so deformed elements are covered.  The bases are the BwdTrans bases,
+ * unchanged.  The quadrature-space image never reaches HBM: per element the call moves 2 nm^d + nq^d scalars where the
+ * three-call chain moves 2 nm^d + 5 nq^d.
+ * Sweep order (it defines the rounding; every sum in ascending index): forward p -> i, q -> j, r -> k as BwdTrans, one
+ * multiply by w per point, then the transposed sweeps in REVERSE order, k -> r', j -> q', i -> p' (IProductWRTBase
+ * on its own sweeps i, j, k: the fused result and the three-call chain agree to rounding, not bit for bit).
+ * Routes: SF_VARIANT_AUTO runs the fused wave kernel for the isotropic orders of its table (3D nq 2..11, 2D nq 2..16,
+ * the IProductWRTBase table) when in / out are 16-byte aligned, else GENERIC; SF_VARIANT_WAVE returns SF_ENOTBUILT off
+ * that table and SF_EALIGN unless in / out are 16-byte aligned; SF_VARIANT_GENERIC (one workgroup per element, latency-
+ * bound) takes any extents up to 16 per direction in 3D and 32 in 2D -- 3D nq 12..16 and 2D nq 17..32 have no fused
+ * matrix-core kernel yet and take it; any other variant SF_ENOTBUILT, extents beyond those bounds SF_ENOTBUILT.  `w`
+ * and the bases need only scalar alignment on every route.
+ * Validation, before any HIP call, in this order: (1) an extent < 2 or a variant outside [0, SF_NUM_VARIANTS):
+ * SF_EINVAL; (2) nelmt == 0: SF_OK; (3) a null basis, w, in or out: SF_EINVAL; (4) any of them not scalar-aligned:
+ * SF_EALIGN; (5) `out` overlapping `in` or `w`, compared as byte ranges of their full sizes: SF_EINVAL; (6) extents
+ * beyond the fallback's bounds: SF_ENOTBUILT; (7) an unsupported variant: SF_ENOTBUILT.
+ * The operator is NOT in-place safe and overlap is refused, not undefined: the kernels read 16-byte words that straddle
+ * the neighbouring element, which another wave may already have overwritten.  `in` may overlap `w`: both are only read.
+ * No internal workspace and no allocation: every call is a single kernel node, capture-safe from the process's first
+ * call.
+ */
+int sf_mass_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                    const double *basis0, const double *basis1, const double *basis2,
+                    const double *w, const double *in, double *out, void *stream);
+int sf_mass_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                            const double *basis0, const double *basis1, const double *basis2,
+                            const double *w, const double *in, double *out, void *stream);
+int sf_mass_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                     const double *basis1, const double *w, const double *in, double *out, void *stream);
+int sf_mass_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt,
+                             const double *basis0, const double *basis1, const double *w,
+                             const double *in, double *out, void *stream);
+/* T = float (AUTO route; w / in / out / bases 4-byte aligned) */
+int sf_mass_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
+                    const float *basis1, const float *basis2, const float *w, const float *in,
+                    float *out, void *stream);
+int sf_mass_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0,
+                     const float *basis1, const float *w, const float *in, float *out, void *stream);
 
 /*
  * benchmark02: x[i] += y[i]  -- replaces add_vector<T,vl><<<>>>
