@@ -225,6 +225,77 @@ def mass_quad(nq, basis0, basis1, w, inp, out=None, variant="auto", stream=None)
     return _mass_call("mass_quad", nq, (basis0, basis1), w, inp, out, variant, stream)
 
 
+def _helmholtz_call(what, nq, bases, derivs, g, w, lam, inp, out, variant, stream):
+    """Shared body of helmholtz_hex / helmholtz_quad: sizes, dtypes and devices checked here (before any library call),
+    pointers, alignment and overlap in the C ABI."""
+    nq = tuple(int(x) for x in nq)
+    dim = len(nq)
+    nmt, nqt = 1, 1
+    for q in nq:
+        nmt, nqt = nmt * (q - 1), nqt * q
+    if nmt <= 0:
+        raise capi.SumfactError(capi.SF_EINVAL, what)
+    lam = float(lam)
+    nelmt = inp.numel() // nmt
+    if nelmt * nmt != inp.numel():
+        raise ValueError(f"{what}: in.numel() is not a multiple of the modes per element ({nmt})")
+    ncomp = dim * (dim + 1) // 2
+    if g.numel() != nelmt * ncomp * nqt:
+        raise ValueError(f"{what}: g has {g.numel()} values, nelmt * {ncomp} * points per element = {nelmt * ncomp * nqt}")
+    if w is None:
+        if lam != 0.0:
+            raise ValueError(f"{what}: w=None needs lam == 0")
+    elif w.numel() != nelmt * nqt:
+        raise ValueError(f"{what}: w has {w.numel()} values, nelmt * points per element = {nelmt * nqt}")
+    for name, t in (("g", g), ("w", w)) + tuple((f"deriv{d}", t) for d, t in enumerate(derivs)):
+        if t is None:
+            continue
+        if t.dtype != inp.dtype:
+            raise ValueError(f"{what}: {name} is {t.dtype}, in is {inp.dtype}")
+        if t.device != inp.device:
+            raise ValueError(f"{what}: {name} is on {t.device}, in is on {inp.device}")
+    for d, (t, q) in enumerate(zip(derivs, nq)):
+        if t.numel() != q * q:
+            raise ValueError(f"{what}: deriv{d} has {t.numel()} values, nq*nq = {q * q}")
+    if out is None:
+        out = torch.empty(nelmt * nmt, dtype=inp.dtype, device=inp.device)
+    elif out.numel() != nelmt * nmt:
+        raise ValueError(f"{what}: out has the wrong size")
+    _check_sizes(what, bases, nq, None, 0)
+    v = _variant(variant)
+    shape = "hex" if dim == 3 else "quad"
+    if inp.dtype == torch.float32:
+        if v != VARIANTS["auto"]:
+            raise ValueError(f"{what}: float32 has the AUTO route only")
+        fn, ptr, head = getattr(capi.lib(), f"sf_helmholtz_{shape}_f32"), _dev_f32, ()
+    else:
+        fn, ptr, head = getattr(capi.lib(), f"sf_helmholtz_{shape}_f64_variant"), _dev_f64, (v,)
+    with torch.cuda.device(inp.device):
+        rc = fn(*head, *nq, nelmt, *[ptr(b, f"basis{d}") for d, b in enumerate(bases)],
+                *[ptr(t, f"deriv{d}") for d, t in enumerate(derivs)], ptr(g, "g"),
+                ptr(w, "w") if w is not None else None, ctypes.c_double(lam), ptr(inp, "in"), ptr(out, "out"),
+                _stream(stream, inp.device))
+    capi.check(rc, what)
+    return out
+
+
+def helmholtz_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, g, w, lam, inp, out=None, variant="auto",
+                  stream=None):
+    """The fused Helmholtz operator y_e = B^T [lam diag(w_e) + sum_ab D_a^T diag(G_ab,e) D_b] B x_e in one kernel, on
+    inp's device.  The bases of bwdtrans_hex; deriv_d row-major nq_d x nq_d with (D_d u)[i] = sum_m deriv_d[i][m] u[m];
+    g[e][c][k][j][i] with c = 0..5 for (00, 01, 02, 11, 12, 22); w[e][k][j][i], or None with lam == 0 (the Laplacian);
+    inp and out hold nm0*nm1*nm2 modes per element.  out may not overlap inp, g or w.  float64 takes variant "auto",
+    "wave" or "generic"; float32 the AUTO route.  A plain function: no autograd."""
+    return _helmholtz_call("helmholtz_hex", nq, (basis0, basis1, basis2), (deriv0, deriv1, deriv2), g, w, lam, inp, out,
+                           variant, stream)
+
+
+def helmholtz_quad(nq, basis0, basis1, deriv0, deriv1, g, w, lam, inp, out=None, variant="auto", stream=None):
+    """The fused Helmholtz operator in 2D: g[e][c][j][i] with c = 0..2 for (00, 01, 11), w[e][j][i] or None with
+    lam == 0."""
+    return _helmholtz_call("helmholtz_quad", nq, (basis0, basis1), (deriv0, deriv1), g, w, lam, inp, out, variant, stream)
+
+
 class _BwdTrans(torch.autograd.Function):
     """AUTO BwdTrans forward; its input gradient is IProductWRTBase of the output gradient (the exact transpose)."""
 

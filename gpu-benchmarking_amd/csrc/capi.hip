@@ -1,7 +1,8 @@
 // capi.hip -- the extern "C" boundary of libsumfact.so (declared in include/sumfact.h).
 // Validation + dispatch only; kernels live in bwdtrans_hex.hip / bwdtrans_quad.hip /
 // bwdtrans_generic.hip / aux_kernels.hip, IProductWRTBase in iproduct.hip / iproduct_generic.hip, the fused mass
-// operator in mass.hip / mass_f32.hip / mass_generic.hip.
+// operator in mass.hip / mass_f32.hip / mass_generic.hip, the fused Helmholtz operator in helmholtz.hip /
+// helmholtz_f32.hip / helmholtz_generic.hip.
 #include "sf_dispatch.h"
 
 #include <cstdio>
@@ -170,6 +171,90 @@ static int mass(int variant, const unsigned (&nq)[3], size_t nelmt, const T *con
     if (variant == SF_VARIANT_AUTO && wave_ok && vec_ok)
         return mass_wave(nq[0], a, w, s);
     return mass_generic(nq, a, w, s);
+}
+
+// ---- the fused Helmholtz operator: one validation and routing for both dimensions and both scalar types ---------------
+static int helm_wave(unsigned nq, const HexArgs &a, const HelmArgsT<double> &x, hipStream_t s)
+{
+    return launch_hex_helmholtz_wave_nq(nq, a, x, s);
+}
+static int helm_wave(unsigned nq, const HexArgsT<float> &a, const HelmArgsT<float> &x, hipStream_t s)
+{
+    return launch_hex_helmholtz_wave_f32_nq(nq, a, x, s);
+}
+static int helm_wave(unsigned nq, const QuadArgs &a, const HelmArgsT<double> &x, hipStream_t s)
+{
+    return launch_quad_helmholtz_wave_nq(nq, a, x, s);
+}
+static int helm_wave(unsigned nq, const QuadArgsT<float> &a, const HelmArgsT<float> &x, hipStream_t s)
+{
+    return launch_quad_helmholtz_wave_f32_nq(nq, a, x, s);
+}
+static int helm_generic(const unsigned (&nq)[3], const HexArgs &a, const HelmArgsT<double> &x, hipStream_t s)
+{
+    return launch_hex_helmholtz_generic(nq[0], nq[1], nq[2], a, x, s);
+}
+static int helm_generic(const unsigned (&nq)[3], const HexArgsT<float> &a, const HelmArgsT<float> &x, hipStream_t s)
+{
+    return launch_hex_helmholtz_generic_f32(nq[0], nq[1], nq[2], a, x, s);
+}
+static int helm_generic(const unsigned (&nq)[3], const QuadArgs &a, const HelmArgsT<double> &x, hipStream_t s)
+{
+    return launch_quad_helmholtz_generic(nq[0], nq[1], a, x, s);
+}
+static int helm_generic(const unsigned (&nq)[3], const QuadArgsT<float> &a, const HelmArgsT<float> &x, hipStream_t s)
+{
+    return launch_quad_helmholtz_generic_f32(nq[0], nq[1], a, x, s);
+}
+
+// Validation before any HIP call, in the order documented in include/sumfact.h (that of sf_mass_*, extended to the
+// derivative matrices, g and lambda); `w` is looked at only when lambda != 0.  Then AUTO takes the wave kernel for an
+// isotropic order of its table when in / out are 16-byte aligned, and the any-extent kernel otherwise.
+template <int DIM, class Args, typename T>
+static int helmholtz(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *const (&d)[3],
+                     const T *g, const T *w, double lambda, const T *in, T *out, void *stream)
+{
+    if (nq[0] < 2 || nq[1] < 2 || (DIM == 3 && nq[2] < 2) || variant < 0 || variant >= SF_NUM_VARIANTS)
+        return SF_EINVAL;
+    if (nelmt == 0)
+        return SF_OK;
+    const bool has_w = lambda != 0.0; // false for NaN too, which is refused next
+    if (!b[0] || !b[1] || (DIM == 3 && !b[2]) || !d[0] || !d[1] || (DIM == 3 && !d[2]) || !g || !in || !out ||
+        (has_w && !w) || !(lambda - lambda == 0.0))
+        return SF_EINVAL;
+    if (!aligned(in, sizeof(T)) || !aligned(out, sizeof(T)) || !aligned(g, sizeof(T)) || (has_w && !aligned(w, sizeof(T))) ||
+        !aligned(b[0], sizeof(T)) || !aligned(b[1], sizeof(T)) || (DIM == 3 && !aligned(b[2], sizeof(T))) ||
+        !aligned(d[0], sizeof(T)) || !aligned(d[1], sizeof(T)) || (DIM == 3 && !aligned(d[2], sizeof(T))))
+        return SF_EALIGN;
+    // not in-place safe, as sf_mass_*
+    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
+    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
+    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
+    if (overlaps(out, modes_bytes, in, modes_bytes) || overlaps(out, modes_bytes, g, (DIM == 3 ? 6 : 3) * points_bytes) ||
+        (has_w && overlaps(out, modes_bytes, w, points_bytes)))
+        return SF_EINVAL;
+    if (!helmholtz_generic_built(DIM, nq[0], nq[1], nq[2]))
+        return SF_ENOTBUILT;
+    if (variant != SF_VARIANT_AUTO && variant != SF_VARIANT_WAVE && variant != SF_VARIANT_GENERIC)
+        return SF_ENOTBUILT;
+    const hipStream_t s = (hipStream_t)stream;
+    Args a{};
+    if constexpr (DIM == 3)
+        a = Args{b[0], b[1], b[2], in, nullptr, out, (uint64_t)nelmt};
+    else
+        a = Args{b[0], b[1], in, nullptr, out, (uint64_t)nelmt};
+    const HelmArgsT<T> x{d[0], d[1], d[2], g, has_w ? w : nullptr, (T)lambda}; // lambda is rounded to T here, once
+    const bool wave_ok = nq[0] == nq[1] && (DIM == 2 || nq[1] == nq[2]) && helmholtz_wave_built(DIM, nq[0]);
+    const bool vec_ok  = aligned(in, 16) && aligned(out, 16);
+    if (variant == SF_VARIANT_WAVE)
+    {
+        if (!wave_ok)
+            return SF_ENOTBUILT;
+        return vec_ok ? helm_wave(nq[0], a, x, s) : SF_EALIGN;
+    }
+    if (variant == SF_VARIANT_AUTO && wave_ok && vec_ok)
+        return helm_wave(nq[0], a, x, s);
+    return helm_generic(nq, a, x, s);
 }
 
 extern "C" {
@@ -520,6 +605,57 @@ int sf_mass_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basi
 {
     return mass<2, QuadArgsT<float>, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, w, in, out,
                                             stream);
+}
+
+// ---- the fused Helmholtz operator: BwdTrans, derivatives, metric, transposed derivatives, IProductWRTBase in one kernel -
+int sf_helmholtz_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
+                                 const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
+                                 const double *deriv2, const double *g, const double *w, double lambda, const double *in,
+                                 double *out, void *stream)
+{
+    return helmholtz<3, HexArgs, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
+                                         {deriv0, deriv1, deriv2}, g, w, lambda, in, out, stream);
+}
+
+int sf_helmholtz_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
+                         const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
+                         const double *deriv2, const double *g, const double *w, double lambda, const double *in,
+                         double *out, void *stream)
+{
+    return helmholtz<3, HexArgs, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
+                                         {deriv0, deriv1, deriv2}, g, w, lambda, in, out, stream);
+}
+
+int sf_helmholtz_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                                  const double *basis1, const double *deriv0, const double *deriv1, const double *g,
+                                  const double *w, double lambda, const double *in, double *out, void *stream)
+{
+    return helmholtz<2, QuadArgs, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
+                                          {deriv0, deriv1, nullptr}, g, w, lambda, in, out, stream);
+}
+
+int sf_helmholtz_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                          const double *deriv0, const double *deriv1, const double *g, const double *w, double lambda,
+                          const double *in, double *out, void *stream)
+{
+    return helmholtz<2, QuadArgs, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
+                                          {deriv0, deriv1, nullptr}, g, w, lambda, in, out, stream);
+}
+
+int sf_helmholtz_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
+                         const float *basis2, const float *deriv0, const float *deriv1, const float *deriv2,
+                         const float *g, const float *w, double lambda, const float *in, float *out, void *stream)
+{
+    return helmholtz<3, HexArgsT<float>, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
+                                                {deriv0, deriv1, deriv2}, g, w, lambda, in, out, stream);
+}
+
+int sf_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
+                          const float *deriv0, const float *deriv1, const float *g, const float *w, double lambda,
+                          const float *in, float *out, void *stream)
+{
+    return helmholtz<2, QuadArgsT<float>, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
+                                                 {deriv0, deriv1, nullptr}, g, w, lambda, in, out, stream);
 }
 
 int sf_sumsq_f32(const float *x, size_t n, double *result_host, void *stream)

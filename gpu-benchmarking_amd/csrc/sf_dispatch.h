@@ -89,6 +89,30 @@ int launch_hex_mass_generic_f32(unsigned nq0, unsigned nq1, unsigned nq2, const 
 int launch_quad_mass_generic(unsigned nq0, unsigned nq1, const QuadArgs &a, const double *w, hipStream_t s);
 int launch_quad_mass_generic_f32(unsigned nq0, unsigned nq1, const QuadArgsT<float> &a, const float *w, hipStream_t s);
 bool mass_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
+// The fused Helmholtz operator B^T [lambda diag(w) + sum_ab D_a^T diag(G_ab) D_b] B (helmholtz.hip / helmholtz_f32.hip:
+// the wave kernels of helmholtz_wave.h, SF_ENOTBUILT off their table -- 3D isotropic nq 2..8, 2D 2..16;
+// helmholtz_generic.hip: any extents up to 12 per direction in 3D and 32 in 2D, SF_ENOTBUILT beyond).  What the operator
+// takes beyond the BwdTrans arguments: the derivative matrices, the metric planes, the mass weight (null: lambda == 0,
+// never read) and lambda in the scalar type.
+template <typename T> struct HelmArgsT
+{
+    const T *d0, *d1, *d2, *g, *w;
+    T lam;
+};
+int launch_hex_helmholtz_wave_nq(unsigned nq, const HexArgs &a, const HelmArgsT<double> &x, hipStream_t s);
+int launch_hex_helmholtz_wave_f32_nq(unsigned nq, const HexArgsT<float> &a, const HelmArgsT<float> &x, hipStream_t s);
+int launch_quad_helmholtz_wave_nq(unsigned nq, const QuadArgs &a, const HelmArgsT<double> &x, hipStream_t s);
+int launch_quad_helmholtz_wave_f32_nq(unsigned nq, const QuadArgsT<float> &a, const HelmArgsT<float> &x, hipStream_t s);
+bool helmholtz_wave_built(int dim, unsigned nq);
+int launch_hex_helmholtz_generic(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, const HelmArgsT<double> &x,
+                                 hipStream_t s);
+int launch_hex_helmholtz_generic_f32(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgsT<float> &a,
+                                     const HelmArgsT<float> &x, hipStream_t s);
+int launch_quad_helmholtz_generic(unsigned nq0, unsigned nq1, const QuadArgs &a, const HelmArgsT<double> &x,
+                                  hipStream_t s);
+int launch_quad_helmholtz_generic_f32(unsigned nq0, unsigned nq1, const QuadArgsT<float> &a, const HelmArgsT<float> &x,
+                                      hipStream_t s);
+bool helmholtz_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
 int sumsq_f32_blocking(const float *x, size_t n, double *result_host, hipStream_t s);
 int fill_sincos_f32(float *in, size_t nelmt, size_t nm_tot, hipStream_t s);
 int fill_basis_f32(float *b, size_t nm, size_t nq, hipStream_t s);

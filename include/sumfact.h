@@ -177,8 +177,8 @@ int sf_fill_random_f32(float *x, size_t n, uint64_t seed, uint64_t first_idx, vo
  * element (p fastest).  The bases are the BwdTrans bases, unchanged: basis[p*nq + i], row-major nm x nq.  Sweeps i -> p,
  * j -> q, k -> r, each sum in ascending index.  Quadrature weights of tensor-product form fold into the bases
  * (B_d'[p][i] = B_d[p][i] * w_d[i]), so the kernels carry no weight array.  BwdTrans -> pointwise weight ->
- * IProductWRTBase is a mass operator: sf_mass_* below runs that chain as ONE kernel (chain the three calls yourself
- * only for what it does not cover, e.g. a Helmholtz operator); this is also the gradient of BwdTrans with respect to
+ * IProductWRTBase is a mass operator: sf_mass_* below runs that chain as ONE kernel (and sf_helmholtz_* the
+ * Helmholtz operator; chain the three calls yourself only for what neither covers); this is also the gradient of BwdTrans with respect to
  * its input.
  * Variants: SF_VARIANT_AUTO (the wave kernel for the isotropic orders of its table -- 3D nq 2..11, 2D nq 2..16 -- when
  * in / out are 16-byte aligned, else GENERIC), SF_VARIANT_WAVE (SF_ENOTBUILT off that table, SF_EALIGN unless 16-byte
@@ -248,6 +248,69 @@ int sf_mass_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, cons
                     float *out, void *stream);
 int sf_mass_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0,
                      const float *basis1, const float *w, const float *in, float *out, void *stream);
+
+/*
+ * The fused Helmholtz operator, what a Poisson / Helmholtz / implicit-diffusion solve applies every Krylov iteration:
+ *   y_e = B^T [ lambda diag(w_e) + sum_a sum_b D_a^T diag(G_ab,e) D_b ] B x_e
+ * BwdTrans, the collocation derivatives, the per-point metric contraction, the transposed derivatives and
+ * IProductWRTBase in ONE kernel; lambda == 0 is the stiffness (Laplacian) operator, g == 0 and lambda == 1 the mass
+ * operator of sf_mass_*.  Per element the call moves 2 nm^d + (1 + d(d+1)/2) nq^d scalars; no quadrature-space image
+ * reaches HBM.
+ * Layout: `in` and `out` hold nm0*nm1[*nm2] modes per element (p fastest, the BwdTrans input layout).  basis_d: the
+ * BwdTrans bases, unchanged.  deriv_d: row-major nq_d x nq_d, deriv_d[i*nq_d + m] = l'_m(xi_i), the derivative of the
+ * m-th Lagrange polynomial of the quadrature points at point i, so (D_d u)[i] = sum_m deriv_d[i*nq_d + m] u[m].
+ * w[e][k][j][i]: one mass weight per point, as in sf_mass_*.  g[e][c][k][j][i]: the symmetric metric tensor per point
+ * (Jacobian determinant x quadrature weight x grad xi_a . grad xi_b) as component planes per element, each plane laid
+ * out like w.  Component order: 3D c = 0..5 for (a,b) = (00, 01, 02, 11, 12, 22), 2D c = 0..2 for (00, 01, 11);
+ * G_ba = G_ab is not stored.  g may be indefinite; the operator is symmetric for any g.
+ * If lambda == 0, `w` may be NULL: it is then never read (nor validated), and the operator moves one plane less.
+ * Summation order (it defines the rounding; every sum in ascending index, the first product a multiply, then FMAs):
+ *   1. forward sweeps p -> i, q -> j, r -> k, as BwdTrans:                  u
+ *   2. du_a = D_a u for each direction a
+ *   3. f_a = sum_b G_ab du_b, b ascending
+ *   4. v = ((lambda w) u + D_0^T f_0) + D_1^T f_1 [+ D_2^T f_2]            (lambda == 0: the first term is 0)
+ *   5. transposed sweeps k -> r', j -> q', i -> p', as sf_mass_*
+ * lambda is a double in every entry point; the f32 entry points round it to float once, before the launch.
+ * Routes: SF_VARIANT_AUTO runs the fused wave kernel for the isotropic orders of its table (3D nq 2..8, 2D nq 2..16)
+ * when in / out are 16-byte aligned, else GENERIC; SF_VARIANT_WAVE returns SF_ENOTBUILT off that table and SF_EALIGN
+ * unless in / out are 16-byte aligned; SF_VARIANT_GENERIC (one workgroup per element, latency-bound) takes any extents
+ * up to 12 per direction in 3D and 32 in 2D -- 3D nq 9..11 are NOT in the wave table and take it, as do all anisotropic
+ * shapes; any other variant SF_ENOTBUILT, extents beyond those bounds SF_ENOTBUILT.  g, w, the bases and the derivative
+ * matrices need only scalar alignment on every route.
+ * Validation, before any HIP call, in this order: (1) an extent < 2 or a variant outside [0, SF_NUM_VARIANTS):
+ * SF_EINVAL; (2) nelmt == 0: SF_OK; (3) a null basis, deriv, g, in or out, a null w with lambda != 0, or a lambda that
+ * is not finite: SF_EINVAL; (4) any of them (w only if lambda != 0) not scalar-aligned: SF_EALIGN; (5) `out` overlapping
+ * `in`, `g` or (if lambda != 0) `w`, compared as byte ranges of their full sizes: SF_EINVAL; (6) extents beyond the
+ * fallback's bounds: SF_ENOTBUILT; (7) an unsupported variant: SF_ENOTBUILT.
+ * NOT in-place safe, for the reason given under sf_mass_*; the inputs may overlap each other (all are only read).
+ * No internal workspace and no allocation: every call is a single kernel node, capture-safe from the process's first
+ * call.
+ */
+int sf_helmholtz_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                         const double *basis0, const double *basis1, const double *basis2,
+                         const double *deriv0, const double *deriv1, const double *deriv2,
+                         const double *g, const double *w, double lambda,
+                         const double *in, double *out, void *stream);
+int sf_helmholtz_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                                 const double *basis0, const double *basis1, const double *basis2,
+                                 const double *deriv0, const double *deriv1, const double *deriv2,
+                                 const double *g, const double *w, double lambda,
+                                 const double *in, double *out, void *stream);
+int sf_helmholtz_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                          const double *deriv0, const double *deriv1, const double *g, const double *w,
+                          double lambda, const double *in, double *out, void *stream);
+int sf_helmholtz_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                                  const double *basis1, const double *deriv0, const double *deriv1,
+                                  const double *g, const double *w, double lambda, const double *in,
+                                  double *out, void *stream);
+/* T = float (AUTO route; g / w / in / out / bases / derivative matrices 4-byte aligned; lambda stays a double) */
+int sf_helmholtz_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
+                         const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
+                         const float *deriv2, const float *g, const float *w, double lambda, const float *in,
+                         float *out, void *stream);
+int sf_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
+                          const float *deriv0, const float *deriv1, const float *g, const float *w,
+                          double lambda, const float *in, float *out, void *stream);
 
 /*
  * benchmark02: x[i] += y[i]  -- replaces add_vector<T,vl><<<>>>
