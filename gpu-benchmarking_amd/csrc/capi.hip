@@ -7,6 +7,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 
 
 using namespace sf;
@@ -16,112 +17,6 @@ static inline bool aligned(const void *p, size_t a)
     return ((uintptr_t)p & (a - 1)) == 0;
 }
 
-// ---- IProductWRTBase: one validation and routing for both dimensions and both scalar types ---------------------------
-static int iprod_wave(unsigned nq, const HexArgs &a, hipStream_t s)
-{
-    return launch_hex_iprod_wave_nq(nq, a, s);
-}
-static int iprod_wave(unsigned nq, const HexArgsT<float> &a, hipStream_t s)
-{
-    return launch_hex_iprod_wave_f32_nq(nq, a, s);
-}
-static int iprod_wave(unsigned nq, const QuadArgs &a, hipStream_t s)
-{
-    return launch_quad_iprod_wave_nq(nq, a, s);
-}
-static int iprod_wave(unsigned nq, const QuadArgsT<float> &a, hipStream_t s)
-{
-    return launch_quad_iprod_wave_f32_nq(nq, a, s);
-}
-static int iprod_generic(const unsigned (&nq)[3], const HexArgs &a, hipStream_t s)
-{
-    return launch_hex_iprod_generic(nq[0], nq[1], nq[2], a, s);
-}
-static int iprod_generic(const unsigned (&nq)[3], const HexArgsT<float> &a, hipStream_t s)
-{
-    return launch_hex_iprod_generic_f32(nq[0], nq[1], nq[2], a, s);
-}
-static int iprod_generic(const unsigned (&nq)[3], const QuadArgs &a, hipStream_t s)
-{
-    return launch_quad_iprod_generic(nq[0], nq[1], a, s);
-}
-static int iprod_generic(const unsigned (&nq)[3], const QuadArgsT<float> &a, hipStream_t s)
-{
-    return launch_quad_iprod_generic_f32(nq[0], nq[1], a, s);
-}
-
-// Validation before any HIP call, in the order of sf_bwdtrans_*; then AUTO takes the wave kernel for an isotropic order
-// of its table when in / out are 16-byte aligned, and the any-extent kernel otherwise.
-template <int DIM, class Args, typename T>
-static int iprod(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *in, T *out,
-                 void *stream)
-{
-    if (nq[0] < 2 || nq[1] < 2 || (DIM == 3 && nq[2] < 2) || variant < 0 || variant >= SF_NUM_VARIANTS)
-        return SF_EINVAL;
-    if (nelmt == 0)
-        return SF_OK;
-    if (!b[0] || !b[1] || (DIM == 3 && !b[2]) || !in || !out)
-        return SF_EINVAL;
-    if (!aligned(in, sizeof(T)) || !aligned(out, sizeof(T)) || !aligned(b[0], sizeof(T)) || !aligned(b[1], sizeof(T)) ||
-        (DIM == 3 && !aligned(b[2], sizeof(T))))
-        return SF_EALIGN;
-    if (!iprod_generic_built(DIM, nq[0], nq[1], nq[2]))
-        return SF_ENOTBUILT;
-    if (variant != SF_VARIANT_AUTO && variant != SF_VARIANT_WAVE && variant != SF_VARIANT_GENERIC)
-        return SF_ENOTBUILT;
-    const hipStream_t s = (hipStream_t)stream;
-    Args a{};
-    if constexpr (DIM == 3)
-        a = Args{b[0], b[1], b[2], in, nullptr, out, (uint64_t)nelmt};
-    else
-        a = Args{b[0], b[1], in, nullptr, out, (uint64_t)nelmt};
-    const bool wave_ok = nq[0] == nq[1] && (DIM == 2 || nq[1] == nq[2]) && iprod_wave_built(DIM, nq[0]);
-    const bool vec_ok  = aligned(in, 16) && aligned(out, 16);
-    if (variant == SF_VARIANT_WAVE)
-    {
-        if (!wave_ok)
-            return SF_ENOTBUILT;
-        return vec_ok ? iprod_wave(nq[0], a, s) : SF_EALIGN;
-    }
-    if (variant == SF_VARIANT_AUTO && wave_ok && vec_ok)
-        return iprod_wave(nq[0], a, s);
-    return iprod_generic(nq, a, s);
-}
-
-// ---- the fused mass operator B^T diag(w) B: one validation and routing for both dimensions and both scalar types ----
-static int mass_wave(unsigned nq, const HexArgs &a, const double *w, hipStream_t s)
-{
-    return launch_hex_mass_wave_nq(nq, a, w, s);
-}
-static int mass_wave(unsigned nq, const HexArgsT<float> &a, const float *w, hipStream_t s)
-{
-    return launch_hex_mass_wave_f32_nq(nq, a, w, s);
-}
-static int mass_wave(unsigned nq, const QuadArgs &a, const double *w, hipStream_t s)
-{
-    return launch_quad_mass_wave_nq(nq, a, w, s);
-}
-static int mass_wave(unsigned nq, const QuadArgsT<float> &a, const float *w, hipStream_t s)
-{
-    return launch_quad_mass_wave_f32_nq(nq, a, w, s);
-}
-static int mass_generic(const unsigned (&nq)[3], const HexArgs &a, const double *w, hipStream_t s)
-{
-    return launch_hex_mass_generic(nq[0], nq[1], nq[2], a, w, s);
-}
-static int mass_generic(const unsigned (&nq)[3], const HexArgsT<float> &a, const float *w, hipStream_t s)
-{
-    return launch_hex_mass_generic_f32(nq[0], nq[1], nq[2], a, w, s);
-}
-static int mass_generic(const unsigned (&nq)[3], const QuadArgs &a, const double *w, hipStream_t s)
-{
-    return launch_quad_mass_generic(nq[0], nq[1], a, w, s);
-}
-static int mass_generic(const unsigned (&nq)[3], const QuadArgsT<float> &a, const float *w, hipStream_t s)
-{
-    return launch_quad_mass_generic_f32(nq[0], nq[1], a, w, s);
-}
-
 // byte ranges [p, p + np) and [q, q + nq) share a byte
 static inline bool overlaps(const void *p, size_t np, const void *q, size_t nq)
 {
@@ -129,103 +24,117 @@ static inline bool overlaps(const void *p, size_t np, const void *q, size_t nq)
     return a < b + nq && b < a + np;
 }
 
-// Validation before any HIP call, in the order documented in include/sumfact.h; then AUTO takes the wave kernel for an
-// isotropic order of its table when in / out are 16-byte aligned, and the any-extent kernel otherwise.
-template <int DIM, class Args, typename T>
-static int mass(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *w, const T *in,
-                T *out, void *stream)
+// Steps (1)-(4) of the validation order documented in include/sumfact.h, before any HIP call: the extents / variant range
+// (SF_EINVAL), an empty batch (SF_OK), a null among `ptrs` or a refused value (SF_EINVAL), a pointer of `ptrs` that is
+// not `align`-aligned (SF_EALIGN).  kProceed: none of these, the caller goes on.  A pointer the call does not take (the
+// third basis in 2D, a weight that is never read) is passed as one that it does.
+constexpr int kProceed = 1 << 30; // neither an SF_* code nor a hipError_t
+static int validate(bool range_ok, size_t nelmt, std::initializer_list<const void *> ptrs, size_t align,
+                    bool values_ok = true)
 {
-    if (nq[0] < 2 || nq[1] < 2 || (DIM == 3 && nq[2] < 2) || variant < 0 || variant >= SF_NUM_VARIANTS)
+    if (!range_ok)
         return SF_EINVAL;
     if (nelmt == 0)
         return SF_OK;
-    if (!b[0] || !b[1] || (DIM == 3 && !b[2]) || !w || !in || !out)
+    for (const void *p : ptrs)
+        if (!p)
+            return SF_EINVAL;
+    if (!values_ok)
         return SF_EINVAL;
-    if (!aligned(in, sizeof(T)) || !aligned(out, sizeof(T)) || !aligned(w, sizeof(T)) || !aligned(b[0], sizeof(T)) ||
-        !aligned(b[1], sizeof(T)) || (DIM == 3 && !aligned(b[2], sizeof(T))))
-        return SF_EALIGN;
+    for (const void *p : ptrs)
+        if (!aligned(p, align))
+            return SF_EALIGN;
+    return kProceed;
+}
+
+template <int DIM> static bool range_ok(int variant, const unsigned (&nq)[3])
+{
+    return nq[0] >= 2 && nq[1] >= 2 && (DIM == 2 || nq[2] >= 2) && variant >= 0 && variant < SF_NUM_VARIANTS;
+}
+
+template <int DIM, typename T>
+static ArgsT<DIM, T> make_args(const T *const (&b)[3], const T *in, T *out, size_t nelmt)
+{
+    if constexpr (DIM == 3)
+        return {b[0], b[1], b[2], in, nullptr, out, (uint64_t)nelmt};
+    else
+        return {b[0], b[1], in, nullptr, out, (uint64_t)nelmt};
+}
+
+// The shared tail of sf_iproduct_*, sf_mass_* and sf_helmholtz_*: AUTO takes the wave kernel for an isotropic order of
+// its table (`wave_built`) when in / out are 16-byte aligned, and the any-extent kernel otherwise.
+template <int DIM, class Wave, class Generic>
+static int route(int variant, const unsigned (&nq)[3], bool generic_built, bool wave_built, const void *in,
+                 const void *out, Wave wave, Generic generic)
+{
+    if (!generic_built)
+        return SF_ENOTBUILT;
+    if (variant != SF_VARIANT_AUTO && variant != SF_VARIANT_WAVE && variant != SF_VARIANT_GENERIC)
+        return SF_ENOTBUILT;
+    const bool wave_ok = nq[0] == nq[1] && (DIM == 2 || nq[1] == nq[2]) && wave_built;
+    const bool vec_ok  = aligned(in, 16) && aligned(out, 16);
+    if (variant == SF_VARIANT_WAVE)
+    {
+        if (!wave_ok)
+            return SF_ENOTBUILT;
+        return vec_ok ? wave() : SF_EALIGN;
+    }
+    if (variant == SF_VARIANT_AUTO && wave_ok && vec_ok)
+        return wave();
+    return generic();
+}
+
+// ---- IProductWRTBase: one validation and routing for both dimensions and both scalar types ---------------------------
+template <int DIM, typename T>
+static int iprod(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *in, T *out,
+                 void *stream)
+{
+    const int rc = validate(range_ok<DIM>(variant, nq), nelmt, {b[0], b[1], DIM == 3 ? b[2] : b[0], in, out}, sizeof(T));
+    if (rc != kProceed)
+        return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    const auto a        = make_args<DIM, T>(b, in, out, nelmt);
+    return route<DIM>(
+        variant, nq, iprod_generic_built(DIM, nq[0], nq[1], nq[2]), iprod_wave_built(DIM, nq[0]), in, out,
+        [&] { return launch_iprod_wave<DIM, T>(nq[0], a, s); }, [&] { return launch_iprod_generic<DIM, T>(nq, a, s); });
+}
+
+// ---- the fused mass operator B^T diag(w) B: one validation and routing for both dimensions and both scalar types ----
+template <int DIM, typename T>
+static int mass(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *w, const T *in,
+                T *out, void *stream)
+{
+    const int rc =
+        validate(range_ok<DIM>(variant, nq), nelmt, {b[0], b[1], DIM == 3 ? b[2] : b[0], w, in, out}, sizeof(T));
+    if (rc != kProceed)
+        return rc;
     // not in-place safe (the word-grid loads of a chunk read 16-byte words that straddle the neighbouring element)
     const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
     const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
     const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
     if (overlaps(out, modes_bytes, in, modes_bytes) || overlaps(out, modes_bytes, w, points_bytes))
         return SF_EINVAL;
-    if (!mass_generic_built(DIM, nq[0], nq[1], nq[2]))
-        return SF_ENOTBUILT;
-    if (variant != SF_VARIANT_AUTO && variant != SF_VARIANT_WAVE && variant != SF_VARIANT_GENERIC)
-        return SF_ENOTBUILT;
     const hipStream_t s = (hipStream_t)stream;
-    Args a{};
-    if constexpr (DIM == 3)
-        a = Args{b[0], b[1], b[2], in, nullptr, out, (uint64_t)nelmt};
-    else
-        a = Args{b[0], b[1], in, nullptr, out, (uint64_t)nelmt};
-    const bool wave_ok = nq[0] == nq[1] && (DIM == 2 || nq[1] == nq[2]) && mass_wave_built(DIM, nq[0]);
-    const bool vec_ok  = aligned(in, 16) && aligned(out, 16);
-    if (variant == SF_VARIANT_WAVE)
-    {
-        if (!wave_ok)
-            return SF_ENOTBUILT;
-        return vec_ok ? mass_wave(nq[0], a, w, s) : SF_EALIGN;
-    }
-    if (variant == SF_VARIANT_AUTO && wave_ok && vec_ok)
-        return mass_wave(nq[0], a, w, s);
-    return mass_generic(nq, a, w, s);
+    const auto a        = make_args<DIM, T>(b, in, out, nelmt);
+    return route<DIM>(
+        variant, nq, mass_generic_built(DIM, nq[0], nq[1], nq[2]), mass_wave_built(DIM, nq[0]), in, out,
+        [&] { return launch_mass_wave<DIM, T>(nq[0], a, w, s); },
+        [&] { return launch_mass_generic<DIM, T>(nq, a, w, s); });
 }
 
 // ---- the fused Helmholtz operator: one validation and routing for both dimensions and both scalar types ---------------
-static int helm_wave(unsigned nq, const HexArgs &a, const HelmArgsT<double> &x, hipStream_t s)
-{
-    return launch_hex_helmholtz_wave_nq(nq, a, x, s);
-}
-static int helm_wave(unsigned nq, const HexArgsT<float> &a, const HelmArgsT<float> &x, hipStream_t s)
-{
-    return launch_hex_helmholtz_wave_f32_nq(nq, a, x, s);
-}
-static int helm_wave(unsigned nq, const QuadArgs &a, const HelmArgsT<double> &x, hipStream_t s)
-{
-    return launch_quad_helmholtz_wave_nq(nq, a, x, s);
-}
-static int helm_wave(unsigned nq, const QuadArgsT<float> &a, const HelmArgsT<float> &x, hipStream_t s)
-{
-    return launch_quad_helmholtz_wave_f32_nq(nq, a, x, s);
-}
-static int helm_generic(const unsigned (&nq)[3], const HexArgs &a, const HelmArgsT<double> &x, hipStream_t s)
-{
-    return launch_hex_helmholtz_generic(nq[0], nq[1], nq[2], a, x, s);
-}
-static int helm_generic(const unsigned (&nq)[3], const HexArgsT<float> &a, const HelmArgsT<float> &x, hipStream_t s)
-{
-    return launch_hex_helmholtz_generic_f32(nq[0], nq[1], nq[2], a, x, s);
-}
-static int helm_generic(const unsigned (&nq)[3], const QuadArgs &a, const HelmArgsT<double> &x, hipStream_t s)
-{
-    return launch_quad_helmholtz_generic(nq[0], nq[1], a, x, s);
-}
-static int helm_generic(const unsigned (&nq)[3], const QuadArgsT<float> &a, const HelmArgsT<float> &x, hipStream_t s)
-{
-    return launch_quad_helmholtz_generic_f32(nq[0], nq[1], a, x, s);
-}
-
-// Validation before any HIP call, in the order documented in include/sumfact.h (that of sf_mass_*, extended to the
-// derivative matrices, g and lambda); `w` is looked at only when lambda != 0.  Then AUTO takes the wave kernel for an
-// isotropic order of its table when in / out are 16-byte aligned, and the any-extent kernel otherwise.
-template <int DIM, class Args, typename T>
+// The order of sf_mass_*, extended to the derivative matrices, g and lambda; `w` is looked at only when lambda != 0.
+template <int DIM, typename T>
 static int helmholtz(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *const (&d)[3],
                      const T *g, const T *w, double lambda, const T *in, T *out, void *stream)
 {
-    if (nq[0] < 2 || nq[1] < 2 || (DIM == 3 && nq[2] < 2) || variant < 0 || variant >= SF_NUM_VARIANTS)
-        return SF_EINVAL;
-    if (nelmt == 0)
-        return SF_OK;
-    const bool has_w = lambda != 0.0; // false for NaN too, which is refused next
-    if (!b[0] || !b[1] || (DIM == 3 && !b[2]) || !d[0] || !d[1] || (DIM == 3 && !d[2]) || !g || !in || !out ||
-        (has_w && !w) || !(lambda - lambda == 0.0))
-        return SF_EINVAL;
-    if (!aligned(in, sizeof(T)) || !aligned(out, sizeof(T)) || !aligned(g, sizeof(T)) || (has_w && !aligned(w, sizeof(T))) ||
-        !aligned(b[0], sizeof(T)) || !aligned(b[1], sizeof(T)) || (DIM == 3 && !aligned(b[2], sizeof(T))) ||
-        !aligned(d[0], sizeof(T)) || !aligned(d[1], sizeof(T)) || (DIM == 3 && !aligned(d[2], sizeof(T))))
-        return SF_EALIGN;
+    const bool has_w = lambda != 0.0; // false for NaN too, which is refused with the nulls
+    const int rc     = validate(range_ok<DIM>(variant, nq), nelmt,
+                                {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], g, in, out,
+                                 has_w ? w : g},
+                                sizeof(T), lambda - lambda == 0.0);
+    if (rc != kProceed)
+        return rc;
     // not in-place safe, as sf_mass_*
     const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
     const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
@@ -233,28 +142,13 @@ static int helmholtz(int variant, const unsigned (&nq)[3], size_t nelmt, const T
     if (overlaps(out, modes_bytes, in, modes_bytes) || overlaps(out, modes_bytes, g, (DIM == 3 ? 6 : 3) * points_bytes) ||
         (has_w && overlaps(out, modes_bytes, w, points_bytes)))
         return SF_EINVAL;
-    if (!helmholtz_generic_built(DIM, nq[0], nq[1], nq[2]))
-        return SF_ENOTBUILT;
-    if (variant != SF_VARIANT_AUTO && variant != SF_VARIANT_WAVE && variant != SF_VARIANT_GENERIC)
-        return SF_ENOTBUILT;
     const hipStream_t s = (hipStream_t)stream;
-    Args a{};
-    if constexpr (DIM == 3)
-        a = Args{b[0], b[1], b[2], in, nullptr, out, (uint64_t)nelmt};
-    else
-        a = Args{b[0], b[1], in, nullptr, out, (uint64_t)nelmt};
+    const auto a        = make_args<DIM, T>(b, in, out, nelmt);
     const HelmArgsT<T> x{d[0], d[1], d[2], g, has_w ? w : nullptr, (T)lambda}; // lambda is rounded to T here, once
-    const bool wave_ok = nq[0] == nq[1] && (DIM == 2 || nq[1] == nq[2]) && helmholtz_wave_built(DIM, nq[0]);
-    const bool vec_ok  = aligned(in, 16) && aligned(out, 16);
-    if (variant == SF_VARIANT_WAVE)
-    {
-        if (!wave_ok)
-            return SF_ENOTBUILT;
-        return vec_ok ? helm_wave(nq[0], a, x, s) : SF_EALIGN;
-    }
-    if (variant == SF_VARIANT_AUTO && wave_ok && vec_ok)
-        return helm_wave(nq[0], a, x, s);
-    return helm_generic(nq, a, x, s);
+    return route<DIM>(
+        variant, nq, helmholtz_generic_built(DIM, nq[0], nq[1], nq[2]), helmholtz_wave_built(DIM, nq[0]), in, out,
+        [&] { return launch_helmholtz_wave<DIM, T>(nq[0], a, x, s); },
+        [&] { return launch_helmholtz_generic<DIM, T>(nq, a, x, s); });
 }
 
 extern "C" {
@@ -291,15 +185,9 @@ int sf_bwdtrans_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigne
                                 const double *basis2, const double *in, double *wsp, double *out,
                                 void *stream)
 {
-    if (nq0 < 2 || nq1 < 2 || nq2 < 2 || variant < 0 || variant >= SF_NUM_VARIANTS)
-        return SF_EINVAL;
-    if (nelmt == 0)
-        return SF_OK;
-    if (!basis0 || !basis1 || !basis2 || !in || !out)
-        return SF_EINVAL;
-    if (!aligned(in, 8) || !aligned(out, 8) || !aligned(basis0, 8) || !aligned(basis1, 8) ||
-        !aligned(basis2, 8))
-        return SF_EALIGN;
+    const int pre = validate(range_ok<3>(variant, {nq0, nq1, nq2}), nelmt, {basis0, basis1, basis2, in, out}, 8);
+    if (pre != kProceed)
+        return pre;
     hipStream_t s = (hipStream_t)stream;
     HexArgs a{basis0, basis1, basis2, in, wsp, out, (uint64_t)nelmt};
     const bool iso = (nq0 == nq1 && nq1 == nq2);
@@ -371,14 +259,9 @@ int sf_bwdtrans_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t
                                  const double *basis0, const double *basis1, const double *in,
                                  double *wsp, double *out, void *stream)
 {
-    if (nq0 < 2 || nq1 < 2 || variant < 0 || variant >= SF_NUM_VARIANTS)
-        return SF_EINVAL;
-    if (nelmt == 0)
-        return SF_OK;
-    if (!basis0 || !basis1 || !in || !out)
-        return SF_EINVAL;
-    if (!aligned(in, 8) || !aligned(out, 8) || !aligned(basis0, 8) || !aligned(basis1, 8))
-        return SF_EALIGN;
+    const int pre = validate(range_ok<2>(variant, {nq0, nq1, 0u}), nelmt, {basis0, basis1, in, out}, 8);
+    if (pre != kProceed)
+        return pre;
     hipStream_t s = (hipStream_t)stream;
     QuadArgs a{basis0, basis1, in, wsp, out, (uint64_t)nelmt};
     const bool iso    = (nq0 == nq1);
@@ -454,7 +337,7 @@ int sf_bwdtrans_hex_f64_interleaved(unsigned nq0, unsigned nq1, unsigned nq2, si
         return SF_OK;
     if (!basis0 || !basis1 || !basis2 || !in_il || !wsp_il || !out_il)
         return SF_EINVAL;
-    if (!aligned(in_il, 8) || !aligned(out_il, 8) || !aligned(wsp_il, 8))
+    if (!aligned(in_il, 8) || !aligned(out_il, 8) || !aligned(wsp_il, 8)) // not the bases: validate() would check them
         return SF_EALIGN;
     HexArgs a{basis0, basis1, basis2, in_il, wsp_il, out_il, (uint64_t)nelmt};
     return launch_hex_interleaved(nq0, nq1, nq2, a, (hipStream_t)stream);
@@ -473,15 +356,10 @@ int sf_bwdtrans_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, 
                         const float *basis1, const float *basis2, const float *in, float *out,
                         void *stream)
 {
-    if (nq0 < 2 || nq1 < 2 || nq2 < 2)
-        return SF_EINVAL;
-    if (nelmt == 0)
-        return SF_OK;
-    if (!basis0 || !basis1 || !basis2 || !in || !out)
-        return SF_EINVAL;
-    if (!aligned(in, 4) || !aligned(out, 4) || !aligned(basis0, 4) || !aligned(basis1, 4) ||
-        !aligned(basis2, 4))
-        return SF_EALIGN;
+    const int pre =
+        validate(range_ok<3>(SF_VARIANT_AUTO, {nq0, nq1, nq2}), nelmt, {basis0, basis1, basis2, in, out}, 4);
+    if (pre != kProceed)
+        return pre;
     hipStream_t s = (hipStream_t)stream;
     HexArgsT<float> a{basis0, basis1, basis2, in, nullptr, out, (uint64_t)nelmt};
     if (nq0 == nq1 && nq1 == nq2 && aligned(in, 16) && aligned(out, 16))
@@ -502,14 +380,9 @@ int sf_bwdtrans_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, 
 int sf_bwdtrans_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0,
                          const float *basis1, const float *in, float *out, void *stream)
 {
-    if (nq0 < 2 || nq1 < 2)
-        return SF_EINVAL;
-    if (nelmt == 0)
-        return SF_OK;
-    if (!basis0 || !basis1 || !in || !out)
-        return SF_EINVAL;
-    if (!aligned(in, 4) || !aligned(out, 4) || !aligned(basis0, 4) || !aligned(basis1, 4))
-        return SF_EALIGN;
+    const int pre = validate(range_ok<2>(SF_VARIANT_AUTO, {nq0, nq1, 0u}), nelmt, {basis0, basis1, in, out}, 4);
+    if (pre != kProceed)
+        return pre;
     hipStream_t s = (hipStream_t)stream;
     QuadArgsT<float> a{basis0, basis1, in, nullptr, out, (uint64_t)nelmt};
     if (nq0 == nq1 && aligned(in, 16) && aligned(out, 16))
@@ -532,38 +405,38 @@ int sf_iproduct_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigne
                                 const double *basis0, const double *basis1, const double *basis2, const double *in,
                                 double *out, void *stream)
 {
-    return iprod<3, HexArgs, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, out, stream);
+    return iprod<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, out, stream);
 }
 
 int sf_iproduct_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
                         const double *basis1, const double *basis2, const double *in, double *out, void *stream)
 {
-    return iprod<3, HexArgs, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, out, stream);
+    return iprod<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, out, stream);
 }
 
 int sf_iproduct_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
                                  const double *basis1, const double *in, double *out, void *stream)
 {
-    return iprod<2, QuadArgs, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, out, stream);
+    return iprod<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, out, stream);
 }
 
 int sf_iproduct_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
                          const double *in, double *out, void *stream)
 {
-    return iprod<2, QuadArgs, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, out, stream);
+    return iprod<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, out, stream);
 }
 
 int sf_iproduct_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
                         const float *basis1, const float *basis2, const float *in, float *out, void *stream)
 {
-    return iprod<3, HexArgsT<float>, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, out,
+    return iprod<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, out,
                                      stream);
 }
 
 int sf_iproduct_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
                          const float *in, float *out, void *stream)
 {
-    return iprod<2, QuadArgsT<float>, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, out,
+    return iprod<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, out,
                                       stream);
 }
 
@@ -572,38 +445,38 @@ int sf_mass_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq
                             const double *basis1, const double *basis2, const double *w, const double *in, double *out,
                             void *stream)
 {
-    return mass<3, HexArgs, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, w, in, out, stream);
+    return mass<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, w, in, out, stream);
 }
 
 int sf_mass_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0, const double *basis1,
                     const double *basis2, const double *w, const double *in, double *out, void *stream)
 {
-    return mass<3, HexArgs, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, w, in, out, stream);
+    return mass<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, w, in, out, stream);
 }
 
 int sf_mass_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
                              const double *basis1, const double *w, const double *in, double *out, void *stream)
 {
-    return mass<2, QuadArgs, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, w, in, out, stream);
+    return mass<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, w, in, out, stream);
 }
 
 int sf_mass_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
                      const double *w, const double *in, double *out, void *stream)
 {
-    return mass<2, QuadArgs, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, w, in, out, stream);
+    return mass<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, w, in, out, stream);
 }
 
 int sf_mass_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
                     const float *basis2, const float *w, const float *in, float *out, void *stream)
 {
-    return mass<3, HexArgsT<float>, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, w, in, out,
+    return mass<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, w, in, out,
                                            stream);
 }
 
 int sf_mass_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1, const float *w,
                      const float *in, float *out, void *stream)
 {
-    return mass<2, QuadArgsT<float>, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, w, in, out,
+    return mass<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, w, in, out,
                                             stream);
 }
 
@@ -613,7 +486,7 @@ int sf_helmholtz_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsign
                                  const double *deriv2, const double *g, const double *w, double lambda, const double *in,
                                  double *out, void *stream)
 {
-    return helmholtz<3, HexArgs, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
+    return helmholtz<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
                                          {deriv0, deriv1, deriv2}, g, w, lambda, in, out, stream);
 }
 
@@ -622,7 +495,7 @@ int sf_helmholtz_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
                          const double *deriv2, const double *g, const double *w, double lambda, const double *in,
                          double *out, void *stream)
 {
-    return helmholtz<3, HexArgs, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
+    return helmholtz<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
                                          {deriv0, deriv1, deriv2}, g, w, lambda, in, out, stream);
 }
 
@@ -630,7 +503,7 @@ int sf_helmholtz_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_
                                   const double *basis1, const double *deriv0, const double *deriv1, const double *g,
                                   const double *w, double lambda, const double *in, double *out, void *stream)
 {
-    return helmholtz<2, QuadArgs, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
+    return helmholtz<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
                                           {deriv0, deriv1, nullptr}, g, w, lambda, in, out, stream);
 }
 
@@ -638,7 +511,7 @@ int sf_helmholtz_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double
                           const double *deriv0, const double *deriv1, const double *g, const double *w, double lambda,
                           const double *in, double *out, void *stream)
 {
-    return helmholtz<2, QuadArgs, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
+    return helmholtz<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
                                           {deriv0, deriv1, nullptr}, g, w, lambda, in, out, stream);
 }
 
@@ -646,7 +519,7 @@ int sf_helmholtz_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
                          const float *basis2, const float *deriv0, const float *deriv1, const float *deriv2,
                          const float *g, const float *w, double lambda, const float *in, float *out, void *stream)
 {
-    return helmholtz<3, HexArgsT<float>, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
+    return helmholtz<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
                                                 {deriv0, deriv1, deriv2}, g, w, lambda, in, out, stream);
 }
 
@@ -654,7 +527,7 @@ int sf_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float 
                           const float *deriv0, const float *deriv1, const float *g, const float *w, double lambda,
                           const float *in, float *out, void *stream)
 {
-    return helmholtz<2, QuadArgsT<float>, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
+    return helmholtz<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
                                                  {deriv0, deriv1, nullptr}, g, w, lambda, in, out, stream);
 }
 
@@ -823,15 +696,12 @@ int sf_bwdtrans_specialised(int dim, unsigned nq0, unsigned nq1, unsigned nq2, i
                             void *stream)
 {
     const unsigned mx = dim == 3 ? 16u : 24u;
-    if ((dim != 2 && dim != 3) || (scalar_bytes != 4 && scalar_bytes != 8) || nq0 < 2 || nq1 < 2 || nq0 > mx ||
-        nq1 > mx || (dim == 3 && (nq2 < 2 || nq2 > mx)))
-        return SF_EINVAL;
-    if (nelmt == 0)
-        return SF_OK;
-    if (!basis0 || !basis1 || (dim == 3 && !basis2) || !in || !out)
-        return SF_EINVAL;
-    if (!aligned(in, 16) || !aligned(out, 16) || !aligned(basis0, scalar_bytes) || !aligned(basis1, scalar_bytes) ||
-        (dim == 3 && !aligned(basis2, scalar_bytes)))
+    const bool range  = (dim == 2 || dim == 3) && (scalar_bytes == 4 || scalar_bytes == 8) && nq0 >= 2 && nq1 >= 2 &&
+                       nq0 <= mx && nq1 <= mx && (dim == 2 || (nq2 >= 2 && nq2 <= mx));
+    const int pre = validate(range, nelmt, {basis0, basis1, dim == 3 ? basis2 : basis0, in, out}, (size_t)scalar_bytes);
+    if (pre != kProceed)
+        return pre;
+    if (!aligned(in, 16) || !aligned(out, 16)) // the specialised kernels have no scalar-aligned path
         return SF_EALIGN;
     return launch_specialised(dim, nq0, nq1, dim == 3 ? nq2 : 0, scalar_bytes, basis0, basis1, basis2, in, out,
                               (uint64_t)nelmt, (hipStream_t)stream);

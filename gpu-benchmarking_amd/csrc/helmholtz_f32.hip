@@ -5,26 +5,7 @@
 namespace sf
 {
 
-int launch_hex_helmholtz_wave_f32_nq(unsigned nq, const HexArgsT<float> &a, const HelmArgsT<float> &x, hipStream_t s)
-{
-    switch (nq)
-    {
-#define SF_CASE(N) case N: return go_hex_helmholtz<N, float>(a, x, s);
-        SF_HELM_HEX_CASES(SF_CASE)
-#undef SF_CASE
-    default: return SF_ENOTBUILT;
-    }
-}
-
-int launch_quad_helmholtz_wave_f32_nq(unsigned nq, const QuadArgsT<float> &a, const HelmArgsT<float> &x, hipStream_t s)
-{
-    switch (nq)
-    {
-#define SF_CASE(N) case N: return go_quad_helmholtz<N, float>(a, x, s);
-        SF_HELM_QUAD_CASES(SF_CASE)
-#undef SF_CASE
-    default: return SF_ENOTBUILT;
-    }
-}
+template int launch_helmholtz_wave<3, float>(unsigned, const HexArgsT<float> &, const HelmArgsT<float> &, hipStream_t);
+template int launch_helmholtz_wave<2, float>(unsigned, const QuadArgsT<float> &, const HelmArgsT<float> &, hipStream_t);
 
 } // namespace sf

@@ -15,31 +15,13 @@
 // dereferenced when has_w is false.  Latency-bound (a barrier per sweep, one element per workgroup), not a roofline
 // target.  Extents up to 12 per direction in 3D (four images of 12^3 doubles: 55 296 bytes of the 64 KB of static LDS)
 // and 32 in 2D; beyond, SF_ENOTBUILT.
-#include "sf_dispatch.h"
+#include "any_extent.h"
 
 namespace sf
 {
 
 constexpr unsigned kHelmMax3D = 12, kHelmMax2D = 32;
 constexpr int kHelmSmallCap = 2048, kHelmLargeCap = 4 * 12 * 12 * 12; // scalars; 2D 32^2 needs 3 * 1024
-
-__device__ __forceinline__ double hfma(double a, double b, double c)
-{
-    return __builtin_fma(a, b, c);
-}
-__device__ __forceinline__ float hfma(float a, float b, float c)
-{
-    return __builtin_fmaf(a, b, c);
-}
-
-// a = sum_{m < n} u[m*us] * b[m*bs], ascending m, the first product a multiply
-template <typename T> __device__ __forceinline__ T hdot(const T *u, int us, const T *b, int bs, int n)
-{
-    T a = u[0] * b[0];
-    for (int m = 1; m < n; ++m)
-        a = hfma(u[m * us], b[m * bs], a);
-    return a;
-}
 
 template <typename T, int DIM, int CAP, int NT>
 __global__ __launch_bounds__(NT) void helmholtz_generic_kernel(
@@ -71,22 +53,22 @@ __global__ __launch_bounds__(NT) void helmholtz_generic_kernel(
             for (int x = tid; x < nm1 * nq0; x += NT)
             {
                 const int i = x % nq0, q = x / nq0;
-                P2[x] = hdot(P1 + q * nm0, 1, b0 + i, nq0, nm0);
+                P2[x] = dot_strided(P1 + q * nm0, 1, b0 + i, nq0, nm0);
             }
             __syncthreads();
             // forward 1: u[j][i] = sum_q w1[q][i] * B1[q][j]
             for (int x = tid; x < nqt; x += NT)
             {
                 const int i = x % nq0, j = x / nq0;
-                P0[x] = hdot(P2 + i, nq0, b1 + j, nq1, nm1);
+                P0[x] = dot_strided(P2 + i, nq0, b1 + j, nq1, nm1);
             }
             __syncthreads();
             // du_0[j][i] = sum_m D0[i][m] u[j][m];  du_1[j][i] = sum_m D1[j][m] u[m][i]
             for (int x = tid; x < nqt; x += NT)
             {
                 const int i = x % nq0, j = x / nq0;
-                P1[x] = hdot(P0 + j * nq0, 1, d0 + i * nq0, 1, nq0);
-                P2[x] = hdot(P0 + i, nq0, d1 + j * nq1, 1, nq1);
+                P1[x] = dot_strided(P0 + j * nq0, 1, d0 + i * nq0, 1, nq0);
+                P2[x] = dot_strided(P0 + i, nq0, d1 + j * nq1, 1, nq1);
             }
             __syncthreads();
             // fluxes in place, the mass term over u (every thread touches its own points only)
@@ -94,8 +76,8 @@ __global__ __launch_bounds__(NT) void helmholtz_generic_kernel(
             {
                 const T x0 = P1[x], x1 = P2[x];
                 const T g00 = ge[x], g01 = ge[nqt + x], g11 = ge[2 * nqt + x];
-                P1[x] = hfma(g01, x1, g00 * x0);
-                P2[x] = hfma(g11, x1, g01 * x0);
+                P1[x] = sfma(g01, x1, g00 * x0);
+                P2[x] = sfma(g11, x1, g01 * x0);
                 P0[x] = has_w ? (lam * wt[x]) * P0[x] : T(0);
             }
             __syncthreads();
@@ -103,8 +85,8 @@ __global__ __launch_bounds__(NT) void helmholtz_generic_kernel(
             for (int x = tid; x < nqt; x += NT)
             {
                 const int i = x % nq0, j = x / nq0;
-                const T t0 = hdot(P1 + j * nq0, 1, d0 + i, nq0, nq0);
-                const T t1 = hdot(P2 + i, nq0, d1 + j, nq1, nq1);
+                const T t0 = dot_strided(P1 + j * nq0, 1, d0 + i, nq0, nq0);
+                const T t1 = dot_strided(P2 + i, nq0, d1 + j, nq1, nq1);
                 P0[x]      = (P0[x] + t0) + t1;
             }
             __syncthreads();
@@ -112,14 +94,14 @@ __global__ __launch_bounds__(NT) void helmholtz_generic_kernel(
             for (int x = tid; x < nm1 * nq0; x += NT)
             {
                 const int i = x % nq0, q = x / nq0;
-                P1[x] = hdot(P0 + i, nq0, b1 + q * nq1, 1, nq1);
+                P1[x] = dot_strided(P0 + i, nq0, b1 + q * nq1, 1, nq1);
             }
             __syncthreads();
             // transposed 0: out[q'][p'] = sum_i t1[q'][i] * B0[p'][i]
             for (int x = tid; x < nmt; x += NT)
             {
                 const int p = x % nm0, q = x / nm0;
-                dst[x] = hdot(P1 + q * nq0, 1, b0 + p * nq0, 1, nq0);
+                dst[x] = dot_strided(P1 + q * nq0, 1, b0 + p * nq0, 1, nq0);
             }
         }
         else
@@ -128,30 +110,30 @@ __global__ __launch_bounds__(NT) void helmholtz_generic_kernel(
             for (int x = tid; x < nq0 * nm1 * nm2; x += NT)
             {
                 const int i = x % nq0, rq = x / nq0;
-                P0[x] = hdot(P1 + rq * nm0, 1, b0 + i, nq0, nm0);
+                P0[x] = dot_strided(P1 + rq * nm0, 1, b0 + i, nq0, nm0);
             }
             __syncthreads();
             // forward 1: w2[r][j][i] = sum_q w1[r][q][i] * B1[q][j]
             for (int x = tid; x < n01 * nm2; x += NT)
             {
                 const int i = x % nq0, rj = x / nq0, j = rj % nq1, r = rj / nq1;
-                P1[x] = hdot(P0 + r * nm1 * nq0 + i, nq0, b1 + j, nq1, nm1);
+                P1[x] = dot_strided(P0 + r * nm1 * nq0 + i, nq0, b1 + j, nq1, nm1);
             }
             __syncthreads();
             // forward 2: u[k][j][i] = sum_r w2[r][j][i] * B2[r][k]
             for (int x = tid; x < nqt; x += NT)
             {
                 const int ji = x % n01, k = x / n01;
-                P0[x] = hdot(P1 + ji, n01, b2 + k, nq2, nm2);
+                P0[x] = dot_strided(P1 + ji, n01, b2 + k, nq2, nm2);
             }
             __syncthreads();
             // du_0 = D0 u along i, du_1 = D1 u along j, du_2 = D2 u along k
             for (int x = tid; x < nqt; x += NT)
             {
                 const int i = x % nq0, kj = x / nq0, j = kj % nq1, k = kj / nq1;
-                P1[x] = hdot(P0 + kj * nq0, 1, d0 + i * nq0, 1, nq0);
-                P2[x] = hdot(P0 + k * n01 + i, nq0, d1 + j * nq1, 1, nq1);
-                P3[x] = hdot(P0 + j * nq0 + i, n01, d2 + k * nq2, 1, nq2);
+                P1[x] = dot_strided(P0 + kj * nq0, 1, d0 + i * nq0, 1, nq0);
+                P2[x] = dot_strided(P0 + k * n01 + i, nq0, d1 + j * nq1, 1, nq1);
+                P3[x] = dot_strided(P0 + j * nq0 + i, n01, d2 + k * nq2, 1, nq2);
             }
             __syncthreads();
             // fluxes in place, the mass term over u (every thread touches its own points only)
@@ -160,9 +142,9 @@ __global__ __launch_bounds__(NT) void helmholtz_generic_kernel(
                 const T x0 = P1[x], x1 = P2[x], x2 = P3[x];
                 const T g00 = ge[x], g01 = ge[nqt + x], g02 = ge[2 * nqt + x];
                 const T g11 = ge[3 * nqt + x], g12 = ge[4 * nqt + x], g22 = ge[5 * nqt + x];
-                P1[x] = hfma(g02, x2, hfma(g01, x1, g00 * x0));
-                P2[x] = hfma(g12, x2, hfma(g11, x1, g01 * x0));
-                P3[x] = hfma(g22, x2, hfma(g12, x1, g02 * x0));
+                P1[x] = sfma(g02, x2, sfma(g01, x1, g00 * x0));
+                P2[x] = sfma(g12, x2, sfma(g11, x1, g01 * x0));
+                P3[x] = sfma(g22, x2, sfma(g12, x1, g02 * x0));
                 P0[x] = has_w ? (lam * wt[x]) * P0[x] : T(0);
             }
             __syncthreads();
@@ -170,9 +152,9 @@ __global__ __launch_bounds__(NT) void helmholtz_generic_kernel(
             for (int x = tid; x < nqt; x += NT)
             {
                 const int i = x % nq0, kj = x / nq0, j = kj % nq1, k = kj / nq1;
-                const T t0 = hdot(P1 + kj * nq0, 1, d0 + i, nq0, nq0);
-                const T t1 = hdot(P2 + k * n01 + i, nq0, d1 + j, nq1, nq1);
-                const T t2 = hdot(P3 + j * nq0 + i, n01, d2 + k, nq2, nq2);
+                const T t0 = dot_strided(P1 + kj * nq0, 1, d0 + i, nq0, nq0);
+                const T t1 = dot_strided(P2 + k * n01 + i, nq0, d1 + j, nq1, nq1);
+                const T t2 = dot_strided(P3 + j * nq0 + i, n01, d2 + k, nq2, nq2);
                 P0[x]      = ((P0[x] + t0) + t1) + t2;
             }
             __syncthreads();
@@ -180,21 +162,21 @@ __global__ __launch_bounds__(NT) void helmholtz_generic_kernel(
             for (int x = tid; x < n01 * nm2; x += NT)
             {
                 const int ji = x % n01, r = x / n01;
-                P1[x] = hdot(P0 + ji, n01, b2 + r * nq2, 1, nq2);
+                P1[x] = dot_strided(P0 + ji, n01, b2 + r * nq2, 1, nq2);
             }
             __syncthreads();
             // transposed 1: t2[r'][q'][i] = sum_j t1[r'][j][i] * B1[q'][j]
             for (int x = tid; x < nq0 * nm1 * nm2; x += NT)
             {
                 const int i = x % nq0, rq = x / nq0, q = rq % nm1, r = rq / nm1;
-                P2[x] = hdot(P1 + r * n01 + i, nq0, b1 + q * nq1, 1, nq1);
+                P2[x] = dot_strided(P1 + r * n01 + i, nq0, b1 + q * nq1, 1, nq1);
             }
             __syncthreads();
             // transposed 0: out[r'][q'][p'] = sum_i t2[r'][q'][i] * B0[p'][i]
             for (int x = tid; x < nmt; x += NT)
             {
                 const int p = x % nm0, rq = x / nm0;
-                dst[x] = hdot(P2 + rq * nq0, 1, b0 + p * nq0, 1, nq0);
+                dst[x] = dot_strided(P2 + rq * nq0, 1, b0 + p * nq0, 1, nq0);
             }
         }
         __syncthreads(); // the next element overwrites the images
@@ -207,47 +189,27 @@ static unsigned helm_need(int dim, unsigned nq0, unsigned nq1, unsigned nq2)
     return dim == 3 ? 4 * nq0 * nq1 * nq2 : 3 * nq0 * nq1;
 }
 
-template <typename T, int DIM>
-static int launch_helm_generic(unsigned nq0, unsigned nq1, unsigned nq2, const T *b0, const T *b1, const T *b2,
-                               const HelmArgsT<T> &x, const T *in, T *out, uint64_t nelmt, hipStream_t s)
+template <int DIM, typename T>
+int launch_helmholtz_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const HelmArgsT<T> &x, hipStream_t s)
 {
-    if (!helmholtz_generic_built(DIM, nq0, nq1, nq2))
+    if (!helmholtz_generic_built(DIM, nq[0], nq[1], nq[2]))
         return SF_ENOTBUILT;
-    if (nelmt == 0)
+    if (a.nelmt == 0)
         return SF_OK;
-    const unsigned need = helm_need(DIM, nq0, nq1, nq2);
-    const unsigned grid = nelmt < (1ull << 22) ? (unsigned)nelmt : (1u << 22);
-    const bool has_w    = x.w != nullptr;
-    if (need <= (unsigned)kHelmSmallCap)
-        helmholtz_generic_kernel<T, DIM, kHelmSmallCap, 64><<<grid, 64, 0, s>>>(
-            b0, b1, b2, x.d0, x.d1, x.d2, x.g, x.w, x.lam, has_w, in, out, nelmt, (int)nq0, (int)nq1, (int)nq2);
-    else
-        helmholtz_generic_kernel<T, DIM, kHelmLargeCap, 256><<<grid, 256, 0, s>>>(
-            b0, b1, b2, x.d0, x.d1, x.d2, x.g, x.w, x.lam, has_w, in, out, nelmt, (int)nq0, (int)nq1, (int)nq2);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
+    return launch_lds_class(helm_need(DIM, nq[0], nq[1], nq[2]) <= (unsigned)kHelmSmallCap,
+                            helmholtz_generic_kernel<T, DIM, kHelmSmallCap, 64>,
+                            helmholtz_generic_kernel<T, DIM, kHelmLargeCap, 256>, a.nelmt, s, a.b0, a.b1, basis2(a), x.d0,
+                            x.d1, x.d2, x.g, x.w, x.lam, x.w != nullptr, a.in, a.out, a.nelmt, (int)nq[0], (int)nq[1],
+                            (int)nq[2]);
 }
-
-int launch_hex_helmholtz_generic(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, const HelmArgsT<double> &x,
-                                 hipStream_t s)
-{
-    return launch_helm_generic<double, 3>(nq0, nq1, nq2, a.b0, a.b1, a.b2, x, a.in, a.out, a.nelmt, s);
-}
-int launch_hex_helmholtz_generic_f32(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgsT<float> &a,
-                                     const HelmArgsT<float> &x, hipStream_t s)
-{
-    return launch_helm_generic<float, 3>(nq0, nq1, nq2, a.b0, a.b1, a.b2, x, a.in, a.out, a.nelmt, s);
-}
-int launch_quad_helmholtz_generic(unsigned nq0, unsigned nq1, const QuadArgs &a, const HelmArgsT<double> &x,
-                                  hipStream_t s)
-{
-    return launch_helm_generic<double, 2>(nq0, nq1, 0, a.b0, a.b1, nullptr, x, a.in, a.out, a.nelmt, s);
-}
-int launch_quad_helmholtz_generic_f32(unsigned nq0, unsigned nq1, const QuadArgsT<float> &a, const HelmArgsT<float> &x,
-                                      hipStream_t s)
-{
-    return launch_helm_generic<float, 2>(nq0, nq1, 0, a.b0, a.b1, nullptr, x, a.in, a.out, a.nelmt, s);
-}
+template int launch_helmholtz_generic<3, double>(const unsigned (&)[3], const HexArgs &, const HelmArgsT<double> &,
+                                                 hipStream_t);
+template int launch_helmholtz_generic<3, float>(const unsigned (&)[3], const HexArgsT<float> &, const HelmArgsT<float> &,
+                                                hipStream_t);
+template int launch_helmholtz_generic<2, double>(const unsigned (&)[3], const QuadArgs &, const HelmArgsT<double> &,
+                                                 hipStream_t);
+template int launch_helmholtz_generic<2, float>(const unsigned (&)[3], const QuadArgsT<float> &, const HelmArgsT<float> &,
+                                                hipStream_t);
 
 // within the extent bounds AND the images fit the large LDS class (true for every extent within the bounds: 3D 12^3
 // needs 6912, 2D 32^2 3072; derived all the same, not assumed)

@@ -24,41 +24,21 @@
 namespace sf
 {
 
-template <int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP, int MEMF, bool HASW, typename T>
-static int launch_hex_helmholtz_k(const HexArgsT<T> &a, const HelmArgsT<T> &x, hipStream_t s)
+template <int DIM, int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP, int MEMF, bool HASW, typename T>
+static int launch_helmholtz_k(const ArgsT<DIM, T> &a, const HelmArgsT<T> &x, hipStream_t s)
 {
     static OccCache cache = {};
-    auto kern            = hex_helmholtz_wave_kernel<NQ, EC, WPB, BMODE, MINW, KMAP, MEMF, HASW, T>;
-    constexpr size_t lds = helmholtz_lds_bytes<NQ, EC, 3, WPB, T>();
+    constexpr size_t lds = helmholtz_lds_bytes<NQ, EC, DIM, WPB, T>();
     static_assert(lds <= 160 * 1024, "LDS slab exceeds 160 KiB");
-    const uint64_t nchunk = (a.nelmt + EC - 1) / EC;
-    const uint64_t per    = (uint64_t)WPB * KMAP;
-    const uint64_t grid   = (nchunk + per - 1) / per;
-    (void)resident_blocks(kern, kWave * WPB, lds, cache); // raises the kernel's LDS limit once per device
-    if (grid > 0x7fffffffull)
-        return SF_EINVAL;
-    kern<<<(unsigned)grid, kWave * WPB, lds, s>>>(a.b0, a.b1, a.b2, x.d0, x.d1, x.d2, x.g, x.w, x.lam, a.in, a.out,
-                                                  a.nelmt);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
-}
-
-template <int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP, int MEMF, bool HASW, typename T>
-static int launch_quad_helmholtz_k(const QuadArgsT<T> &a, const HelmArgsT<T> &x, hipStream_t s)
-{
-    static OccCache cache = {};
-    auto kern            = quad_helmholtz_wave_kernel<NQ, EC, WPB, BMODE, MINW, KMAP, MEMF, HASW, T>;
-    constexpr size_t lds = helmholtz_lds_bytes<NQ, EC, 2, WPB, T>();
-    static_assert(lds <= 160 * 1024, "LDS slab exceeds 160 KiB");
-    const uint64_t nchunk = (a.nelmt + EC - 1) / EC;
-    const uint64_t per    = (uint64_t)WPB * KMAP;
-    const uint64_t grid   = (nchunk + per - 1) / per;
-    (void)resident_blocks(kern, kWave * WPB, lds, cache);
-    if (grid > 0x7fffffffull)
-        return SF_EINVAL;
-    kern<<<(unsigned)grid, kWave * WPB, lds, s>>>(a.b0, a.b1, x.d0, x.d1, x.g, x.w, x.lam, a.in, a.out, a.nelmt);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
+    static_assert(KMAP > 0, "short-lived waves: the grid covers the batch");
+    if constexpr (DIM == 3)
+        return launch_chunked<WPB, EC, KMAP>(hex_helmholtz_wave_kernel<NQ, EC, WPB, BMODE, MINW, KMAP, MEMF, HASW, T>,
+                                             cache, lds, 0, s, a.nelmt, a.b0, a.b1, a.b2, x.d0, x.d1, x.d2, x.g, x.w,
+                                             x.lam, a.in, a.out, a.nelmt);
+    else
+        return launch_chunked<WPB, EC, KMAP>(quad_helmholtz_wave_kernel<NQ, EC, WPB, BMODE, MINW, KMAP, MEMF, HASW, T>,
+                                             cache, lds, 0, s, a.nelmt, a.b0, a.b1, x.d0, x.d1, x.g, x.w, x.lam, a.in,
+                                             a.out, a.nelmt);
 }
 
 constexpr int helm_hex_ec(int nq, int row_ec, int scalar_bytes)
@@ -88,24 +68,35 @@ template <int NQ, typename T> struct HelmQuadCfg
     static constexpr int KM = R::KM, MF = R::MF | 8;
 };
 
-template <int NQ, typename T> static int go_hex_helmholtz(const HexArgsT<T> &a, const HelmArgsT<T> &x, hipStream_t s)
+template <int DIM, int NQ, typename T>
+static int go_helmholtz(const ArgsT<DIM, T> &a, const HelmArgsT<T> &x, hipStream_t s)
 {
-    using C = HelmHexCfg<NQ, T>;
-    if (a.nelmt == 0)
-        return SF_OK;
-    return x.w ? launch_hex_helmholtz_k<NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, C::MF, true, T>(a, x, s)
-               : launch_hex_helmholtz_k<NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, C::MF, false, T>(a, x, s);
-}
-template <int NQ, typename T> static int go_quad_helmholtz(const QuadArgsT<T> &a, const HelmArgsT<T> &x, hipStream_t s)
-{
-    using C = HelmQuadCfg<NQ, T>;
-    if (a.nelmt == 0)
-        return SF_OK;
-    return x.w ? launch_quad_helmholtz_k<NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, C::MF, true, T>(a, x, s)
-               : launch_quad_helmholtz_k<NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, C::MF, false, T>(a, x, s);
+    using C = typename std::conditional<DIM == 3, HelmHexCfg<NQ, T>, HelmQuadCfg<NQ, T>>::type;
+    return x.w ? launch_helmholtz_k<DIM, NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, C::MF, true, T>(a, x, s)
+               : launch_helmholtz_k<DIM, NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, C::MF, false, T>(a, x, s);
 }
 
 #define SF_HELM_HEX_CASES(F) F(2) F(3) F(4) F(5) F(6) F(7) F(8)
 #define SF_HELM_QUAD_CASES(F) F(2) F(3) F(4) F(5) F(6) F(7) F(8) F(9) F(10) F(11) F(12) F(13) F(14) F(15) F(16)
+
+// SF_ENOTBUILT when the order has no instantiation (helmholtz_wave_built()); instantiated for double in helmholtz.hip and
+// for float in helmholtz_f32.hip
+template <int DIM, typename T>
+int launch_helmholtz_wave(unsigned nq, const ArgsT<DIM, T> &a, const HelmArgsT<T> &x, hipStream_t s)
+{
+#define SF_CASE(N) case N: return go_helmholtz<DIM, N, T>(a, x, s);
+    if constexpr (DIM == 3)
+        switch (nq)
+        {
+            SF_HELM_HEX_CASES(SF_CASE)
+        }
+    else
+        switch (nq)
+        {
+            SF_HELM_QUAD_CASES(SF_CASE)
+        }
+#undef SF_CASE
+    return SF_ENOTBUILT;
+}
 
 } // namespace sf

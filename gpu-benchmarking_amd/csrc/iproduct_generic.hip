@@ -5,8 +5,9 @@
 // in 3D the second intermediate over the input.  One thread per output value of a sweep; each sum runs in ascending
 // index, sweeps i -> p, j -> q, k -> r, the order of the wave kernels.  The bases are read straight from global memory
 // (nm*nq values each, cache-resident).  No workspace: every launch is a single kernel node, capture-safe from the first
-// call.  Extents up to 16 per direction in 3D and 32 in 2D; beyond, SF_ENOTBUILT.
-#include "sf_dispatch.h"
+// call.  Extents up to 16 per direction in 3D and 32 in 2D; beyond, SF_ENOTBUILT.  The sums are written out where
+// mass_generic.hip and helmholtz_generic.hip call dot_strided(): the compiler schedules the two forms differently here.
+#include "any_extent.h"
 
 namespace sf
 {
@@ -14,15 +15,6 @@ namespace sf
 // LDS classes in scalars: input image + first intermediate.  3D 16^3: 4096 + 15*16*16 = 7936; 2D 32^2: 1024 + 31*32.
 constexpr int kIprodSmallCap = 2048, kIprodLargeCap = 7936;
 constexpr unsigned kIprodMax3D = 16, kIprodMax2D = 32;
-
-__device__ __forceinline__ double gfma(double a, double b, double c)
-{
-    return __builtin_fma(a, b, c);
-}
-__device__ __forceinline__ float gfma(float a, float b, float c)
-{
-    return __builtin_fmaf(a, b, c);
-}
 
 template <typename T, int DIM, int CAP, int NT>
 __global__ __launch_bounds__(NT) void iprod_generic_kernel(const T *__restrict__ b0, const T *__restrict__ b1,
@@ -51,7 +43,7 @@ __global__ __launch_bounds__(NT) void iprod_generic_kernel(const T *__restrict__
             const T *u = img + kj * nq0, *b = b0 + p * nq0;
             T a = u[0] * b[0];
             for (int i = 1; i < nq0; ++i)
-                a = gfma(u[i], b[i], a);
+                a = sfma(u[i], b[i], a);
             w1[x] = a;
         }
         __syncthreads();
@@ -65,7 +57,7 @@ __global__ __launch_bounds__(NT) void iprod_generic_kernel(const T *__restrict__
                 const T *b = b1 + q * nq1;
                 T a = w1[p] * b[0];
                 for (int j = 1; j < nq1; ++j)
-                    a = gfma(w1[j * nm0 + p], b[j], a);
+                    a = sfma(w1[j * nm0 + p], b[j], a);
                 dst[x] = a;
             }
         }
@@ -79,7 +71,7 @@ __global__ __launch_bounds__(NT) void iprod_generic_kernel(const T *__restrict__
                 const T *u = w1 + k * nq1 * nm0 + p, *b = b1 + q * nq1;
                 T a = u[0] * b[0];
                 for (int j = 1; j < nq1; ++j)
-                    a = gfma(u[j * nm0], b[j], a);
+                    a = sfma(u[j * nm0], b[j], a);
                 img[x] = a;
             }
             __syncthreads();
@@ -91,7 +83,7 @@ __global__ __launch_bounds__(NT) void iprod_generic_kernel(const T *__restrict__
                 const T *u = img + qp, *b = b2 + r * nq2;
                 T a = u[0] * b[0];
                 for (int k = 1; k < nq2; ++k)
-                    a = gfma(u[k * nqp], b[k], a);
+                    a = sfma(u[k * nqp], b[k], a);
                 dst[x] = a;
             }
         }
@@ -99,44 +91,22 @@ __global__ __launch_bounds__(NT) void iprod_generic_kernel(const T *__restrict__
     }
 }
 
-template <typename T, int DIM>
-static int launch_iprod_generic(unsigned nq0, unsigned nq1, unsigned nq2, const T *b0, const T *b1, const T *b2,
-                                const T *in, T *out, uint64_t nelmt, hipStream_t s)
+template <int DIM, typename T> int launch_iprod_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, hipStream_t s)
 {
-    const unsigned mx = DIM == 3 ? kIprodMax3D : kIprodMax2D;
-    if (nq0 > mx || nq1 > mx || (DIM == 3 && nq2 > mx))
+    if (!iprod_generic_built(DIM, nq[0], nq[1], nq[2]))
         return SF_ENOTBUILT;
-    if (nelmt == 0)
+    if (a.nelmt == 0)
         return SF_OK;
-    const unsigned nz   = DIM == 3 ? nq2 : 1;
-    const unsigned need = nq0 * nq1 * nz + (nq0 - 1) * nq1 * nz;
-    const unsigned grid = nelmt < (1ull << 22) ? (unsigned)nelmt : (1u << 22);
-    if (need <= (unsigned)kIprodSmallCap)
-        iprod_generic_kernel<T, DIM, kIprodSmallCap, 64>
-            <<<grid, 64, 0, s>>>(b0, b1, b2, in, out, nelmt, (int)nq0, (int)nq1, (int)nq2);
-    else
-        iprod_generic_kernel<T, DIM, kIprodLargeCap, 256>
-            <<<grid, 256, 0, s>>>(b0, b1, b2, in, out, nelmt, (int)nq0, (int)nq1, (int)nq2);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
+    const unsigned nz   = DIM == 3 ? nq[2] : 1;
+    const unsigned need = nq[0] * nq[1] * nz + (nq[0] - 1) * nq[1] * nz;
+    return launch_lds_class(need <= (unsigned)kIprodSmallCap, iprod_generic_kernel<T, DIM, kIprodSmallCap, 64>,
+                            iprod_generic_kernel<T, DIM, kIprodLargeCap, 256>, a.nelmt, s, a.b0, a.b1, basis2(a), a.in,
+                            a.out, a.nelmt, (int)nq[0], (int)nq[1], (int)nq[2]);
 }
-
-int launch_hex_iprod_generic(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, hipStream_t s)
-{
-    return launch_iprod_generic<double, 3>(nq0, nq1, nq2, a.b0, a.b1, a.b2, a.in, a.out, a.nelmt, s);
-}
-int launch_hex_iprod_generic_f32(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgsT<float> &a, hipStream_t s)
-{
-    return launch_iprod_generic<float, 3>(nq0, nq1, nq2, a.b0, a.b1, a.b2, a.in, a.out, a.nelmt, s);
-}
-int launch_quad_iprod_generic(unsigned nq0, unsigned nq1, const QuadArgs &a, hipStream_t s)
-{
-    return launch_iprod_generic<double, 2>(nq0, nq1, 0, a.b0, a.b1, nullptr, a.in, a.out, a.nelmt, s);
-}
-int launch_quad_iprod_generic_f32(unsigned nq0, unsigned nq1, const QuadArgsT<float> &a, hipStream_t s)
-{
-    return launch_iprod_generic<float, 2>(nq0, nq1, 0, a.b0, a.b1, nullptr, a.in, a.out, a.nelmt, s);
-}
+template int launch_iprod_generic<3, double>(const unsigned (&)[3], const HexArgs &, hipStream_t);
+template int launch_iprod_generic<3, float>(const unsigned (&)[3], const HexArgsT<float> &, hipStream_t);
+template int launch_iprod_generic<2, double>(const unsigned (&)[3], const QuadArgs &, hipStream_t);
+template int launch_iprod_generic<2, float>(const unsigned (&)[3], const QuadArgsT<float> &, hipStream_t);
 
 bool iprod_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2)
 {

@@ -5,29 +5,10 @@
 namespace sf
 {
 
-// SF_ENOTBUILT when the order has no instantiation (3D isotropic nq 2..11, 2D isotropic nq 2..16)
-int launch_hex_mass_wave_nq(unsigned nq, const HexArgs &a, const double *w, hipStream_t s)
-{
-    switch (nq)
-    {
-#define SF_CASE(N) case N: return go_hex_mass<N, double>(a, w, s);
-        SF_MASS_HEX_CASES(SF_CASE)
-#undef SF_CASE
-    default: return SF_ENOTBUILT;
-    }
-}
+template int launch_mass_wave<3, double>(unsigned, const HexArgs &, const double *, hipStream_t);
+template int launch_mass_wave<2, double>(unsigned, const QuadArgs &, const double *, hipStream_t);
 
-int launch_quad_mass_wave_nq(unsigned nq, const QuadArgs &a, const double *w, hipStream_t s)
-{
-    switch (nq)
-    {
-#define SF_CASE(N) case N: return go_quad_mass<N, double>(a, w, s);
-        SF_MASS_QUAD_CASES(SF_CASE)
-#undef SF_CASE
-    default: return SF_ENOTBUILT;
-    }
-}
-
+// 3D isotropic nq 2..11, 2D isotropic nq 2..16
 bool mass_wave_built(int dim, unsigned nq)
 {
     return nq >= 2 && nq <= (dim == 3 ? 11u : 16u);

@@ -5,26 +5,7 @@
 namespace sf
 {
 
-int launch_hex_mass_wave_f32_nq(unsigned nq, const HexArgsT<float> &a, const float *w, hipStream_t s)
-{
-    switch (nq)
-    {
-#define SF_CASE(N) case N: return go_hex_mass<N, float>(a, w, s);
-        SF_MASS_HEX_CASES(SF_CASE)
-#undef SF_CASE
-    default: return SF_ENOTBUILT;
-    }
-}
-
-int launch_quad_mass_wave_f32_nq(unsigned nq, const QuadArgsT<float> &a, const float *w, hipStream_t s)
-{
-    switch (nq)
-    {
-#define SF_CASE(N) case N: return go_quad_mass<N, float>(a, w, s);
-        SF_MASS_QUAD_CASES(SF_CASE)
-#undef SF_CASE
-    default: return SF_ENOTBUILT;
-    }
-}
+template int launch_mass_wave<3, float>(unsigned, const HexArgsT<float> &, const float *, hipStream_t);
+template int launch_mass_wave<2, float>(unsigned, const QuadArgsT<float> &, const float *, hipStream_t);
 
 } // namespace sf

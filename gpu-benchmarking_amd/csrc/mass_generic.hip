@@ -13,7 +13,7 @@
 // (fp32: 4-byte) aligned are fine.  No workspace: every launch is a single kernel node, capture-safe from the first
 // call.  Latency-bound (a barrier per sweep, one element per workgroup), not a roofline target.  Extents up to 16 per
 // direction in 3D and 32 in 2D; beyond, SF_ENOTBUILT.
-#include "sf_dispatch.h"
+#include "any_extent.h"
 
 namespace sf
 {
@@ -21,24 +21,6 @@ namespace sf
 // LDS classes in scalars (those of iproduct_generic.hip).  3D 16^3: 4096 + 3840 = 7936; 2D 32^2: 1024 + 992.
 constexpr int kMassSmallCap = 2048, kMassLargeCap = 7936;
 constexpr unsigned kMassMax3D = 16, kMassMax2D = 32;
-
-__device__ __forceinline__ double mfma_s(double a, double b, double c)
-{
-    return __builtin_fma(a, b, c);
-}
-__device__ __forceinline__ float mfma_s(float a, float b, float c)
-{
-    return __builtin_fmaf(a, b, c);
-}
-
-// a = sum_{m < n} u[m*us] * b[m*bs], ascending m, the first product a multiply
-template <typename T> __device__ __forceinline__ T dot_strided(const T *u, int us, const T *b, int bs, int n)
-{
-    T a = u[0] * b[0];
-    for (int m = 1; m < n; ++m)
-        a = mfma_s(u[m * us], b[m * bs], a);
-    return a;
-}
 
 template <typename T, int DIM, int CAP, int NT>
 __global__ __launch_bounds__(NT) void mass_generic_kernel(const T *__restrict__ b0, const T *__restrict__ b1,
@@ -158,45 +140,23 @@ static void mass_regions(int dim, unsigned nq0, unsigned nq1, unsigned nq2, unsi
     }
 }
 
-template <typename T, int DIM>
-static int launch_mass_generic(unsigned nq0, unsigned nq1, unsigned nq2, const T *b0, const T *b1, const T *b2,
-                               const T *w, const T *in, T *out, uint64_t nelmt, hipStream_t s)
+template <int DIM, typename T>
+int launch_mass_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const T *w, hipStream_t s)
 {
-    if (!mass_generic_built(DIM, nq0, nq1, nq2))
+    if (!mass_generic_built(DIM, nq[0], nq[1], nq[2]))
         return SF_ENOTBUILT;
-    if (nelmt == 0)
+    if (a.nelmt == 0)
         return SF_OK;
     unsigned sizeA, sizeB;
-    mass_regions(DIM, nq0, nq1, nq2, sizeA, sizeB);
-    const unsigned need = sizeA + sizeB;
-    const unsigned grid = nelmt < (1ull << 22) ? (unsigned)nelmt : (1u << 22);
-    if (need <= (unsigned)kMassSmallCap)
-        mass_generic_kernel<T, DIM, kMassSmallCap, 64>
-            <<<grid, 64, 0, s>>>(b0, b1, b2, w, in, out, nelmt, (int)nq0, (int)nq1, (int)nq2, (int)sizeA);
-    else
-        mass_generic_kernel<T, DIM, kMassLargeCap, 256>
-            <<<grid, 256, 0, s>>>(b0, b1, b2, w, in, out, nelmt, (int)nq0, (int)nq1, (int)nq2, (int)sizeA);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
+    mass_regions(DIM, nq[0], nq[1], nq[2], sizeA, sizeB);
+    return launch_lds_class(sizeA + sizeB <= (unsigned)kMassSmallCap, mass_generic_kernel<T, DIM, kMassSmallCap, 64>,
+                            mass_generic_kernel<T, DIM, kMassLargeCap, 256>, a.nelmt, s, a.b0, a.b1, basis2(a), w, a.in,
+                            a.out, a.nelmt, (int)nq[0], (int)nq[1], (int)nq[2], (int)sizeA);
 }
-
-int launch_hex_mass_generic(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, const double *w, hipStream_t s)
-{
-    return launch_mass_generic<double, 3>(nq0, nq1, nq2, a.b0, a.b1, a.b2, w, a.in, a.out, a.nelmt, s);
-}
-int launch_hex_mass_generic_f32(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgsT<float> &a, const float *w,
-                                hipStream_t s)
-{
-    return launch_mass_generic<float, 3>(nq0, nq1, nq2, a.b0, a.b1, a.b2, w, a.in, a.out, a.nelmt, s);
-}
-int launch_quad_mass_generic(unsigned nq0, unsigned nq1, const QuadArgs &a, const double *w, hipStream_t s)
-{
-    return launch_mass_generic<double, 2>(nq0, nq1, 0, a.b0, a.b1, nullptr, w, a.in, a.out, a.nelmt, s);
-}
-int launch_quad_mass_generic_f32(unsigned nq0, unsigned nq1, const QuadArgsT<float> &a, const float *w, hipStream_t s)
-{
-    return launch_mass_generic<float, 2>(nq0, nq1, 0, a.b0, a.b1, nullptr, w, a.in, a.out, a.nelmt, s);
-}
+template int launch_mass_generic<3, double>(const unsigned (&)[3], const HexArgs &, const double *, hipStream_t);
+template int launch_mass_generic<3, float>(const unsigned (&)[3], const HexArgsT<float> &, const float *, hipStream_t);
+template int launch_mass_generic<2, double>(const unsigned (&)[3], const QuadArgs &, const double *, hipStream_t);
+template int launch_mass_generic<2, float>(const unsigned (&)[3], const QuadArgsT<float> &, const float *, hipStream_t);
 
 // within the extent bounds AND the two regions fit the large LDS class (true for every extent within the bounds:
 // 3D 16^3 needs 4096 + 3840, 2D 32^2 1024 + 992; derived all the same, not assumed)

@@ -17,44 +17,19 @@
 namespace sf
 {
 
-template <int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP, int MEMF, typename T>
-static int launch_hex_mass(const HexArgsT<T> &a, const T *w, hipStream_t s)
+template <int DIM, int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP, int MEMF, typename T>
+static int launch_mass(const ArgsT<DIM, T> &a, const T *w, hipStream_t s)
 {
     static OccCache cache = {};
-    auto kern            = hex_mass_wave_kernel<NQ, EC, WPB, BMODE, MINW, KMAP, OUT_LDS, MEMF, T>;
-    constexpr size_t lds = mass_lds_bytes<NQ, EC, 3, WPB, T>();
+    constexpr size_t lds = mass_lds_bytes<NQ, EC, DIM, WPB, T>();
     static_assert(lds <= 160 * 1024, "LDS slab exceeds 160 KiB");
-    if (a.nelmt == 0)
-        return SF_OK;
-    const uint64_t nchunk = (a.nelmt + EC - 1) / EC;
-    const uint64_t per    = (uint64_t)WPB * KMAP;
-    const uint64_t grid   = (nchunk + per - 1) / per;
-    (void)resident_blocks(kern, kWave * WPB, lds, cache); // raises the kernel's LDS limit once per device
-    if (grid > 0x7fffffffull)
-        return SF_EINVAL;
-    kern<<<(unsigned)grid, kWave * WPB, lds, s>>>(a.b0, a.b1, a.b2, w, a.in, a.out, a.nelmt);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
-}
-
-template <int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP, int MEMF, typename T>
-static int launch_quad_mass(const QuadArgsT<T> &a, const T *w, hipStream_t s)
-{
-    static OccCache cache = {};
-    auto kern            = quad_mass_wave_kernel<NQ, EC, WPB, BMODE, MINW, KMAP, OUT_LDS, MEMF, T>;
-    constexpr size_t lds = mass_lds_bytes<NQ, EC, 2, WPB, T>();
-    static_assert(lds <= 160 * 1024, "LDS slab exceeds 160 KiB");
-    if (a.nelmt == 0)
-        return SF_OK;
-    const uint64_t nchunk = (a.nelmt + EC - 1) / EC;
-    const uint64_t per    = (uint64_t)WPB * KMAP;
-    const uint64_t grid   = (nchunk + per - 1) / per;
-    (void)resident_blocks(kern, kWave * WPB, lds, cache);
-    if (grid > 0x7fffffffull)
-        return SF_EINVAL;
-    kern<<<(unsigned)grid, kWave * WPB, lds, s>>>(a.b0, a.b1, w, a.in, a.out, a.nelmt);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
+    static_assert(KMAP > 0, "short-lived waves: the grid covers the batch");
+    if constexpr (DIM == 3)
+        return launch_chunked<WPB, EC, KMAP>(hex_mass_wave_kernel<NQ, EC, WPB, BMODE, MINW, KMAP, OUT_LDS, MEMF, T>,
+                                             cache, lds, 0, s, a.nelmt, a.b0, a.b1, a.b2, w, a.in, a.out, a.nelmt);
+    else
+        return launch_chunked<WPB, EC, KMAP>(quad_mass_wave_kernel<NQ, EC, WPB, BMODE, MINW, KMAP, OUT_LDS, MEMF, T>,
+                                             cache, lds, 0, s, a.nelmt, a.b0, a.b1, w, a.in, a.out, a.nelmt);
 }
 
 // the BwdTrans row of the order unless overridden below
@@ -65,18 +40,32 @@ template <int NQ, typename T> struct MassQuadCfg : std::conditional<sizeof(T) ==
 {
 };
 
-template <int NQ, typename T> static int go_hex_mass(const HexArgsT<T> &a, const T *w, hipStream_t s)
+template <int DIM, int NQ, typename T> static int go_mass(const ArgsT<DIM, T> &a, const T *w, hipStream_t s)
 {
-    using C = MassHexCfg<NQ, T>;
-    return launch_hex_mass<NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, (C::MF | 8), T>(a, w, s);
-}
-template <int NQ, typename T> static int go_quad_mass(const QuadArgsT<T> &a, const T *w, hipStream_t s)
-{
-    using C = MassQuadCfg<NQ, T>;
-    return launch_quad_mass<NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, (C::MF | 8), T>(a, w, s);
+    using C = typename std::conditional<DIM == 3, MassHexCfg<NQ, T>, MassQuadCfg<NQ, T>>::type;
+    return launch_mass<DIM, NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, (C::MF | 8), T>(a, w, s);
 }
 
 #define SF_MASS_HEX_CASES(F) F(2) F(3) F(4) F(5) F(6) F(7) F(8) F(9) F(10) F(11)
 #define SF_MASS_QUAD_CASES(F) F(2) F(3) F(4) F(5) F(6) F(7) F(8) F(9) F(10) F(11) F(12) F(13) F(14) F(15) F(16)
+
+// SF_ENOTBUILT when the order has no instantiation (mass_wave_built()); instantiated for double in mass.hip and for float
+// in mass_f32.hip
+template <int DIM, typename T> int launch_mass_wave(unsigned nq, const ArgsT<DIM, T> &a, const T *w, hipStream_t s)
+{
+#define SF_CASE(N) case N: return go_mass<DIM, N, T>(a, w, s);
+    if constexpr (DIM == 3)
+        switch (nq)
+        {
+            SF_MASS_HEX_CASES(SF_CASE)
+        }
+    else
+        switch (nq)
+        {
+            SF_MASS_QUAD_CASES(SF_CASE)
+        }
+#undef SF_CASE
+    return SF_ENOTBUILT;
+}
 
 } // namespace sf

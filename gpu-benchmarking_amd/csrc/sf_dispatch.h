@@ -6,6 +6,7 @@
 #include "sf_common.h"
 
 #include <mutex>
+#include <type_traits>
 
 namespace sf
 {
@@ -63,55 +64,40 @@ int launch_specialised(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int sc
                        const void *b1, const void *b2, const void *in, void *out, uint64_t nelmt, hipStream_t s);
 const char *rtc_last_log();
 int rtc_release();
-// IProductWRTBase (iproduct.hip: the wave kernels, SF_ENOTBUILT off their table -- 3D isotropic nq 2..11, 2D 2..16;
-// iproduct_generic.hip: any extents up to 16 per direction in 3D and 32 in 2D, SF_ENOTBUILT beyond)
-int launch_hex_iprod_wave_nq(unsigned nq, const HexArgs &a, hipStream_t s);
-int launch_hex_iprod_wave_f32_nq(unsigned nq, const HexArgsT<float> &a, hipStream_t s);
-int launch_quad_iprod_wave_nq(unsigned nq, const QuadArgs &a, hipStream_t s);
-int launch_quad_iprod_wave_f32_nq(unsigned nq, const QuadArgsT<float> &a, hipStream_t s);
+// IProductWRTBase, the fused mass operator and the fused Helmholtz operator have one pair of entry points each, for both
+// dimensions and both scalar types: the wave kernels of an isotropic order (SF_ENOTBUILT off their table) and the
+// any-extent kernels (nq[2] is 0 in 2D; SF_ENOTBUILT beyond their bounds).  Each is defined for <3, T> and <2, T> in the
+// translation unit that holds the kernels of T.
+template <int DIM, typename T> using ArgsT = typename std::conditional<DIM == 3, HexArgsT<T>, QuadArgsT<T>>::type;
+// IProductWRTBase (iproduct.hip: the wave kernels, 3D nq 2..11, 2D 2..16; iproduct_generic.hip: any extents up to 16 per
+// direction in 3D and 32 in 2D)
+template <int DIM, typename T> int launch_iprod_wave(unsigned nq, const ArgsT<DIM, T> &a, hipStream_t s);
+template <int DIM, typename T> int launch_iprod_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, hipStream_t s);
 bool iprod_wave_built(int dim, unsigned nq);
-int launch_hex_iprod_generic(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, hipStream_t s);
-int launch_hex_iprod_generic_f32(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgsT<float> &a, hipStream_t s);
-int launch_quad_iprod_generic(unsigned nq0, unsigned nq1, const QuadArgs &a, hipStream_t s);
-int launch_quad_iprod_generic_f32(unsigned nq0, unsigned nq1, const QuadArgsT<float> &a, hipStream_t s);
 bool iprod_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
-// The fused mass operator B^T diag(w) B (mass.hip / mass_f32.hip: the wave kernels of mass_wave.h, SF_ENOTBUILT off their
-// table -- 3D isotropic nq 2..11, 2D 2..16; mass_generic.hip: any extents up to 16 per direction in 3D and 32 in 2D,
-// SF_ENOTBUILT beyond).  `w`: one weight per quadrature point per element; a.wsp is not used.
-int launch_hex_mass_wave_nq(unsigned nq, const HexArgs &a, const double *w, hipStream_t s);
-int launch_hex_mass_wave_f32_nq(unsigned nq, const HexArgsT<float> &a, const float *w, hipStream_t s);
-int launch_quad_mass_wave_nq(unsigned nq, const QuadArgs &a, const double *w, hipStream_t s);
-int launch_quad_mass_wave_f32_nq(unsigned nq, const QuadArgsT<float> &a, const float *w, hipStream_t s);
+// The fused mass operator B^T diag(w) B (mass.hip / mass_f32.hip: the wave kernels of mass_wave.h, 3D nq 2..11, 2D 2..16;
+// mass_generic.hip: any extents up to 16 per direction in 3D and 32 in 2D).  `w`: one weight per quadrature point per
+// element; a.wsp is not used.
+template <int DIM, typename T>
+int launch_mass_wave(unsigned nq, const ArgsT<DIM, T> &a, const T *w, hipStream_t s);
+template <int DIM, typename T>
+int launch_mass_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const T *w, hipStream_t s);
 bool mass_wave_built(int dim, unsigned nq);
-int launch_hex_mass_generic(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, const double *w, hipStream_t s);
-int launch_hex_mass_generic_f32(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgsT<float> &a, const float *w,
-                                hipStream_t s);
-int launch_quad_mass_generic(unsigned nq0, unsigned nq1, const QuadArgs &a, const double *w, hipStream_t s);
-int launch_quad_mass_generic_f32(unsigned nq0, unsigned nq1, const QuadArgsT<float> &a, const float *w, hipStream_t s);
 bool mass_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
 // The fused Helmholtz operator B^T [lambda diag(w) + sum_ab D_a^T diag(G_ab) D_b] B (helmholtz.hip / helmholtz_f32.hip:
-// the wave kernels of helmholtz_wave.h, SF_ENOTBUILT off their table -- 3D isotropic nq 2..8, 2D 2..16;
-// helmholtz_generic.hip: any extents up to 12 per direction in 3D and 32 in 2D, SF_ENOTBUILT beyond).  What the operator
-// takes beyond the BwdTrans arguments: the derivative matrices, the metric planes, the mass weight (null: lambda == 0,
-// never read) and lambda in the scalar type.
+// the wave kernels of helmholtz_wave.h, 3D nq 2..8, 2D 2..16; helmholtz_generic.hip: any extents up to 12 per direction
+// in 3D and 32 in 2D).  What the operator takes beyond the BwdTrans arguments: the derivative matrices, the metric
+// planes, the mass weight (null: lambda == 0, never read) and lambda in the scalar type.
 template <typename T> struct HelmArgsT
 {
     const T *d0, *d1, *d2, *g, *w;
     T lam;
 };
-int launch_hex_helmholtz_wave_nq(unsigned nq, const HexArgs &a, const HelmArgsT<double> &x, hipStream_t s);
-int launch_hex_helmholtz_wave_f32_nq(unsigned nq, const HexArgsT<float> &a, const HelmArgsT<float> &x, hipStream_t s);
-int launch_quad_helmholtz_wave_nq(unsigned nq, const QuadArgs &a, const HelmArgsT<double> &x, hipStream_t s);
-int launch_quad_helmholtz_wave_f32_nq(unsigned nq, const QuadArgsT<float> &a, const HelmArgsT<float> &x, hipStream_t s);
+template <int DIM, typename T>
+int launch_helmholtz_wave(unsigned nq, const ArgsT<DIM, T> &a, const HelmArgsT<T> &x, hipStream_t s);
+template <int DIM, typename T>
+int launch_helmholtz_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const HelmArgsT<T> &x, hipStream_t s);
 bool helmholtz_wave_built(int dim, unsigned nq);
-int launch_hex_helmholtz_generic(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, const HelmArgsT<double> &x,
-                                 hipStream_t s);
-int launch_hex_helmholtz_generic_f32(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgsT<float> &a,
-                                     const HelmArgsT<float> &x, hipStream_t s);
-int launch_quad_helmholtz_generic(unsigned nq0, unsigned nq1, const QuadArgs &a, const HelmArgsT<double> &x,
-                                  hipStream_t s);
-int launch_quad_helmholtz_generic_f32(unsigned nq0, unsigned nq1, const QuadArgsT<float> &a, const HelmArgsT<float> &x,
-                                      hipStream_t s);
 bool helmholtz_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
 int sumsq_f32_blocking(const float *x, size_t n, double *result_host, hipStream_t s);
 int fill_sincos_f32(float *in, size_t nelmt, size_t nm_tot, hipStream_t s);

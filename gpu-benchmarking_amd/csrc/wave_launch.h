@@ -49,17 +49,18 @@ template <class K> inline int resident_blocks(K kern, int threads, size_t lds, s
     return cached * device_info().num_cu;
 }
 
-template <int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP = 0, int OUTM = OUT_ST8, int MEMF = 0,
-          typename T = double>
-inline int launch_hex_wave(const HexArgsT<T> &a, hipStream_t s, int grid_override = 0)
+// The one chunked launch behind every launcher below and those of iproduct.hip, mass_launch.h and helmholtz_launch.h.
+// A chunk is EC elements (1: the kernel counts elements), a workgroup has WPB waves; KMAP != 0: short-lived waves of
+// |KMAP| chunks each on a grid that covers the batch; KMAP == 0: a persistent grid of the resident workgroups (or
+// grid_override), never more than there are chunks.  `cache` is the occupancy cache of this kernel instantiation; the
+// occupancy query runs on every path because it also raises the kernel's LDS limit, once per device.
+template <int WPB, int EC, int KMAP, class K, class... A>
+inline int launch_chunked(K kern, std::atomic<int> *cache, size_t lds, int grid_override, hipStream_t s, uint64_t nelmt,
+                          A... args)
 {
-    static OccCache cache = {};
-    auto kern            = hex_wave_kernel<NQ, EC, WPB, BMODE, MINW, KMAP, OUTM, MEMF, T>;
-    constexpr size_t lds = wave_lds_bytes<NQ, EC, 3, WPB, BMODE, OUTM, T>();
-    static_assert(lds <= 160 * 1024, "LDS slab exceeds 160 KiB");
-    if (a.nelmt == 0)
+    if (nelmt == 0)
         return SF_OK;
-    const uint64_t nchunk = (a.nelmt + EC - 1) / EC;
+    const uint64_t nchunk = (nelmt + EC - 1) / EC;
     const uint64_t per    = (uint64_t)WPB * (KMAP > 0 ? KMAP : (KMAP < 0 ? -KMAP : 1));
     const uint64_t need   = (nchunk + per - 1) / per;
     uint64_t grid         = (uint64_t)resident_blocks(kern, kWave * WPB, lds, cache);
@@ -69,9 +70,20 @@ inline int launch_hex_wave(const HexArgsT<T> &a, hipStream_t s, int grid_overrid
         grid = need;
     if (grid > 0x7fffffffull)
         return SF_EINVAL;
-    kern<<<(unsigned)grid, kWave * WPB, lds, s>>>(a.b0, a.b1, a.b2, a.in, a.out, a.nelmt);
+    kern<<<(unsigned)grid, kWave * WPB, lds, s>>>(args...);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? SF_OK : (int)e;
+}
+
+template <int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP = 0, int OUTM = OUT_ST8, int MEMF = 0,
+          typename T = double>
+inline int launch_hex_wave(const HexArgsT<T> &a, hipStream_t s, int grid_override = 0)
+{
+    static OccCache cache = {};
+    constexpr size_t lds = wave_lds_bytes<NQ, EC, 3, WPB, BMODE, OUTM, T>();
+    static_assert(lds <= 160 * 1024, "LDS slab exceeds 160 KiB");
+    return launch_chunked<WPB, EC, KMAP>(hex_wave_kernel<NQ, EC, WPB, BMODE, MINW, KMAP, OUTM, MEMF, T>, cache, lds,
+                                         grid_override, s, a.nelmt, a.b0, a.b1, a.b2, a.in, a.out, a.nelmt);
 }
 
 template <int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP = 0, int OUTM = OUT_ST8, int MEMF = 0,
@@ -79,48 +91,20 @@ template <int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP = 0, int OUTM =
 inline int launch_quad_wave(const QuadArgsT<T> &a, hipStream_t s, int grid_override = 0)
 {
     static OccCache cache = {};
-    auto kern            = quad_wave_kernel<NQ, EC, WPB, BMODE, MINW, KMAP, OUTM, MEMF, T>;
     constexpr size_t lds = wave_lds_bytes<NQ, EC, 2, WPB, BMODE, OUTM, T>();
     static_assert(lds <= 160 * 1024, "LDS slab exceeds 160 KiB");
-    if (a.nelmt == 0)
-        return SF_OK;
-    const uint64_t nchunk = (a.nelmt + EC - 1) / EC;
-    const uint64_t per    = (uint64_t)WPB * (KMAP > 0 ? KMAP : (KMAP < 0 ? -KMAP : 1));
-    const uint64_t need   = (nchunk + per - 1) / per;
-    uint64_t grid         = (uint64_t)resident_blocks(kern, kWave * WPB, lds, cache);
-    if (grid_override > 0)
-        grid = (uint64_t)grid_override;
-    if (grid > need || KMAP != 0)
-        grid = need;
-    if (grid > 0x7fffffffull)
-        return SF_EINVAL;
-    kern<<<(unsigned)grid, kWave * WPB, lds, s>>>(a.b0, a.b1, a.in, a.out, a.nelmt);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
+    return launch_chunked<WPB, EC, KMAP>(quad_wave_kernel<NQ, EC, WPB, BMODE, MINW, KMAP, OUTM, MEMF, T>, cache, lds,
+                                         grid_override, s, a.nelmt, a.b0, a.b1, a.in, a.out, a.nelmt);
 }
 
 template <int NQ, int EC, int WPB, int MINW, int KMAP, bool OUTL = false, int XG = 0, typename T = double>
 inline int launch_quad_mfma(const QuadArgsT<T> &a, hipStream_t s, int grid_override = 0)
 {
     static OccCache cache = {};
-    auto kern            = quad_mfma_kernel<NQ, EC, WPB, MINW, KMAP, OUTL, XG, T>;
     constexpr size_t lds = mfma_lds_bytes<NQ, EC, WPB, T>();
     static_assert(lds <= 160 * 1024, "LDS slab exceeds 160 KiB");
-    if (a.nelmt == 0)
-        return SF_OK;
-    const uint64_t nchunk = (a.nelmt + EC - 1) / EC;
-    const uint64_t per    = (uint64_t)WPB * (KMAP > 0 ? KMAP : (KMAP < 0 ? -KMAP : 1));
-    const uint64_t need   = (nchunk + per - 1) / per;
-    uint64_t grid         = (uint64_t)resident_blocks(kern, kWave * WPB, lds, cache);
-    if (grid_override > 0)
-        grid = (uint64_t)grid_override;
-    if (grid > need || KMAP != 0)
-        grid = need;
-    if (grid > 0x7fffffffull)
-        return SF_EINVAL;
-    kern<<<(unsigned)grid, kWave * WPB, lds, s>>>(a.b0, a.b1, a.in, a.out, a.nelmt);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
+    return launch_chunked<WPB, EC, KMAP>(quad_mfma_kernel<NQ, EC, WPB, MINW, KMAP, OUTL, XG, T>, cache, lds,
+                                         grid_override, s, a.nelmt, a.b0, a.b1, a.in, a.out, a.nelmt);
 }
 
 template <int NQ, int EB, int WPB, int MINW, int GJ, int KMAP, int XG, bool SHB, int DYNB, bool PEEL = true, bool SPLIT = false,
@@ -132,35 +116,20 @@ inline int launch_quad_mfma4_impl(const QuadArgs &a, hipStream_t s)
     constexpr size_t lds = mfma4_lds_bytes<NQ, EB, WPB, SHB>();
     static_assert(lds <= 160 * 1024, "LDS slab exceeds 160 KiB");
     static_assert(DYNB == 0 || KMAP == 0, "the batch counter feeds a persistent grid");
-    const uint64_t nchunk = (a.nelmt + EB - 1) / EB;
-    const uint64_t per    = (uint64_t)WPB * (KMAP > 0 ? KMAP : (KMAP < 0 ? -KMAP : 1));
-    const uint64_t need   = (nchunk + per - 1) / per;
-    uint64_t grid         = (uint64_t)resident_blocks(kern, kWave * WPB, lds, cache); // also raises the LDS limit
-    if (grid > need || KMAP != 0)
-        grid = need;
-    if (grid > 0x7fffffffull)
-        return SF_EINVAL;
+    unsigned long long *ctr = nullptr;
     if constexpr (DYNB > 0)
     {
         // the batch counter comes from the device's counter ring (never evicted: a pointer baked into a captured graph
         // stays valid until sf_shutdown); no counter to be had (ring exhausted, or first use inside a capture) -> the
         // same kernel with a fixed share per wave
-        unsigned long long *ctr = nullptr;
         if (counter_acquire(s, &ctr) != SF_OK)
             return launch_quad_mfma4_impl<NQ, EB, WPB, MINW, GJ, KMAP, XG, SHB, 0, PEEL, SPLIT, 0>(a, s);
         // zeroed by a one-thread kernel, not a memset: under stream capture a memset node on a pointer INSIDE an
         // allocation did not zero the counter on ROCm 7.2 (the replayed grid then saw a stale ticket and exited)
         counter_reset_kernel<<<1, 8, 0, s>>>(ctr);
-        kern<<<(unsigned)grid, kWave * WPB, lds, s>>>(a.b0, a.b1, a.in, a.out, a.nelmt, ctr, nullptr);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? SF_OK : (int)e;
     }
-    else
-    {
-        kern<<<(unsigned)grid, kWave * WPB, lds, s>>>(a.b0, a.b1, a.in, a.out, a.nelmt, nullptr, nullptr);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? SF_OK : (int)e;
-    }
+    return launch_chunked<WPB, EB, KMAP>(kern, cache, lds, 0, s, a.nelmt, a.b0, a.b1, a.in, a.out, a.nelmt, ctr,
+                                         (unsigned long long *)nullptr);
 }
 
 // SHBONLY: the configuration only fits the LDS with one basis copy (b0 == b1)
@@ -182,47 +151,21 @@ template <int NQ, int EC, int WPB, int MINW, int KMAP, int XG = 0, typename T = 
 inline int launch_hex_mfma(const HexArgsT<T> &a, hipStream_t s, int grid_override = 0)
 {
     static OccCache cache = {};
-    auto kern            = hex_mfma_kernel<NQ, EC, WPB, MINW, KMAP, XG, T>;
     constexpr size_t lds = hex_mfma_lds_bytes<NQ, EC, WPB, T>();
     static_assert(lds <= 160 * 1024, "LDS slab exceeds 160 KiB");
-    if (a.nelmt == 0)
-        return SF_OK;
-    const uint64_t nchunk = (a.nelmt + EC - 1) / EC;
-    const uint64_t per    = (uint64_t)WPB * (KMAP > 0 ? KMAP : (KMAP < 0 ? -KMAP : 1));
-    const uint64_t need   = (nchunk + per - 1) / per;
-    uint64_t grid         = (uint64_t)resident_blocks(kern, kWave * WPB, lds, cache);
-    if (grid_override > 0)
-        grid = (uint64_t)grid_override;
-    if (grid > need || KMAP != 0)
-        grid = need;
-    if (grid > 0x7fffffffull)
-        return SF_EINVAL;
-    kern<<<(unsigned)grid, kWave * WPB, lds, s>>>(a.b0, a.b1, a.b2, a.in, a.out, a.nelmt);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
+    return launch_chunked<WPB, EC, KMAP>(hex_mfma_kernel<NQ, EC, WPB, MINW, KMAP, XG, T>, cache, lds, grid_override, s,
+                                         a.nelmt, a.b0, a.b1, a.b2, a.in, a.out, a.nelmt);
 }
 
+// one element per chunk
 template <int NQ, int WPB, int MINW, int KMAP, int XG = 0, bool DIRECT = false, bool NTS = true, bool PEEL = true>
 inline int launch_hex_mfma4(const HexArgs &a, hipStream_t s, int grid_override = 0)
 {
     static OccCache cache = {};
-    auto kern            = hex_mfma4_kernel<NQ, WPB, MINW, KMAP, XG, false, DIRECT, NTS, PEEL>;
     constexpr size_t lds = hex_mfma4_lds_bytes<NQ, WPB, DIRECT>();
     static_assert(lds <= 160 * 1024, "LDS slab exceeds 160 KiB");
-    if (a.nelmt == 0)
-        return SF_OK;
-    const uint64_t per  = (uint64_t)WPB * (KMAP > 0 ? KMAP : (KMAP < 0 ? -KMAP : 1));
-    const uint64_t need = (a.nelmt + per - 1) / per;
-    uint64_t grid       = (uint64_t)resident_blocks(kern, kWave * WPB, lds, cache);
-    if (grid_override > 0)
-        grid = (uint64_t)grid_override;
-    if (grid > need || KMAP != 0)
-        grid = need;
-    if (grid > 0x7fffffffull)
-        return SF_EINVAL;
-    kern<<<(unsigned)grid, kWave * WPB, lds, s>>>(a.b0, a.b1, a.b2, a.in, a.out, a.nelmt, nullptr);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
+    return launch_chunked<WPB, 1, KMAP>(hex_mfma4_kernel<NQ, WPB, MINW, KMAP, XG, false, DIRECT, NTS, PEEL>, cache, lds,
+                                        grid_override, s, a.nelmt, a.b0, a.b1, a.b2, a.in, a.out, a.nelmt, nullptr);
 }
 
 } // namespace sf
