@@ -18,5 +18,5 @@ from .bwdtrans import (  # noqa: F401
     stream_copy, device_info, interleave64, bwdtrans_hex_interleaved, fill_vecadd, vector_add, fill_matvec, matvec, hex_wsp_doubles, quad_wsp_doubles, VARIANTS,
     specialise, specialisation_state, specialise_log, bwdtrans_specialised,
     iproduct_hex, iproduct_quad, bwdtrans_autograd, mass_hex, mass_quad,
-    helmholtz_hex, helmholtz_quad,
+    helmholtz_hex, helmholtz_quad, affine_helmholtz_hex, affine_helmholtz_quad,
 )

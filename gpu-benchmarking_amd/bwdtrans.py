@@ -296,6 +296,84 @@ def helmholtz_quad(nq, basis0, basis1, deriv0, deriv1, g, w, lam, inp, out=None,
     return _helmholtz_call("helmholtz_quad", nq, (basis0, basis1), (deriv0, deriv1), g, w, lam, inp, out, variant, stream)
 
 
+def _affine_call(what, nq, bases, derivs, qws, ge, je, lam, inp, out, variant, stream):
+    """Shared body of affine_helmholtz_hex / affine_helmholtz_quad: sizes, dtypes and devices checked here (before any
+    library call), pointers, alignment and overlap in the C ABI."""
+    nq = tuple(int(x) for x in nq)
+    dim = len(nq)
+    nmt = 1
+    for q in nq:
+        nmt *= q - 1
+    if nmt <= 0:
+        raise capi.SumfactError(capi.SF_EINVAL, what)
+    lam = float(lam)
+    nelmt = inp.numel() // nmt
+    if nelmt * nmt != inp.numel():
+        raise ValueError(f"{what}: in.numel() is not a multiple of the modes per element ({nmt})")
+    ncomp = dim * (dim + 1) // 2
+    if ge.numel() != nelmt * ncomp:
+        raise ValueError(f"{what}: ge has {ge.numel()} values, nelmt * {ncomp} = {nelmt * ncomp}")
+    if je is None:
+        if lam != 0.0:
+            raise ValueError(f"{what}: je=None needs lam == 0")
+    elif je.numel() != nelmt:
+        raise ValueError(f"{what}: je has {je.numel()} values, nelmt = {nelmt}")
+    named = ((("ge", ge), ("je", je)) + tuple((f"deriv{d}", t) for d, t in enumerate(derivs))
+             + tuple((f"qw{d}", t) for d, t in enumerate(qws)))
+    for name, t in named:
+        if t is None:
+            continue
+        if t.dtype != inp.dtype:
+            raise ValueError(f"{what}: {name} is {t.dtype}, in is {inp.dtype}")
+        if t.device != inp.device:
+            raise ValueError(f"{what}: {name} is on {t.device}, in is on {inp.device}")
+    for d, (t, qw, q) in enumerate(zip(derivs, qws, nq)):
+        if t.numel() != q * q:
+            raise ValueError(f"{what}: deriv{d} has {t.numel()} values, nq*nq = {q * q}")
+        if qw.numel() != q:
+            raise ValueError(f"{what}: qw{d} has {qw.numel()} values, nq = {q}")
+    if out is None:
+        out = torch.empty(nelmt * nmt, dtype=inp.dtype, device=inp.device)
+    elif out.numel() != nelmt * nmt:
+        raise ValueError(f"{what}: out has the wrong size")
+    _check_sizes(what, bases, nq, None, 0)
+    v = _variant(variant)
+    shape = "hex" if dim == 3 else "quad"
+    if inp.dtype == torch.float32:
+        if v != VARIANTS["auto"]:
+            raise ValueError(f"{what}: float32 has the AUTO route only")
+        fn, ptr, head = getattr(capi.lib(), f"sf_affine_helmholtz_{shape}_f32"), _dev_f32, ()
+    else:
+        fn, ptr, head = getattr(capi.lib(), f"sf_affine_helmholtz_{shape}_f64_variant"), _dev_f64, (v,)
+    with torch.cuda.device(inp.device):
+        rc = fn(*head, *nq, nelmt, *[ptr(b, f"basis{d}") for d, b in enumerate(bases)],
+                *[ptr(t, f"deriv{d}") for d, t in enumerate(derivs)], *[ptr(t, f"qw{d}") for d, t in enumerate(qws)],
+                ptr(ge, "ge"), ptr(je, "je") if je is not None else None, ctypes.c_double(lam), ptr(inp, "in"),
+                ptr(out, "out"), _stream(stream, inp.device))
+    capi.check(rc, what)
+    return out
+
+
+def affine_helmholtz_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, qw0, qw1, qw2, ge, je, lam, inp, out=None,
+                         variant="auto", stream=None):
+    """The fused Helmholtz operator on affine elements in one kernel, on inp's device: helmholtz_hex with
+    g[e][c][k][j][i] = ge[e][c] qw2[k] qw1[j] qw0[i] and w[e][k][j][i] = je[e] qw2[k] qw1[j] qw0[i].  The bases and
+    derivative matrices of helmholtz_hex; qw_d the nq_d one-dimensional quadrature weights; ge[e][c] with c = 0..5 for
+    (00, 01, 02, 11, 12, 22), the element's |det J| J^-1 J^-T; je[e] = |det J|, or None with lam == 0 (the Laplacian).
+    out may not overlap inp, ge or je.  float64 takes variant "auto", "wave" or "generic"; float32 the AUTO route.  A
+    plain function: no autograd."""
+    return _affine_call("affine_helmholtz_hex", nq, (basis0, basis1, basis2), (deriv0, deriv1, deriv2), (qw0, qw1, qw2),
+                        ge, je, lam, inp, out, variant, stream)
+
+
+def affine_helmholtz_quad(nq, basis0, basis1, deriv0, deriv1, qw0, qw1, ge, je, lam, inp, out=None, variant="auto",
+                          stream=None):
+    """The fused Helmholtz operator on affine elements in 2D: ge[e][c] with c = 0..2 for (00, 01, 11), je[e] or None with
+    lam == 0."""
+    return _affine_call("affine_helmholtz_quad", nq, (basis0, basis1), (deriv0, deriv1), (qw0, qw1), ge, je, lam, inp,
+                        out, variant, stream)
+
+
 class _BwdTrans(torch.autograd.Function):
     """AUTO BwdTrans forward; its input gradient is IProductWRTBase of the output gradient (the exact transpose)."""
 

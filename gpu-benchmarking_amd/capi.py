@@ -57,6 +57,12 @@ SYMBOLS = {
     "sf_helmholtz_quad_f64_variant": (_i, [_i, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp]),
     "sf_helmholtz_hex_f32": (_i, [_u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp]),
     "sf_helmholtz_quad_f32": (_i, [_u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp]),
+    "sf_affine_helmholtz_hex_f64": (_i, [_u, _u, _u, _sz] + [_vp] * 11 + [ctypes.c_double, _vp, _vp, _vp]),
+    "sf_affine_helmholtz_hex_f64_variant": (_i, [_i, _u, _u, _u, _sz] + [_vp] * 11 + [ctypes.c_double, _vp, _vp, _vp]),
+    "sf_affine_helmholtz_quad_f64": (_i, [_u, _u, _sz] + [_vp] * 8 + [ctypes.c_double, _vp, _vp, _vp]),
+    "sf_affine_helmholtz_quad_f64_variant": (_i, [_i, _u, _u, _sz] + [_vp] * 8 + [ctypes.c_double, _vp, _vp, _vp]),
+    "sf_affine_helmholtz_hex_f32": (_i, [_u, _u, _u, _sz] + [_vp] * 11 + [ctypes.c_double, _vp, _vp, _vp]),
+    "sf_affine_helmholtz_quad_f32": (_i, [_u, _u, _sz] + [_vp] * 8 + [ctypes.c_double, _vp, _vp, _vp]),
     "sf_vector_add_f64": (_i, [_vp, _vp, _sz, _vp]),
     "sf_fill_vecadd_f64": (_i, [_vp, _vp, _sz, _vp]),
     "sf_matvec_f64": (_i, [_u, _u, _vp, _vp, _vp, _vp]),

@@ -2,7 +2,7 @@
 // Validation + dispatch only; kernels live in bwdtrans_hex.hip / bwdtrans_quad.hip /
 // bwdtrans_generic.hip / aux_kernels.hip, IProductWRTBase in iproduct.hip / iproduct_generic.hip, the fused mass
 // operator in mass.hip / mass_f32.hip / mass_generic.hip, the fused Helmholtz operator in helmholtz.hip /
-// helmholtz_f32.hip / helmholtz_generic.hip.
+// helmholtz_f32.hip / helmholtz_generic.hip, its affine-element form in affine.hip / affine_f32.hip / affine_generic.hip.
 #include "sf_dispatch.h"
 
 #include <cstdio>
@@ -61,7 +61,7 @@ static ArgsT<DIM, T> make_args(const T *const (&b)[3], const T *in, T *out, size
         return {b[0], b[1], in, nullptr, out, (uint64_t)nelmt};
 }
 
-// The shared tail of sf_iproduct_*, sf_mass_* and sf_helmholtz_*: AUTO takes the wave kernel for an isotropic order of
+// The shared tail of sf_iproduct_*, sf_mass_*, sf_helmholtz_* and sf_affine_helmholtz_*: AUTO takes the wave kernel for an isotropic order of
 // its table (`wave_built`) when in / out are 16-byte aligned, and the any-extent kernel otherwise.
 template <int DIM, class Wave, class Generic>
 static int route(int variant, const unsigned (&nq)[3], bool generic_built, bool wave_built, const void *in,
@@ -149,6 +149,36 @@ static int helmholtz(int variant, const unsigned (&nq)[3], size_t nelmt, const T
         variant, nq, helmholtz_generic_built(DIM, nq[0], nq[1], nq[2]), helmholtz_wave_built(DIM, nq[0]), in, out,
         [&] { return launch_helmholtz_wave<DIM, T>(nq[0], a, x, s); },
         [&] { return launch_helmholtz_generic<DIM, T>(nq, a, x, s); });
+}
+
+// ---- the fused Helmholtz operator on affine elements: one validation and routing for both dimensions and scalar types --
+// The order of sf_helmholtz_*, with the quadrature weights and ge in the place of g and je in the place of w: `je` is
+// looked at only when lambda != 0.
+template <int DIM, typename T>
+static int affine(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *const (&d)[3],
+                  const T *const (&qw)[3], const T *ge, const T *je, double lambda, const T *in, T *out, void *stream)
+{
+    const bool has_j = lambda != 0.0; // false for NaN too, which is refused with the nulls
+    const int rc     = validate(range_ok<DIM>(variant, nq), nelmt,
+                                {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], qw[0], qw[1],
+                                 DIM == 3 ? qw[2] : qw[0], ge, in, out, has_j ? je : ge},
+                                sizeof(T), lambda - lambda == 0.0);
+    if (rc != kProceed)
+        return rc;
+    // not in-place safe, as sf_mass_*
+    const size_t mz          = DIM == 3 ? nq[2] - 1 : 1;
+    const size_t modes_bytes = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
+    if (overlaps(out, modes_bytes, in, modes_bytes) || overlaps(out, modes_bytes, ge, sizeof(T) * nelmt * (DIM == 3 ? 6 : 3)) ||
+        (has_j && overlaps(out, modes_bytes, je, sizeof(T) * nelmt)))
+        return SF_EINVAL;
+    const hipStream_t s = (hipStream_t)stream;
+    const auto a        = make_args<DIM, T>(b, in, out, nelmt);
+    // lambda is rounded to T here, once
+    const AffineArgsT<T> x{d[0], d[1], d[2], qw[0], qw[1], qw[2], ge, has_j ? je : nullptr, (T)lambda};
+    return route<DIM>(
+        variant, nq, affine_generic_built(DIM, nq[0], nq[1], nq[2]), affine_wave_built(DIM, nq[0]), in, out,
+        [&] { return launch_affine_wave<DIM, T>(nq[0], a, x, s); },
+        [&] { return launch_affine_generic<DIM, T>(nq, a, x, s); });
 }
 
 extern "C" {
@@ -529,6 +559,64 @@ int sf_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float 
 {
     return helmholtz<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
                                                  {deriv0, deriv1, nullptr}, g, w, lambda, in, out, stream);
+}
+
+// ---- the fused Helmholtz operator on affine elements: a constant metric per element, shared quadrature weights ---------
+int sf_affine_helmholtz_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                                        const double *basis0, const double *basis1, const double *basis2,
+                                        const double *deriv0, const double *deriv1, const double *deriv2,
+                                        const double *qw0, const double *qw1, const double *qw2, const double *ge,
+                                        const double *je, double lambda, const double *in, double *out, void *stream)
+{
+    return affine<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
+                             {qw0, qw1, qw2}, ge, je, lambda, in, out, stream);
+}
+
+int sf_affine_helmholtz_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
+                                const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
+                                const double *deriv2, const double *qw0, const double *qw1, const double *qw2,
+                                const double *ge, const double *je, double lambda, const double *in, double *out,
+                                void *stream)
+{
+    return affine<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
+                             {deriv0, deriv1, deriv2}, {qw0, qw1, qw2}, ge, je, lambda, in, out, stream);
+}
+
+int sf_affine_helmholtz_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                                         const double *basis1, const double *deriv0, const double *deriv1,
+                                         const double *qw0, const double *qw1, const double *ge, const double *je,
+                                         double lambda, const double *in, double *out, void *stream)
+{
+    return affine<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
+                             {qw0, qw1, nullptr}, ge, je, lambda, in, out, stream);
+}
+
+int sf_affine_helmholtz_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                                 const double *deriv0, const double *deriv1, const double *qw0, const double *qw1,
+                                 const double *ge, const double *je, double lambda, const double *in, double *out,
+                                 void *stream)
+{
+    return affine<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
+                             {deriv0, deriv1, nullptr}, {qw0, qw1, nullptr}, ge, je, lambda, in, out, stream);
+}
+
+int sf_affine_helmholtz_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
+                                const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
+                                const float *deriv2, const float *qw0, const float *qw1, const float *qw2,
+                                const float *ge, const float *je, double lambda, const float *in, float *out,
+                                void *stream)
+{
+    return affine<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
+                            {deriv0, deriv1, deriv2}, {qw0, qw1, qw2}, ge, je, lambda, in, out, stream);
+}
+
+int sf_affine_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
+                                 const float *deriv0, const float *deriv1, const float *qw0, const float *qw1,
+                                 const float *ge, const float *je, double lambda, const float *in, float *out,
+                                 void *stream)
+{
+    return affine<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
+                            {deriv0, deriv1, nullptr}, {qw0, qw1, nullptr}, ge, je, lambda, in, out, stream);
 }
 
 int sf_sumsq_f32(const float *x, size_t n, double *result_host, void *stream)

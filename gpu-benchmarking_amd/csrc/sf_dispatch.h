@@ -99,6 +99,22 @@ template <int DIM, typename T>
 int launch_helmholtz_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const HelmArgsT<T> &x, hipStream_t s);
 bool helmholtz_wave_built(int dim, unsigned nq);
 bool helmholtz_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
+// The fused Helmholtz operator on affine elements, G_ab,e = ge[e][ab] (x) qw, w_e = je[e] (x) qw (affine.hip /
+// affine_f32.hip: the wave kernels of affine_wave.h, the Helmholtz table; affine_generic.hip: any extents up to 12 per
+// direction in 3D and 32 in 2D).  What the operator takes beyond the BwdTrans arguments: the derivative matrices, the
+// one-dimensional quadrature weights, the constants of every element (je null: lambda == 0, never read) and lambda in
+// the scalar type.
+template <typename T> struct AffineArgsT
+{
+    const T *d0, *d1, *d2, *qw0, *qw1, *qw2, *ge, *je;
+    T lam;
+};
+template <int DIM, typename T>
+int launch_affine_wave(unsigned nq, const ArgsT<DIM, T> &a, const AffineArgsT<T> &x, hipStream_t s);
+template <int DIM, typename T>
+int launch_affine_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const AffineArgsT<T> &x, hipStream_t s);
+bool affine_wave_built(int dim, unsigned nq);
+bool affine_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
 int sumsq_f32_blocking(const float *x, size_t n, double *result_host, hipStream_t s);
 int fill_sincos_f32(float *in, size_t nelmt, size_t nm_tot, hipStream_t s);
 int fill_basis_f32(float *b, size_t nm, size_t nq, hipStream_t s);

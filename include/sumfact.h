@@ -313,6 +313,75 @@ int sf_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float 
                           double lambda, const float *in, float *out, void *stream);
 
 /*
+ * The fused Helmholtz operator on AFFINE elements (parallelepipeds, parallelograms: a constant Jacobian J_e), where the
+ * metric of sf_helmholtz_* factorises into constants of the element times quadrature weights that all elements share:
+ *   G_ab,e[k][j][i] = ge[e][ab] * qw2[k] qw1[j] qw0[i]        w_e[k][j][i] = je[e] * qw2[k] qw1[j] qw0[i]
+ *   y_e = B^T [ lambda diag(w_e) + sum_a sum_b D_a^T diag(G_ab,e) D_b ] B x_e
+ * The same operator in one kernel, without the metric stream: per element the call moves 2 nm^d + d(d+1)/2 + 1 scalars
+ * where sf_helmholtz_* moves 2 nm^d + (1 + d(d+1)/2) nq^d, and the caller stores d(d+1)/2 + 1 scalars per element
+ * instead of (1 + d(d+1)/2) nq^d.
+ * Layout: basis_d, deriv_d, `in` and `out` exactly as in sf_helmholtz_*.  qw_d: the nq_d one-dimensional quadrature
+ * weights of direction d.  ge[e][c]: the constant symmetric tensor |det J_e| J_e^-1 J_e^-T of the element, d(d+1)/2
+ * scalars per element, c in the order of the planes of g: 3D c = 0..5 for (a,b) = (00, 01, 02, 11, 12, 22), 2D c = 0..2
+ * for (00, 01, 11).  ge may be indefinite; the operator is symmetric for any ge.  je[e]: |det J_e|, one scalar per
+ * element.  If lambda == 0, `je` may be NULL: it is then never read (nor validated).
+ * Summation order (it defines the rounding; every sum in ascending index, the first product a multiply, then FMAs; the
+ * wave kernels and the fallback follow it alike):
+ *   1. forward sweeps p -> i, q -> j, r -> k, as BwdTrans:                  u
+ *   2. du_a = D_a u for each direction a
+ *   3. q = qw2[k] * (qw1[j] * qw0[i])  (2D: q = qw1[j] * qw0[i]);   f_a = q * (sum_b ge_ab du_b), b ascending
+ *   4. v = (((lambda je_e) * q) * u + D_0^T f_0) + D_1^T f_1 [+ D_2^T f_2]  (lambda == 0: the first term is 0)
+ *   5. transposed sweeps k -> r', j -> q', i -> p', as sf_mass_*
+ * lambda is a double in every entry point; it is rounded to the scalar type once, before the launch, and lambda je_e
+ * is formed in the scalar type.
+ * Routes, as sf_helmholtz_*: SF_VARIANT_AUTO runs the fused wave kernel for the isotropic orders of its table (3D nq
+ * 2..8, 2D nq 2..16) when in / out are 16-byte aligned, else GENERIC; SF_VARIANT_WAVE returns SF_ENOTBUILT off that
+ * table and SF_EALIGN unless in / out are 16-byte aligned; SF_VARIANT_GENERIC (one workgroup per element, latency-
+ * bound) takes any extents up to 12 per direction in 3D and 32 in 2D -- 3D nq 9..11 and all anisotropic shapes take it;
+ * any other variant SF_ENOTBUILT, extents beyond those bounds SF_ENOTBUILT.  ge, je, the quadrature weights, the bases
+ * and the derivative matrices need only scalar alignment on every route.
+ * Validation, before any HIP call, in this order: (1) an extent < 2 or a variant outside [0, SF_NUM_VARIANTS):
+ * SF_EINVAL; (2) nelmt == 0: SF_OK; (3) a null basis, deriv, qw, ge, in or out, a null je with lambda != 0, or a lambda
+ * that is not finite: SF_EINVAL; (4) any of them (je only if lambda != 0) not scalar-aligned: SF_EALIGN;
+ * (5) `out` overlapping `in`, `ge` or (if lambda != 0) `je`, compared as byte ranges of their full sizes: SF_EINVAL;
+ * (6) extents beyond the fallback's bounds: SF_ENOTBUILT; (7) an unsupported variant: SF_ENOTBUILT.
+ * NOT in-place safe, for the reason given under sf_mass_*; the inputs may overlap each other (all are only read).
+ * No internal workspace and no allocation: every call is a single kernel node, capture-safe from the process's first
+ * call.
+ */
+int sf_affine_helmholtz_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                                const double *basis0, const double *basis1, const double *basis2,
+                                const double *deriv0, const double *deriv1, const double *deriv2,
+                                const double *qw0, const double *qw1, const double *qw2,
+                                const double *ge, const double *je, double lambda,
+                                const double *in, double *out, void *stream);
+int sf_affine_helmholtz_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                                        const double *basis0, const double *basis1, const double *basis2,
+                                        const double *deriv0, const double *deriv1, const double *deriv2,
+                                        const double *qw0, const double *qw1, const double *qw2,
+                                        const double *ge, const double *je, double lambda,
+                                        const double *in, double *out, void *stream);
+int sf_affine_helmholtz_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                                 const double *basis1, const double *deriv0, const double *deriv1,
+                                 const double *qw0, const double *qw1, const double *ge, const double *je,
+                                 double lambda, const double *in, double *out, void *stream);
+int sf_affine_helmholtz_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt,
+                                         const double *basis0, const double *basis1, const double *deriv0,
+                                         const double *deriv1, const double *qw0, const double *qw1,
+                                         const double *ge, const double *je, double lambda, const double *in,
+                                         double *out, void *stream);
+/* T = float (AUTO route; every array 4-byte aligned; lambda stays a double) */
+int sf_affine_helmholtz_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
+                                const float *basis1, const float *basis2, const float *deriv0,
+                                const float *deriv1, const float *deriv2, const float *qw0, const float *qw1,
+                                const float *qw2, const float *ge, const float *je, double lambda,
+                                const float *in, float *out, void *stream);
+int sf_affine_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0,
+                                 const float *basis1, const float *deriv0, const float *deriv1,
+                                 const float *qw0, const float *qw1, const float *ge, const float *je,
+                                 double lambda, const float *in, float *out, void *stream);
+
+/*
  * benchmark02: x[i] += y[i]  -- replaces add_vector<T,vl><<<>>>
  * (benchmark02/benchmark02.cc:16-58); 24 bytes of HBM traffic per element (:255), so its GB/s is the
  * measured stream rate used as the second roofline denominator.  fill: data1/data2 of :84-85.
