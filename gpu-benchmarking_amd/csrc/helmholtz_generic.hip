@@ -15,13 +15,36 @@
 // dereferenced when has_w is false.  Latency-bound (a barrier per sweep, one element per workgroup), not a roofline
 // target.  Extents up to 12 per direction in 3D (four images of 12^3 doubles: 55 296 bytes of the 64 KB of static LDS)
 // and 32 in 2D; beyond, SF_ENOTBUILT.
-#include "any_extent.h"
+// The kernel body, helm_generic_body, is in helmholtz_generic.h and shared with affine_generic.hip; the metric of this
+// unit is the PlaneGeneric policy below: the planes g and the weight w per point.
+#include "helmholtz_generic.h"
 
 namespace sf
 {
 
-constexpr unsigned kHelmMax3D = 12, kHelmMax2D = 32;
-constexpr int kHelmSmallCap = 2048, kHelmLargeCap = 4 * 12 * 12 * 12; // scalars; 2D 32^2 needs 3 * 1024
+template <typename T, int DIM> struct PlaneGeneric
+{
+    static constexpr bool SCALED = false;
+    static constexpr int NCOMP   = DIM == 3 ? 6 : 3;
+    const T *__restrict__ g, *__restrict__ w;
+    const T lam;
+    const bool has_w;
+    const T *ge, *wt; // of the element
+
+    __device__ __forceinline__ void element(uint64_t e, int nqt)
+    {
+        ge = g + e * (uint64_t)(NCOMP * nqt);
+        wt = has_w ? w + e * (uint64_t)nqt : nullptr;
+    }
+    __device__ __forceinline__ void coef(int x, int nqt, T (&gg)[NCOMP]) const
+    {
+#pragma unroll
+        for (int c = 0; c < NCOMP; ++c)
+            gg[c] = ge[c * nqt + x];
+    }
+    __device__ __forceinline__ T scale(int, int, int) const { return T(1); }
+    __device__ __forceinline__ T mass(int x, T, T u) const { return has_w ? (lam * wt[x]) * u : T(0); }
+};
 
 template <typename T, int DIM, int CAP, int NT>
 __global__ __launch_bounds__(NT) void helmholtz_generic_kernel(
@@ -30,163 +53,8 @@ __global__ __launch_bounds__(NT) void helmholtz_generic_kernel(
     bool has_w, const T *__restrict__ in, T *__restrict__ out, uint64_t nelmt, int nq0, int nq1, int nq2)
 {
     __shared__ T lds[CAP];
-    const int nm0 = nq0 - 1, nm1 = nq1 - 1, nm2 = DIM == 3 ? nq2 - 1 : 1;
-    const int nz  = DIM == 3 ? nq2 : 1;
-    const int n01 = nq0 * nq1;
-    const int nqt = n01 * nz;        // points per element
-    const int nmt = nm0 * nm1 * nm2; // modes per element
-    constexpr int NCOMP = DIM == 3 ? 6 : 3;
-    T *P0 = lds, *P1 = lds + nqt, *P2 = lds + 2 * nqt, *P3 = lds + (DIM == 3 ? 3 : 2) * nqt;
-    const int tid = threadIdx.x;
-    for (uint64_t e = blockIdx.x; e < nelmt; e += gridDim.x)
-    {
-        const T *src = in + e * (uint64_t)nmt;
-        const T *ge  = g + e * (uint64_t)(NCOMP * nqt);
-        const T *wt  = has_w ? w + e * (uint64_t)nqt : nullptr;
-        T *dst       = out + e * (uint64_t)nmt;
-        for (int x = tid; x < nmt; x += NT)
-            P1[x] = src[x];
-        __syncthreads();
-        if constexpr (DIM == 2)
-        {
-            // forward 0: w1[q][i] = sum_p in[q][p] * B0[p][i]
-            for (int x = tid; x < nm1 * nq0; x += NT)
-            {
-                const int i = x % nq0, q = x / nq0;
-                P2[x] = dot_strided(P1 + q * nm0, 1, b0 + i, nq0, nm0);
-            }
-            __syncthreads();
-            // forward 1: u[j][i] = sum_q w1[q][i] * B1[q][j]
-            for (int x = tid; x < nqt; x += NT)
-            {
-                const int i = x % nq0, j = x / nq0;
-                P0[x] = dot_strided(P2 + i, nq0, b1 + j, nq1, nm1);
-            }
-            __syncthreads();
-            // du_0[j][i] = sum_m D0[i][m] u[j][m];  du_1[j][i] = sum_m D1[j][m] u[m][i]
-            for (int x = tid; x < nqt; x += NT)
-            {
-                const int i = x % nq0, j = x / nq0;
-                P1[x] = dot_strided(P0 + j * nq0, 1, d0 + i * nq0, 1, nq0);
-                P2[x] = dot_strided(P0 + i, nq0, d1 + j * nq1, 1, nq1);
-            }
-            __syncthreads();
-            // fluxes in place, the mass term over u (every thread touches its own points only)
-            for (int x = tid; x < nqt; x += NT)
-            {
-                const T x0 = P1[x], x1 = P2[x];
-                const T g00 = ge[x], g01 = ge[nqt + x], g11 = ge[2 * nqt + x];
-                P1[x] = sfma(g01, x1, g00 * x0);
-                P2[x] = sfma(g11, x1, g01 * x0);
-                P0[x] = has_w ? (lam * wt[x]) * P0[x] : T(0);
-            }
-            __syncthreads();
-            // v = ((lambda w) u + D_0^T f_0) + D_1^T f_1, over the mass term
-            for (int x = tid; x < nqt; x += NT)
-            {
-                const int i = x % nq0, j = x / nq0;
-                const T t0 = dot_strided(P1 + j * nq0, 1, d0 + i, nq0, nq0);
-                const T t1 = dot_strided(P2 + i, nq0, d1 + j, nq1, nq1);
-                P0[x]      = (P0[x] + t0) + t1;
-            }
-            __syncthreads();
-            // transposed 1: t1[q'][i] = sum_j v[j][i] * B1[q'][j]
-            for (int x = tid; x < nm1 * nq0; x += NT)
-            {
-                const int i = x % nq0, q = x / nq0;
-                P1[x] = dot_strided(P0 + i, nq0, b1 + q * nq1, 1, nq1);
-            }
-            __syncthreads();
-            // transposed 0: out[q'][p'] = sum_i t1[q'][i] * B0[p'][i]
-            for (int x = tid; x < nmt; x += NT)
-            {
-                const int p = x % nm0, q = x / nm0;
-                dst[x] = dot_strided(P1 + q * nq0, 1, b0 + p * nq0, 1, nq0);
-            }
-        }
-        else
-        {
-            // forward 0: w1[r][q][i] = sum_p in[r][q][p] * B0[p][i]
-            for (int x = tid; x < nq0 * nm1 * nm2; x += NT)
-            {
-                const int i = x % nq0, rq = x / nq0;
-                P0[x] = dot_strided(P1 + rq * nm0, 1, b0 + i, nq0, nm0);
-            }
-            __syncthreads();
-            // forward 1: w2[r][j][i] = sum_q w1[r][q][i] * B1[q][j]
-            for (int x = tid; x < n01 * nm2; x += NT)
-            {
-                const int i = x % nq0, rj = x / nq0, j = rj % nq1, r = rj / nq1;
-                P1[x] = dot_strided(P0 + r * nm1 * nq0 + i, nq0, b1 + j, nq1, nm1);
-            }
-            __syncthreads();
-            // forward 2: u[k][j][i] = sum_r w2[r][j][i] * B2[r][k]
-            for (int x = tid; x < nqt; x += NT)
-            {
-                const int ji = x % n01, k = x / n01;
-                P0[x] = dot_strided(P1 + ji, n01, b2 + k, nq2, nm2);
-            }
-            __syncthreads();
-            // du_0 = D0 u along i, du_1 = D1 u along j, du_2 = D2 u along k
-            for (int x = tid; x < nqt; x += NT)
-            {
-                const int i = x % nq0, kj = x / nq0, j = kj % nq1, k = kj / nq1;
-                P1[x] = dot_strided(P0 + kj * nq0, 1, d0 + i * nq0, 1, nq0);
-                P2[x] = dot_strided(P0 + k * n01 + i, nq0, d1 + j * nq1, 1, nq1);
-                P3[x] = dot_strided(P0 + j * nq0 + i, n01, d2 + k * nq2, 1, nq2);
-            }
-            __syncthreads();
-            // fluxes in place, the mass term over u (every thread touches its own points only)
-            for (int x = tid; x < nqt; x += NT)
-            {
-                const T x0 = P1[x], x1 = P2[x], x2 = P3[x];
-                const T g00 = ge[x], g01 = ge[nqt + x], g02 = ge[2 * nqt + x];
-                const T g11 = ge[3 * nqt + x], g12 = ge[4 * nqt + x], g22 = ge[5 * nqt + x];
-                P1[x] = sfma(g02, x2, sfma(g01, x1, g00 * x0));
-                P2[x] = sfma(g12, x2, sfma(g11, x1, g01 * x0));
-                P3[x] = sfma(g22, x2, sfma(g12, x1, g02 * x0));
-                P0[x] = has_w ? (lam * wt[x]) * P0[x] : T(0);
-            }
-            __syncthreads();
-            // v = (((lambda w) u + D_0^T f_0) + D_1^T f_1) + D_2^T f_2, over the mass term
-            for (int x = tid; x < nqt; x += NT)
-            {
-                const int i = x % nq0, kj = x / nq0, j = kj % nq1, k = kj / nq1;
-                const T t0 = dot_strided(P1 + kj * nq0, 1, d0 + i, nq0, nq0);
-                const T t1 = dot_strided(P2 + k * n01 + i, nq0, d1 + j, nq1, nq1);
-                const T t2 = dot_strided(P3 + j * nq0 + i, n01, d2 + k, nq2, nq2);
-                P0[x]      = ((P0[x] + t0) + t1) + t2;
-            }
-            __syncthreads();
-            // transposed 2: t1[r'][j][i] = sum_k v[k][j][i] * B2[r'][k]
-            for (int x = tid; x < n01 * nm2; x += NT)
-            {
-                const int ji = x % n01, r = x / n01;
-                P1[x] = dot_strided(P0 + ji, n01, b2 + r * nq2, 1, nq2);
-            }
-            __syncthreads();
-            // transposed 1: t2[r'][q'][i] = sum_j t1[r'][j][i] * B1[q'][j]
-            for (int x = tid; x < nq0 * nm1 * nm2; x += NT)
-            {
-                const int i = x % nq0, rq = x / nq0, q = rq % nm1, r = rq / nm1;
-                P2[x] = dot_strided(P1 + r * n01 + i, nq0, b1 + q * nq1, 1, nq1);
-            }
-            __syncthreads();
-            // transposed 0: out[r'][q'][p'] = sum_i t2[r'][q'][i] * B0[p'][i]
-            for (int x = tid; x < nmt; x += NT)
-            {
-                const int p = x % nm0, rq = x / nm0;
-                dst[x] = dot_strided(P2 + rq * nq0, 1, b0 + p * nq0, 1, nq0);
-            }
-        }
-        __syncthreads(); // the next element overwrites the images
-    }
-}
-
-// scalars of LDS the extents need: one point image per region
-static unsigned helm_need(int dim, unsigned nq0, unsigned nq1, unsigned nq2)
-{
-    return dim == 3 ? 4 * nq0 * nq1 * nq2 : 3 * nq0 * nq1;
+    PlaneGeneric<T, DIM> met{g, w, lam, has_w, nullptr, nullptr};
+    helm_generic_body<T, DIM, NT>(lds, b0, b1, b2, d0, d1, d2, met, in, out, nelmt, nq0, nq1, nq2);
 }
 
 template <int DIM, typename T>
@@ -211,14 +79,9 @@ template int launch_helmholtz_generic<2, double>(const unsigned (&)[3], const Qu
 template int launch_helmholtz_generic<2, float>(const unsigned (&)[3], const QuadArgsT<float> &, const HelmArgsT<float> &,
                                                 hipStream_t);
 
-// within the extent bounds AND the images fit the large LDS class (true for every extent within the bounds: 3D 12^3
-// needs 6912, 2D 32^2 3072; derived all the same, not assumed)
 bool helmholtz_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2)
 {
-    const unsigned mx = dim == 3 ? kHelmMax3D : kHelmMax2D;
-    if (nq0 < 2 || nq1 < 2 || (dim == 3 && nq2 < 2) || nq0 > mx || nq1 > mx || (dim == 3 && nq2 > mx))
-        return false;
-    return helm_need(dim, nq0, nq1, dim == 3 ? nq2 : 0) <= (unsigned)kHelmLargeCap;
+    return helm_extents_built(dim, nq0, nq1, nq2);
 }
 
 } // namespace sf

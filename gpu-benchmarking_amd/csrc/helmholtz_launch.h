@@ -24,21 +24,36 @@
 namespace sf
 {
 
-template <int DIM, int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP, int MEMF, bool HASW, typename T>
-static int launch_helmholtz_k(const ArgsT<DIM, T> &a, const HelmArgsT<T> &x, hipStream_t s)
+// One launcher for the kernels of helmholtz_wave.h and of affine_wave.h (affine_launch.h).  The struct of the extra
+// arguments, X = HelmArgsT<T> / AffineArgsT<T>, picks the family: HelmFamily<X> names its kernels, hands them their
+// arguments and says whether the mass term is on.
+template <class X> struct HelmFamily;
+template <typename T> struct HelmFamily<HelmArgsT<T>>
+{
+    static bool has_mass(const HelmArgsT<T> &x) { return x.w != nullptr; }
+    template <int DIM, int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP, int MEMF, bool HASW>
+    static int launch(std::atomic<int> *cache, size_t lds, const ArgsT<DIM, T> &a, const HelmArgsT<T> &x, hipStream_t s)
+    {
+        if constexpr (DIM == 3)
+            return launch_chunked<WPB, EC, KMAP>(hex_helmholtz_wave_kernel<NQ, EC, WPB, BMODE, MINW, KMAP, MEMF, HASW, T>,
+                                                 cache, lds, 0, s, a.nelmt, a.b0, a.b1, a.b2, x.d0, x.d1, x.d2, x.g, x.w,
+                                                 x.lam, a.in, a.out, a.nelmt);
+        else
+            return launch_chunked<WPB, EC, KMAP>(quad_helmholtz_wave_kernel<NQ, EC, WPB, BMODE, MINW, KMAP, MEMF, HASW, T>,
+                                                 cache, lds, 0, s, a.nelmt, a.b0, a.b1, x.d0, x.d1, x.g, x.w, x.lam, a.in,
+                                                 a.out, a.nelmt);
+    }
+};
+
+// the occupancy cache is one per kernel instantiation: X is among the template arguments
+template <int DIM, int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP, int MEMF, bool HASM, typename T, class X>
+static int launch_helm_k(const ArgsT<DIM, T> &a, const X &x, hipStream_t s)
 {
     static OccCache cache = {};
     constexpr size_t lds = helmholtz_lds_bytes<NQ, EC, DIM, WPB, T>();
     static_assert(lds <= 160 * 1024, "LDS slab exceeds 160 KiB");
     static_assert(KMAP > 0, "short-lived waves: the grid covers the batch");
-    if constexpr (DIM == 3)
-        return launch_chunked<WPB, EC, KMAP>(hex_helmholtz_wave_kernel<NQ, EC, WPB, BMODE, MINW, KMAP, MEMF, HASW, T>,
-                                             cache, lds, 0, s, a.nelmt, a.b0, a.b1, a.b2, x.d0, x.d1, x.d2, x.g, x.w,
-                                             x.lam, a.in, a.out, a.nelmt);
-    else
-        return launch_chunked<WPB, EC, KMAP>(quad_helmholtz_wave_kernel<NQ, EC, WPB, BMODE, MINW, KMAP, MEMF, HASW, T>,
-                                             cache, lds, 0, s, a.nelmt, a.b0, a.b1, x.d0, x.d1, x.g, x.w, x.lam, a.in,
-                                             a.out, a.nelmt);
+    return HelmFamily<X>::template launch<DIM, NQ, EC, WPB, BMODE, MINW, KMAP, MEMF, HASM>(cache, lds, a, x, s);
 }
 
 constexpr int helm_hex_ec(int nq, int row_ec, int scalar_bytes)
@@ -68,23 +83,22 @@ template <int NQ, typename T> struct HelmQuadCfg
     static constexpr int KM = R::KM, MF = R::MF | 8;
 };
 
-template <int DIM, int NQ, typename T>
-static int go_helmholtz(const ArgsT<DIM, T> &a, const HelmArgsT<T> &x, hipStream_t s)
+template <int DIM, int NQ, typename T, class X> static int go_helm(const ArgsT<DIM, T> &a, const X &x, hipStream_t s)
 {
     using C = typename std::conditional<DIM == 3, HelmHexCfg<NQ, T>, HelmQuadCfg<NQ, T>>::type;
-    return x.w ? launch_helmholtz_k<DIM, NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, C::MF, true, T>(a, x, s)
-               : launch_helmholtz_k<DIM, NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, C::MF, false, T>(a, x, s);
+    return HelmFamily<X>::has_mass(x)
+               ? launch_helm_k<DIM, NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, C::MF, true, T>(a, x, s)
+               : launch_helm_k<DIM, NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, C::MF, false, T>(a, x, s);
 }
 
 #define SF_HELM_HEX_CASES(F) F(2) F(3) F(4) F(5) F(6) F(7) F(8)
 #define SF_HELM_QUAD_CASES(F) F(2) F(3) F(4) F(5) F(6) F(7) F(8) F(9) F(10) F(11) F(12) F(13) F(14) F(15) F(16)
 
-// SF_ENOTBUILT when the order has no instantiation (helmholtz_wave_built()); instantiated for double in helmholtz.hip and
-// for float in helmholtz_f32.hip
-template <int DIM, typename T>
-int launch_helmholtz_wave(unsigned nq, const ArgsT<DIM, T> &a, const HelmArgsT<T> &x, hipStream_t s)
+// SF_ENOTBUILT when the order has no instantiation (helmholtz_wave_built() / affine_wave_built())
+template <int DIM, typename T, class X>
+static int launch_helm_wave(unsigned nq, const ArgsT<DIM, T> &a, const X &x, hipStream_t s)
 {
-#define SF_CASE(N) case N: return go_helmholtz<DIM, N, T>(a, x, s);
+#define SF_CASE(N) case N: return go_helm<DIM, N, T>(a, x, s);
     if constexpr (DIM == 3)
         switch (nq)
         {
@@ -97,6 +111,13 @@ int launch_helmholtz_wave(unsigned nq, const ArgsT<DIM, T> &a, const HelmArgsT<T
         }
 #undef SF_CASE
     return SF_ENOTBUILT;
+}
+
+// instantiated for double in helmholtz.hip and for float in helmholtz_f32.hip
+template <int DIM, typename T>
+int launch_helmholtz_wave(unsigned nq, const ArgsT<DIM, T> &a, const HelmArgsT<T> &x, hipStream_t s)
+{
+    return launch_helm_wave<DIM, T>(nq, a, x, s);
 }
 
 } // namespace sf
