@@ -5,6 +5,7 @@ Argument meaning follows the reference kernels (benchmark05/benchmark05.cc:291-2
 benchmark04/benchmark04.cc:353-358): extents nq (nm = nq-1), basis row-major nm x nq,
 in[e][r][q][p], out[e][k][j][i].
 """
+import collections
 import ctypes
 
 import torch
@@ -22,23 +23,29 @@ def _stream(stream, device=None):
     return ctypes.c_void_p(stream.cuda_stream)
 
 
-def _check_sizes(what, basis, nq, wsp, wsp_need):
-    """The C ABI takes raw pointers: a short basis or workspace would be read / written out of bounds."""
-    for d, (b, q) in enumerate(zip(basis, nq)):
-        if b.numel() != (q - 1) * q:
-            raise ValueError(f"{what}: basis{d} has {b.numel()} values, nm*nq = {(q - 1) * q}")
-    if wsp is not None and wsp.numel() < wsp_need:
-        raise ValueError(f"{what}: wsp has {wsp.numel()} values, the variant needs {wsp_need}")
+def _check_operands(what, operands, inp, lam=None):
+    """The C ABI takes raw pointers: a short operand would be read / written out of bounds, one of another dtype or device
+    misread.  `operands`: (name, tensor, expected numel, may be None); a None stands for a term that lam == 0 switches off."""
+    for name, t, need, optional in operands:
+        if t is None and optional:
+            if lam != 0.0:
+                raise ValueError(f"{what}: {name}=None needs lam == 0")
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: {name} must be a tensor")
+        if t.numel() != need:
+            raise ValueError(f"{what}: {name} has {t.numel()} values, not {need}")
+        if t.dtype != inp.dtype:
+            raise ValueError(f"{what}: {name} is {t.dtype}, in is {inp.dtype}")
+        if t.device != inp.device:
+            raise ValueError(f"{what}: {name} is on {t.device}, in is on {inp.device}")
 
 
-def _dev_f64(t, name, dtype=torch.float64):
+def _dev_ptr(t, name, dtype=torch.float64):
+    """The device address of `t` as a ctypes pointer."""
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
         raise TypeError(f"{name} must be a contiguous {dtype} CUDA/HIP tensor")
     return ctypes.c_void_p(t.data_ptr())
-
-
-def _dev_f32(t, name):
-    return _dev_f64(t, name, torch.float32)
 
 
 def _variant(v):
@@ -57,158 +64,90 @@ def quad_wsp_doubles(nq, nelmt):
     return nelmt * nq0 * (nq1 - 1)
 
 
-def bwdtrans_hex(nq, basis0, basis1, basis2, inp, out=None, variant="auto", wsp=None, stream=None):
-    """out[e][k][j][i] = sum_rqp in[e][r][q][p] B0[p][i] B1[q][j] B2[r][k] on inp's device."""
-    nq0, nq1, nq2 = (int(x) for x in nq)
-    nmt = (nq0 - 1) * (nq1 - 1) * (nq2 - 1)
-    if nmt <= 0:
-        raise capi.SumfactError(capi.SF_EINVAL, "bwdtrans_hex")
-    nelmt = inp.numel() // nmt
-    if nelmt * nmt != inp.numel():
-        raise ValueError("in.numel() is not a multiple of nm0*nm1*nm2")
-    if out is None:
-        out = torch.empty(nelmt * nq0 * nq1 * nq2, dtype=inp.dtype, device=inp.device)
-    elif out.numel() != nelmt * nq0 * nq1 * nq2:
-        raise ValueError("out has the wrong size")
-    v = _variant(variant)
-    _check_sizes("bwdtrans_hex", (basis0, basis1, basis2), (nq0, nq1, nq2), wsp,
-                 {2: nelmt * ((nq1 - 1) * (nq2 - 1) + (nq2 - 1)),
-                  4: hex_wsp_doubles((nq0, nq1, nq2), nelmt)}.get(v, 0))
-    if inp.dtype == torch.float32:      # T = float instantiation (SURVEY s8(f)-3); AUTO strategy only
-        with torch.cuda.device(inp.device):
-            rc = capi.lib().sf_bwdtrans_hex_f32(
-                nq0, nq1, nq2, nelmt, _dev_f32(basis0, "basis0"), _dev_f32(basis1, "basis1"),
-                _dev_f32(basis2, "basis2"), _dev_f32(inp, "in"), _dev_f32(out, "out"),
-                _stream(stream, inp.device))
-        capi.check(rc, "sf_bwdtrans_hex_f32")
-        return out
-    v = _variant(variant)
-    if wsp is None and v in (2, 4) and nelmt:
-        wsp = torch.empty(hex_wsp_doubles((nq0, nq1, nq2), nelmt), dtype=torch.float64,
-                          device=inp.device)
-    with torch.cuda.device(inp.device):
-        rc = capi.lib().sf_bwdtrans_hex_f64_variant(
-            v, nq0, nq1, nq2, nelmt, _dev_f64(basis0, "basis0"), _dev_f64(basis1, "basis1"),
-            _dev_f64(basis2, "basis2"), _dev_f64(inp, "in"),
-            _dev_f64(wsp, "wsp") if wsp is not None else None, _dev_f64(out, "out"),
-            _stream(stream, inp.device))
-    capi.check(rc, "sf_bwdtrans_hex_f64")
-    return out
+# What one operator family is to _operator_call: the stem of its symbols (sf_<stem>_{hex,quad}_{f64_variant,f32}); whether
+# `inp` / `out` hold quadrature points per element (else modes); extras(nelmt, points per element) -> the operands between
+# the bases and `in`, in the order of the C signature, as (name, tensor, expected numel, may be None); lam, or None for a
+# family without one; whether float32 quietly takes the AUTO route for any `variant` (BwdTrans) or refuses all but "auto";
+# BwdTrans only: wsp_need(nelmt) -> {variant: numel of the caller-owned workspace it needs}.
+_Family = collections.namedtuple("_Family", "stem inp_points out_points extras lam f32_ignores_variant wsp_need",
+                                 defaults=(lambda nelmt, nqt: [], None, False, None))
 
 
-def bwdtrans_quad(nq, basis0, basis1, inp, out=None, variant="auto", wsp=None, stream=None):
-    """out[e][j][i] = sum_qp in[e][q][p] B0[p][i] B1[q][j] on inp's device."""
-    nq0, nq1 = (int(x) for x in nq)
-    nmt = (nq0 - 1) * (nq1 - 1)
-    if nmt <= 0:
-        raise capi.SumfactError(capi.SF_EINVAL, "bwdtrans_quad")
-    nelmt = inp.numel() // nmt
-    if nelmt * nmt != inp.numel():
-        raise ValueError("in.numel() is not a multiple of nm0*nm1")
-    if out is None:
-        out = torch.empty(nelmt * nq0 * nq1, dtype=inp.dtype, device=inp.device)
-    elif out.numel() != nelmt * nq0 * nq1:
-        raise ValueError("out has the wrong size")
-    v = _variant(variant)
-    _check_sizes("bwdtrans_quad", (basis0, basis1), (nq0, nq1), wsp,
-                 {2: nelmt * (nq1 - 1), 4: quad_wsp_doubles((nq0, nq1), nelmt)}.get(v, 0))
-    if inp.dtype == torch.float32:
-        with torch.cuda.device(inp.device):
-            rc = capi.lib().sf_bwdtrans_quad_f32(
-                nq0, nq1, nelmt, _dev_f32(basis0, "basis0"), _dev_f32(basis1, "basis1"),
-                _dev_f32(inp, "in"), _dev_f32(out, "out"), _stream(stream, inp.device))
-        capi.check(rc, "sf_bwdtrans_quad_f32")
-        return out
-    v = _variant(variant)
-    if wsp is None and v in (2, 4) and nelmt:
-        wsp = torch.empty(quad_wsp_doubles((nq0, nq1), nelmt), dtype=torch.float64,
-                          device=inp.device)
-    with torch.cuda.device(inp.device):
-        rc = capi.lib().sf_bwdtrans_quad_f64_variant(
-            v, nq0, nq1, nelmt, _dev_f64(basis0, "basis0"), _dev_f64(basis1, "basis1"),
-            _dev_f64(inp, "in"), _dev_f64(wsp, "wsp") if wsp is not None else None,
-            _dev_f64(out, "out"), _stream(stream, inp.device))
-    capi.check(rc, "sf_bwdtrans_quad_f64")
-    return out
-
-
-def _iprod_call(what, nq, bases, inp, out, variant, stream):
-    """Shared body of iproduct_hex / iproduct_quad: sizes checked here, pointers and alignment in the C ABI."""
+def _operator_call(what, fam, nq, bases, inp, out, variant, stream, wsp=None):
+    """The one call path of bwdtrans_* / iproduct_* / mass_* / helmholtz_* / affine_helmholtz_*: sizes, dtypes and devices
+    are checked here (before any library call), pointers, alignment and overlap in the C ABI."""
     nq = tuple(int(x) for x in nq)
     nmt, nqt = 1, 1
     for q in nq:
         nmt, nqt = nmt * (q - 1), nqt * q
     if nmt <= 0:
         raise capi.SumfactError(capi.SF_EINVAL, what)
-    nelmt = inp.numel() // nqt
-    if nelmt * nqt != inp.numel():
-        raise ValueError(f"{what}: in.numel() is not a multiple of the points per element ({nqt})")
+    n_in, n_out = nqt if fam.inp_points else nmt, nqt if fam.out_points else nmt
+    nelmt = inp.numel() // n_in
+    if nelmt * n_in != inp.numel():
+        raise ValueError(f"{what}: in.numel() is not a multiple of the {'points' if fam.inp_points else 'modes'} per "
+                         f"element ({n_in})")
     if out is None:
-        out = torch.empty(nelmt * nmt, dtype=inp.dtype, device=inp.device)
-    elif out.numel() != nelmt * nmt:
-        raise ValueError(f"{what}: out has the wrong size")
-    _check_sizes(what, bases, nq, None, 0)
-    v = _variant(variant)
-    if inp.dtype == torch.float32:
-        if v != VARIANTS["auto"]:
-            raise ValueError(f"{what}: float32 has the AUTO route only")
-        fn, ptr = getattr(capi.lib(), f"sf_iproduct_{'hex' if len(nq) == 3 else 'quad'}_f32"), _dev_f32
-        head = ()
-    else:
-        fn, ptr = getattr(capi.lib(), f"sf_iproduct_{'hex' if len(nq) == 3 else 'quad'}_f64_variant"), _dev_f64
-        head = (v,)
+        out = torch.empty(nelmt * n_out, dtype=inp.dtype, device=inp.device)
+    lam = None if fam.lam is None else float(fam.lam)
+    operands = [(f"basis{d}", b, (q - 1) * q, False) for d, (b, q) in enumerate(zip(bases, nq))]
+    operands += fam.extras(nelmt, nqt)
+    _check_operands(what, operands + [("out", out, nelmt * n_out, False)], inp, lam)
+    v, f32 = _variant(variant), inp.dtype == torch.float32
+    if fam.wsp_need is not None:        # BwdTrans: the caller-owned workspace of the thread and block-glb variants
+        need = fam.wsp_need(nelmt)
+        if wsp is not None and wsp.numel() < need.get(v, 0):
+            raise ValueError(f"{what}: wsp has {wsp.numel()} values, the variant needs {need[v]}")
+        if wsp is None and not f32 and v in need and nelmt:
+            wsp = torch.empty(max(need.values()), dtype=torch.float64, device=inp.device)
+    if f32 and v != VARIANTS["auto"] and not fam.f32_ignores_variant:
+        raise ValueError(f"{what}: float32 has the AUTO route only")
+    dtype = torch.float32 if f32 else torch.float64
+    fn = getattr(capi.lib(), f"sf_{fam.stem}_{'hex' if len(nq) == 3 else 'quad'}_{'f32' if f32 else 'f64_variant'}")
+    ptrs = [None if t is None else _dev_ptr(t, name, dtype) for name, t, _, _ in operands]
+    if lam is not None:
+        ptrs.append(ctypes.c_double(lam))
+    ptrs.append(_dev_ptr(inp, "in", dtype))
+    if fam.wsp_need is not None and not f32:
+        ptrs.append(None if wsp is None else _dev_ptr(wsp, "wsp", dtype))
     with torch.cuda.device(inp.device):
-        rc = fn(*head, *nq, nelmt, *[ptr(b, f"basis{d}") for d, b in enumerate(bases)], ptr(inp, "in"),
-                ptr(out, "out"), _stream(stream, inp.device))
+        rc = fn(*(() if f32 else (v,)), *nq, nelmt, *ptrs, _dev_ptr(out, "out", dtype), _stream(stream, inp.device))
     capi.check(rc, what)
     return out
+
+
+def bwdtrans_hex(nq, basis0, basis1, basis2, inp, out=None, variant="auto", wsp=None, stream=None):
+    """out[e][k][j][i] = sum_rqp in[e][r][q][p] B0[p][i] B1[q][j] B2[r][k] on inp's device."""
+    _, nq1, nq2 = nq
+    fam = _Family("bwdtrans", False, True, f32_ignores_variant=True,       # T = float (SURVEY s8(f)-3): AUTO strategy only
+                  wsp_need=lambda n: {2: n * ((nq1 - 1) * (nq2 - 1) + (nq2 - 1)), 4: hex_wsp_doubles(nq, n)})
+    return _operator_call("bwdtrans_hex", fam, nq, (basis0, basis1, basis2), inp, out, variant, stream, wsp)
+
+
+def bwdtrans_quad(nq, basis0, basis1, inp, out=None, variant="auto", wsp=None, stream=None):
+    """out[e][j][i] = sum_qp in[e][q][p] B0[p][i] B1[q][j] on inp's device."""
+    fam = _Family("bwdtrans", False, True, f32_ignores_variant=True,
+                  wsp_need=lambda n: {2: n * (nq[1] - 1), 4: quad_wsp_doubles(nq, n)})
+    return _operator_call("bwdtrans_quad", fam, nq, (basis0, basis1), inp, out, variant, stream, wsp)
+
+
+_IPROD = _Family("iproduct", True, False)
 
 
 def iproduct_hex(nq, basis0, basis1, basis2, inp, out=None, variant="auto", stream=None):
     """IProductWRTBase, the transpose of bwdtrans_hex: out[e][r][q][p] = sum_kji in[e][k][j][i] B0[p][i] B1[q][j]
     B2[r][k] on inp's device.  Same bases as bwdtrans_hex; inp holds nq0*nq1*nq2 values per element, out nm0*nm1*nm2.
     float64 takes variant "auto", "wave" or "generic"; float32 the AUTO route."""
-    return _iprod_call("iproduct_hex", nq, (basis0, basis1, basis2), inp, out, variant, stream)
+    return _operator_call("iproduct_hex", _IPROD, nq, (basis0, basis1, basis2), inp, out, variant, stream)
 
 
 def iproduct_quad(nq, basis0, basis1, inp, out=None, variant="auto", stream=None):
     """IProductWRTBase, the transpose of bwdtrans_quad: out[e][q][p] = sum_ji in[e][j][i] B0[p][i] B1[q][j]."""
-    return _iprod_call("iproduct_quad", nq, (basis0, basis1), inp, out, variant, stream)
+    return _operator_call("iproduct_quad", _IPROD, nq, (basis0, basis1), inp, out, variant, stream)
 
 
-def _mass_call(what, nq, bases, w, inp, out, variant, stream):
-    """Shared body of mass_hex / mass_quad: sizes checked here, pointers, alignment and overlap in the C ABI."""
-    nq = tuple(int(x) for x in nq)
-    nmt, nqt = 1, 1
-    for q in nq:
-        nmt, nqt = nmt * (q - 1), nqt * q
-    if nmt <= 0:
-        raise capi.SumfactError(capi.SF_EINVAL, what)
-    nelmt = inp.numel() // nmt
-    if nelmt * nmt != inp.numel():
-        raise ValueError(f"{what}: in.numel() is not a multiple of the modes per element ({nmt})")
-    if w.numel() != nelmt * nqt:
-        raise ValueError(f"{what}: w has {w.numel()} values, nelmt * points per element = {nelmt * nqt}")
-    if w.dtype != inp.dtype:
-        raise ValueError(f"{what}: w is {w.dtype}, in is {inp.dtype}")
-    if out is None:
-        out = torch.empty(nelmt * nmt, dtype=inp.dtype, device=inp.device)
-    elif out.numel() != nelmt * nmt:
-        raise ValueError(f"{what}: out has the wrong size")
-    _check_sizes(what, bases, nq, None, 0)
-    v = _variant(variant)
-    shape = "hex" if len(nq) == 3 else "quad"
-    if inp.dtype == torch.float32:
-        if v != VARIANTS["auto"]:
-            raise ValueError(f"{what}: float32 has the AUTO route only")
-        fn, ptr, head = getattr(capi.lib(), f"sf_mass_{shape}_f32"), _dev_f32, ()
-    else:
-        fn, ptr, head = getattr(capi.lib(), f"sf_mass_{shape}_f64_variant"), _dev_f64, (v,)
-    with torch.cuda.device(inp.device):
-        rc = fn(*head, *nq, nelmt, *[ptr(b, f"basis{d}") for d, b in enumerate(bases)], ptr(w, "w"), ptr(inp, "in"),
-                ptr(out, "out"), _stream(stream, inp.device))
-    capi.check(rc, what)
-    return out
+def _mass(w):
+    return _Family("mass", False, False, lambda nelmt, nqt: [("w", w, nelmt * nqt, False)])
 
 
 def mass_hex(nq, basis0, basis1, basis2, w, inp, out=None, variant="auto", stream=None):
@@ -216,67 +155,23 @@ def mass_hex(nq, basis0, basis1, basis2, w, inp, out=None, variant="auto", strea
     w[e][k][j][i] (sum_rqp in[e][r][q][p] B0[p][i] B1[q][j] B2[r][k]) on inp's device.  The bases of bwdtrans_hex; inp and
     out hold nm0*nm1*nm2 modes per element, w nq0*nq1*nq2 weights per element.  out may not overlap inp or w.  float64
     takes variant "auto", "wave" or "generic"; float32 the AUTO route.  A plain function: no autograd."""
-    return _mass_call("mass_hex", nq, (basis0, basis1, basis2), w, inp, out, variant, stream)
+    return _operator_call("mass_hex", _mass(w), nq, (basis0, basis1, basis2), inp, out, variant, stream)
 
 
 def mass_quad(nq, basis0, basis1, w, inp, out=None, variant="auto", stream=None):
     """The fused mass operator in 2D: out[e][q'][p'] = sum_ji B0[p'][i] B1[q'][j] w[e][j][i] (sum_qp in[e][q][p] B0[p][i]
     B1[q][j])."""
-    return _mass_call("mass_quad", nq, (basis0, basis1), w, inp, out, variant, stream)
+    return _operator_call("mass_quad", _mass(w), nq, (basis0, basis1), inp, out, variant, stream)
 
 
-def _helmholtz_call(what, nq, bases, derivs, g, w, lam, inp, out, variant, stream):
-    """Shared body of helmholtz_hex / helmholtz_quad: sizes, dtypes and devices checked here (before any library call),
-    pointers, alignment and overlap in the C ABI."""
-    nq = tuple(int(x) for x in nq)
-    dim = len(nq)
-    nmt, nqt = 1, 1
-    for q in nq:
-        nmt, nqt = nmt * (q - 1), nqt * q
-    if nmt <= 0:
-        raise capi.SumfactError(capi.SF_EINVAL, what)
-    lam = float(lam)
-    nelmt = inp.numel() // nmt
-    if nelmt * nmt != inp.numel():
-        raise ValueError(f"{what}: in.numel() is not a multiple of the modes per element ({nmt})")
-    ncomp = dim * (dim + 1) // 2
-    if g.numel() != nelmt * ncomp * nqt:
-        raise ValueError(f"{what}: g has {g.numel()} values, nelmt * {ncomp} * points per element = {nelmt * ncomp * nqt}")
-    if w is None:
-        if lam != 0.0:
-            raise ValueError(f"{what}: w=None needs lam == 0")
-    elif w.numel() != nelmt * nqt:
-        raise ValueError(f"{what}: w has {w.numel()} values, nelmt * points per element = {nelmt * nqt}")
-    for name, t in (("g", g), ("w", w)) + tuple((f"deriv{d}", t) for d, t in enumerate(derivs)):
-        if t is None:
-            continue
-        if t.dtype != inp.dtype:
-            raise ValueError(f"{what}: {name} is {t.dtype}, in is {inp.dtype}")
-        if t.device != inp.device:
-            raise ValueError(f"{what}: {name} is on {t.device}, in is on {inp.device}")
-    for d, (t, q) in enumerate(zip(derivs, nq)):
-        if t.numel() != q * q:
-            raise ValueError(f"{what}: deriv{d} has {t.numel()} values, nq*nq = {q * q}")
-    if out is None:
-        out = torch.empty(nelmt * nmt, dtype=inp.dtype, device=inp.device)
-    elif out.numel() != nelmt * nmt:
-        raise ValueError(f"{what}: out has the wrong size")
-    _check_sizes(what, bases, nq, None, 0)
-    v = _variant(variant)
-    shape = "hex" if dim == 3 else "quad"
-    if inp.dtype == torch.float32:
-        if v != VARIANTS["auto"]:
-            raise ValueError(f"{what}: float32 has the AUTO route only")
-        fn, ptr, head = getattr(capi.lib(), f"sf_helmholtz_{shape}_f32"), _dev_f32, ()
-    else:
-        fn, ptr, head = getattr(capi.lib(), f"sf_helmholtz_{shape}_f64_variant"), _dev_f64, (v,)
-    with torch.cuda.device(inp.device):
-        rc = fn(*head, *nq, nelmt, *[ptr(b, f"basis{d}") for d, b in enumerate(bases)],
-                *[ptr(t, f"deriv{d}") for d, t in enumerate(derivs)], ptr(g, "g"),
-                ptr(w, "w") if w is not None else None, ctypes.c_double(lam), ptr(inp, "in"), ptr(out, "out"),
-                _stream(stream, inp.device))
-    capi.check(rc, what)
-    return out
+def _per_direction(name, tensors, numel, nq):
+    return [(f"{name}{d}", t, numel(int(q)), False) for d, (t, q) in enumerate(zip(tensors, nq))]
+
+
+def _helmholtz(nq, derivs, g, w, lam):
+    ncomp = len(nq) * (len(nq) + 1) // 2
+    return _Family("helmholtz", False, False, lambda nelmt, nqt: _per_direction("deriv", derivs, lambda q: q * q, nq) + [
+        ("g", g, nelmt * ncomp * nqt, False), ("w", w, nelmt * nqt, True)], lam)
 
 
 def helmholtz_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, g, w, lam, inp, out=None, variant="auto",
@@ -286,72 +181,22 @@ def helmholtz_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, g, w, lam,
     g[e][c][k][j][i] with c = 0..5 for (00, 01, 02, 11, 12, 22); w[e][k][j][i], or None with lam == 0 (the Laplacian);
     inp and out hold nm0*nm1*nm2 modes per element.  out may not overlap inp, g or w.  float64 takes variant "auto",
     "wave" or "generic"; float32 the AUTO route.  A plain function: no autograd."""
-    return _helmholtz_call("helmholtz_hex", nq, (basis0, basis1, basis2), (deriv0, deriv1, deriv2), g, w, lam, inp, out,
-                           variant, stream)
+    return _operator_call("helmholtz_hex", _helmholtz(nq, (deriv0, deriv1, deriv2), g, w, lam), nq,
+                          (basis0, basis1, basis2), inp, out, variant, stream)
 
 
 def helmholtz_quad(nq, basis0, basis1, deriv0, deriv1, g, w, lam, inp, out=None, variant="auto", stream=None):
     """The fused Helmholtz operator in 2D: g[e][c][j][i] with c = 0..2 for (00, 01, 11), w[e][j][i] or None with
     lam == 0."""
-    return _helmholtz_call("helmholtz_quad", nq, (basis0, basis1), (deriv0, deriv1), g, w, lam, inp, out, variant, stream)
+    return _operator_call("helmholtz_quad", _helmholtz(nq, (deriv0, deriv1), g, w, lam), nq, (basis0, basis1), inp, out,
+                          variant, stream)
 
 
-def _affine_call(what, nq, bases, derivs, qws, ge, je, lam, inp, out, variant, stream):
-    """Shared body of affine_helmholtz_hex / affine_helmholtz_quad: sizes, dtypes and devices checked here (before any
-    library call), pointers, alignment and overlap in the C ABI."""
-    nq = tuple(int(x) for x in nq)
-    dim = len(nq)
-    nmt = 1
-    for q in nq:
-        nmt *= q - 1
-    if nmt <= 0:
-        raise capi.SumfactError(capi.SF_EINVAL, what)
-    lam = float(lam)
-    nelmt = inp.numel() // nmt
-    if nelmt * nmt != inp.numel():
-        raise ValueError(f"{what}: in.numel() is not a multiple of the modes per element ({nmt})")
-    ncomp = dim * (dim + 1) // 2
-    if ge.numel() != nelmt * ncomp:
-        raise ValueError(f"{what}: ge has {ge.numel()} values, nelmt * {ncomp} = {nelmt * ncomp}")
-    if je is None:
-        if lam != 0.0:
-            raise ValueError(f"{what}: je=None needs lam == 0")
-    elif je.numel() != nelmt:
-        raise ValueError(f"{what}: je has {je.numel()} values, nelmt = {nelmt}")
-    named = ((("ge", ge), ("je", je)) + tuple((f"deriv{d}", t) for d, t in enumerate(derivs))
-             + tuple((f"qw{d}", t) for d, t in enumerate(qws)))
-    for name, t in named:
-        if t is None:
-            continue
-        if t.dtype != inp.dtype:
-            raise ValueError(f"{what}: {name} is {t.dtype}, in is {inp.dtype}")
-        if t.device != inp.device:
-            raise ValueError(f"{what}: {name} is on {t.device}, in is on {inp.device}")
-    for d, (t, qw, q) in enumerate(zip(derivs, qws, nq)):
-        if t.numel() != q * q:
-            raise ValueError(f"{what}: deriv{d} has {t.numel()} values, nq*nq = {q * q}")
-        if qw.numel() != q:
-            raise ValueError(f"{what}: qw{d} has {qw.numel()} values, nq = {q}")
-    if out is None:
-        out = torch.empty(nelmt * nmt, dtype=inp.dtype, device=inp.device)
-    elif out.numel() != nelmt * nmt:
-        raise ValueError(f"{what}: out has the wrong size")
-    _check_sizes(what, bases, nq, None, 0)
-    v = _variant(variant)
-    shape = "hex" if dim == 3 else "quad"
-    if inp.dtype == torch.float32:
-        if v != VARIANTS["auto"]:
-            raise ValueError(f"{what}: float32 has the AUTO route only")
-        fn, ptr, head = getattr(capi.lib(), f"sf_affine_helmholtz_{shape}_f32"), _dev_f32, ()
-    else:
-        fn, ptr, head = getattr(capi.lib(), f"sf_affine_helmholtz_{shape}_f64_variant"), _dev_f64, (v,)
-    with torch.cuda.device(inp.device):
-        rc = fn(*head, *nq, nelmt, *[ptr(b, f"basis{d}") for d, b in enumerate(bases)],
-                *[ptr(t, f"deriv{d}") for d, t in enumerate(derivs)], *[ptr(t, f"qw{d}") for d, t in enumerate(qws)],
-                ptr(ge, "ge"), ptr(je, "je") if je is not None else None, ctypes.c_double(lam), ptr(inp, "in"),
-                ptr(out, "out"), _stream(stream, inp.device))
-    capi.check(rc, what)
-    return out
+def _affine(nq, derivs, qws, ge, je, lam):
+    ncomp = len(nq) * (len(nq) + 1) // 2
+    return _Family("affine_helmholtz", False, False, lambda nelmt, nqt: (
+        _per_direction("deriv", derivs, lambda q: q * q, nq) + _per_direction("qw", qws, lambda q: q, nq)
+        + [("ge", ge, nelmt * ncomp, False), ("je", je, nelmt, True)]), lam)
 
 
 def affine_helmholtz_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, qw0, qw1, qw2, ge, je, lam, inp, out=None,
@@ -362,16 +207,16 @@ def affine_helmholtz_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, qw0
     (00, 01, 02, 11, 12, 22), the element's |det J| J^-1 J^-T; je[e] = |det J|, or None with lam == 0 (the Laplacian).
     out may not overlap inp, ge or je.  float64 takes variant "auto", "wave" or "generic"; float32 the AUTO route.  A
     plain function: no autograd."""
-    return _affine_call("affine_helmholtz_hex", nq, (basis0, basis1, basis2), (deriv0, deriv1, deriv2), (qw0, qw1, qw2),
-                        ge, je, lam, inp, out, variant, stream)
+    return _operator_call("affine_helmholtz_hex", _affine(nq, (deriv0, deriv1, deriv2), (qw0, qw1, qw2), ge, je, lam), nq,
+                          (basis0, basis1, basis2), inp, out, variant, stream)
 
 
 def affine_helmholtz_quad(nq, basis0, basis1, deriv0, deriv1, qw0, qw1, ge, je, lam, inp, out=None, variant="auto",
                           stream=None):
     """The fused Helmholtz operator on affine elements in 2D: ge[e][c] with c = 0..2 for (00, 01, 11), je[e] or None with
     lam == 0."""
-    return _affine_call("affine_helmholtz_quad", nq, (basis0, basis1), (deriv0, deriv1), (qw0, qw1), ge, je, lam, inp,
-                        out, variant, stream)
+    return _operator_call("affine_helmholtz_quad", _affine(nq, (deriv0, deriv1), (qw0, qw1), ge, je, lam), nq,
+                          (basis0, basis1), inp, out, variant, stream)
 
 
 class _BwdTrans(torch.autograd.Function):
@@ -454,13 +299,12 @@ def bwdtrans_specialised(nq, *bases, inp, out=None, stream=None):
         raise ValueError("in.numel() is not a multiple of the modes per element")
     if out is None:
         out = torch.empty(nelmt * nqt, dtype=inp.dtype, device=inp.device)
-    elif out.numel() != nelmt * nqt:
-        raise ValueError("out has the wrong size")
-    _check_sizes("bwdtrans_specialised", bases, ext, None, 0)
-    ptrs = [_dev_f64(b, f"basis{d}", inp.dtype) for d, b in enumerate(bases)] + [None] * (3 - dim)
+    _check_operands("bwdtrans_specialised", [(f"basis{d}", b, (q - 1) * q, False) for d, (b, q) in enumerate(zip(bases, ext))]
+                    + [("out", out, nelmt * nqt, False)], inp)
+    ptrs = [_dev_ptr(b, f"basis{d}", inp.dtype) for d, b in enumerate(bases)] + [None] * (3 - dim)
     with torch.cuda.device(inp.device):
-        rc = capi.lib().sf_bwdtrans_specialised(*args, nelmt, *ptrs, _dev_f64(inp, "in", inp.dtype),
-                                                _dev_f64(out, "out", inp.dtype), _stream(stream, inp.device))
+        rc = capi.lib().sf_bwdtrans_specialised(*args, nelmt, *ptrs, _dev_ptr(inp, "in", inp.dtype),
+                                                _dev_ptr(out, "out", inp.dtype), _stream(stream, inp.device))
     capi.check(rc, "sf_bwdtrans_specialised")
     return out
 
@@ -470,7 +314,7 @@ def interleave64(src, nelmt, n, inverse=False, stream=None):
     padded = (nelmt + 63) // 64 * 64
     dst = torch.zeros((nelmt if inverse else padded) * n, dtype=torch.float64, device=src.device)
     with torch.cuda.device(src.device):
-        capi.check(capi.lib().sf_interleave64_f64(_dev_f64(src, "src"), _dev_f64(dst, "dst"), nelmt,
+        capi.check(capi.lib().sf_interleave64_f64(_dev_ptr(src, "src"), _dev_ptr(dst, "dst"), nelmt,
                                                   n, 1 if inverse else 0, _stream(stream, src.device)),
                    "sf_interleave64_f64")
     return dst
@@ -486,9 +330,9 @@ def bwdtrans_hex_interleaved(nq, basis0, basis1, basis2, in_il, nelmt, stream=No
                       device=in_il.device)
     with torch.cuda.device(in_il.device):
         rc = capi.lib().sf_bwdtrans_hex_f64_interleaved(
-            nq0, nq1, nq2, nelmt, _dev_f64(basis0, "basis0"), _dev_f64(basis1, "basis1"),
-            _dev_f64(basis2, "basis2"), _dev_f64(in_il, "in_il"), _dev_f64(wsp, "wsp"),
-            _dev_f64(out, "out_il"), _stream(stream, in_il.device))
+            nq0, nq1, nq2, nelmt, _dev_ptr(basis0, "basis0"), _dev_ptr(basis1, "basis1"),
+            _dev_ptr(basis2, "basis2"), _dev_ptr(in_il, "in_il"), _dev_ptr(wsp, "wsp"),
+            _dev_ptr(out, "out_il"), _stream(stream, in_il.device))
     capi.check(rc, "sf_bwdtrans_hex_f64_interleaved")
     return out
 
@@ -498,10 +342,10 @@ def sumsq(x, stream=None):
     res = ctypes.c_double(0.0)
     with torch.cuda.device(x.device):
         if x.dtype == torch.float32:
-            rc = capi.lib().sf_sumsq_f32(_dev_f32(x, "x"), x.numel(), ctypes.byref(res),
+            rc = capi.lib().sf_sumsq_f32(_dev_ptr(x, "x", torch.float32), x.numel(), ctypes.byref(res),
                                          _stream(stream, x.device))
         else:
-            rc = capi.lib().sf_sumsq_f64(_dev_f64(x, "x"), x.numel(), ctypes.byref(res),
+            rc = capi.lib().sf_sumsq_f64(_dev_ptr(x, "x"), x.numel(), ctypes.byref(res),
                                          _stream(stream, x.device))
     capi.check(rc, "sf_sumsq")
     return res.value
@@ -549,7 +393,7 @@ def fill_l2norm(n, device="cuda", stream=None):
 
 def stream_copy(src, dst, stream=None):
     with torch.cuda.device(src.device):
-        capi.check(capi.lib().sf_stream_copy_f64(_dev_f64(src, "src"), _dev_f64(dst, "dst"),
+        capi.check(capi.lib().sf_stream_copy_f64(_dev_ptr(src, "src"), _dev_ptr(dst, "dst"),
                                                  src.numel(), _stream(stream, src.device)),
                    "sf_stream_copy_f64")
     return dst
@@ -560,7 +404,7 @@ def fill_vecadd(n, device="cuda", stream=None):
     x = torch.empty(n, dtype=torch.float64, device=device)
     y = torch.empty(n, dtype=torch.float64, device=device)
     with torch.cuda.device(x.device):
-        capi.check(capi.lib().sf_fill_vecadd_f64(_dev_f64(x, "x"), _dev_f64(y, "y"), n,
+        capi.check(capi.lib().sf_fill_vecadd_f64(_dev_ptr(x, "x"), _dev_ptr(y, "y"), n,
                                                  _stream(stream, x.device)), "sf_fill_vecadd_f64")
     return x, y
 
@@ -568,7 +412,7 @@ def fill_vecadd(n, device="cuda", stream=None):
 def vector_add(x, y, stream=None):
     """x += y in place (benchmark02's operation)."""
     with torch.cuda.device(x.device):
-        capi.check(capi.lib().sf_vector_add_f64(_dev_f64(x, "x"), _dev_f64(y, "y"), x.numel(),
+        capi.check(capi.lib().sf_vector_add_f64(_dev_ptr(x, "x"), _dev_ptr(y, "y"), x.numel(),
                                                 _stream(stream, x.device)), "sf_vector_add_f64")
     return x
 
@@ -578,7 +422,7 @@ def fill_matvec(m, n, device="cuda", stream=None):
     a = torch.empty(m * n, dtype=torch.float64, device=device)
     x = torch.empty(n, dtype=torch.float64, device=device)
     with torch.cuda.device(a.device):
-        capi.check(capi.lib().sf_fill_matvec_f64(_dev_f64(a, "A"), _dev_f64(x, "x"), m, n,
+        capi.check(capi.lib().sf_fill_matvec_f64(_dev_ptr(a, "A"), _dev_ptr(x, "x"), m, n,
                                                  _stream(stream, a.device)), "sf_fill_matvec_f64")
     return a, x
 
@@ -588,8 +432,8 @@ def matvec(m, n, a, x, y=None, stream=None):
     if y is None:
         y = torch.empty(m, dtype=torch.float64, device=a.device)
     with torch.cuda.device(a.device):
-        capi.check(capi.lib().sf_matvec_f64(m, n, _dev_f64(a, "A"), _dev_f64(x, "x"),
-                                            _dev_f64(y, "y"), _stream(stream, a.device)), "sf_matvec_f64")
+        capi.check(capi.lib().sf_matvec_f64(m, n, _dev_ptr(a, "A"), _dev_ptr(x, "x"),
+                                            _dev_ptr(y, "y"), _stream(stream, a.device)), "sf_matvec_f64")
     return y
 
 

@@ -19,10 +19,6 @@ SYMBOLS = {
     "sf_version": (_i, []),
     "sf_error_string": (ctypes.c_char_p, [_i]),
     "sf_variant_name": (ctypes.c_char_p, [_i]),
-    "sf_bwdtrans_hex_f64": (_i, [_u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sf_bwdtrans_hex_f64_variant": (_i, [_i, _u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sf_bwdtrans_quad_f64": (_i, [_u, _u, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "sf_bwdtrans_quad_f64_variant": (_i, [_i, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sf_sumsq_f64": (_i, [_vp, _sz, ctypes.POINTER(ctypes.c_double), _vp]),
     "sf_sumsq_f64_async": (_i, [_vp, _sz, _vp, _vp]),
     "sf_fill_sincos_f64": (_i, [_vp, _sz, _sz, _vp]),
@@ -32,37 +28,10 @@ SYMBOLS = {
     "sf_stream_copy_f64": (_i, [_vp, _vp, _sz, _vp]),
     "sf_bwdtrans_hex_f64_interleaved": (_i, [_u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sf_interleave64_f64": (_i, [_vp, _vp, _sz, _sz, _i, _vp]),
-    "sf_bwdtrans_hex_f32": (_i, [_u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sf_bwdtrans_quad_f32": (_i, [_u, _u, _sz, _vp, _vp, _vp, _vp, _vp]),
     "sf_sumsq_f32": (_i, [_vp, _sz, ctypes.POINTER(ctypes.c_double), _vp]),
     "sf_fill_sincos_f32": (_i, [_vp, _sz, _sz, _vp]),
     "sf_fill_basis_f32": (_i, [_vp, _sz, _sz, _vp]),
     "sf_fill_random_f32": (_i, [_vp, _sz, _u64, _u64, _vp]),
-    "sf_iproduct_hex_f64": (_i, [_u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sf_iproduct_hex_f64_variant": (_i, [_i, _u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sf_iproduct_quad_f64": (_i, [_u, _u, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "sf_iproduct_quad_f64_variant": (_i, [_i, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "sf_iproduct_hex_f32": (_i, [_u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sf_iproduct_quad_f32": (_i, [_u, _u, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "sf_mass_hex_f64": (_i, [_u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sf_mass_hex_f64_variant": (_i, [_i, _u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sf_mass_quad_f64": (_i, [_u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sf_mass_quad_f64_variant": (_i, [_i, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sf_mass_hex_f32": (_i, [_u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sf_mass_quad_f32": (_i, [_u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sf_helmholtz_hex_f64": (_i, [_u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp]),
-    "sf_helmholtz_hex_f64_variant": (_i, [_i, _u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double,
-                                          _vp, _vp, _vp]),
-    "sf_helmholtz_quad_f64": (_i, [_u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp]),
-    "sf_helmholtz_quad_f64_variant": (_i, [_i, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp]),
-    "sf_helmholtz_hex_f32": (_i, [_u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp]),
-    "sf_helmholtz_quad_f32": (_i, [_u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp]),
-    "sf_affine_helmholtz_hex_f64": (_i, [_u, _u, _u, _sz] + [_vp] * 11 + [ctypes.c_double, _vp, _vp, _vp]),
-    "sf_affine_helmholtz_hex_f64_variant": (_i, [_i, _u, _u, _u, _sz] + [_vp] * 11 + [ctypes.c_double, _vp, _vp, _vp]),
-    "sf_affine_helmholtz_quad_f64": (_i, [_u, _u, _sz] + [_vp] * 8 + [ctypes.c_double, _vp, _vp, _vp]),
-    "sf_affine_helmholtz_quad_f64_variant": (_i, [_i, _u, _u, _sz] + [_vp] * 8 + [ctypes.c_double, _vp, _vp, _vp]),
-    "sf_affine_helmholtz_hex_f32": (_i, [_u, _u, _u, _sz] + [_vp] * 11 + [ctypes.c_double, _vp, _vp, _vp]),
-    "sf_affine_helmholtz_quad_f32": (_i, [_u, _u, _sz] + [_vp] * 8 + [ctypes.c_double, _vp, _vp, _vp]),
     "sf_vector_add_f64": (_i, [_vp, _vp, _sz, _vp]),
     "sf_fill_vecadd_f64": (_i, [_vp, _vp, _sz, _vp]),
     "sf_matvec_f64": (_i, [_u, _u, _vp, _vp, _vp, _vp]),
@@ -75,6 +44,23 @@ SYMBOLS = {
     "sf_last_specialise_log": (ctypes.c_char_p, []),
     "sf_shutdown": (_i, []),
 }
+
+
+def _operator_symbols():
+    """sf_<stem>_{hex,quad}_{f64,f64_variant,f32} of the five operator families: [variant,] the extents, nelmt, the pointer
+    operands in front of `in` (so many per direction, so many per call), [lambda,] in, [BwdTrans _variant: wsp,] out, stream."""
+    rows = {"bwdtrans": (1, 0, False), "iproduct": (1, 0, False), "mass": (1, 1, False), "helmholtz": (2, 2, True),
+            "affine_helmholtz": (3, 2, True)}
+    for stem, (per_direction, per_call, has_lambda) in rows.items():
+        for shape, dim in (("hex", 3), ("quad", 2)):
+            tail = [_vp] * (per_direction * dim + per_call) + ([ctypes.c_double] if has_lambda else []) + [_vp, _vp, _vp]
+            for sfx in ("f64", "f64_variant", "f32"):
+                head = [_i] if sfx == "f64_variant" else []
+                wsp = [_vp] if (stem, sfx) == ("bwdtrans", "f64_variant") else []
+                yield f"sf_{stem}_{shape}_{sfx}", (_i, head + [_u] * dim + [_sz] + tail + wsp)
+
+
+SYMBOLS.update(_operator_symbols())
 
 _lib = None
 

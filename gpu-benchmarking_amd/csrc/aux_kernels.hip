@@ -603,12 +603,6 @@ int release_workspaces()
     return SF_OK;
 }
 
-static inline int launch_rc()
-{
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
-}
-
 static inline unsigned fill_grid(uint64_t n)
 {
     const uint64_t want = (n + 255) / 256;

@@ -330,12 +330,6 @@ __global__ __launch_bounds__(256) void interleave64_kernel(const double *__restr
 }
 
 // ------------------------------------------------------------------------------------------------
-static inline int launch_rc()
-{
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
-}
-
 constexpr size_t kMaxDynLds = 160 * 1024;
 
 // Launch hints = the reference drivers' `threads` / `elblocks` CLI arguments
@@ -382,7 +376,7 @@ static inline unsigned hinted_grid(uint64_t nelmt, uint64_t cap)
 }
 
 template <typename T>
-int launch_hex_generic_t(int variant, unsigned nq0, unsigned nq1, unsigned nq2, const HexArgsT<T> &a,
+static int launch_hex_generic_t(int variant, unsigned nq0, unsigned nq1, unsigned nq2, const HexArgsT<T> &a,
                          hipStream_t s)
 {
     const size_t nm0 = nq0 - 1, nm1 = nq1 - 1, nm2 = nq2 - 1;
@@ -447,7 +441,7 @@ int launch_hex_generic_t(int variant, unsigned nq0, unsigned nq1, unsigned nq2, 
 }
 
 template <typename T>
-int launch_quad_generic_t(int variant, unsigned nq0, unsigned nq1, const QuadArgsT<T> &a, hipStream_t s)
+static int launch_quad_generic_t(int variant, unsigned nq0, unsigned nq1, const QuadArgsT<T> &a, hipStream_t s)
 {
     const size_t nm0 = nq0 - 1, nm1 = nq1 - 1;
     const size_t nbas = nm0 * nq0 + nm1 * nq1;
@@ -508,11 +502,18 @@ int launch_quad_generic_t(int variant, unsigned nq0, unsigned nq1, const QuadArg
     return launch_rc();
 }
 
-int launch_hex_generic(int variant, unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a,
-                       hipStream_t s)
+template <int DIM, typename T>
+int launch_bwd_generic(int variant, const unsigned (&nq)[3], const ArgsT<DIM, T> &a, hipStream_t s)
 {
-    return launch_hex_generic_t<double>(variant, nq0, nq1, nq2, a, s);
+    if constexpr (DIM == 3)
+        return launch_hex_generic_t<T>(variant, nq[0], nq[1], nq[2], a, s);
+    else
+        return launch_quad_generic_t<T>(variant, nq[0], nq[1], a, s);
 }
+template int launch_bwd_generic<3, double>(int, const unsigned (&)[3], const HexArgs &, hipStream_t);
+template int launch_bwd_generic<3, float>(int, const unsigned (&)[3], const HexArgsT<float> &, hipStream_t);
+template int launch_bwd_generic<2, double>(int, const unsigned (&)[3], const QuadArgs &, hipStream_t);
+template int launch_bwd_generic<2, float>(int, const unsigned (&)[3], const QuadArgsT<float> &, hipStream_t);
 
 int launch_hex_interleaved(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, hipStream_t s)
 {
@@ -541,20 +542,6 @@ int launch_interleave64(const double *src, double *dst, size_t nelmt, size_t n, 
     interleave64_kernel<<<(unsigned)(want > cap ? cap : want), 256, 0, s>>>(src, dst, nelmt, n,
                                                                             inverse);
     return launch_rc();
-}
-int launch_hex_generic_f32(int variant, unsigned nq0, unsigned nq1, unsigned nq2,
-                           const HexArgsT<float> &a, hipStream_t s)
-{
-    return launch_hex_generic_t<float>(variant, nq0, nq1, nq2, a, s);
-}
-int launch_quad_generic(int variant, unsigned nq0, unsigned nq1, const QuadArgs &a, hipStream_t s)
-{
-    return launch_quad_generic_t<double>(variant, nq0, nq1, a, s);
-}
-int launch_quad_generic_f32(int variant, unsigned nq0, unsigned nq1, const QuadArgsT<float> &a,
-                            hipStream_t s)
-{
-    return launch_quad_generic_t<float>(variant, nq0, nq1, a, s);
 }
 
 } // namespace sf

@@ -52,22 +52,10 @@ __global__ __launch_bounds__(256) void hex_nq2_stream_kernel(const double *__res
     }
 }
 
-static int launch_hex_nq2(const HexArgs &a, hipStream_t s)
-{
-    if (a.nelmt == 0)
-        return SF_OK;
-    const uint64_t blocks = (a.nelmt * 4 + 255) / 256;
-    if (blocks > 0x7fffffffull)
-        return SF_EINVAL;
-    hex_nq2_stream_kernel<<<(unsigned)blocks, 256, 0, s>>>(a.b0, a.b1, a.b2, a.in, a.out, a.nelmt);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
-}
-
 template <int NQ> static int go(const HexArgs &a, hipStream_t s)
 {
     if constexpr (NQ == 2)
-        return launch_hex_nq2(a, s);
+        return launch_stream(hex_nq2_stream_kernel, a.nelmt * 4, s, a.b0, a.b1, a.b2, a.in, a.out, a.nelmt);
     using C = HexCfg<NQ>;
     constexpr uint64_t per_block = (uint64_t)C::EC * C::WPB * (C::KM > 0 ? C::KM : 1);
     if (a.nelmt < 2 * per_block * (uint64_t)device_info().num_cu)
@@ -98,7 +86,7 @@ template <int NQ> static int go(const HexArgs &a, hipStream_t s)
 }
 
 // returns SF_ENOTBUILT when nq has no instantiation
-int launch_hex_wave_nq(unsigned nq, const HexArgs &a, hipStream_t s)
+template <> int launch_bwd_wave<3, double>(unsigned nq, const HexArgs &a, hipStream_t s)
 {
     switch (nq)
     {
@@ -140,7 +128,7 @@ template <int NQ> static int go_mfma(const HexArgs &a, hipStream_t s)
     }
 }
 
-int launch_hex_mfma_nq(unsigned nq, const HexArgs &a, hipStream_t s)
+template <> int launch_bwd_mfma<3, double>(unsigned nq, const HexArgs &a, hipStream_t s)
 {
     switch (nq)
     {
@@ -178,7 +166,7 @@ template <int NQ> static int go_mfma4(const HexArgs &a, hipStream_t s)
     return launch_hex_mfma4<NQ, 1, (NQ == 12 ? 1 : 2), 1, 64>(a, s);
 }
 
-int launch_hex_mfma4_nq(unsigned nq, const HexArgs &a, hipStream_t s)
+template <> int launch_bwd_mfma4<3, double>(unsigned nq, const HexArgs &a, hipStream_t s)
 {
     switch (nq)
     {
@@ -192,9 +180,20 @@ int launch_hex_mfma4_nq(unsigned nq, const HexArgs &a, hipStream_t s)
 }
 
 // the measured best matrix-core kernel above the wave kernel's table
-int hex_auto_kernel(unsigned nq)
+static int hex_auto_kernel(unsigned nq)
 {
     return (nq == 12 || nq == 14 || nq == 16) ? SF_VARIANT_MFMA4 : SF_VARIANT_MFMA;
+}
+
+// What SF_VARIANT_AUTO runs in 3D: the wave kernel, and above its table (nq 12..16) the matrix-core kernel that
+// hex_auto_kernel() names.
+template <> int launch_bwd_iso_auto<3, double>(unsigned nq, const HexArgs &a, hipStream_t s)
+{
+    const int rc = launch_bwd_wave<3, double>(nq, a, s);
+    if (rc != SF_ENOTBUILT)
+        return rc;
+    return hex_auto_kernel(nq) == SF_VARIANT_MFMA4 ? launch_bwd_mfma4<3, double>(nq, a, s)
+                                                   : launch_bwd_mfma<3, double>(nq, a, s);
 }
 
 // fp32 (T = float): same kernels with float4 lanes.  Chunks hold twice the fp64 element count (same
@@ -221,16 +220,7 @@ __global__ __launch_bounds__(256) void hex_nq2_stream_f32_kernel(const float *__
 template <int NQ> static int go_f32(const HexArgsT<float> &a, hipStream_t s)
 {
     if constexpr (NQ == 2)
-    {
-        if (a.nelmt == 0)
-            return SF_OK;
-        const uint64_t blocks = (a.nelmt * 2 + 255) / 256;
-        if (blocks > 0x7fffffffull)
-            return SF_EINVAL;
-        hex_nq2_stream_f32_kernel<<<(unsigned)blocks, 256, 0, s>>>(a.b0, a.b1, a.b2, a.in, a.out, a.nelmt);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? SF_OK : (int)e;
-    }
+        return launch_stream(hex_nq2_stream_f32_kernel, a.nelmt * 2, s, a.b0, a.b1, a.b2, a.in, a.out, a.nelmt);
     if constexpr (NQ >= 12)
     {
         // fp32 matrix-core kernel (hex_mfma_kernel, T = float: v_mfma_f32_16x16x4_f32) from nq = 13, where it is ahead of
@@ -253,7 +243,8 @@ template <int NQ> static int go_f32(const HexArgsT<float> &a, hipStream_t s)
     return launch_hex_wave<NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, C::OUT, C::MF, float>(a, s);
 }
 
-int launch_hex_wave_f32_nq(unsigned nq, const HexArgsT<float> &a, hipStream_t s)
+// What AUTO runs in 3D for T = float: the vector kernel up to nq = 12, the fp32 matrix-core kernel at 13..16
+template <> int launch_bwd_iso_auto<3, float>(unsigned nq, const HexArgsT<float> &a, hipStream_t s)
 {
     switch (nq)
     {

@@ -41,22 +41,10 @@ __global__ __launch_bounds__(256) void quad_nq2_stream_kernel(const double *__re
     }
 }
 
-static int launch_quad_nq2(const QuadArgs &a, hipStream_t s)
-{
-    if (a.nelmt == 0)
-        return SF_OK;
-    const uint64_t blocks = (a.nelmt * 2 + 255) / 256;
-    if (blocks > 0x7fffffffull)
-        return SF_EINVAL;
-    quad_nq2_stream_kernel<<<(unsigned)blocks, 256, 0, s>>>(a.b0, a.b1, a.in, a.out, a.nelmt);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
-}
-
 template <int NQ> static int go(const QuadArgs &a, hipStream_t s)
 {
     if constexpr (NQ == 2)
-        return launch_quad_nq2(a, s);
+        return launch_stream(quad_nq2_stream_kernel, a.nelmt * 2, s, a.b0, a.b1, a.in, a.out, a.nelmt);
     using C = QuadCfg<NQ>;
     constexpr uint64_t per_block = (uint64_t)C::EC * C::WPB * (C::KM > 0 ? C::KM : 1);
     if (a.nelmt < 2 * per_block * (uint64_t)device_info().num_cu)
@@ -87,16 +75,7 @@ constexpr int kQuadF32MfmaFrom = 25; // below, the vector kernel is ahead at eve
 template <int NQ> static int go_f32(const QuadArgsT<float> &a, hipStream_t s)
 {
     if constexpr (NQ == 2)
-    {
-        if (a.nelmt == 0)
-            return SF_OK;
-        const uint64_t blocks = (a.nelmt + 255) / 256;
-        if (blocks > 0x7fffffffull)
-            return SF_EINVAL;
-        quad_nq2_stream_f32_kernel<<<(unsigned)blocks, 256, 0, s>>>(a.b0, a.b1, a.in, a.out, a.nelmt);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? SF_OK : (int)e;
-    }
+        return launch_stream(quad_nq2_stream_f32_kernel, a.nelmt, s, a.b0, a.b1, a.in, a.out, a.nelmt);
     if constexpr (NQ >= kQuadF32MfmaFrom)
     {
         // v_mfma_f32_16x16x4_f32 (bwdtrans_mfma.h, T = float): two-element chunks, LDS-staged line-aligned output where the
@@ -128,8 +107,9 @@ template <int NQ> static int go_f32(const QuadArgsT<float> &a, hipStream_t s)
     }
 }
 
-// fp32 (T = float): the vector-ALU kernel up to nq = kQuadF32MfmaFrom - 1, the fp32 matrix-core kernel above
-int launch_quad_wave_f32_nq(unsigned nq, const QuadArgsT<float> &a, hipStream_t s)
+// What AUTO runs in 2D for T = float: the vector-ALU kernel up to nq = kQuadF32MfmaFrom - 1, the fp32 matrix-core kernel
+// above
+template <> int launch_bwd_iso_auto<2, float>(unsigned nq, const QuadArgsT<float> &a, hipStream_t s)
 {
     switch (nq)
     {
@@ -163,7 +143,7 @@ template <int NQ> static int go_mfma(const QuadArgs &a, hipStream_t s)
                             quad_mfma_lds_out(NQ), 64>(a, s);
 }
 
-int launch_quad_mfma_nq(unsigned nq, const QuadArgs &a, hipStream_t s)
+template <> int launch_bwd_mfma<2, double>(unsigned nq, const QuadArgs &a, hipStream_t s)
 {
     switch (nq)
     {
@@ -201,7 +181,7 @@ template <int NQ> static int go_mfma4(const QuadArgs &a, hipStream_t s)
         return launch_quad_mfma4<NQ, 2, 4, 2, 4, 0, 0, false, 4>(a, s); // 28 .. 32: two elements, batches of 4
 }
 
-int launch_quad_mfma4_nq(unsigned nq, const QuadArgs &a, hipStream_t s)
+template <> int launch_bwd_mfma4<2, double>(unsigned nq, const QuadArgs &a, hipStream_t s)
 {
     switch (nq)
     {
@@ -214,25 +194,7 @@ int launch_quad_mfma4_nq(unsigned nq, const QuadArgs &a, hipStream_t s)
     }
 }
 
-// What SF_VARIANT_AUTO runs in 2D: wave kernel up to nq = 20, the 4x4x4_4b matrix-core kernel for 21..31, the 16x16x4
-// matrix-core kernel at 32 (exact 16-wide tiles there), wave kernel again for whatever else is in its table.
-int quad_auto_kernel(unsigned nq)
-{
-    return nq >= 21 && nq <= 31 ? SF_VARIANT_MFMA4 : (nq == 32 ? SF_VARIANT_MFMA : SF_VARIANT_WAVE);
-}
-
-// Orders for which the 16x16x4 kernel is ahead of the wave kernel (kept for the record: AUTO no longer asks): nq >= 25.  On MI355X the fp64 matrix and vector
-// pipes have the same peak, so the exact-size FMAs of the wave kernel win wherever their operands can be fed; with
-// scalar-register basis blocks, four-element chunks and XCD runs that is every order up to 24 (349 / 355 / 358 / 359 /
-// 366 GDOF/s at nq = 12 .. 16 against 344 / 341 / 341 / 336 / 347 on the matrix cores,
-// profiles/r01/tune_quad1[2-6]_xcd_runs.log; 290-351 against 207-282 at nq = 17 .. 24).  From nq = 25 one pencil pass
-// per wave can no longer hide the scalar-load latency and the (padded) 16x16x4 tiles are ahead.
-bool quad_prefers_mfma(unsigned nq)
-{
-    return nq >= 25;
-}
-
-int launch_quad_wave_nq(unsigned nq, const QuadArgs &a, hipStream_t s)
+template <> int launch_bwd_wave<2, double>(unsigned nq, const QuadArgs &a, hipStream_t s)
 {
     switch (nq)
     {
@@ -244,6 +206,32 @@ int launch_quad_wave_nq(unsigned nq, const QuadArgs &a, hipStream_t s)
 #undef SF_CASE
     default: return SF_ENOTBUILT;
     }
+}
+
+// What SF_VARIANT_AUTO runs first in 2D: wave kernel up to nq = 20, the 4x4x4_4b matrix-core kernel for 21..31, the 16x16x4
+// matrix-core kernel at 32 (exact 16-wide tiles there), wave kernel again for whatever else is in its table.
+// Against the 16x16x4 kernel alone the wave kernel is ahead up to nq = 24.  On MI355X the fp64 matrix and vector
+// pipes have the same peak, so the exact-size FMAs of the wave kernel win wherever their operands can be fed; with
+// scalar-register basis blocks, four-element chunks and XCD runs that is every order up to 24 (349 / 355 / 358 / 359 /
+// 366 GDOF/s at nq = 12 .. 16 against 344 / 341 / 341 / 336 / 347 on the matrix cores,
+// profiles/r01/tune_quad1[2-6]_xcd_runs.log; 290-351 against 207-282 at nq = 17 .. 24).  From nq = 25 one pencil pass
+// per wave can no longer hide the scalar-load latency and the (padded) 16x16x4 tiles are ahead.
+static int quad_auto_kernel(unsigned nq)
+{
+    return nq >= 21 && nq <= 31 ? SF_VARIANT_MFMA4 : (nq == 32 ? SF_VARIANT_MFMA : SF_VARIANT_WAVE);
+}
+
+// the kernel quad_auto_kernel() names first, then whatever else is built for the order
+template <> int launch_bwd_iso_auto<2, double>(unsigned nq, const QuadArgs &a, hipStream_t s)
+{
+    const int first = quad_auto_kernel(nq);
+    int rc = first == SF_VARIANT_MFMA4 ? launch_bwd_mfma4<2, double>(nq, a, s)
+                                       : (first == SF_VARIANT_MFMA ? launch_bwd_mfma<2, double>(nq, a, s) : SF_ENOTBUILT);
+    if (rc == SF_ENOTBUILT)
+        rc = launch_bwd_wave<2, double>(nq, a, s);
+    if (rc == SF_ENOTBUILT)
+        rc = launch_bwd_mfma<2, double>(nq, a, s);
+    return rc;
 }
 
 } // namespace sf

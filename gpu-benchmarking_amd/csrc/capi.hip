@@ -1,5 +1,7 @@
 // capi.hip -- the extern "C" boundary of libsumfact.so (declared in include/sumfact.h).
-// Validation + dispatch only; kernels live in bwdtrans_hex.hip / bwdtrans_quad.hip /
+// Validation + dispatch only: every operator entry point forwards to one template <int DIM, typename T> function below
+// (bwdtrans, iprod, mass, helmholtz, affine), which validates, builds ArgsT<DIM, T> and routes to the launchers that
+// sf_dispatch.h declares.  Kernels live in bwdtrans_hex.hip / bwdtrans_quad.hip / bwdtrans_rt.hip /
 // bwdtrans_generic.hip / aux_kernels.hip, IProductWRTBase in iproduct.hip / iproduct_generic.hip, the fused mass
 // operator in mass.hip / mass_f32.hip / mass_generic.hip, the fused Helmholtz operator in helmholtz.hip /
 // helmholtz_f32.hip / helmholtz_generic.hip, its affine-element form in affine.hip / affine_f32.hip / affine_generic.hip.
@@ -53,12 +55,12 @@ template <int DIM> static bool range_ok(int variant, const unsigned (&nq)[3])
 }
 
 template <int DIM, typename T>
-static ArgsT<DIM, T> make_args(const T *const (&b)[3], const T *in, T *out, size_t nelmt)
+static ArgsT<DIM, T> make_args(const T *const (&b)[3], const T *in, T *wsp, T *out, size_t nelmt)
 {
     if constexpr (DIM == 3)
-        return {b[0], b[1], b[2], in, nullptr, out, (uint64_t)nelmt};
+        return {b[0], b[1], b[2], in, wsp, out, (uint64_t)nelmt};
     else
-        return {b[0], b[1], in, nullptr, out, (uint64_t)nelmt};
+        return {b[0], b[1], in, wsp, out, (uint64_t)nelmt};
 }
 
 // The shared tail of sf_iproduct_*, sf_mass_*, sf_helmholtz_* and sf_affine_helmholtz_*: AUTO takes the wave kernel for an isotropic order of
@@ -84,6 +86,76 @@ static int route(int variant, const unsigned (&nq)[3], bool generic_built, bool 
     return generic();
 }
 
+// ---- BwdTrans: one validation and routing for both dimensions and both scalar types ----------------------------------
+// The wave and matrix-core kernels read `in` and write `out` with 16-byte lanes (`vec_ok`) and are built for isotropic
+// extents (`iso`), 3D also for the anisotropic triples of bwdtrans_rt.hip.  The fp32 entry points pass SF_VARIANT_AUTO.
+template <int DIM, typename T>
+static int bwdtrans(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *in, T *wsp, T *out,
+                    void *stream)
+{
+    const int pre = validate(range_ok<DIM>(variant, nq), nelmt, {b[0], b[1], DIM == 3 ? b[2] : b[0], in, out}, sizeof(T));
+    if (pre != kProceed)
+        return pre;
+    constexpr bool f64 = std::is_same<T, double>::value, hex64 = DIM == 3 && f64;
+    const hipStream_t s = (hipStream_t)stream;
+    const auto a        = make_args<DIM, T>(b, in, wsp, out, nelmt);
+    const bool iso      = nq[0] == nq[1] && (DIM == 2 || nq[1] == nq[2]);
+    const bool vec_ok   = aligned(in, 16) && aligned(out, 16);
+    auto wave3          = [&] {
+        if constexpr (hex64)
+            return launch_hex_wave3(nq[0], nq[1], nq[2], a, s);
+        else
+            return (int)SF_ENOTBUILT;
+    };
+    auto wave_rt = [&] {
+        if constexpr (hex64)
+            return launch_hex_rt(nq[0], nq[1], nq[2], a, s);
+        else
+            return (int)SF_ENOTBUILT;
+    };
+    if (variant == SF_VARIANT_AUTO)
+    {
+        // the first leg that answers something other than SF_ENOTBUILT
+        int rc   = SF_ENOTBUILT;
+        auto leg = [&](bool applies, auto launch) {
+            if (rc == SF_ENOTBUILT && applies)
+                rc = launch();
+        };
+        leg(iso && vec_ok, [&] { return launch_bwd_iso_auto<DIM, T>(nq[0], a, s); }); // the order's table
+        leg(!iso && vec_ok, wave3);                                                   // compile-time triples
+        leg(vec_ok, [&] { // a specialisation the caller made ready (sf_specialise)
+            return launch_specialised(DIM, nq[0], nq[1], nq[2], (int)sizeof(T), b[0], b[1], b[2], in, out, a.nelmt, s);
+        });
+        // the run-time-extent wave kernel (bwdtrans_rt.h), also for buffers that are only 8-byte aligned: ahead of the
+        // block kernel up to nq = 8 per direction (0.39-0.52 of the roofline against 0.28-0.34; above that its
+        // unrolled-to-the-bound loops lose: profiles/r03/anisotropic_shapes.log)
+        leg(nq[0] <= 8 && nq[1] <= 8 && nq[2] <= 8, wave_rt);
+        leg(true, [&] { return launch_bwd_generic<DIM, T>(SF_VARIANT_GENERIC, nq, a, s); });
+        return rc;
+    }
+    if constexpr (f64)
+    {
+        // an explicit vector variant: off its table, then 8-byte-aligned buffers, then the launch
+        auto run = [&](bool built, auto launch) {
+            return !built ? (int)SF_ENOTBUILT : (!vec_ok ? (int)SF_EALIGN : launch());
+        };
+        switch (variant)
+        {
+        case SF_VARIANT_WAVE: // 3D: the triple table answers for anisotropic extents at launch, after the alignment
+            return run(iso || hex64, [&] { return iso ? launch_bwd_wave<DIM, T>(nq[0], a, s) : wave3(); });
+        case SF_VARIANT_MFMA: return run(iso, [&] { return launch_bwd_mfma<DIM, T>(nq[0], a, s); });
+        case SF_VARIANT_MFMA4: return run(iso, [&] { return launch_bwd_mfma4<DIM, T>(nq[0], a, s); });
+        case SF_VARIANT_WAVE_RT: return wave_rt();
+        case SF_VARIANT_GENERIC:
+        case SF_VARIANT_THREAD:
+        case SF_VARIANT_BLOCK_LDS:
+        case SF_VARIANT_BLOCK_GLB: return launch_bwd_generic<DIM, T>(variant, nq, a, s);
+        default: break;
+        }
+    }
+    return SF_ENOTBUILT;
+}
+
 // ---- IProductWRTBase: one validation and routing for both dimensions and both scalar types ---------------------------
 template <int DIM, typename T>
 static int iprod(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *in, T *out,
@@ -93,7 +165,7 @@ static int iprod(int variant, const unsigned (&nq)[3], size_t nelmt, const T *co
     if (rc != kProceed)
         return rc;
     const hipStream_t s = (hipStream_t)stream;
-    const auto a        = make_args<DIM, T>(b, in, out, nelmt);
+    const auto a        = make_args<DIM, T>(b, in, nullptr, out, nelmt);
     return route<DIM>(
         variant, nq, iprod_generic_built(DIM, nq[0], nq[1], nq[2]), iprod_wave_built(DIM, nq[0]), in, out,
         [&] { return launch_iprod_wave<DIM, T>(nq[0], a, s); }, [&] { return launch_iprod_generic<DIM, T>(nq, a, s); });
@@ -115,7 +187,7 @@ static int mass(int variant, const unsigned (&nq)[3], size_t nelmt, const T *con
     if (overlaps(out, modes_bytes, in, modes_bytes) || overlaps(out, modes_bytes, w, points_bytes))
         return SF_EINVAL;
     const hipStream_t s = (hipStream_t)stream;
-    const auto a        = make_args<DIM, T>(b, in, out, nelmt);
+    const auto a        = make_args<DIM, T>(b, in, nullptr, out, nelmt);
     return route<DIM>(
         variant, nq, mass_generic_built(DIM, nq[0], nq[1], nq[2]), mass_wave_built(DIM, nq[0]), in, out,
         [&] { return launch_mass_wave<DIM, T>(nq[0], a, w, s); },
@@ -143,7 +215,7 @@ static int helmholtz(int variant, const unsigned (&nq)[3], size_t nelmt, const T
         (has_w && overlaps(out, modes_bytes, w, points_bytes)))
         return SF_EINVAL;
     const hipStream_t s = (hipStream_t)stream;
-    const auto a        = make_args<DIM, T>(b, in, out, nelmt);
+    const auto a        = make_args<DIM, T>(b, in, nullptr, out, nelmt);
     const HelmArgsT<T> x{d[0], d[1], d[2], g, has_w ? w : nullptr, (T)lambda}; // lambda is rounded to T here, once
     return route<DIM>(
         variant, nq, helmholtz_generic_built(DIM, nq[0], nq[1], nq[2]), helmholtz_wave_built(DIM, nq[0]), in, out,
@@ -172,7 +244,7 @@ static int affine(int variant, const unsigned (&nq)[3], size_t nelmt, const T *c
         (has_j && overlaps(out, modes_bytes, je, sizeof(T) * nelmt)))
         return SF_EINVAL;
     const hipStream_t s = (hipStream_t)stream;
-    const auto a        = make_args<DIM, T>(b, in, out, nelmt);
+    const auto a        = make_args<DIM, T>(b, in, nullptr, out, nelmt);
     // lambda is rounded to T here, once
     const AffineArgsT<T> x{d[0], d[1], d[2], qw[0], qw[1], qw[2], ge, has_j ? je : nullptr, (T)lambda};
     return route<DIM>(
@@ -210,151 +282,29 @@ const char *sf_variant_name(int variant)
     return (variant >= 0 && variant < SF_NUM_VARIANTS) ? names[variant] : "?";
 }
 
-int sf_bwdtrans_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2,
-                                size_t nelmt, const double *basis0, const double *basis1,
-                                const double *basis2, const double *in, double *wsp, double *out,
+int sf_bwdtrans_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
+                                const double *basis1, const double *basis2, const double *in, double *wsp, double *out,
                                 void *stream)
 {
-    const int pre = validate(range_ok<3>(variant, {nq0, nq1, nq2}), nelmt, {basis0, basis1, basis2, in, out}, 8);
-    if (pre != kProceed)
-        return pre;
-    hipStream_t s = (hipStream_t)stream;
-    HexArgs a{basis0, basis1, basis2, in, wsp, out, (uint64_t)nelmt};
-    const bool iso = (nq0 == nq1 && nq1 == nq2);
-    // the wave kernels read `in` and write `out` with 16-byte lanes
-    const bool vec_ok = aligned(in, 16) && aligned(out, 16);
-    switch (variant)
-    {
-    case SF_VARIANT_AUTO:
-    {
-        if (iso && vec_ok)
-        {
-            int rc = launch_hex_wave_nq(nq0, a, s);
-            if (rc == SF_ENOTBUILT) // above the wave kernel's table: the measured best matrix-core kernel (nq 12..16)
-                rc = hex_auto_kernel(nq0) == SF_VARIANT_MFMA4 ? launch_hex_mfma4_nq(nq0, a, s) : launch_hex_mfma_nq(nq0, a, s);
-            if (rc != SF_ENOTBUILT)
-                return rc;
-        }
-        // anisotropic extents, or buffers that are only 8-byte aligned: the compile-time triples of bwdtrans_rt.hip, then
-        // the run-time-extent wave kernel (bwdtrans_rt.h), then the barrier-per-sweep block kernel
-        int rc = (!iso && vec_ok) ? launch_hex_wave3(nq0, nq1, nq2, a, s) : SF_ENOTBUILT; // compile-time triples
-        if (rc == SF_ENOTBUILT && vec_ok) // a specialisation the caller made ready (sf_specialise)
-            rc = launch_specialised(3, nq0, nq1, nq2, 8, basis0, basis1, basis2, in, out, a.nelmt, s);
-        // the run-time-extent kernel is ahead of the block kernel up to nq = 8 per direction (0.39-0.52 of the roofline
-        // against 0.28-0.34; above that its unrolled-to-the-bound loops lose: profiles/r03/anisotropic_shapes.log)
-        if (rc == SF_ENOTBUILT && nq0 <= 8 && nq1 <= 8 && nq2 <= 8)
-            rc = launch_hex_rt(nq0, nq1, nq2, a, s);
-        if (rc != SF_ENOTBUILT)
-            return rc;
-        return launch_hex_generic(SF_VARIANT_GENERIC, nq0, nq1, nq2, a, s);
-    }
-    case SF_VARIANT_WAVE_RT:
-        return launch_hex_rt(nq0, nq1, nq2, a, s);
-    case SF_VARIANT_WAVE:
-        if (!vec_ok)
-            return SF_EALIGN;
-        return iso ? launch_hex_wave_nq(nq0, a, s) : launch_hex_wave3(nq0, nq1, nq2, a, s);
-    case SF_VARIANT_MFMA:
-        if (!iso)
-            return SF_ENOTBUILT;
-        if (!vec_ok)
-            return SF_EALIGN;
-        return launch_hex_mfma_nq(nq0, a, s);
-    case SF_VARIANT_MFMA4:
-        if (!iso)
-            return SF_ENOTBUILT;
-        if (!vec_ok)
-            return SF_EALIGN;
-        return launch_hex_mfma4_nq(nq0, a, s);
-    case SF_VARIANT_GENERIC:
-        return launch_hex_generic(SF_VARIANT_GENERIC, nq0, nq1, nq2, a, s);
-    case SF_VARIANT_THREAD:
-    case SF_VARIANT_BLOCK_LDS:
-    case SF_VARIANT_BLOCK_GLB:
-        return launch_hex_generic(variant, nq0, nq1, nq2, a, s);
-    default:
-        return SF_ENOTBUILT;
-    }
+    return bwdtrans<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, wsp, out, stream);
 }
 
-int sf_bwdtrans_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
-                        const double *basis0, const double *basis1, const double *basis2,
-                        const double *in, double *out, void *stream)
+int sf_bwdtrans_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0, const double *basis1,
+                        const double *basis2, const double *in, double *out, void *stream)
 {
-    return sf_bwdtrans_hex_f64_variant(SF_VARIANT_AUTO, nq0, nq1, nq2, nelmt, basis0, basis1, basis2,
-                                       in, nullptr, out, stream);
+    return bwdtrans<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, nullptr, out, stream);
 }
 
-int sf_bwdtrans_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt,
-                                 const double *basis0, const double *basis1, const double *in,
-                                 double *wsp, double *out, void *stream)
+int sf_bwdtrans_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                                 const double *basis1, const double *in, double *wsp, double *out, void *stream)
 {
-    const int pre = validate(range_ok<2>(variant, {nq0, nq1, 0u}), nelmt, {basis0, basis1, in, out}, 8);
-    if (pre != kProceed)
-        return pre;
-    hipStream_t s = (hipStream_t)stream;
-    QuadArgs a{basis0, basis1, in, wsp, out, (uint64_t)nelmt};
-    const bool iso    = (nq0 == nq1);
-    const bool vec_ok = aligned(in, 16) && aligned(out, 16);
-    switch (variant)
-    {
-    case SF_VARIANT_AUTO:
-    {
-        if (iso && vec_ok)
-        {
-            // the measured best kernel of the order first (bwdtrans_quad.hip), then whatever else is built for it
-            const int first = quad_auto_kernel(nq0);
-            int rc = first == SF_VARIANT_MFMA4 ? launch_quad_mfma4_nq(nq0, a, s)
-                                               : (first == SF_VARIANT_MFMA ? launch_quad_mfma_nq(nq0, a, s) : SF_ENOTBUILT);
-            if (rc == SF_ENOTBUILT)
-                rc = launch_quad_wave_nq(nq0, a, s);
-            if (rc == SF_ENOTBUILT)
-                rc = launch_quad_mfma_nq(nq0, a, s);
-            if (rc != SF_ENOTBUILT)
-                return rc;
-        }
-        if (vec_ok) // a specialisation the caller made ready (sf_specialise)
-        {
-            const int rc = launch_specialised(2, nq0, nq1, 0, 8, basis0, basis1, nullptr, in, out, a.nelmt, s);
-            if (rc != SF_ENOTBUILT)
-                return rc;
-        }
-        return launch_quad_generic(SF_VARIANT_GENERIC, nq0, nq1, a, s);
-    }
-    case SF_VARIANT_WAVE:
-        if (!iso)
-            return SF_ENOTBUILT;
-        if (!vec_ok)
-            return SF_EALIGN;
-        return launch_quad_wave_nq(nq0, a, s);
-    case SF_VARIANT_MFMA:
-        if (!iso)
-            return SF_ENOTBUILT;
-        if (!vec_ok)
-            return SF_EALIGN;
-        return launch_quad_mfma_nq(nq0, a, s);
-    case SF_VARIANT_MFMA4:
-        if (!iso)
-            return SF_ENOTBUILT;
-        if (!vec_ok)
-            return SF_EALIGN;
-        return launch_quad_mfma4_nq(nq0, a, s);
-    case SF_VARIANT_GENERIC:
-        return launch_quad_generic(SF_VARIANT_GENERIC, nq0, nq1, a, s);
-    case SF_VARIANT_THREAD:
-    case SF_VARIANT_BLOCK_LDS:
-    case SF_VARIANT_BLOCK_GLB:
-        return launch_quad_generic(variant, nq0, nq1, a, s);
-    default:
-        return SF_ENOTBUILT;
-    }
+    return bwdtrans<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, wsp, out, stream);
 }
 
-int sf_bwdtrans_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
-                         const double *basis1, const double *in, double *out, void *stream)
+int sf_bwdtrans_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                         const double *in, double *out, void *stream)
 {
-    return sf_bwdtrans_quad_f64_variant(SF_VARIANT_AUTO, nq0, nq1, nelmt, basis0, basis1, in,
-                                        nullptr, out, stream);
+    return bwdtrans<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, nullptr, out, stream);
 }
 
 int sf_bwdtrans_hex_f64_interleaved(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
@@ -382,52 +332,16 @@ int sf_interleave64_f64(const double *src, double *dst, size_t nelmt, size_t n, 
 }
 
 // ---- fp32 (T = float) ------------------------------------------------------------------------------
-int sf_bwdtrans_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
-                        const float *basis1, const float *basis2, const float *in, float *out,
-                        void *stream)
+int sf_bwdtrans_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
+                        const float *basis2, const float *in, float *out, void *stream)
 {
-    const int pre =
-        validate(range_ok<3>(SF_VARIANT_AUTO, {nq0, nq1, nq2}), nelmt, {basis0, basis1, basis2, in, out}, 4);
-    if (pre != kProceed)
-        return pre;
-    hipStream_t s = (hipStream_t)stream;
-    HexArgsT<float> a{basis0, basis1, basis2, in, nullptr, out, (uint64_t)nelmt};
-    if (nq0 == nq1 && nq1 == nq2 && aligned(in, 16) && aligned(out, 16))
-    {
-        int rc = launch_hex_wave_f32_nq(nq0, a, s);
-        if (rc != SF_ENOTBUILT)
-            return rc;
-    }
-    if (aligned(in, 16) && aligned(out, 16)) // a specialisation the caller made ready (sf_specialise)
-    {
-        const int rc = launch_specialised(3, nq0, nq1, nq2, 4, basis0, basis1, basis2, in, out, a.nelmt, s);
-        if (rc != SF_ENOTBUILT)
-            return rc;
-    }
-    return launch_hex_generic_f32(SF_VARIANT_GENERIC, nq0, nq1, nq2, a, s);
+    return bwdtrans<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, nullptr, out, stream);
 }
 
-int sf_bwdtrans_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0,
-                         const float *basis1, const float *in, float *out, void *stream)
+int sf_bwdtrans_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1, const float *in,
+                         float *out, void *stream)
 {
-    const int pre = validate(range_ok<2>(SF_VARIANT_AUTO, {nq0, nq1, 0u}), nelmt, {basis0, basis1, in, out}, 4);
-    if (pre != kProceed)
-        return pre;
-    hipStream_t s = (hipStream_t)stream;
-    QuadArgsT<float> a{basis0, basis1, in, nullptr, out, (uint64_t)nelmt};
-    if (nq0 == nq1 && aligned(in, 16) && aligned(out, 16))
-    {
-        int rc = launch_quad_wave_f32_nq(nq0, a, s);
-        if (rc != SF_ENOTBUILT)
-            return rc;
-    }
-    if (aligned(in, 16) && aligned(out, 16)) // a specialisation the caller made ready (sf_specialise)
-    {
-        const int rc = launch_specialised(2, nq0, nq1, 0, 4, basis0, basis1, nullptr, in, out, a.nelmt, s);
-        if (rc != SF_ENOTBUILT)
-            return rc;
-    }
-    return launch_quad_generic_f32(SF_VARIANT_GENERIC, nq0, nq1, a, s);
+    return bwdtrans<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, nullptr, out, stream);
 }
 
 // ---- IProductWRTBase, the transpose of BwdTrans ----------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // sf_dispatch.h -- internal launch / helper entry points shared between the C ABI (capi.hip) and the
-// translation units that define them (bwdtrans_hex.hip, bwdtrans_quad.hip, bwdtrans_generic.hip,
-// aux_kernels.hip).  Every function returns SF_OK, a negative SF_E* code or a positive hipError_t.
+// translation units that define them (bwdtrans_hex.hip, bwdtrans_quad.hip, bwdtrans_generic.hip, bwdtrans_rt.hip,
+// aux_kernels.hip, rtc.hip and those of the fused operators).  Every function returns SF_OK, a negative SF_E* code or a
+// positive hipError_t.
 #pragma once
 
 #include "sf_common.h"
@@ -10,20 +11,29 @@
 
 namespace sf
 {
-int launch_hex_wave_nq(unsigned nq, const HexArgs &a, hipStream_t s);
-int launch_hex_mfma_nq(unsigned nq, const HexArgs &a, hipStream_t s);
-int launch_hex_mfma4_nq(unsigned nq, const HexArgs &a, hipStream_t s);
-int hex_auto_kernel(unsigned nq); // SF_VARIANT_MFMA / SF_VARIANT_MFMA4 above the wave kernel's table
-int launch_quad_wave_nq(unsigned nq, const QuadArgs &a, hipStream_t s);
-int launch_quad_mfma_nq(unsigned nq, const QuadArgs &a, hipStream_t s);
-int launch_quad_mfma4_nq(unsigned nq, const QuadArgs &a, hipStream_t s);
-bool quad_prefers_mfma(unsigned nq);
-int quad_auto_kernel(unsigned nq);
-int launch_hex_generic(int variant, unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a,
-                       hipStream_t s);
+template <int DIM, typename T> using ArgsT = typename std::conditional<DIM == 3, HexArgsT<T>, QuadArgsT<T>>::type;
+// what the launch just enqueued answered
+inline int launch_rc()
+{
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SF_OK : (int)e;
+}
+// BwdTrans, one set of entry points for both dimensions and both scalar types, each specialised in the translation unit
+// that holds its kernels (bwdtrans_hex.hip <3, T>, bwdtrans_quad.hip <2, T>, bwdtrans_generic.hip all four).  The order
+// tables of one kernel family, T = double only (SF_ENOTBUILT off the table): the wave kernel (3D nq 2..11, 2D 2..24 and
+// 32), the 16x16x4 matrix-core kernel (3D 4..16, 2D 11..32), the 4x4x4_4b matrix-core kernel (3D 12..16, 2D 8..32).
+template <int DIM, typename T> int launch_bwd_wave(unsigned nq, const ArgsT<DIM, T> &a, hipStream_t s);
+template <int DIM, typename T> int launch_bwd_mfma(unsigned nq, const ArgsT<DIM, T> &a, hipStream_t s);
+template <int DIM, typename T> int launch_bwd_mfma4(unsigned nq, const ArgsT<DIM, T> &a, hipStream_t s);
+// what SF_VARIANT_AUTO runs for an isotropic order on 16-byte-aligned in / out: the measured best kernel of the order,
+// then whatever else is built for it (SF_ENOTBUILT: nothing is); double and float
+template <int DIM, typename T> int launch_bwd_iso_auto(unsigned nq, const ArgsT<DIM, T> &a, hipStream_t s);
+// the any-extent kernels and the reference's decompositions (SF_VARIANT_GENERIC / THREAD / BLOCK_LDS / BLOCK_GLB; nq[2]
+// is 0 in 2D); double and float
+template <int DIM, typename T>
+int launch_bwd_generic(int variant, const unsigned (&nq)[3], const ArgsT<DIM, T> &a, hipStream_t s);
 int launch_hex_wave3(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, hipStream_t s);
 int launch_hex_rt(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, hipStream_t s);
-int launch_quad_generic(int variant, unsigned nq0, unsigned nq1, const QuadArgs &a, hipStream_t s);
 int sumsq_async(const double *x, size_t n, double *result_dev, hipStream_t s);
 int sumsq_blocking(const double *x, size_t n, double *result_host, hipStream_t s);
 int fill_sincos(double *in, size_t nelmt, size_t nm_tot, hipStream_t s);
@@ -50,12 +60,6 @@ int set_launch_hint(unsigned threads, unsigned elblocks);
 int launch_hex_interleaved(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, hipStream_t s);
 int launch_interleave64(const double *src, double *dst, size_t nelmt, size_t n, int inverse,
                         hipStream_t s);
-int launch_hex_wave_f32_nq(unsigned nq, const HexArgsT<float> &a, hipStream_t s);
-int launch_quad_wave_f32_nq(unsigned nq, const QuadArgsT<float> &a, hipStream_t s);
-int launch_hex_generic_f32(int variant, unsigned nq0, unsigned nq1, unsigned nq2,
-                           const HexArgsT<float> &a, hipStream_t s);
-int launch_quad_generic_f32(int variant, unsigned nq0, unsigned nq1, const QuadArgsT<float> &a,
-                            hipStream_t s);
 // run-time specialisation (rtc.hip): sf_specialise / sf_specialisation_state / the launch of a ready module (SF_ENOTBUILT
 // unless one of the shape is ready on the current device) / the calling thread's last compile log / sf_shutdown's part
 int rtc_specialise(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes);
@@ -68,7 +72,6 @@ int rtc_release();
 // dimensions and both scalar types: the wave kernels of an isotropic order (SF_ENOTBUILT off their table) and the
 // any-extent kernels (nq[2] is 0 in 2D; SF_ENOTBUILT beyond their bounds).  Each is defined for <3, T> and <2, T> in the
 // translation unit that holds the kernels of T.
-template <int DIM, typename T> using ArgsT = typename std::conditional<DIM == 3, HexArgsT<T>, QuadArgsT<T>>::type;
 // IProductWRTBase (iproduct.hip: the wave kernels, 3D nq 2..11, 2D 2..16; iproduct_generic.hip: any extents up to 16 per
 // direction in 3D and 32 in 2D)
 template <int DIM, typename T> int launch_iprod_wave(unsigned nq, const ArgsT<DIM, T> &a, hipStream_t s);

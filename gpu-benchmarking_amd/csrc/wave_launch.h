@@ -5,7 +5,7 @@
 #include "bwdtrans_mfma4.h"
 #include "bwdtrans_hmfma4.h"
 #include "bwdtrans_wave.h"
-#include "sf_dispatch.h" // counter_acquire (batch counter of the persistent 2D kernels)
+#include "sf_dispatch.h" // launch_rc, counter_acquire (batch counter of the persistent 2D kernels)
 
 #include <atomic>
 
@@ -71,8 +71,19 @@ inline int launch_chunked(K kern, std::atomic<int> *cache, size_t lds, int grid_
     if (grid > 0x7fffffffull)
         return SF_EINVAL;
     kern<<<(unsigned)grid, kWave * WPB, lds, s>>>(args...);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
+    return launch_rc();
+}
+
+// The launch of the nq = 2 stream kernels: one thread per 16-byte output vector, workgroups of 256.
+template <class K, class... A> inline int launch_stream(K kern, uint64_t nthreads, hipStream_t s, A... args)
+{
+    if (nthreads == 0)
+        return SF_OK;
+    const uint64_t blocks = (nthreads + 255) / 256;
+    if (blocks > 0x7fffffffull)
+        return SF_EINVAL;
+    kern<<<(unsigned)blocks, 256, 0, s>>>(args...);
+    return launch_rc();
 }
 
 template <int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP = 0, int OUTM = OUT_ST8, int MEMF = 0,

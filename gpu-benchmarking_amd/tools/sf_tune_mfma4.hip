@@ -221,7 +221,7 @@ int main(int argc, char **argv)
     QuadArgs a{b0, b1, in, nullptr, out, nelmt};
     std::printf("nq %d, %zu elements, %d reps; reference = the generic LDS kernel (first row), then the shipped kernels\n",
                 NQ, nelmt, g_reps);
-    run("generic block/LDS (reference result)", a, [&]() { return launch_quad_generic(SF_VARIANT_BLOCK_LDS, NQ, NQ, a, 0); },
+    run("generic block/LDS (reference result)", a, [&]() { return launch_bwd_generic<2, double>(SF_VARIANT_BLOCK_LDS, {NQ, NQ, 0u}, a, 0); },
         true);
     if (argc > 3 && std::string(argv[3]) == "striped")
     {
@@ -258,8 +258,8 @@ int main(int argc, char **argv)
         return 0;
     for (int rep = 0; rep < 2; ++rep)
     {
-        run("shipped wave kernel", a, [&]() { return launch_quad_wave_nq(NQ, a, 0); });
-        run("shipped 16x16x4 matrix-core kernel", a, [&]() { return launch_quad_mfma_nq(NQ, a, 0); });
+        run("shipped wave kernel", a, [&]() { return launch_bwd_wave<2, double>(NQ, a, 0); });
+        run("shipped 16x16x4 matrix-core kernel", a, [&]() { return launch_bwd_mfma<2, double>(NQ, a, 0); });
         m4<2, 4, 2, 4, 1, 64>(a);
         m4<2, 4, 2, 4, 2, 64>(a);
         m4<2, 4, 2, 4, 0, 0>(a);

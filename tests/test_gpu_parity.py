@@ -189,6 +189,43 @@ def test_hex_runtime_extent_kernel_on_8_byte_aligned_views(sf, oracle, torch_mod
             assert bool((obuf[:off_out] == 7.25).all()) and bool((obuf[off_out + nelmt * nqt:] == 7.25).all())
 
 
+AUTO_ROUTES = [((8, 8, 8), "wave", False), ((12, 12, 12), "mfma4", False), ((13, 13, 13), "mfma", False),
+               ((8, 8, 4), "wave", False), ((3, 5, 4), "wave-rt", False), ((5, 9, 13), "generic", False),
+               ((17, 3, 4), "generic", False), ((8, 8, 8), "wave-rt", True), ((9, 9, 9), "generic", True),
+               ((8, 8), "wave", False), ((21, 21), "mfma4", False), ((25, 25), "mfma4", False), ((32, 32), "mfma", False),
+               ((4, 9), "generic", False), ((33, 33), "generic", False), ((8, 8), "generic", True)]
+
+
+@pytest.mark.parametrize("nq,variant,view", AUTO_ROUTES,
+                         ids=["x".join(map(str, n)) + ("-view-" if v else "-") + k for n, k, v in AUTO_ROUTES])
+def test_auto_runs_the_kernel_its_table_names(sf, torch_mod, nq, variant, view):
+    """AUTO against the explicit variant of the kernel that the routing (csrc/capi.hip bwdtrans, launch_bwd_iso_auto)
+    names for the shape: bit-identical outputs, fp64, 37 elements.  `view`: in / out at an odd offset into a larger
+    buffer, so only 8-byte aligned, both calls on the same views.  A necessary condition only (two kernels could agree in
+    bits).  Where the any-extent kernel is expected (for aligned buffers the run-time-extent kernel too) and another test
+    of this process has made a specialisation of the shape ready, AUTO runs that one."""
+    nelmt, dim = 37, len(nq)
+    nm = [q - 1 for q in nq]
+    nmt, nqt = int(np.prod(nm)), int(np.prod(nq))
+    bs = [sf.fill_random(nm[d] * nq[d], 600 + d) for d in range(dim)]     # distinct bases per direction
+    xbuf = sf.fill_random(nelmt * nmt + 2, 61)
+    x = xbuf[1:1 + nelmt * nmt] if view else xbuf[:nelmt * nmt]
+    bwd = sf.bwdtrans_hex if dim == 3 else sf.bwdtrans_quad
+    specialisable = max(nq) <= (16 if dim == 3 else 24)      # beyond, sf_specialisation_state refuses the extents
+    outs = []
+    for v in ("auto", variant):
+        obuf = torch_mod.zeros(nelmt * nqt + 2, dtype=torch_mod.float64, device="cuda")
+        o = obuf[1:1 + nelmt * nqt] if view else obuf[:nelmt * nqt]
+        if v in ("generic", "wave-rt") and not view and specialisable and sf.specialisation_state(nq)[0] == 1:
+            sf.bwdtrans_specialised(nq, *bs, inp=x, out=o)
+        else:
+            bwd(nq, *bs, x, out=o, variant=v)
+        outs.append(o)
+    torch_mod.cuda.synchronize()
+    assert float(outs[0].abs().max()) > 0
+    assert torch_mod.equal(outs[0], outs[1]), (nq, variant, view)
+
+
 def test_mfma_not_built_cases(sf):
     capi = sf.capi
     b = sf.fill_basis(7, 8)
