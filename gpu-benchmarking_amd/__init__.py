@@ -19,4 +19,5 @@ from .bwdtrans import (  # noqa: F401
     specialise, specialisation_state, specialise_log, bwdtrans_specialised,
     iproduct_hex, iproduct_quad, bwdtrans_autograd, mass_hex, mass_quad,
     helmholtz_hex, helmholtz_quad, affine_helmholtz_hex, affine_helmholtz_quad,
+    physderiv_hex, physderiv_quad,
 )

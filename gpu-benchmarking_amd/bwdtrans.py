@@ -25,10 +25,11 @@ def _stream(stream, device=None):
 
 def _check_operands(what, operands, inp, lam=None):
     """The C ABI takes raw pointers: a short operand would be read / written out of bounds, one of another dtype or device
-    misread.  `operands`: (name, tensor, expected numel, may be None); a None stands for a term that lam == 0 switches off."""
+    misread.  `operands`: (name, tensor, expected numel, may be None); a None stands for a term that lam == 0 switches off
+    (in a family without lam: for an operand the call may leave out)."""
     for name, t, need, optional in operands:
         if t is None and optional:
-            if lam != 0.0:
+            if lam is not None and lam != 0.0:
                 raise ValueError(f"{what}: {name}=None needs lam == 0")
             continue
         if not isinstance(t, torch.Tensor):
@@ -68,14 +69,38 @@ def quad_wsp_doubles(nq, nelmt):
 # `inp` / `out` hold quadrature points per element (else modes); extras(nelmt, points per element) -> the operands between
 # the bases and `in`, in the order of the C signature, as (name, tensor, expected numel, may be None); lam, or None for a
 # family without one; whether float32 quietly takes the AUTO route for any `variant` (BwdTrans) or refuses all but "auto";
-# BwdTrans only: wsp_need(nelmt) -> {variant: numel of the caller-owned workspace it needs}.
-_Family = collections.namedtuple("_Family", "stem inp_points out_points extras lam f32_ignores_variant wsp_need",
-                                 defaults=(lambda nelmt, nqt: [], None, False, None))
+# BwdTrans only: wsp_need(nelmt) -> {variant: numel of the caller-owned workspace it needs}; out_parts: the number of
+# separate output arrays of the C call (1: `out` is one flat tensor; d: `out` is a (d, n) tensor or a sequence of d tensors).
+_Family = collections.namedtuple("_Family", "stem inp_points out_points extras lam f32_ignores_variant wsp_need out_parts",
+                                 defaults=(lambda nelmt, nqt: [], None, False, None, 1))
+
+
+def _output_parts(what, out, parts, numel, inp):
+    """(what the call returns, the `parts` flat tensors the C call writes) of a family with several outputs.  `out` is
+    None: a (parts, numel) tensor is allocated whose rows each start 256-byte aligned, as a fresh allocation would (the
+    rows are contiguous, the tensor as a whole need not be), so that an odd numel does not cost the wave route.  `out` is
+    a tensor: (parts, numel) with contiguous rows, or any contiguous tensor of parts * numel values.  `out` is a sequence
+    of `parts` tensors: returned as a tuple."""
+    if out is None:
+        per = 256 // inp.element_size()
+        out = torch.empty((parts, (numel + per - 1) // per * per), dtype=inp.dtype, device=inp.device)[:, :numel]
+    if isinstance(out, torch.Tensor):
+        if out.numel() != parts * numel:
+            raise ValueError(f"{what}: out has {out.numel()} values, not {parts} x {numel}")
+        if not (out.dim() == 2 and out.shape[0] == parts and (numel <= 1 or out.stride(1) == 1)):
+            if not out.is_contiguous():
+                raise TypeError(f"{what}: out must be contiguous, or ({parts}, {numel}) with contiguous rows")
+            out = out.view(parts, numel)
+        return out, [out[a] for a in range(parts)]
+    outs = list(out)
+    if len(outs) != parts:
+        raise ValueError(f"{what}: out holds {len(outs)} tensors, not {parts}")
+    return tuple(outs), outs
 
 
 def _operator_call(what, fam, nq, bases, inp, out, variant, stream, wsp=None):
-    """The one call path of bwdtrans_* / iproduct_* / mass_* / helmholtz_* / affine_helmholtz_*: sizes, dtypes and devices
-    are checked here (before any library call), pointers, alignment and overlap in the C ABI."""
+    """The one call path of bwdtrans_* / iproduct_* / mass_* / helmholtz_* / affine_helmholtz_* / physderiv_*: sizes, dtypes
+    and devices are checked here (before any library call), pointers, alignment and overlap in the C ABI."""
     nq = tuple(int(x) for x in nq)
     nmt, nqt = 1, 1
     for q in nq:
@@ -87,12 +112,17 @@ def _operator_call(what, fam, nq, bases, inp, out, variant, stream, wsp=None):
     if nelmt * n_in != inp.numel():
         raise ValueError(f"{what}: in.numel() is not a multiple of the {'points' if fam.inp_points else 'modes'} per "
                          f"element ({n_in})")
-    if out is None:
-        out = torch.empty(nelmt * n_out, dtype=inp.dtype, device=inp.device)
+    if fam.out_parts > 1:
+        out, outs = _output_parts(what, out, fam.out_parts, nelmt * n_out, inp)
+    else:
+        if out is None:
+            out = torch.empty(nelmt * n_out, dtype=inp.dtype, device=inp.device)
+        outs = [out]
+    out_names = ["out"] if len(outs) == 1 else [f"out{a}" for a in range(len(outs))]
     lam = None if fam.lam is None else float(fam.lam)
     operands = [(f"basis{d}", b, (q - 1) * q, False) for d, (b, q) in enumerate(zip(bases, nq))]
     operands += fam.extras(nelmt, nqt)
-    _check_operands(what, operands + [("out", out, nelmt * n_out, False)], inp, lam)
+    _check_operands(what, operands + [(name, t, nelmt * n_out, False) for name, t in zip(out_names, outs)], inp, lam)
     v, f32 = _variant(variant), inp.dtype == torch.float32
     if fam.wsp_need is not None:        # BwdTrans: the caller-owned workspace of the thread and block-glb variants
         need = fam.wsp_need(nelmt)
@@ -111,7 +141,8 @@ def _operator_call(what, fam, nq, bases, inp, out, variant, stream, wsp=None):
     if fam.wsp_need is not None and not f32:
         ptrs.append(None if wsp is None else _dev_ptr(wsp, "wsp", dtype))
     with torch.cuda.device(inp.device):
-        rc = fn(*(() if f32 else (v,)), *nq, nelmt, *ptrs, _dev_ptr(out, "out", dtype), _stream(stream, inp.device))
+        rc = fn(*(() if f32 else (v,)), *nq, nelmt, *ptrs, *(_dev_ptr(t, name, dtype) for name, t in zip(out_names, outs)),
+                _stream(stream, inp.device))
     capi.check(rc, what)
     return out
 
@@ -217,6 +248,32 @@ def affine_helmholtz_quad(nq, basis0, basis1, deriv0, deriv1, qw0, qw1, ge, je, 
     lam == 0."""
     return _operator_call("affine_helmholtz_quad", _affine(nq, (deriv0, deriv1), (qw0, qw1), ge, je, lam), nq,
                           (basis0, basis1), inp, out, variant, stream)
+
+
+def _physderiv(nq, derivs, df):
+    d = len(nq)
+    return _Family("physderiv", False, True, lambda nelmt, nqt: _per_direction("deriv", derivs, lambda q: q * q, nq) + [
+        ("df", df, nelmt * d * d * nqt, True)], out_parts=d)
+
+
+def physderiv_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, df, inp, out=None, variant="auto", stream=None):
+    """BwdTrans fused with the physical-space gradient in one kernel, on inp's device: with u = B x_e and du_b = D_b u,
+    out[a][e][k][j][i] = sum_b df[e][3 a + b][k][j][i] du_b[e][k][j][i].  The bases and derivative matrices of
+    helmholtz_hex; df[e][c][k][j][i] the nine planes of the inverse Jacobian, c = 3 a + b for d xi_b / d x_a, or None for
+    the reference-space derivatives out[a] = du_a (df is then never read); inp holds nm0*nm1*nm2 modes per element.
+    Returns one tensor of shape (3, nelmt * nq0*nq1*nq2) whose rows are the three outputs of the C call, each in the
+    layout of bwdtrans_hex's output (rows contiguous and 256-byte aligned; the tensor as a whole need not be
+    contiguous); `out` may be such a tensor, or a sequence of three flat tensors (then returned as a tuple).  No output may overlap inp, df or another output.  float64 takes variant "auto", "wave" or "generic"; float32
+    the AUTO route.  A plain function: no autograd."""
+    return _operator_call("physderiv_hex", _physderiv(nq, (deriv0, deriv1, deriv2), df), nq, (basis0, basis1, basis2), inp,
+                          out, variant, stream)
+
+
+def physderiv_quad(nq, basis0, basis1, deriv0, deriv1, df, inp, out=None, variant="auto", stream=None):
+    """BwdTrans fused with the physical-space gradient in 2D: out[a][e][j][i] = sum_b df[e][2 a + b][j][i] du_b[e][j][i],
+    four planes of df (or None), a (2, nelmt * nq0*nq1) result."""
+    return _operator_call("physderiv_quad", _physderiv(nq, (deriv0, deriv1), df), nq, (basis0, basis1), inp, out, variant,
+                          stream)
 
 
 class _BwdTrans(torch.autograd.Function):

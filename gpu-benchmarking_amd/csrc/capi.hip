@@ -1,10 +1,11 @@
 // capi.hip -- the extern "C" boundary of libsumfact.so (declared in include/sumfact.h).
 // Validation + dispatch only: every operator entry point forwards to one template <int DIM, typename T> function below
-// (bwdtrans, iprod, mass, helmholtz, affine), which validates, builds ArgsT<DIM, T> and routes to the launchers that
+// (bwdtrans, iprod, mass, helmholtz, affine, physderiv), which validates, builds ArgsT<DIM, T> and routes to the launchers that
 // sf_dispatch.h declares.  Kernels live in bwdtrans_hex.hip / bwdtrans_quad.hip / bwdtrans_rt.hip /
 // bwdtrans_generic.hip / aux_kernels.hip, IProductWRTBase in iproduct.hip / iproduct_generic.hip, the fused mass
 // operator in mass.hip / mass_f32.hip / mass_generic.hip, the fused Helmholtz operator in helmholtz.hip /
-// helmholtz_f32.hip / helmholtz_generic.hip, its affine-element form in affine.hip / affine_f32.hip / affine_generic.hip.
+// helmholtz_f32.hip / helmholtz_generic.hip, its affine-element form in affine.hip / affine_f32.hip / affine_generic.hip,
+// BwdTrans fused with the physical-space gradient in physderiv.hip / physderiv_f32.hip / physderiv_generic.hip.
 #include "sf_dispatch.h"
 
 #include <cstdio>
@@ -63,7 +64,7 @@ static ArgsT<DIM, T> make_args(const T *const (&b)[3], const T *in, T *wsp, T *o
         return {b[0], b[1], in, wsp, out, (uint64_t)nelmt};
 }
 
-// The shared tail of sf_iproduct_*, sf_mass_*, sf_helmholtz_* and sf_affine_helmholtz_*: AUTO takes the wave kernel for an isotropic order of
+// The shared tail of sf_iproduct_*, sf_mass_*, sf_helmholtz_*, sf_affine_helmholtz_* and sf_physderiv_*: AUTO takes the wave kernel for an isotropic order of
 // its table (`wave_built`) when in / out are 16-byte aligned, and the any-extent kernel otherwise.
 template <int DIM, class Wave, class Generic>
 static int route(int variant, const unsigned (&nq)[3], bool generic_built, bool wave_built, const void *in,
@@ -251,6 +252,43 @@ static int affine(int variant, const unsigned (&nq)[3], size_t nelmt, const T *c
         variant, nq, affine_generic_built(DIM, nq[0], nq[1], nq[2]), affine_wave_built(DIM, nq[0]), in, out,
         [&] { return launch_affine_wave<DIM, T>(nq[0], a, x, s); },
         [&] { return launch_affine_generic<DIM, T>(nq, a, x, s); });
+}
+
+// ---- BwdTrans fused with the physical-space gradient: one validation and routing for both dimensions and scalar types --
+// The order of sf_helmholtz_*, with df in the place of g (looked at only when it is not null) and DIM outputs of nq^d
+// points per element each.
+template <int DIM, typename T>
+static int physderiv(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *const (&d)[3],
+                     const T *df, const T *in, T *const (&out)[3], void *stream)
+{
+    const int rc = validate(range_ok<DIM>(variant, nq), nelmt,
+                            {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], in, out[0], out[1],
+                             DIM == 3 ? out[2] : out[0], df ? df : in},
+                            sizeof(T));
+    if (rc != kProceed)
+        return rc;
+    // an output may not overlap what the call reads or another output
+    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
+    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
+    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
+    uintptr_t out_bits        = 0; // 16-byte aligned exactly when every output is
+    for (int a = 0; a < DIM; ++a)
+    {
+        if (overlaps(out[a], points_bytes, in, modes_bytes) ||
+            (df && overlaps(out[a], points_bytes, df, DIM * DIM * points_bytes)))
+            return SF_EINVAL;
+        for (int c = 0; c < a; ++c)
+            if (overlaps(out[a], points_bytes, out[c], points_bytes))
+                return SF_EINVAL;
+        out_bits |= (uintptr_t)out[a];
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    const auto a        = make_args<DIM, T>(b, in, nullptr, nullptr, nelmt);
+    const PhysDerivArgsT<T> x{d[0], d[1], d[2], df, out[0], out[1], out[2]};
+    return route<DIM>(
+        variant, nq, physderiv_generic_built(DIM, nq[0], nq[1], nq[2]), physderiv_wave_built(DIM, nq[0]), in,
+        (const void *)out_bits, [&] { return launch_physderiv_wave<DIM, T>(nq[0], a, x, s); },
+        [&] { return launch_physderiv_generic<DIM, T>(nq, a, x, s); });
 }
 
 extern "C" {
@@ -531,6 +569,57 @@ int sf_affine_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const
 {
     return affine<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
                             {deriv0, deriv1, nullptr}, {qw0, qw1, nullptr}, ge, je, lambda, in, out, stream);
+}
+
+// ---- BwdTrans fused with the physical-space gradient: d outputs, no point image in HBM ---------------------------------
+int sf_physderiv_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
+                                 const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
+                                 const double *deriv2, const double *df, const double *in, double *out0, double *out1,
+                                 double *out2, void *stream)
+{
+    return physderiv<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2}, df, in,
+                                {out0, out1, out2}, stream);
+}
+
+int sf_physderiv_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
+                         const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
+                         const double *deriv2, const double *df, const double *in, double *out0, double *out1,
+                         double *out2, void *stream)
+{
+    return physderiv<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
+                                {deriv0, deriv1, deriv2}, df, in, {out0, out1, out2}, stream);
+}
+
+int sf_physderiv_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                                  const double *basis1, const double *deriv0, const double *deriv1, const double *df,
+                                  const double *in, double *out0, double *out1, void *stream)
+{
+    return physderiv<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr}, df, in,
+                                {out0, out1, nullptr}, stream);
+}
+
+int sf_physderiv_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                          const double *deriv0, const double *deriv1, const double *df, const double *in, double *out0,
+                          double *out1, void *stream)
+{
+    return physderiv<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
+                                {deriv0, deriv1, nullptr}, df, in, {out0, out1, nullptr}, stream);
+}
+
+int sf_physderiv_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
+                         const float *basis2, const float *deriv0, const float *deriv1, const float *deriv2,
+                         const float *df, const float *in, float *out0, float *out1, float *out2, void *stream)
+{
+    return physderiv<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
+                               {deriv0, deriv1, deriv2}, df, in, {out0, out1, out2}, stream);
+}
+
+int sf_physderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
+                          const float *deriv0, const float *deriv1, const float *df, const float *in, float *out0,
+                          float *out1, void *stream)
+{
+    return physderiv<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
+                               {deriv0, deriv1, nullptr}, df, in, {out0, out1, nullptr}, stream);
 }
 
 int sf_sumsq_f32(const float *x, size_t n, double *result_host, void *stream)

@@ -118,6 +118,22 @@ template <int DIM, typename T>
 int launch_affine_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const AffineArgsT<T> &x, hipStream_t s);
 bool affine_wave_built(int dim, unsigned nq);
 bool affine_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
+// BwdTrans fused with the physical-space gradient, out_a = sum_b df_ab D_b B x (physderiv.hip / physderiv_f32.hip: the
+// wave kernels of physderiv_wave.h, the Helmholtz table; physderiv_generic.hip: any extents up to 12 per direction in 3D
+// and 32 in 2D).  What the operator takes beyond the BwdTrans arguments: the derivative matrices, the d*d planes of the
+// inverse Jacobian (null: never read, the reference-space derivatives) and its d outputs -- `out` of the BwdTrans
+// arguments is not used.
+template <typename T> struct PhysDerivArgsT
+{
+    const T *d0, *d1, *d2, *df;
+    T *out0, *out1, *out2;
+};
+template <int DIM, typename T>
+int launch_physderiv_wave(unsigned nq, const ArgsT<DIM, T> &a, const PhysDerivArgsT<T> &x, hipStream_t s);
+template <int DIM, typename T>
+int launch_physderiv_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const PhysDerivArgsT<T> &x, hipStream_t s);
+bool physderiv_wave_built(int dim, unsigned nq);
+bool physderiv_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
 int sumsq_f32_blocking(const float *x, size_t n, double *result_host, hipStream_t s);
 int fill_sincos_f32(float *in, size_t nelmt, size_t nm_tot, hipStream_t s);
 int fill_basis_f32(float *b, size_t nm, size_t nq, hipStream_t s);

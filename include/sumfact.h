@@ -382,6 +382,67 @@ int sf_affine_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const
                                  double lambda, const float *in, float *out, void *stream);
 
 /*
+ * BwdTrans fused with the physical-space gradient (PhysDeriv), what an explicit advection or diffusion step, a pointwise
+ * flux or an error norm needs at the quadrature points:
+ *   u = B x_e,   du_b = D_b u,   out_a[e][k][j][i] = sum_b df[e][a*d + b][k][j][i] * du_b[e][k][j][i],   a = 0 .. d-1
+ * BwdTrans, the d collocation derivatives and the d x d product with the inverse Jacobian in ONE kernel.  Per element
+ * the call moves nm^d + (d*d + d) nq^d scalars (nm^d + d nq^d without df); no intermediate point image reaches HBM.
+ * Layout: basis_d, deriv_d (deriv_d[i*nq_d + m] = l'_m(xi_i)) and `in` (nm0*nm1[*nm2] modes per element) exactly as in
+ * sf_helmholtz_*.  df[e][c][k][j][i]: the inverse Jacobian per point as d*d component planes per element, component
+ * order c = a*d + b for d xi_b / d x_a (row a: the physical direction of out_a; column b: the reference direction of
+ * du_b), each plane laid out like the output of BwdTrans.  df is NOT symmetric: all d*d planes are stored, 9 in 3D and
+ * 4 in 2D.  out_a: d separate caller-owned arrays of nq0*nq1[*nq2] points per element in the BwdTrans output layout
+ * (i fastest); each can go straight into sf_iproduct_* or sf_mass_*.
+ * If df is NULL it is never read (nor validated): the call returns the reference-space derivatives out_a = du_a, with
+ * no multiplication by one, and moves d*d planes less.
+ * Summation order (it defines the rounding; every sum in ascending index, the first product a multiply, then FMAs; the
+ * wave kernels and the fallback follow it alike):
+ *   1. forward sweeps p -> i, q -> j, r -> k, as BwdTrans:                  u
+ *   2. du_a = D_a u for each direction a
+ *   3. out_a = sum_b df_ab du_b, b ascending                                (df NULL: out_a = du_a)
+ * Routes, as sf_helmholtz_*: SF_VARIANT_AUTO runs the fused wave kernel for the isotropic orders of its table (3D nq
+ * 2..8, 2D nq 2..16) when `in` and every out_a are 16-byte aligned, else GENERIC; SF_VARIANT_WAVE returns SF_ENOTBUILT
+ * off that table and SF_EALIGN unless `in` and every out_a are 16-byte aligned; SF_VARIANT_GENERIC (one workgroup per
+ * element, latency-bound) takes any extents up to 12 per direction in 3D and 32 in 2D -- 3D nq 9..11 and all
+ * anisotropic shapes take it; any other variant SF_ENOTBUILT, extents beyond those bounds SF_ENOTBUILT.  df, the bases
+ * and the derivative matrices need only scalar alignment on every route.
+ * Validation, before any HIP call, in this order: (1) an extent < 2 or a variant outside [0, SF_NUM_VARIANTS):
+ * SF_EINVAL; (2) nelmt == 0: SF_OK; (3) a null basis, deriv, in or out_a: SF_EINVAL (df may be null); (4) any of them
+ * (df only if it is not null) not scalar-aligned: SF_EALIGN; (5) any out_a overlapping `in`, `df` or another out_b,
+ * compared as byte ranges of their full sizes: SF_EINVAL; (6) extents beyond the fallback's bounds: SF_ENOTBUILT; (7) an
+ * unsupported variant: SF_ENOTBUILT.
+ * NOT in-place safe: an output that overlaps an input or another output is refused, not undefined; the inputs may overlap
+ * each other (all are only read).
+ * No internal workspace and no allocation: every call is a single kernel node, capture-safe from the process's first
+ * call.
+ */
+int sf_physderiv_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                         const double *basis0, const double *basis1, const double *basis2,
+                         const double *deriv0, const double *deriv1, const double *deriv2,
+                         const double *df, const double *in,
+                         double *out0, double *out1, double *out2, void *stream);
+int sf_physderiv_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                                 const double *basis0, const double *basis1, const double *basis2,
+                                 const double *deriv0, const double *deriv1, const double *deriv2,
+                                 const double *df, const double *in,
+                                 double *out0, double *out1, double *out2, void *stream);
+int sf_physderiv_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                          const double *deriv0, const double *deriv1, const double *df, const double *in,
+                          double *out0, double *out1, void *stream);
+int sf_physderiv_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                                  const double *basis1, const double *deriv0, const double *deriv1,
+                                  const double *df, const double *in, double *out0, double *out1,
+                                  void *stream);
+/* T = float (AUTO route; every array 4-byte aligned) */
+int sf_physderiv_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
+                         const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
+                         const float *deriv2, const float *df, const float *in, float *out0, float *out1,
+                         float *out2, void *stream);
+int sf_physderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
+                          const float *deriv0, const float *deriv1, const float *df, const float *in,
+                          float *out0, float *out1, void *stream);
+
+/*
  * benchmark02: x[i] += y[i]  -- replaces add_vector<T,vl><<<>>>
  * (benchmark02/benchmark02.cc:16-58); 24 bytes of HBM traffic per element (:255), so its GB/s is the
  * measured stream rate used as the second roofline denominator.  fill: data1/data2 of :84-85.
