@@ -20,4 +20,5 @@ from .bwdtrans import (  # noqa: F401
     iproduct_hex, iproduct_quad, bwdtrans_autograd, mass_hex, mass_quad,
     helmholtz_hex, helmholtz_quad, affine_helmholtz_hex, affine_helmholtz_quad,
     physderiv_hex, physderiv_quad,
+    iprodderiv_hex, iprodderiv_quad, physderiv_autograd,
 )

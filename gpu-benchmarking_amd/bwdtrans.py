@@ -70,9 +70,10 @@ def quad_wsp_doubles(nq, nelmt):
 # the bases and `in`, in the order of the C signature, as (name, tensor, expected numel, may be None); lam, or None for a
 # family without one; whether float32 quietly takes the AUTO route for any `variant` (BwdTrans) or refuses all but "auto";
 # BwdTrans only: wsp_need(nelmt) -> {variant: numel of the caller-owned workspace it needs}; out_parts: the number of
-# separate output arrays of the C call (1: `out` is one flat tensor; d: `out` is a (d, n) tensor or a sequence of d tensors).
-_Family = collections.namedtuple("_Family", "stem inp_points out_points extras lam f32_ignores_variant wsp_need out_parts",
-                                 defaults=(lambda nelmt, nqt: [], None, False, None, 1))
+# separate output arrays of the C call (1: `out` is one flat tensor; d: `out` is a (d, n) tensor or a sequence of d tensors);
+# inp_parts: the same for the input arrays (1: `inp` is one flat tensor; d: a (d, n) tensor or a sequence of d tensors).
+_Family = collections.namedtuple("_Family", "stem inp_points out_points extras lam f32_ignores_variant wsp_need out_parts "
+                                 "inp_parts", defaults=(lambda nelmt, nqt: [], None, False, None, 1, 1))
 
 
 def _output_parts(what, out, parts, numel, inp):
@@ -98,10 +99,39 @@ def _output_parts(what, out, parts, numel, inp):
     return tuple(outs), outs
 
 
+def _input_parts(what, inp, parts):
+    """The `parts` flat tensors the C call reads, of a family with several inputs.  `inp` is a (parts, n) tensor with
+    contiguous rows (what physderiv_* returns: taken row by row, no copy, the tensor as a whole need not be contiguous),
+    any contiguous tensor of parts * n values, or a sequence of `parts` flat tensors.  Every part has the size, dtype and
+    device of the first."""
+    if isinstance(inp, torch.Tensor):
+        if not (inp.dim() == 2 and inp.shape[0] == parts and (inp.shape[1] <= 1 or inp.stride(1) == 1)):
+            if inp.numel() % parts:
+                raise ValueError(f"{what}: in has {inp.numel()} values, no multiple of its {parts} parts")
+            if not inp.is_contiguous():
+                raise TypeError(f"{what}: in must be contiguous, or ({parts}, n) with contiguous rows")
+            inp = inp.view(parts, -1)
+        ins = [inp[a] for a in range(parts)]
+    else:
+        ins = list(inp)
+        if len(ins) != parts:
+            raise ValueError(f"{what}: in holds {len(ins)} tensors, not {parts}")
+        for a, t in enumerate(ins):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{what}: in{a} must be a tensor")
+    _check_operands(what, [(f"in{a}", t, ins[0].numel(), False) for a, t in enumerate(ins)], ins[0])
+    return ins
+
+
 def _operator_call(what, fam, nq, bases, inp, out, variant, stream, wsp=None):
-    """The one call path of bwdtrans_* / iproduct_* / mass_* / helmholtz_* / affine_helmholtz_* / physderiv_*: sizes, dtypes
-    and devices are checked here (before any library call), pointers, alignment and overlap in the C ABI."""
+    """The one call path of bwdtrans_* / iproduct_* / mass_* / helmholtz_* / affine_helmholtz_* / physderiv_* /
+    iprodderiv_*: sizes, dtypes and devices are checked here (before any library call), pointers, alignment and overlap in
+    the C ABI."""
     nq = tuple(int(x) for x in nq)
+    ins = None
+    if fam.inp_parts > 1:               # every part like the first, which stands for them below
+        ins = _input_parts(what, inp, fam.inp_parts)
+        inp = ins[0]
     nmt, nqt = 1, 1
     for q in nq:
         nmt, nqt = nmt * (q - 1), nqt * q
@@ -137,7 +167,10 @@ def _operator_call(what, fam, nq, bases, inp, out, variant, stream, wsp=None):
     ptrs = [None if t is None else _dev_ptr(t, name, dtype) for name, t, _, _ in operands]
     if lam is not None:
         ptrs.append(ctypes.c_double(lam))
-    ptrs.append(_dev_ptr(inp, "in", dtype))
+    if ins is None:
+        ptrs.append(_dev_ptr(inp, "in", dtype))
+    else:
+        ptrs += [_dev_ptr(t, f"in{a}", dtype) for a, t in enumerate(ins)]
     if fam.wsp_need is not None and not f32:
         ptrs.append(None if wsp is None else _dev_ptr(wsp, "wsp", dtype))
     with torch.cuda.device(inp.device):
@@ -276,6 +309,32 @@ def physderiv_quad(nq, basis0, basis1, deriv0, deriv1, df, inp, out=None, varian
                           stream)
 
 
+def _iprodderiv(nq, derivs, df, w):
+    d = len(nq)
+    return _Family("iprodderiv", True, False, lambda nelmt, nqt: _per_direction("deriv", derivs, lambda q: q * q, nq) + [
+        ("df", df, nelmt * d * d * nqt, True), ("w", w, nelmt * nqt, True)], inp_parts=d)
+
+
+def iprodderiv_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, df, w, inp, out=None, variant="auto", stream=None):
+    """IProductWRTDerivBase, the weak divergence and the transpose of physderiv_hex, in one kernel on inp's device: with
+    g_b = w sum_a df[e][3 a + b] inp[a] per point, out[e][r][q][p] = sum_b (B^T D_b^T g_b)[e][r][q][p].  The bases,
+    derivative matrices and df of physderiv_hex (the sum runs over the row index a of df), or df=None for g_b = w inp[b];
+    w[e][k][j][i] as in mass_hex, or None for no weight (then the exact transpose of physderiv_hex on the same df); df and
+    w are never read when None.  inp: the three point arrays, each in the layout of bwdtrans_hex's output -- a (3, n)
+    tensor with contiguous rows (what physderiv_hex returns, taken without a copy), a contiguous tensor of 3 n values, or
+    a sequence of three flat tensors.  out holds nm0*nm1*nm2 modes per element and may not overlap an input, df or w.
+    float64 takes variant "auto", "wave" or "generic"; float32 the AUTO route.  A plain function: no autograd."""
+    return _operator_call("iprodderiv_hex", _iprodderiv(nq, (deriv0, deriv1, deriv2), df, w), nq, (basis0, basis1, basis2),
+                          inp, out, variant, stream)
+
+
+def iprodderiv_quad(nq, basis0, basis1, deriv0, deriv1, df, w, inp, out=None, variant="auto", stream=None):
+    """IProductWRTDerivBase in 2D: g_b = w sum_a df[e][2 a + b] inp[a], out[e][q][p] = sum_b (B^T D_b^T g_b)[e][q][p]; four
+    planes of df (or None), one of w (or None), inp a (2, n) tensor or a sequence of two flat tensors."""
+    return _operator_call("iprodderiv_quad", _iprodderiv(nq, (deriv0, deriv1), df, w), nq, (basis0, basis1), inp, out,
+                          variant, stream)
+
+
 class _BwdTrans(torch.autograd.Function):
     """AUTO BwdTrans forward; its input gradient is IProductWRTBase of the output gradient (the exact transpose)."""
 
@@ -302,6 +361,38 @@ def bwdtrans_autograd(nq, bases, inp):
     if any(b.requires_grad for b in bases):
         raise ValueError("bwdtrans_autograd: the bases are constants; detach them (no gradient flows to a basis)")
     return _BwdTrans.apply(inp, nq, *bases)
+
+
+class _PhysDeriv(torch.autograd.Function):
+    """AUTO physderiv_* forward; its input gradient is iprodderiv_*(df, None, grad_out) (the exact transpose)."""
+
+    @staticmethod
+    def forward(ctx, inp, nq, df, *mats):
+        ctx.nq, ctx.shape, ctx.has_df = nq, inp.shape, df is not None
+        ctx.save_for_backward(*mats, *((df,) if df is not None else ()))
+        x = inp.contiguous()
+        return physderiv_hex(nq, *mats, df, x) if len(nq) == 3 else physderiv_quad(nq, *mats, df, x)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        saved = ctx.saved_tensors
+        mats, df = saved[:2 * len(ctx.nq)], saved[-1] if ctx.has_df else None
+        g = grad_out if grad_out.shape[1] <= 1 or grad_out.stride(1) == 1 else grad_out.contiguous()
+        f = iprodderiv_hex if len(ctx.nq) == 3 else iprodderiv_quad
+        return (f(ctx.nq, *mats, df, None, g).reshape(ctx.shape), None, None) + (None,) * len(mats)
+
+
+def physderiv_autograd(nq, bases, derivs, df, inp):
+    """physderiv_* (AUTO) with a backward pass: the gradient with respect to `inp` is iprodderiv_*(df, None, grad_out),
+    enqueued on the current stream.  The bases, the derivative matrices and df (which may be None) are constants: one that
+    requires grad is refused.  Returns the (d, n) output of physderiv_*."""
+    nq, bases, derivs = tuple(int(x) for x in nq), tuple(bases), tuple(derivs)
+    if len(nq) not in (2, 3) or len(bases) != len(nq) or len(derivs) != len(nq):
+        raise ValueError("physderiv_autograd: 2 or 3 extents, one basis and one derivative matrix per extent")
+    if any(t.requires_grad for t in bases + derivs + ((df,) if df is not None else ())):
+        raise ValueError("physderiv_autograd: the bases, the derivative matrices and df are constants; detach them (no "
+                         "gradient flows to them)")
+    return _PhysDeriv.apply(inp, nq, df, *bases, *derivs)
 
 
 def _spec_args(nq, dtype):

@@ -47,15 +47,18 @@ SYMBOLS = {
 
 
 def _operator_symbols():
-    """sf_<stem>_{hex,quad}_{f64,f64_variant,f32} of the six operator families: [variant,] the extents, nelmt, the pointer
-    operands in front of `in` (so many per direction, so many per call), [lambda,] in, [BwdTrans _variant: wsp,] out (or one
-    output per direction), stream."""
-    rows = {"bwdtrans": (1, 0, False, False), "iproduct": (1, 0, False, False), "mass": (1, 1, False, False),
-            "helmholtz": (2, 2, True, False), "affine_helmholtz": (3, 2, True, False), "physderiv": (2, 1, False, True)}
-    for stem, (per_direction, per_call, has_lambda, out_per_direction) in rows.items():
+    """sf_<stem>_{hex,quad}_{f64,f64_variant,f32} of the seven operator families: [variant,] the extents, nelmt, the pointer
+    operands in front of `in` (so many per direction, so many per call), [lambda,] in (or one input per direction),
+    [BwdTrans _variant: wsp,] out (or one output per direction), stream."""
+    rows = {"bwdtrans": (1, 0, False, False, False), "iproduct": (1, 0, False, False, False),
+            "mass": (1, 1, False, False, False), "helmholtz": (2, 2, True, False, False),
+            "affine_helmholtz": (3, 2, True, False, False), "physderiv": (2, 1, False, True, False),
+            "iprodderiv": (2, 2, False, False, True)}
+    for stem, (per_direction, per_call, has_lambda, out_per_direction, in_per_direction) in rows.items():
         for shape, dim in (("hex", 3), ("quad", 2)):
+            ins = [_vp] * (dim if in_per_direction else 1)
             outs = [_vp] * (dim if out_per_direction else 1)
-            tail = [_vp] * (per_direction * dim + per_call) + ([ctypes.c_double] if has_lambda else []) + [_vp] + outs + [_vp]
+            tail = [_vp] * (per_direction * dim + per_call) + ([ctypes.c_double] if has_lambda else []) + ins + outs + [_vp]
             for sfx in ("f64", "f64_variant", "f32"):
                 head = [_i] if sfx == "f64_variant" else []
                 wsp = [_vp] if (stem, sfx) == ("bwdtrans", "f64_variant") else []

@@ -1,11 +1,12 @@
 // capi.hip -- the extern "C" boundary of libsumfact.so (declared in include/sumfact.h).
 // Validation + dispatch only: every operator entry point forwards to one template <int DIM, typename T> function below
-// (bwdtrans, iprod, mass, helmholtz, affine, physderiv), which validates, builds ArgsT<DIM, T> and routes to the launchers that
+// (bwdtrans, iprod, mass, helmholtz, affine, physderiv, iprodderiv), which validates, builds ArgsT<DIM, T> and routes to the launchers that
 // sf_dispatch.h declares.  Kernels live in bwdtrans_hex.hip / bwdtrans_quad.hip / bwdtrans_rt.hip /
 // bwdtrans_generic.hip / aux_kernels.hip, IProductWRTBase in iproduct.hip / iproduct_generic.hip, the fused mass
 // operator in mass.hip / mass_f32.hip / mass_generic.hip, the fused Helmholtz operator in helmholtz.hip /
 // helmholtz_f32.hip / helmholtz_generic.hip, its affine-element form in affine.hip / affine_f32.hip / affine_generic.hip,
-// BwdTrans fused with the physical-space gradient in physderiv.hip / physderiv_f32.hip / physderiv_generic.hip.
+// BwdTrans fused with the physical-space gradient in physderiv.hip / physderiv_f32.hip / physderiv_generic.hip, its
+// transpose IProductWRTDerivBase in iprodderiv.hip / iprodderiv_f32.hip / iprodderiv_generic.hip.
 #include "sf_dispatch.h"
 
 #include <cstdio>
@@ -64,7 +65,7 @@ static ArgsT<DIM, T> make_args(const T *const (&b)[3], const T *in, T *wsp, T *o
         return {b[0], b[1], in, wsp, out, (uint64_t)nelmt};
 }
 
-// The shared tail of sf_iproduct_*, sf_mass_*, sf_helmholtz_*, sf_affine_helmholtz_* and sf_physderiv_*: AUTO takes the wave kernel for an isotropic order of
+// The shared tail of sf_iproduct_*, sf_mass_*, sf_helmholtz_*, sf_affine_helmholtz_*, sf_physderiv_* and sf_iprodderiv_*: AUTO takes the wave kernel for an isotropic order of
 // its table (`wave_built`) when in / out are 16-byte aligned, and the any-extent kernel otherwise.
 template <int DIM, class Wave, class Generic>
 static int route(int variant, const unsigned (&nq)[3], bool generic_built, bool wave_built, const void *in,
@@ -289,6 +290,37 @@ static int physderiv(int variant, const unsigned (&nq)[3], size_t nelmt, const T
         variant, nq, physderiv_generic_built(DIM, nq[0], nq[1], nq[2]), physderiv_wave_built(DIM, nq[0]), in,
         (const void *)out_bits, [&] { return launch_physderiv_wave<DIM, T>(nq[0], a, x, s); },
         [&] { return launch_physderiv_generic<DIM, T>(nq, a, x, s); });
+}
+
+// ---- IProductWRTDerivBase, the transpose of the gradient: one validation and routing for both dimensions and scalar types --
+// The order of sf_physderiv_*, with DIM inputs of nq^d points per element each, df and w in front of them (each looked at
+// only when it is not null) and one output of modes.  Only `out` is a 16-byte stream of the wave kernels.
+template <int DIM, typename T>
+static int iprodderiv(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *const (&d)[3],
+                      const T *df, const T *w, const T *const (&in)[3], T *out, void *stream)
+{
+    const int rc = validate(range_ok<DIM>(variant, nq), nelmt,
+                            {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], in[0], in[1],
+                             DIM == 3 ? in[2] : in[0], out, df ? df : in[0], w ? w : in[0]},
+                            sizeof(T));
+    if (rc != kProceed)
+        return rc;
+    // the output may not overlap what the call reads
+    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
+    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
+    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
+    for (int a = 0; a < DIM; ++a)
+        if (overlaps(out, modes_bytes, in[a], points_bytes))
+            return SF_EINVAL;
+    if ((df && overlaps(out, modes_bytes, df, DIM * DIM * points_bytes)) || (w && overlaps(out, modes_bytes, w, points_bytes)))
+        return SF_EINVAL;
+    const hipStream_t s = (hipStream_t)stream;
+    const auto a        = make_args<DIM, T>(b, nullptr, nullptr, out, nelmt);
+    const IprodDerivArgsT<T> x{d[0], d[1], d[2], df, w, in[0], in[1], in[2]};
+    return route<DIM>(
+        variant, nq, iprodderiv_generic_built(DIM, nq[0], nq[1], nq[2]), iprodderiv_wave_built(DIM, nq[0]), out, out,
+        [&] { return launch_iprodderiv_wave<DIM, T>(nq[0], a, x, s); },
+        [&] { return launch_iprodderiv_generic<DIM, T>(nq, a, x, s); });
 }
 
 extern "C" {
@@ -620,6 +652,58 @@ int sf_physderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float 
 {
     return physderiv<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
                                {deriv0, deriv1, nullptr}, df, in, {out0, out1, nullptr}, stream);
+}
+
+// ---- IProductWRTDerivBase: d inputs at the points, the weak divergence in modes -----------------------------------------
+int sf_iprodderiv_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                                  const double *basis0, const double *basis1, const double *basis2, const double *deriv0,
+                                  const double *deriv1, const double *deriv2, const double *df, const double *w,
+                                  const double *in0, const double *in1, const double *in2, double *out, void *stream)
+{
+    return iprodderiv<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2}, df, w,
+                                 {in0, in1, in2}, out, stream);
+}
+
+int sf_iprodderiv_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
+                          const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
+                          const double *deriv2, const double *df, const double *w, const double *in0, const double *in1,
+                          const double *in2, double *out, void *stream)
+{
+    return iprodderiv<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
+                                 {deriv0, deriv1, deriv2}, df, w, {in0, in1, in2}, out, stream);
+}
+
+int sf_iprodderiv_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                                   const double *basis1, const double *deriv0, const double *deriv1, const double *df,
+                                   const double *w, const double *in0, const double *in1, double *out, void *stream)
+{
+    return iprodderiv<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr}, df, w,
+                                 {in0, in1, nullptr}, out, stream);
+}
+
+int sf_iprodderiv_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                           const double *deriv0, const double *deriv1, const double *df, const double *w,
+                           const double *in0, const double *in1, double *out, void *stream)
+{
+    return iprodderiv<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
+                                 {deriv0, deriv1, nullptr}, df, w, {in0, in1, nullptr}, out, stream);
+}
+
+int sf_iprodderiv_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
+                          const float *basis2, const float *deriv0, const float *deriv1, const float *deriv2,
+                          const float *df, const float *w, const float *in0, const float *in1, const float *in2,
+                          float *out, void *stream)
+{
+    return iprodderiv<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
+                                {deriv0, deriv1, deriv2}, df, w, {in0, in1, in2}, out, stream);
+}
+
+int sf_iprodderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
+                           const float *deriv0, const float *deriv1, const float *df, const float *w, const float *in0,
+                           const float *in1, float *out, void *stream)
+{
+    return iprodderiv<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
+                                {deriv0, deriv1, nullptr}, df, w, {in0, in1, nullptr}, out, stream);
 }
 
 int sf_sumsq_f32(const float *x, size_t n, double *result_host, void *stream)

@@ -134,6 +134,26 @@ template <int DIM, typename T>
 int launch_physderiv_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const PhysDerivArgsT<T> &x, hipStream_t s);
 bool physderiv_wave_built(int dim, unsigned nq);
 bool physderiv_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
+// IProductWRTDerivBase, out = sum_b B^T D_b^T (w sum_a df_ab in_a), the transpose of the gradient above (iprodderiv.hip /
+// iprodderiv_f32.hip: the wave kernels of iprodderiv_wave.h, the Helmholtz table; iprodderiv_generic.hip: any extents up
+// to 12 per direction in 3D and 32 in 2D).  What the operator takes beyond the BwdTrans arguments: the derivative
+// matrices, the d*d planes of the inverse Jacobian (null: never read), the weight plane (null: never read) and its d
+// inputs -- `in` of the BwdTrans arguments is not used.  The wave launcher carries one switch (df); the weight picks one
+// of two argument structs.
+template <typename T> struct IprodDerivArgsT
+{
+    const T *d0, *d1, *d2, *df, *w;
+    const T *in0, *in1, *in2;
+};
+template <typename T> struct IprodDerivWArgsT : IprodDerivArgsT<T> // w is not null
+{
+};
+template <int DIM, typename T>
+int launch_iprodderiv_wave(unsigned nq, const ArgsT<DIM, T> &a, const IprodDerivArgsT<T> &x, hipStream_t s);
+template <int DIM, typename T>
+int launch_iprodderiv_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const IprodDerivArgsT<T> &x, hipStream_t s);
+bool iprodderiv_wave_built(int dim, unsigned nq);
+bool iprodderiv_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
 int sumsq_f32_blocking(const float *x, size_t n, double *result_host, hipStream_t s);
 int fill_sincos_f32(float *in, size_t nelmt, size_t nm_tot, hipStream_t s);
 int fill_basis_f32(float *b, size_t nm, size_t nq, hipStream_t s);

@@ -502,6 +502,72 @@ const char *sf_last_specialise_log(void);
  * never). */
 int sf_shutdown(void);
 
+/*
+ * IProductWRTDerivBase, the weak divergence sum_a int d phi / d x_a f_a: what every explicit advection, diffusion or DG
+ * volume term ends in, and the exact transpose of sf_physderiv_*.  With f_a = in_a[e][k][j][i], a = 0 .. d-1:
+ *   g_b[e][k][j][i] = w[e][k][j][i] * sum_a df[e][a*d + b][k][j][i] * in_a[e][k][j][i]            (per point; b = 0 .. d-1)
+ *   out[e][r][q][p] = sum_b (B^T D_b^T g_b)[e][r][q][p]
+ * The d x d product with the inverse Jacobian, the weight, the d transposed collocation derivatives and IProductWRTBase
+ * in ONE kernel.  Per element the call moves (d*d + d + 1) nq^d + nm^d scalars (less d*d nq^d without df, less nq^d
+ * without w); no intermediate point image reaches HBM.
+ * Layout: basis_d and deriv_d exactly as in sf_physderiv_*.  in_a: d separate caller-owned arrays of nq0*nq1[*nq2]
+ * points per element in the BwdTrans output layout (i fastest) -- exactly what sf_physderiv_* writes.  df: the d*d planes
+ * of sf_physderiv_*, the same array in the same component order c = a*d + b for d xi_b / d x_a; the sum here runs over
+ * the ROW index a (the transpose of the product in sf_physderiv_*).  w: one plane per element, laid out like the w of
+ * sf_mass_* (Jacobian times quadrature weight).  out: nm0*nm1[*nm2] modes per element, the layout of sf_iproduct_*'s
+ * output.
+ * If df is NULL it is never read (nor validated): g_b = w * in_b.  If w is NULL it is never read (nor validated): no
+ * multiplication happens.  With both NULL the call is sum_b B^T D_b^T in_b.  With w == NULL the call is bit for bit the
+ * algebraic transpose of sf_physderiv_* on the same df.
+ * Summation order (it defines the rounding; every sum in ascending index, the first product a multiply, then FMAs; the
+ * wave kernels and the fallback follow it alike):
+ *   1. t_b = sum_a df_ab in_a, a ascending                                  (df NULL: t_b = in_b)
+ *   2. g_b = w * t_b                                                        (w NULL: g_b = t_b)
+ *   3. v = (D_0^T g_0 + D_1^T g_1) [+ D_2^T g_2]
+ *   4. transposed sweeps k -> r, j -> q, i -> p, as sf_iproduct_* / sf_mass_*
+ * Routes, as sf_physderiv_*: SF_VARIANT_AUTO runs the fused wave kernel for the isotropic orders of its table (3D nq
+ * 2..8, 2D nq 2..16) when `out` is 16-byte aligned, else GENERIC; SF_VARIANT_WAVE returns SF_ENOTBUILT off that table and
+ * SF_EALIGN unless `out` is 16-byte aligned; SF_VARIANT_GENERIC (one workgroup per element, latency-bound) takes any
+ * extents up to 12 per direction in 3D and 32 in 2D -- 3D nq 9..11 and all anisotropic shapes take it; any other variant
+ * SF_ENOTBUILT, extents beyond those bounds SF_ENOTBUILT.  Only `out` needs 16-byte alignment for the wave route (it is
+ * flushed as the 16-byte stream); every in_a, df, w, the bases and the derivative matrices are read one scalar per lane
+ * and need only scalar alignment on every route.
+ * Validation, before any HIP call, in this order: (1) an extent < 2 or a variant outside [0, SF_NUM_VARIANTS):
+ * SF_EINVAL; (2) nelmt == 0: SF_OK; (3) a null basis, deriv, in_a or out: SF_EINVAL (df and w may be null); (4) any of
+ * them (df, w only if not null) not scalar-aligned: SF_EALIGN; (5) `out` overlapping any in_a, `df` or `w`, compared as
+ * byte ranges of their full sizes: SF_EINVAL; (6) extents beyond the fallback's bounds: SF_ENOTBUILT; (7) an unsupported
+ * variant: SF_ENOTBUILT.
+ * NOT in-place safe: an output that overlaps an input is refused, not undefined; the inputs may overlap each other (all
+ * are only read).
+ * No internal workspace and no allocation: every call is a single kernel node, capture-safe from the process's first
+ * call.
+ */
+int sf_iprodderiv_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                          const double *basis0, const double *basis1, const double *basis2,
+                          const double *deriv0, const double *deriv1, const double *deriv2,
+                          const double *df, const double *w,
+                          const double *in0, const double *in1, const double *in2, double *out, void *stream);
+int sf_iprodderiv_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                                  const double *basis0, const double *basis1, const double *basis2,
+                                  const double *deriv0, const double *deriv1, const double *deriv2,
+                                  const double *df, const double *w,
+                                  const double *in0, const double *in1, const double *in2, double *out, void *stream);
+int sf_iprodderiv_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                           const double *deriv0, const double *deriv1, const double *df, const double *w,
+                           const double *in0, const double *in1, double *out, void *stream);
+int sf_iprodderiv_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                                   const double *basis1, const double *deriv0, const double *deriv1,
+                                   const double *df, const double *w, const double *in0, const double *in1,
+                                   double *out, void *stream);
+/* T = float (AUTO route; every array 4-byte aligned) */
+int sf_iprodderiv_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
+                          const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
+                          const float *deriv2, const float *df, const float *w, const float *in0,
+                          const float *in1, const float *in2, float *out, void *stream);
+int sf_iprodderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
+                           const float *deriv0, const float *deriv1, const float *df, const float *w,
+                           const float *in0, const float *in1, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
