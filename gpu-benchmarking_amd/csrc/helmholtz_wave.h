@@ -7,7 +7,14 @@
 // component planes g[e][c][k][j][i] (3D: c = 00, 01, 02, 11, 12, 22; 2D: c = 00, 01, 11), w the mass weight per point.
 // BwdTrans, three (two) derivatives, the metric contraction, the transposed derivatives and IProductWRTBase in ONE
 // kernel: the quadrature-space images never exist in HBM.  The front (chunk_fetch / chunk_stage, the forward sweeps) and
-// the back (the transposed sweeps, chunk_flush) are those of the mass kernel (mass_wave.h); the middle is new.
+// the back (the transposed sweeps, chunk_flush) are those of the mass kernel, the same text: csrc/frag/*.inc, included
+// in place (mass_wave.h says how the fragments work and which names they expect).  A kernel below is, in order:
+//   wave_slab, [imgU, imgD], wave_chunks, lane_roles, chunk_fetch_first | per chunk: chunk_head, chunk_stage, [the
+//   first slices of the metric ring], chunk_fetch_next, forward0, forward1 (3D), point_values (steps 1 end and 2),
+//   [the walk: steps 3 and the mass term], deriv_transposed (D_a^T), [the sum of step 4], transposed_last,
+//   transposed1 (3D), transposed0.
+// The bracketed parts are this header's own; affine_wave.h, physderiv_wave.h and iprodderiv_wave.h put other middles
+// between the same fragments.  dreg is the register pencil of the last direction: du_2 before the walk, f_2 after it.
 //
 // Order of operations (it defines the rounding; every sum in ascending index, the first product a multiply, then FMAs):
 //   1. forward sweeps p -> i, q -> j, r -> k                                   (u, the point values)
@@ -150,48 +157,18 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_helmholtz_wave_kernel(
     constexpr int PL = NQ * NQP, ES = NQ * PL; // plane and element stride of a point image
     static_assert(KMAP > 0, "short-lived waves only");
 
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wib  = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    T *slab        = reinterpret_cast<T *>(lds_raw) + wib * G::SLAB;
-    T *imgU        = slab;          // u, then du_1, f_1, D_1^T f_1
-    T *imgD        = slab + G::IMG; // du_0, f_0, D_0^T f_0
-
-    const uint64_t nchunk = (nelmt + EC - 1) / EC;
-    const ChunkIter it    = chunk_iter<KMAP, WPB, ((MEMF >> 4) & 0xfff)>(nchunk, wib);
-    if (it.count == 0)
-        return;
-
-    // the three roles of a lane per pass: column (e,j,i) walking k, pencil (e,k,j) over i, pencil (e,k,i) over j
-    bool own[NPASS];
-    int colp[NPASS], colo[NPASS], ecol[NPASS], bi[NPASS], bj[NPASS];
-#pragma unroll
-    for (int s = 0; s < NPASS; ++s)
-    {
-        const int t  = s * kWave + lane;
-        own[s]       = (s + 1) * kWave <= NP || t < NP;
-        const int tc = own[s] ? t : NP - 1;
-        const int e = tc / NQ2, ab = tc - e * NQ2, a = ab / NQ, b = ab - a * NQ;
-        ecol[s] = e;
-        colp[s] = ab;                    // (j,i): offset inside a plane of g / w
-        colo[s] = e * ES + a * NQP + b;  // (e,j,i): offset of the column's k = 0 point in an image
-        bi[s]   = tc * NQP;              // (e,k,j): its i-pencil
-        bj[s]   = e * ES + a * PL + b;   // (e,k,i): its j-pencil, stride NQP
-    }
-
-    constexpr bool AL = (MEMF & 4) && IO::ALIGN_OK;
-    typename IO::Vec st[IO::NLD];
-    chunk_fetch<IO, EC, !(MEMF & 1), AL>(st, in, it.first, nelmt, lane);
+#include "frag/wave_slab.inc"
+    T *imgU = slab;          // u, then du_1, f_1, D_1^T f_1
+    T *imgD = slab + G::IMG; // du_0, f_0, D_0^T f_0
+#include "frag/wave_chunks.inc"
+#include "frag/lane_roles_3d.inc"
+#include "frag/chunk_fetch_first.inc"
 
     uint64_t c = it.first;
     for (uint64_t n = 0; n < it.count; ++n, c += it.step)
     {
-        const uint64_t left = nelmt - c * EC;
-        const int evalid    = left >= EC ? EC : (int)left;
-
-        chunk_stage<IO, AL>(st, slab, lane,
-                            IO::VEC2 ? (AL ? align_shift(in + c * IO::IN_DBL) : 0) : line_offset<T>(in + c * IO::IN_DBL));
-        wave_lds_fence();
+#include "frag/chunk_head.inc"
+#include "frag/chunk_stage.inc"
         // the metric ring: the first slices, requested once the staging registers are consumed
         const T *gc = g + c * (uint64_t)(EC * G::NCOMP * NQT);
         const T *wc = HASW ? w + c * (uint64_t)(EC * NQT) : nullptr;
@@ -207,73 +184,13 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_helmholtz_wave_kernel(
 #pragma unroll
         for (int r = 0; r < RING; ++r)
             load_metric_slice<NPASS, G::NCOMP, NQ2, NQT, HASW>(gv[r], wv[r], gc, wc, goff, woff, r);
-        if (n + 1 < it.count)
-            chunk_fetch<IO, EC, !(MEMF & 1), AL>(st, in, c + it.step, nelmt, lane);
-
-        // ---- forward 0: w1[(e,i,r)][q] = sum_p in[(e,r,q)][p] * B0[p][i] ---------------------------
-        {
-            T u[F::PASS0][NM], acc[F::PASS0][NQ];
-            read_pencils<NM, F::PASS0, F::P0, F::IN_STRIDE>(u, slab, lane);
-            contract<NM, NQ, F::PASS0, BMODE>(u, acc, b0);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < F::PASS0; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= F::P0 || t < F::P0)
-                {
-                    const int e = t / NM2, rq = t - e * NM2, r = rq / NM, q = rq - r * NM;
-                    T *dst = slab + (e * NQ * NM + r) * NMP + q;
-#pragma unroll
-                    for (int i = 0; i < NQ; ++i)
-                        dst[i * NM * NMP] = acc[s][i];
-                }
-            }
-            wave_lds_fence();
-        }
-        // ---- forward 1: w2[(e,j,i)][r] = sum_q w1[(e,i,r)][q] * B1[q][j] ---------------------------
-        {
-            T u[F::PASS1][NM], acc[F::PASS1][NQ];
-            read_pencils<NM, F::PASS1, F::P1, NMP>(u, slab, lane);
-            contract<NM, NQ, F::PASS1, BMODE>(u, acc, b1);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < F::PASS1; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= F::P1 || t < F::P1)
-                {
-                    const int e = t / (NQ * NM), ir = t - e * (NQ * NM), i = ir / NM, r = ir - i * NM;
-                    T *dst = slab + (e * NQ2 + i) * NMP + r;
-#pragma unroll
-                    for (int j = 0; j < NQ; ++j)
-                        dst[j * NQ * NMP] = acc[s][j];
-                }
-            }
-            wave_lds_fence();
-        }
+#include "frag/chunk_fetch_next.inc"
+#include "frag/forward0_3d.inc"
+#include "frag/forward1_3d.inc"
         // ---- forward 2 and everything at the points: lane (e,j,i) keeps its k-pencil in registers ---
         {
-            T u[NPASS][NQ], f2[NPASS][NQ], acc[NPASS][NM];
-            {
-                T m[NPASS][NM];
-                read_pencils<NM, NPASS, NP, NMP>(m, slab, lane);
-                contract<NM, NQ, NPASS, BMODE>(m, u, b2);
-            }
-            wave_lds_fence(); // the forward images are dead: the point images take their place
-#pragma unroll
-            for (int s = 0; s < NPASS; ++s)
-                if (own[s])
-                {
-#pragma unroll
-                    for (int k = 0; k < NQ; ++k)
-                        imgU[colo[s] + k * PL] = u[s][k];
-                }
-            wave_lds_fence();
-            // du_2[k] = sum_m D2[k][m] u[m] in registers; du_0 into imgD; du_1 over u in imgU
-            contract_dot<NQ, NQ, NPASS, BMODE>(u, f2, d2);
-            image_sweep<NQ, NPASS, 1, BMODE, true>(imgU, imgD, bi, own, d0);
-            image_sweep<NQ, NPASS, NQP, BMODE, true>(imgU, imgU, bj, own, d1);
+            T u[NPASS][NQ], dreg[NPASS][NQ], acc[NPASS][NM];
+#include "frag/point_values_3d.inc"
             // ---- the walk over k: fluxes f_a = sum_b G_ab du_b, mass term (lambda w) u --------------
             {
                 T a0[2][NPASS], a1[2][NPASS];
@@ -299,10 +216,10 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_helmholtz_wave_kernel(
                     for (int s = 0; s < NPASS; ++s)
                     {
                         const T(&gg)[G::NCOMP] = gv[k % RING][s];
-                        const T x0 = a0[k % 2][s], x1 = a1[k % 2][s], x2 = f2[s][k];
+                        const T x0 = a0[k % 2][s], x1 = a1[k % 2][s], x2 = dreg[s][k];
                         const T f0 = fma_t(gg[2], x2, fma_t(gg[1], x1, gg[0] * x0));
                         const T f1 = fma_t(gg[4], x2, fma_t(gg[3], x1, gg[1] * x0));
-                        f2[s][k]   = fma_t(gg[5], x2, fma_t(gg[4], x1, gg[2] * x0));
+                        dreg[s][k] = fma_t(gg[5], x2, fma_t(gg[4], x1, gg[2] * x0)); // f_2
                         u[s][k]    = HASW ? (lam * wv[k % RING][s]) * u[s][k] : T(0);
                         if (own[s])
                         {
@@ -316,78 +233,16 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_helmholtz_wave_kernel(
                     __builtin_amdgcn_sched_barrier(0); // the ring stays a ring: no load moves up across a slice
                 }
             }
-            wave_lds_fence();
-            // D_2^T f_2 in registers, D_0^T f_0 and D_1^T f_1 in place in the images
-            T t2[NPASS][NQ];
-            contract<NQ, NQ, NPASS, BMODE>(f2, t2, d2);
-            image_sweep<NQ, NPASS, 1, BMODE, false>(imgD, imgD, bi, own, d0);
-            image_sweep<NQ, NPASS, NQP, BMODE, false>(imgU, imgU, bj, own, d1);
+#include "frag/deriv_transposed_3d.inc"
 #pragma unroll
             for (int s = 0; s < NPASS; ++s)
 #pragma unroll
                 for (int k = 0; k < NQ; ++k)
                     u[s][k] = ((u[s][k] + imgD[colo[s] + k * PL]) + imgU[colo[s] + k * PL]) + t2[s][k];
-            // ---- transposed 2: t2[(e,r',i)][j] = sum_k v[k] * B2[r'][k] ------------------------------
-            contract_dot<NQ, NM, NPASS, BMODE>(u, acc, b2);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < NPASS; ++s)
-            {
-                const int t = s * kWave + lane;
-                if (own[s])
-                {
-                    const int e = t / NQ2, ji = t - e * NQ2, j = ji / NQ, i = ji - j * NQ;
-                    T *dst = slab + (e * NM * NQ + i) * NQP + j;
-#pragma unroll
-                    for (int r = 0; r < NM; ++r)
-                        dst[r * NQ * NQP] = acc[s][r];
-                }
-            }
-            wave_lds_fence();
+#include "frag/transposed_last_3d.inc"
         }
-        // ---- transposed 1: t1[(e,r',q')][i] = sum_j t2[(e,r',i)][j] * B1[q'][j] --------------------
-        {
-            T u[M::PASST2][NQ], acc[M::PASST2][NM];
-            read_pencils<NQ, M::PASST2, M::PT2, NQP>(u, slab, lane);
-            contract_dot<NQ, NM, M::PASST2, BMODE>(u, acc, b1);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < M::PASST2; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= M::PT2 || t < M::PT2)
-                {
-                    const int er = t / NQ, i = t - er * NQ; // er = e*NM + r'
-                    T *dst = slab + er * NM * NQP + i;
-#pragma unroll
-                    for (int q = 0; q < NM; ++q)
-                        dst[q * NQP] = acc[s][q];
-                }
-            }
-            wave_lds_fence();
-        }
-        // ---- transposed 0: out[e][r'][q'][p'] = sum_i t1[(e,r',q')][i] * B0[p'][i] -----------------
-        {
-            T u[M::PASST1][NQ], acc[M::PASST1][NM];
-            read_pencils<NQ, M::PASST1, M::PT1, NQP>(u, slab, lane);
-            contract_dot<NQ, NM, M::PASST1, BMODE>(u, acc, b0);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < M::PASST1; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= M::PT1 || t < M::PT1)
-                {
-                    T *dst = slab + t * NM; // t = (e*NM + r')*NM + q'
-#pragma unroll
-                    for (int p = 0; p < NM; ++p)
-                        dst[p] = acc[s][p];
-                }
-            }
-            wave_lds_fence();
-            chunk_flush<IO, !(MEMF & 2), (MEMF & 8) != 0>(slab, out + c * (uint64_t)M::OUT_DBL, evalid * G::F::NMT, lane);
-            wave_lds_fence(); // slab is rewritten by the next chunk's staging
-        }
+#include "frag/transposed1_3d.inc"
+#include "frag/transposed0.inc"
     }
 }
 
@@ -409,46 +264,18 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_helmholtz_wave_kernel(
     constexpr int ES = NQ * NQP; // element stride of the point image
     static_assert(KMAP > 0, "short-lived waves only");
 
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wib  = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    T *slab        = reinterpret_cast<T *>(lds_raw) + wib * G::SLAB;
-    T *imgU        = slab; // u, then du_0, f_0, D_0^T f_0
-
-    const uint64_t nchunk = (nelmt + EC - 1) / EC;
-    const ChunkIter it    = chunk_iter<KMAP, WPB, ((MEMF >> 4) & 0xfff)>(nchunk, wib);
-    if (it.count == 0)
-        return;
-
-    // the two roles of a lane per pass: column (e,i) walking j, pencil (e,j) over i
-    bool own[NPASS];
-    int colp[NPASS], colo[NPASS], ecol[NPASS], bi[NPASS];
-#pragma unroll
-    for (int s = 0; s < NPASS; ++s)
-    {
-        const int t  = s * kWave + lane;
-        own[s]       = (s + 1) * kWave <= NP || t < NP;
-        const int tc = own[s] ? t : NP - 1;
-        const int e = tc / NQ, b = tc - e * NQ;
-        ecol[s] = e;
-        colp[s] = b;          // i: offset inside a row of g / w
-        colo[s] = e * ES + b; // (e,i): offset of the column's j = 0 point in the image, stride NQP
-        bi[s]   = tc * NQP;   // (e,j): its i-pencil
-    }
-
-    constexpr bool AL = (MEMF & 4) && IO::ALIGN_OK;
-    typename IO::Vec st[IO::NLD];
-    chunk_fetch<IO, EC, !(MEMF & 1), AL>(st, in, it.first, nelmt, lane);
+#include "frag/wave_slab.inc"
+    T *imgU = slab; // u, then du_0, f_0, D_0^T f_0
+#include "frag/wave_chunks.inc"
+#include "frag/lane_roles_2d.inc"
+#include "frag/chunk_fetch_first.inc"
 
     uint64_t c = it.first;
     for (uint64_t n = 0; n < it.count; ++n, c += it.step)
     {
-        const uint64_t left = nelmt - c * EC;
-        const int evalid    = left >= EC ? EC : (int)left;
-
-        chunk_stage<IO, AL>(st, slab, lane,
-                            IO::VEC2 ? (AL ? align_shift(in + c * IO::IN_DBL) : 0) : line_offset<T>(in + c * IO::IN_DBL));
-        wave_lds_fence();
+#include "frag/chunk_head.inc"
+#include "frag/chunk_stage.inc"
+        // the metric ring, as in the 3D kernel
         const T *gc = g + c * (uint64_t)(EC * G::NCOMP * NQT);
         const T *wc = HASW ? w + c * (uint64_t)(EC * NQT) : nullptr;
         int goff[NPASS], woff[NPASS];
@@ -463,51 +290,12 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_helmholtz_wave_kernel(
 #pragma unroll
         for (int r = 0; r < RING; ++r)
             load_metric_slice<NPASS, G::NCOMP, NQ, NQT, HASW>(gv[r], wv[r], gc, wc, goff, woff, r);
-        if (n + 1 < it.count)
-            chunk_fetch<IO, EC, !(MEMF & 1), AL>(st, in, c + it.step, nelmt, lane);
-
-        // ---- forward 0: w1[(e,i)][q] = sum_p in[(e,q)][p] * B0[p][i] -------------------------------
-        {
-            T u[F::PASS0][NM], acc[F::PASS0][NQ];
-            read_pencils<NM, F::PASS0, F::P0, F::IN_STRIDE>(u, slab, lane);
-            contract<NM, NQ, F::PASS0, BMODE>(u, acc, b0);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < F::PASS0; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= F::P0 || t < F::P0)
-                {
-                    const int e = t / NM, q = t - e * NM;
-                    T *dst = slab + e * NQ * NMP + q;
-#pragma unroll
-                    for (int i = 0; i < NQ; ++i)
-                        dst[i * NMP] = acc[s][i];
-                }
-            }
-            wave_lds_fence();
-        }
+#include "frag/chunk_fetch_next.inc"
+#include "frag/forward0_2d.inc"
         // ---- forward 1 and everything at the points: lane (e,i) keeps its j-pencil in registers -----
         {
-            T u[NPASS][NQ], f1[NPASS][NQ], acc[NPASS][NM];
-            {
-                T m[NPASS][NM];
-                read_pencils<NM, NPASS, NP, NMP>(m, slab, lane);
-                contract<NM, NQ, NPASS, BMODE>(m, u, b1);
-            }
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < NPASS; ++s)
-                if (own[s])
-                {
-#pragma unroll
-                    for (int j = 0; j < NQ; ++j)
-                        imgU[colo[s] + j * NQP] = u[s][j];
-                }
-            wave_lds_fence();
-            // du_1[j] = sum_m D1[j][m] u[m] in registers; du_0 over u in the image
-            contract_dot<NQ, NQ, NPASS, BMODE>(u, f1, d1);
-            image_sweep<NQ, NPASS, 1, BMODE, true>(imgU, imgU, bi, own, d0);
+            T u[NPASS][NQ], dreg[NPASS][NQ], acc[NPASS][NM];
+#include "frag/point_values_2d.inc"
             // ---- the walk over j ----------------------------------------------------------------------
             {
                 T a0[2][NPASS];
@@ -527,9 +315,9 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_helmholtz_wave_kernel(
                     for (int s = 0; s < NPASS; ++s)
                     {
                         const T(&gg)[G::NCOMP] = gv[j % RING][s];
-                        const T x0 = a0[j % 2][s], x1 = f1[s][j];
+                        const T x0 = a0[j % 2][s], x1 = dreg[s][j];
                         const T f0 = fma_t(gg[1], x1, gg[0] * x0);
-                        f1[s][j]   = fma_t(gg[2], x1, gg[1] * x0);
+                        dreg[s][j] = fma_t(gg[2], x1, gg[1] * x0); // f_1
                         u[s][j]    = HASW ? (lam * wv[j % RING][s]) * u[s][j] : T(0);
                         if (own[s])
                             imgU[colo[s] + j * NQP] = f0;
@@ -540,55 +328,15 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_helmholtz_wave_kernel(
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            wave_lds_fence();
-            T t1[NPASS][NQ];
-            contract<NQ, NQ, NPASS, BMODE>(f1, t1, d1);
-            image_sweep<NQ, NPASS, 1, BMODE, false>(imgU, imgU, bi, own, d0);
+#include "frag/deriv_transposed_2d.inc"
 #pragma unroll
             for (int s = 0; s < NPASS; ++s)
 #pragma unroll
                 for (int j = 0; j < NQ; ++j)
                     u[s][j] = (u[s][j] + imgU[colo[s] + j * NQP]) + t1[s][j];
-            // ---- transposed 1: t1[(e,q')][i] = sum_j v[j] * B1[q'][j] --------------------------------
-            contract_dot<NQ, NM, NPASS, BMODE>(u, acc, b1);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < NPASS; ++s)
-            {
-                const int t = s * kWave + lane;
-                if (own[s])
-                {
-                    const int e = t / NQ, i = t - e * NQ;
-                    T *dst = slab + e * NM * NQP + i;
-#pragma unroll
-                    for (int q = 0; q < NM; ++q)
-                        dst[q * NQP] = acc[s][q];
-                }
-            }
-            wave_lds_fence();
+#include "frag/transposed_last_2d.inc"
         }
-        // ---- transposed 0: out[e][q'][p'] = sum_i t1[(e,q')][i] * B0[p'][i] ------------------------
-        {
-            T u[M::PASST1][NQ], acc[M::PASST1][NM];
-            read_pencils<NQ, M::PASST1, M::PT1, NQP>(u, slab, lane);
-            contract_dot<NQ, NM, M::PASST1, BMODE>(u, acc, b0);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < M::PASST1; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= M::PT1 || t < M::PT1)
-                {
-                    T *dst = slab + t * NM; // t = e*NM + q'
-#pragma unroll
-                    for (int p = 0; p < NM; ++p)
-                        dst[p] = acc[s][p];
-                }
-            }
-            wave_lds_fence();
-            chunk_flush<IO, !(MEMF & 2), (MEMF & 8) != 0>(slab, out + c * (uint64_t)M::OUT_DBL, evalid * G::F::NMT, lane);
-            wave_lds_fence();
-        }
+#include "frag/transposed0.inc"
     }
 }
 

@@ -8,14 +8,13 @@
 // sum here runs over the ROW index a), w one plane per element as in sf_mass_*, f_a d separate point arrays in the
 // BwdTrans output layout (what sf_physderiv_* writes), out nm^d modes per element (the layout of sf_iproduct_*).
 //
-// COPY NOTE.  This is a fourth copy of Helmholtz text (after helmholtz_wave.h itself, affine_wave.h and
-// physderiv_wave.h): the lane roles, the walk over a ring of planes, and everything after the walk -- the transposed
-// derivative steps, the three transposed sweeps and chunk_flush -- are the text of the back half of
-// hex_helmholtz_wave_kernel / quad_helmholtz_wave_kernel.  A change to that back half has to be made here too.  The
-// existing kernels were not refactored to share it: DESIGN s9 item 7 records why helpers changed their code.
-// HelmGeom, image_sweep and the pencil helpers are those of helmholtz_wave.h.
+// Shared text.  The lane roles and everything after the walk -- the transposed derivative steps, the three transposed
+// sweeps and chunk_flush -- are the back half of the Helmholtz kernels, the same text: csrc/frag/*.inc, included in
+// place (helmholtz_wave.h lists the sequence; here it is wave_slab, [imgU, imgD], wave_chunks, lane_roles | per chunk:
+// chunk_head, [the ring and the walk], deriv_transposed, [the sum of step 3], transposed_last, transposed1 (3D),
+// transposed0).  HelmGeom, image_sweep and the pencil helpers are those of helmholtz_wave.h.
 //
-// What is new: a kernel with NO front half (there are no modes to read: no chunk_fetch / chunk_stage, no forward
+// This header's own: a kernel with NO front half (there are no modes to read: no chunk_fetch / chunk_stage, no forward
 // sweeps), d input streams, and a ring that carries the inputs as well as the metric.
 //
 // Order of operations (it defines the rounding; every sum in ascending index, the first product a multiply, then FMAs):
@@ -94,40 +93,16 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_iprodderiv_wave_kernel(
     constexpr int PL = NQ * NQP, ES = NQ * PL; // plane and element stride of a point image
     static_assert(KMAP > 0, "short-lived waves only");
 
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wib  = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    T *slab        = reinterpret_cast<T *>(lds_raw) + wib * G::SLAB;
-    T *imgU        = slab;          // g_1, then D_1^T g_1
-    T *imgD        = slab + G::IMG; // g_0, then D_0^T g_0
-
-    const uint64_t nchunk = (nelmt + EC - 1) / EC;
-    const ChunkIter it    = chunk_iter<KMAP, WPB, ((MEMF >> 4) & 0xfff)>(nchunk, wib);
-    if (it.count == 0)
-        return;
-
-    // the three roles of a lane per pass: column (e,j,i) walking k, pencil (e,k,j) over i, pencil (e,k,i) over j
-    bool own[NPASS];
-    int colp[NPASS], colo[NPASS], ecol[NPASS], bi[NPASS], bj[NPASS];
-#pragma unroll
-    for (int s = 0; s < NPASS; ++s)
-    {
-        const int t  = s * kWave + lane;
-        own[s]       = (s + 1) * kWave <= NP || t < NP;
-        const int tc = own[s] ? t : NP - 1;
-        const int e = tc / NQ2, ab = tc - e * NQ2, a = ab / NQ, b = ab - a * NQ;
-        ecol[s] = e;
-        colp[s] = ab;                   // (j,i): offset inside a plane of in_a / df / w
-        colo[s] = e * ES + a * NQP + b; // (e,j,i): offset of the column's k = 0 point in an image
-        bi[s]   = tc * NQP;             // (e,k,j): its i-pencil
-        bj[s]   = e * ES + a * PL + b;  // (e,k,i): its j-pencil, stride NQP
-    }
+#include "frag/wave_slab.inc"
+    T *imgU = slab;          // g_1, then D_1^T g_1
+    T *imgD = slab + G::IMG; // g_0, then D_0^T g_0
+#include "frag/wave_chunks.inc"
+#include "frag/lane_roles_3d.inc"
 
     uint64_t c = it.first;
     for (uint64_t n = 0; n < it.count; ++n, c += it.step)
     {
-        const uint64_t left = nelmt - c * EC;
-        const int evalid    = left >= EC ? EC : (int)left;
+#include "frag/chunk_head.inc"
 
         // the ring: inputs, df and w of the first slices
         const T *const fc[3] = {in0 + c * (uint64_t)(EC * NQT), in1 + c * (uint64_t)(EC * NQT),
@@ -149,7 +124,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_iprodderiv_wave_kernel(
             load_ipd_slice<NPASS, 3, NQ2, NQT, HASDF, HASW>(fv[r], dv[r], wv[r], fc, dc, wc, foff, doff, r);
 
         {
-            T u[NPASS][NQ], g2[NPASS][NQ], acc[NPASS][NM];
+            T u[NPASS][NQ], dreg[NPASS][NQ], acc[NPASS][NM];
             // ---- the walk over k: t_b = sum_a df_ab f_a, g_b = w t_b --------------------------------
 #pragma unroll
             for (int k = 0; k < NQ; ++k)
@@ -171,7 +146,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_iprodderiv_wave_kernel(
                         const T ww = wv[k % RING][s];
                         t0 = ww * t0, t1 = ww * t1, t2 = ww * t2;
                     }
-                    g2[s][k] = t2;
+                    dreg[s][k] = t2; // g_2
                     if (own[s])
                     {
                         imgD[colo[s] + k * PL] = t0;
@@ -183,78 +158,16 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_iprodderiv_wave_kernel(
                                                                     foff, doff, k + RING);
                 __builtin_amdgcn_sched_barrier(0); // the ring stays a ring: no load moves up across a slice
             }
-            wave_lds_fence();
-            // D_2^T g_2 in registers, D_0^T g_0 and D_1^T g_1 in place in the images
-            T t2[NPASS][NQ];
-            contract<NQ, NQ, NPASS, BMODE>(g2, t2, d2);
-            image_sweep<NQ, NPASS, 1, BMODE, false>(imgD, imgD, bi, own, d0);
-            image_sweep<NQ, NPASS, NQP, BMODE, false>(imgU, imgU, bj, own, d1);
+#include "frag/deriv_transposed_3d.inc"
 #pragma unroll
             for (int s = 0; s < NPASS; ++s)
 #pragma unroll
                 for (int k = 0; k < NQ; ++k)
                     u[s][k] = (imgD[colo[s] + k * PL] + imgU[colo[s] + k * PL]) + t2[s][k];
-            // ---- transposed 2: t2[(e,r',i)][j] = sum_k v[k] * B2[r'][k] ------------------------------
-            contract_dot<NQ, NM, NPASS, BMODE>(u, acc, b2);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < NPASS; ++s)
-            {
-                const int t = s * kWave + lane;
-                if (own[s])
-                {
-                    const int e = t / NQ2, ji = t - e * NQ2, j = ji / NQ, i = ji - j * NQ;
-                    T *dst = slab + (e * NM * NQ + i) * NQP + j;
-#pragma unroll
-                    for (int r = 0; r < NM; ++r)
-                        dst[r * NQ * NQP] = acc[s][r];
-                }
-            }
-            wave_lds_fence();
+#include "frag/transposed_last_3d.inc"
         }
-        // ---- transposed 1: t1[(e,r',q')][i] = sum_j t2[(e,r',i)][j] * B1[q'][j] --------------------
-        {
-            T u[M::PASST2][NQ], acc[M::PASST2][NM];
-            read_pencils<NQ, M::PASST2, M::PT2, NQP>(u, slab, lane);
-            contract_dot<NQ, NM, M::PASST2, BMODE>(u, acc, b1);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < M::PASST2; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= M::PT2 || t < M::PT2)
-                {
-                    const int er = t / NQ, i = t - er * NQ; // er = e*NM + r'
-                    T *dst = slab + er * NM * NQP + i;
-#pragma unroll
-                    for (int q = 0; q < NM; ++q)
-                        dst[q * NQP] = acc[s][q];
-                }
-            }
-            wave_lds_fence();
-        }
-        // ---- transposed 0: out[e][r'][q'][p'] = sum_i t1[(e,r',q')][i] * B0[p'][i] -----------------
-        {
-            T u[M::PASST1][NQ], acc[M::PASST1][NM];
-            read_pencils<NQ, M::PASST1, M::PT1, NQP>(u, slab, lane);
-            contract_dot<NQ, NM, M::PASST1, BMODE>(u, acc, b0);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < M::PASST1; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= M::PT1 || t < M::PT1)
-                {
-                    T *dst = slab + t * NM; // t = (e*NM + r')*NM + q'
-#pragma unroll
-                    for (int p = 0; p < NM; ++p)
-                        dst[p] = acc[s][p];
-                }
-            }
-            wave_lds_fence();
-            chunk_flush<IO, !(MEMF & 2), (MEMF & 8) != 0>(slab, out + c * (uint64_t)M::OUT_DBL, evalid * G::F::NMT, lane);
-            wave_lds_fence(); // slab is rewritten by the next chunk's walk
-        }
+#include "frag/transposed1_3d.inc"
+#include "frag/transposed0.inc"
     }
 }
 
@@ -276,39 +189,17 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_iprodderiv_wave_kernel(
     constexpr int ES = NQ * NQP; // element stride of the point image
     static_assert(KMAP > 0, "short-lived waves only");
 
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wib  = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    T *slab        = reinterpret_cast<T *>(lds_raw) + wib * G::SLAB;
-    T *imgU        = slab; // g_0, then D_0^T g_0
-
-    const uint64_t nchunk = (nelmt + EC - 1) / EC;
-    const ChunkIter it    = chunk_iter<KMAP, WPB, ((MEMF >> 4) & 0xfff)>(nchunk, wib);
-    if (it.count == 0)
-        return;
-
-    // the two roles of a lane per pass: column (e,i) walking j, pencil (e,j) over i
-    bool own[NPASS];
-    int colp[NPASS], colo[NPASS], ecol[NPASS], bi[NPASS];
-#pragma unroll
-    for (int s = 0; s < NPASS; ++s)
-    {
-        const int t  = s * kWave + lane;
-        own[s]       = (s + 1) * kWave <= NP || t < NP;
-        const int tc = own[s] ? t : NP - 1;
-        const int e = tc / NQ, b = tc - e * NQ;
-        ecol[s] = e;
-        colp[s] = b;          // i: offset inside a row of in_a / df / w
-        colo[s] = e * ES + b; // (e,i): offset of the column's j = 0 point in the image, stride NQP
-        bi[s]   = tc * NQP;   // (e,j): its i-pencil
-    }
+#include "frag/wave_slab.inc"
+    T *imgU = slab; // g_0, then D_0^T g_0
+#include "frag/wave_chunks.inc"
+#include "frag/lane_roles_2d.inc"
 
     uint64_t c = it.first;
     for (uint64_t n = 0; n < it.count; ++n, c += it.step)
     {
-        const uint64_t left = nelmt - c * EC;
-        const int evalid    = left >= EC ? EC : (int)left;
+#include "frag/chunk_head.inc"
 
+        // the ring, as in the 3D kernel
         const T *const fc[2] = {in0 + c * (uint64_t)(EC * NQT), in1 + c * (uint64_t)(EC * NQT)};
         const T *dc          = HASDF ? df + c * (uint64_t)(EC * NCOMP * NQT) : nullptr;
         const T *wc          = HASW ? w + c * (uint64_t)(EC * NQT) : nullptr;
@@ -327,7 +218,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_iprodderiv_wave_kernel(
             load_ipd_slice<NPASS, 2, NQ, NQT, HASDF, HASW>(fv[r], dv[r], wv[r], fc, dc, wc, foff, doff, r);
 
         {
-            T u[NPASS][NQ], g1[NPASS][NQ], acc[NPASS][NM];
+            T u[NPASS][NQ], dreg[NPASS][NQ], acc[NPASS][NM];
             // ---- the walk over j ----------------------------------------------------------------------
 #pragma unroll
             for (int j = 0; j < NQ; ++j)
@@ -348,7 +239,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_iprodderiv_wave_kernel(
                         const T ww = wv[j % RING][s];
                         t0 = ww * t0, t1 = ww * t1;
                     }
-                    g1[s][j] = t1;
+                    dreg[s][j] = t1; // g_1
                     if (own[s])
                         imgU[colo[s] + j * NQP] = t0;
                 }
@@ -357,55 +248,15 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_iprodderiv_wave_kernel(
                                                                    foff, doff, j + RING);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            wave_lds_fence();
-            T t1[NPASS][NQ];
-            contract<NQ, NQ, NPASS, BMODE>(g1, t1, d1);
-            image_sweep<NQ, NPASS, 1, BMODE, false>(imgU, imgU, bi, own, d0);
+#include "frag/deriv_transposed_2d.inc"
 #pragma unroll
             for (int s = 0; s < NPASS; ++s)
 #pragma unroll
                 for (int j = 0; j < NQ; ++j)
                     u[s][j] = imgU[colo[s] + j * NQP] + t1[s][j];
-            // ---- transposed 1: t1[(e,q')][i] = sum_j v[j] * B1[q'][j] --------------------------------
-            contract_dot<NQ, NM, NPASS, BMODE>(u, acc, b1);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < NPASS; ++s)
-            {
-                const int t = s * kWave + lane;
-                if (own[s])
-                {
-                    const int e = t / NQ, i = t - e * NQ;
-                    T *dst = slab + e * NM * NQP + i;
-#pragma unroll
-                    for (int q = 0; q < NM; ++q)
-                        dst[q * NQP] = acc[s][q];
-                }
-            }
-            wave_lds_fence();
+#include "frag/transposed_last_2d.inc"
         }
-        // ---- transposed 0: out[e][q'][p'] = sum_i t1[(e,q')][i] * B0[p'][i] ------------------------
-        {
-            T u[M::PASST1][NQ], acc[M::PASST1][NM];
-            read_pencils<NQ, M::PASST1, M::PT1, NQP>(u, slab, lane);
-            contract_dot<NQ, NM, M::PASST1, BMODE>(u, acc, b0);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < M::PASST1; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= M::PT1 || t < M::PT1)
-                {
-                    T *dst = slab + t * NM; // t = e*NM + q'
-#pragma unroll
-                    for (int p = 0; p < NM; ++p)
-                        dst[p] = acc[s][p];
-                }
-            }
-            wave_lds_fence();
-            chunk_flush<IO, !(MEMF & 2), (MEMF & 8) != 0>(slab, out + c * (uint64_t)M::OUT_DBL, evalid * G::F::NMT, lane);
-            wave_lds_fence();
-        }
+#include "frag/transposed0.inc"
     }
 }
 

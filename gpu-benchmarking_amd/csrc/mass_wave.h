@@ -28,6 +28,18 @@
 //
 // LDS per chunk, 3D: 6 images (input, two forward intermediates, two transposed intermediates, output) against the 8 of
 // the two separate kernels.  The slab is the maximum over them and never exceeds the IProductWRTBase slab of the order.
+//
+// Shared text.  The front and the back of a fused wave kernel are the same text in every operator built on this one
+// (helmholtz_wave.h, affine_wave.h, physderiv_wave.h, iprodderiv_wave.h).  That text lives once, in csrc/frag/*.inc:
+// plain kernel-body text that a kernel #includes at the place it runs, so the compiler sees one body per kernel, as if
+// it were written out (helper functions changed the code of tuned instantiations, DESIGN s9 item 7).  Every fragment
+// opens with its contract: what it computes, the names it expects in scope and declares, the slab before and after.
+// The names the kernels agree on: G the geometry whose SLAB the wave owns, M the MassGeom (transposed half, output), F
+// the WaveGeom (forward half), IO the chunk I/O view; NP / NPASS the point columns per chunk and their passes.  A
+// kernel below reads as its own lines between the includes:
+//   wave_slab, wave_chunks, chunk_fetch_first | per chunk: chunk_head, chunk_stage, [the weight loads],
+//   chunk_fetch_next, forward0_{3d,2d}, forward1_3d, [last forward sweep, weight, first transposed sweep],
+//   transposed1_3d, transposed0 (which ends with chunk_flush and the closing fence).
 #pragma once
 
 #include "iproduct_wave.h"
@@ -103,104 +115,55 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_mass_wave_kernel(
     const T *__restrict__ b0, const T *__restrict__ b1, const T *__restrict__ b2, const T *__restrict__ w,
     const T *__restrict__ in, T *__restrict__ out, uint64_t nelmt)
 {
-    using G          = MassGeom<NQ, EC, 3, T>;
-    using F          = typename G::F;
-    using IO         = MassIo<G>;
-    constexpr int NM = G::NM, NMP = F::NMP, NQP = G::NQP, NM2 = NM * NM, NQ2 = NQ * NQ;
+    using M          = MassGeom<NQ, EC, 3, T>;
+    using G          = M; // the slab is the mass slab
+    using F          = typename M::F;
+    using IO         = MassIo<M>;
+    constexpr int NM = M::NM, NMP = F::NMP, NQP = M::NQP, NM2 = NM * NM, NQ2 = NQ * NQ;
+    constexpr int NPASS = F::PASS2, NP = F::P2; // the point columns (e,j,i)
     static_assert(OUTM == OUT_LDS, "the output (nm^3 per element) leaves through the LDS stream");
     static_assert(KMAP > 0, "short-lived waves only");
 
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wib  = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    T *slab        = reinterpret_cast<T *>(lds_raw) + wib * G::SLAB;
-
-    const uint64_t nchunk = (nelmt + EC - 1) / EC;
-    const ChunkIter it    = chunk_iter<KMAP, WPB, ((MEMF >> 4) & 0xfff)>(nchunk, wib);
-    if (it.count == 0)
-        return;
-
-    constexpr bool AL = (MEMF & 4) && IO::ALIGN_OK;
-    typename IO::Vec st[IO::NLD];
-    chunk_fetch<IO, EC, !(MEMF & 1), AL>(st, in, it.first, nelmt, lane);
+#include "frag/wave_slab.inc"
+#include "frag/wave_chunks.inc"
+#include "frag/chunk_fetch_first.inc"
 
     uint64_t c = it.first;
     for (uint64_t n = 0; n < it.count; ++n, c += it.step)
     {
-        const uint64_t left = nelmt - c * EC;
-        const int evalid    = left >= EC ? EC : (int)left;
-
-        chunk_stage<IO, AL>(st, slab, lane,
-                            IO::VEC2 ? (AL ? align_shift(in + c * IO::IN_DBL) : 0) : line_offset<T>(in + c * IO::IN_DBL));
-        wave_lds_fence();
+#include "frag/chunk_head.inc"
+#include "frag/chunk_stage.inc"
         // This chunk's weights, requested as soon as the staging registers are consumed: in flight under the three
         // forward sweeps.  (Requested above chunk_stage they would be waited for there: behind the conditional loads
         // hipcc no longer counts and emits s_waitcnt vmcnt(0) for the staging registers.)
-        T wv[F::PASS2][NQ];
-        load_weights<NQ, F::PASS2, F::P2, NQ2>(wv, w + c * (uint64_t)(EC * G::NQT), evalid, lane);
-        if (n + 1 < it.count)
-            chunk_fetch<IO, EC, !(MEMF & 1), AL>(st, in, c + it.step, nelmt, lane);
-
-        // ---- forward 0: w1[(e,i,r)][q] = sum_p in[(e,r,q)][p] * B0[p][i] ---------------------------
-        {
-            T u[F::PASS0][NM], acc[F::PASS0][NQ];
-            read_pencils<NM, F::PASS0, F::P0, F::IN_STRIDE>(u, slab, lane);
-            contract<NM, NQ, F::PASS0, BMODE>(u, acc, b0);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < F::PASS0; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= F::P0 || t < F::P0)
-                {
-                    const int e = t / NM2, rq = t - e * NM2, r = rq / NM, q = rq - r * NM;
-                    T *dst = slab + (e * NQ * NM + r) * NMP + q;
-#pragma unroll
-                    for (int i = 0; i < NQ; ++i)
-                        dst[i * NM * NMP] = acc[s][i];
-                }
-            }
-            wave_lds_fence();
-        }
-        // ---- forward 1: w2[(e,j,i)][r] = sum_q w1[(e,i,r)][q] * B1[q][j] ---------------------------
-        {
-            T u[F::PASS1][NM], acc[F::PASS1][NQ];
-            read_pencils<NM, F::PASS1, F::P1, NMP>(u, slab, lane);
-            contract<NM, NQ, F::PASS1, BMODE>(u, acc, b1);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < F::PASS1; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= F::P1 || t < F::P1)
-                {
-                    const int e = t / (NQ * NM), ir = t - e * (NQ * NM), i = ir / NM, r = ir - i * NM;
-                    T *dst = slab + (e * NQ2 + i) * NMP + r;
-#pragma unroll
-                    for (int j = 0; j < NQ; ++j)
-                        dst[j * NQ * NMP] = acc[s][j];
-                }
-            }
-            wave_lds_fence();
-        }
-        // ---- forward 2, weight, transposed 2: lane (e,j,i) keeps its k-pencil in registers ---------
+        T wv[NPASS][NQ];
+        load_weights<NQ, NPASS, NP, NQ2>(wv, w + c * (uint64_t)(EC * M::NQT), evalid, lane);
+#include "frag/chunk_fetch_next.inc"
+#include "frag/forward0_3d.inc"
+#include "frag/forward1_3d.inc"
+        // ---- at the points (forward 2, the weight, transposed 2): lane (e,j,i) keeps its k-pencil in registers ----
         //      v[k] = w[e][k][j][i] * sum_r w2[(e,j,i)][r] * B2[r][k];  t2[(e,r',i)][j] = sum_k v[k] * B2[r'][k]
         {
-            T u[F::PASS2][NM], v[F::PASS2][NQ], acc[F::PASS2][NM];
-            read_pencils<NM, F::PASS2, F::P2, NMP>(u, slab, lane);
-            contract<NM, NQ, F::PASS2, BMODE>(u, v, b2);
+            T u[NPASS][NQ], acc[NPASS][NM];
+            {
+                T m[NPASS][NM];
+                read_pencils<NM, NPASS, NP, NMP>(m, slab, lane);
+                contract<NM, NQ, NPASS, BMODE>(m, u, b2);
+            }
 #pragma unroll
-            for (int s = 0; s < F::PASS2; ++s)
+            for (int s = 0; s < NPASS; ++s)
 #pragma unroll
                 for (int k = 0; k < NQ; ++k)
-                    v[s][k] *= wv[s][k];
-            contract_dot<NQ, NM, F::PASS2, BMODE>(v, acc, b2);
+                    u[s][k] *= wv[s][k];
+            // The sweep of frag/transposed_last_3d.inc, written out: with its guard taken from an own[] array the assembly
+            // of 18 of the 52 mass instantiations changes (at nq 2 the pairing of the LDS stores).
+            contract_dot<NQ, NM, NPASS, BMODE>(u, acc, b2);
             wave_lds_fence();
 #pragma unroll
-            for (int s = 0; s < F::PASS2; ++s)
+            for (int s = 0; s < NPASS; ++s)
             {
                 const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= F::P2 || t < F::P2)
+                if ((s + 1) * kWave <= NP || t < NP)
                 {
                     const int e = t / NQ2, ji = t - e * NQ2, j = ji / NQ, i = ji - j * NQ;
                     T *dst = slab + (e * NM * NQ + i) * NQP + j;
@@ -211,49 +174,8 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_mass_wave_kernel(
             }
             wave_lds_fence();
         }
-        // ---- transposed 1: t1[(e,r',q')][i] = sum_j t2[(e,r',i)][j] * B1[q'][j] --------------------
-        {
-            T u[G::PASST2][NQ], acc[G::PASST2][NM];
-            read_pencils<NQ, G::PASST2, G::PT2, NQP>(u, slab, lane);
-            contract_dot<NQ, NM, G::PASST2, BMODE>(u, acc, b1);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < G::PASST2; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= G::PT2 || t < G::PT2)
-                {
-                    const int er = t / NQ, i = t - er * NQ; // er = e*NM + r'
-                    T *dst = slab + er * NM * NQP + i;
-#pragma unroll
-                    for (int q = 0; q < NM; ++q)
-                        dst[q * NQP] = acc[s][q];
-                }
-            }
-            wave_lds_fence();
-        }
-        // ---- transposed 0: out[e][r'][q'][p'] = sum_i t1[(e,r',q')][i] * B0[p'][i] -----------------
-        {
-            T u[G::PASST1][NQ], acc[G::PASST1][NM];
-            read_pencils<NQ, G::PASST1, G::PT1, NQP>(u, slab, lane);
-            contract_dot<NQ, NM, G::PASST1, BMODE>(u, acc, b0);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < G::PASST1; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= G::PT1 || t < G::PT1)
-                {
-                    T *dst = slab + t * NM; // t = (e*NM + r')*NM + q'
-#pragma unroll
-                    for (int p = 0; p < NM; ++p)
-                        dst[p] = acc[s][p];
-                }
-            }
-            wave_lds_fence();
-            chunk_flush<IO, !(MEMF & 2), (MEMF & 8) != 0>(slab, out + c * (uint64_t)G::OUT_DBL, evalid * G::NMT, lane);
-            wave_lds_fence(); // slab is rewritten by the next chunk's staging
-        }
+#include "frag/transposed1_3d.inc"
+#include "frag/transposed0.inc"
     }
 }
 
@@ -265,82 +187,52 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_mass_wave_kernel(
     const T *__restrict__ b0, const T *__restrict__ b1, const T *__restrict__ w, const T *__restrict__ in,
     T *__restrict__ out, uint64_t nelmt)
 {
-    using G          = MassGeom<NQ, EC, 2, T>;
-    using F          = typename G::F;
-    using IO         = MassIo<G>;
-    constexpr int NM = G::NM, NMP = F::NMP, NQP = G::NQP;
+    using M          = MassGeom<NQ, EC, 2, T>;
+    using G          = M; // the slab is the mass slab
+    using F          = typename M::F;
+    using IO         = MassIo<M>;
+    constexpr int NM = M::NM, NMP = F::NMP, NQP = M::NQP;
+    constexpr int NPASS = F::PASS1, NP = F::P1; // the point columns (e,i)
     static_assert(OUTM == OUT_LDS, "the output (nm^2 per element) leaves through the LDS stream");
     static_assert(KMAP > 0, "short-lived waves only");
 
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wib  = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    T *slab        = reinterpret_cast<T *>(lds_raw) + wib * G::SLAB;
-
-    const uint64_t nchunk = (nelmt + EC - 1) / EC;
-    const ChunkIter it    = chunk_iter<KMAP, WPB, ((MEMF >> 4) & 0xfff)>(nchunk, wib);
-    if (it.count == 0)
-        return;
-
-    constexpr bool AL = (MEMF & 4) && IO::ALIGN_OK;
-    typename IO::Vec st[IO::NLD];
-    chunk_fetch<IO, EC, !(MEMF & 1), AL>(st, in, it.first, nelmt, lane);
+#include "frag/wave_slab.inc"
+#include "frag/wave_chunks.inc"
+#include "frag/chunk_fetch_first.inc"
 
     uint64_t c = it.first;
     for (uint64_t n = 0; n < it.count; ++n, c += it.step)
     {
-        const uint64_t left = nelmt - c * EC;
-        const int evalid    = left >= EC ? EC : (int)left;
-
-        chunk_stage<IO, AL>(st, slab, lane,
-                            IO::VEC2 ? (AL ? align_shift(in + c * IO::IN_DBL) : 0) : line_offset<T>(in + c * IO::IN_DBL));
-        wave_lds_fence();
+#include "frag/chunk_head.inc"
+#include "frag/chunk_stage.inc"
         // this chunk's weights (after the staging registers are consumed, see the 3D kernel): lane (e,i) takes
         // w[e][j][i], j = 0 .. nq-1
-        T wv[F::PASS1][NQ];
-        load_weights<NQ, F::PASS1, F::P1, NQ>(wv, w + c * (uint64_t)(EC * G::NQT), evalid, lane);
-        if (n + 1 < it.count)
-            chunk_fetch<IO, EC, !(MEMF & 1), AL>(st, in, c + it.step, nelmt, lane);
-
-        // ---- forward 0: w1[(e,i)][q] = sum_p in[(e,q)][p] * B0[p][i] -------------------------------
-        {
-            T u[F::PASS0][NM], acc[F::PASS0][NQ];
-            read_pencils<NM, F::PASS0, F::P0, F::IN_STRIDE>(u, slab, lane);
-            contract<NM, NQ, F::PASS0, BMODE>(u, acc, b0);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < F::PASS0; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= F::P0 || t < F::P0)
-                {
-                    const int e = t / NM, q = t - e * NM;
-                    T *dst = slab + e * NQ * NMP + q;
-#pragma unroll
-                    for (int i = 0; i < NQ; ++i)
-                        dst[i * NMP] = acc[s][i];
-                }
-            }
-            wave_lds_fence();
-        }
-        // ---- forward 1, weight, transposed 1: lane (e,i) keeps its j-pencil in registers -----------
+        T wv[NPASS][NQ];
+        load_weights<NQ, NPASS, NP, NQ>(wv, w + c * (uint64_t)(EC * M::NQT), evalid, lane);
+#include "frag/chunk_fetch_next.inc"
+#include "frag/forward0_2d.inc"
+        // ---- at the points (forward 1, the weight, transposed 1): lane (e,i) keeps its j-pencil in registers ----
         //      v[j] = w[e][j][i] * sum_q w1[(e,i)][q] * B1[q][j];  t1[(e,q')][i] = sum_j v[j] * B1[q'][j]
         {
-            T u[F::PASS1][NM], v[F::PASS1][NQ], acc[F::PASS1][NM];
-            read_pencils<NM, F::PASS1, F::P1, NMP>(u, slab, lane);
-            contract<NM, NQ, F::PASS1, BMODE>(u, v, b1);
+            T u[NPASS][NQ], acc[NPASS][NM];
+            {
+                T m[NPASS][NM];
+                read_pencils<NM, NPASS, NP, NMP>(m, slab, lane);
+                contract<NM, NQ, NPASS, BMODE>(m, u, b1);
+            }
 #pragma unroll
-            for (int s = 0; s < F::PASS1; ++s)
+            for (int s = 0; s < NPASS; ++s)
 #pragma unroll
                 for (int j = 0; j < NQ; ++j)
-                    v[s][j] *= wv[s][j];
-            contract_dot<NQ, NM, F::PASS1, BMODE>(v, acc, b1);
+                    u[s][j] *= wv[s][j];
+            // the sweep of frag/transposed_last_2d.inc, written out for the same reason as in the 3D kernel
+            contract_dot<NQ, NM, NPASS, BMODE>(u, acc, b1);
             wave_lds_fence();
 #pragma unroll
-            for (int s = 0; s < F::PASS1; ++s)
+            for (int s = 0; s < NPASS; ++s)
             {
                 const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= F::P1 || t < F::P1)
+                if ((s + 1) * kWave <= NP || t < NP)
                 {
                     const int e = t / NQ, i = t - e * NQ;
                     T *dst = slab + e * NM * NQP + i;
@@ -351,28 +243,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_mass_wave_kernel(
             }
             wave_lds_fence();
         }
-        // ---- transposed 0: out[e][q'][p'] = sum_i t1[(e,q')][i] * B0[p'][i] ------------------------
-        {
-            T u[G::PASST1][NQ], acc[G::PASST1][NM];
-            read_pencils<NQ, G::PASST1, G::PT1, NQP>(u, slab, lane);
-            contract_dot<NQ, NM, G::PASST1, BMODE>(u, acc, b0);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < G::PASST1; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= G::PT1 || t < G::PT1)
-                {
-                    T *dst = slab + t * NM; // t = e*NM + q'
-#pragma unroll
-                    for (int p = 0; p < NM; ++p)
-                        dst[p] = acc[s][p];
-                }
-            }
-            wave_lds_fence();
-            chunk_flush<IO, !(MEMF & 2), (MEMF & 8) != 0>(slab, out + c * (uint64_t)G::OUT_DBL, evalid * G::NMT, lane);
-            wave_lds_fence();
-        }
+#include "frag/transposed0.inc"
     }
 }
 

@@ -8,7 +8,9 @@
 // BwdTrans.  d output streams out_a[e][k][j][i] in that layout; no point image reaches HBM.  This is the front half of
 // the Helmholtz kernels (helmholtz_wave.h: chunk_fetch / chunk_stage, the forward sweeps, the derivative steps and a
 // per-point walk over a ring of planes) with a d x d matrix-vector product in the walk and stores in the place of the
-// transposed back half.  HelmGeom, image_sweep and the pencil helpers are those of helmholtz_wave.h.
+// transposed back half.  HelmGeom, image_sweep and the pencil helpers are those of helmholtz_wave.h; the front is the
+// same text, csrc/frag/*.inc, in the sequence helmholtz_wave.h lists up to point_values (dreg holds du_2; 2D: du_1).
+// This header's own: the df ring and the walk with its stores.
 //
 // Order of operations (it defines the rounding; every sum in ascending index, the first product a multiply, then FMAs):
 //   1. forward sweeps p -> i, q -> j, r -> k                                   (u, the point values)
@@ -70,48 +72,18 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_physderiv_wave_kernel(
     constexpr int PL = NQ * NQP, ES = NQ * PL; // plane and element stride of a point image
     static_assert(KMAP > 0, "short-lived waves only");
 
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wib  = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    T *slab        = reinterpret_cast<T *>(lds_raw) + wib * G::SLAB;
-    T *imgU        = slab;          // u, then du_1
-    T *imgD        = slab + G::IMG; // du_0
-
-    const uint64_t nchunk = (nelmt + EC - 1) / EC;
-    const ChunkIter it    = chunk_iter<KMAP, WPB, ((MEMF >> 4) & 0xfff)>(nchunk, wib);
-    if (it.count == 0)
-        return;
-
-    // the three roles of a lane per pass: column (e,j,i) walking k, pencil (e,k,j) over i, pencil (e,k,i) over j
-    bool own[NPASS];
-    int colp[NPASS], colo[NPASS], ecol[NPASS], bi[NPASS], bj[NPASS];
-#pragma unroll
-    for (int s = 0; s < NPASS; ++s)
-    {
-        const int t  = s * kWave + lane;
-        own[s]       = (s + 1) * kWave <= NP || t < NP;
-        const int tc = own[s] ? t : NP - 1;
-        const int e = tc / NQ2, ab = tc - e * NQ2, a = ab / NQ, b = ab - a * NQ;
-        ecol[s] = e;
-        colp[s] = ab;                   // (j,i): offset inside a plane of df / out_a
-        colo[s] = e * ES + a * NQP + b; // (e,j,i): offset of the column's k = 0 point in an image
-        bi[s]   = tc * NQP;             // (e,k,j): its i-pencil
-        bj[s]   = e * ES + a * PL + b;  // (e,k,i): its j-pencil, stride NQP
-    }
-
-    constexpr bool AL = (MEMF & 4) && IO::ALIGN_OK;
-    typename IO::Vec st[IO::NLD];
-    chunk_fetch<IO, EC, !(MEMF & 1), AL>(st, in, it.first, nelmt, lane);
+#include "frag/wave_slab.inc"
+    T *imgU = slab;          // u, then du_1
+    T *imgD = slab + G::IMG; // du_0
+#include "frag/wave_chunks.inc"
+#include "frag/lane_roles_3d.inc"
+#include "frag/chunk_fetch_first.inc"
 
     uint64_t c = it.first;
     for (uint64_t n = 0; n < it.count; ++n, c += it.step)
     {
-        const uint64_t left = nelmt - c * EC;
-        const int evalid    = left >= EC ? EC : (int)left;
-
-        chunk_stage<IO, AL>(st, slab, lane,
-                            IO::VEC2 ? (AL ? align_shift(in + c * IO::IN_DBL) : 0) : line_offset<T>(in + c * IO::IN_DBL));
-        wave_lds_fence();
+#include "frag/chunk_head.inc"
+#include "frag/chunk_stage.inc"
         // the df ring: the first slices, requested once the staging registers are consumed
         const T *dc = HASDF ? df + c * (uint64_t)(EC * NCOMP * NQT) : nullptr;
         int doff[NPASS], ooff[NPASS];
@@ -132,73 +104,13 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_physderiv_wave_kernel(
             for (int r = 0; r < RING; ++r)
                 load_df_slice<NPASS, NCOMP, NQ2, NQT>(dv[r], dc, doff, r);
         }
-        if (n + 1 < it.count)
-            chunk_fetch<IO, EC, !(MEMF & 1), AL>(st, in, c + it.step, nelmt, lane);
-
-        // ---- forward 0: w1[(e,i,r)][q] = sum_p in[(e,r,q)][p] * B0[p][i] ---------------------------
-        {
-            T u[F::PASS0][NM], acc[F::PASS0][NQ];
-            read_pencils<NM, F::PASS0, F::P0, F::IN_STRIDE>(u, slab, lane);
-            contract<NM, NQ, F::PASS0, BMODE>(u, acc, b0);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < F::PASS0; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= F::P0 || t < F::P0)
-                {
-                    const int e = t / NM2, rq = t - e * NM2, r = rq / NM, q = rq - r * NM;
-                    T *dst = slab + (e * NQ * NM + r) * NMP + q;
-#pragma unroll
-                    for (int i = 0; i < NQ; ++i)
-                        dst[i * NM * NMP] = acc[s][i];
-                }
-            }
-            wave_lds_fence();
-        }
-        // ---- forward 1: w2[(e,j,i)][r] = sum_q w1[(e,i,r)][q] * B1[q][j] ---------------------------
-        {
-            T u[F::PASS1][NM], acc[F::PASS1][NQ];
-            read_pencils<NM, F::PASS1, F::P1, NMP>(u, slab, lane);
-            contract<NM, NQ, F::PASS1, BMODE>(u, acc, b1);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < F::PASS1; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= F::P1 || t < F::P1)
-                {
-                    const int e = t / (NQ * NM), ir = t - e * (NQ * NM), i = ir / NM, r = ir - i * NM;
-                    T *dst = slab + (e * NQ2 + i) * NMP + r;
-#pragma unroll
-                    for (int j = 0; j < NQ; ++j)
-                        dst[j * NQ * NMP] = acc[s][j];
-                }
-            }
-            wave_lds_fence();
-        }
+#include "frag/chunk_fetch_next.inc"
+#include "frag/forward0_3d.inc"
+#include "frag/forward1_3d.inc"
         // ---- forward 2 and everything at the points: lane (e,j,i) keeps its k-pencil in registers ---
         {
-            T u[NPASS][NQ], du2[NPASS][NQ];
-            {
-                T m[NPASS][NM];
-                read_pencils<NM, NPASS, NP, NMP>(m, slab, lane);
-                contract<NM, NQ, NPASS, BMODE>(m, u, b2);
-            }
-            wave_lds_fence(); // the forward images are dead: the point images take their place
-#pragma unroll
-            for (int s = 0; s < NPASS; ++s)
-                if (own[s])
-                {
-#pragma unroll
-                    for (int k = 0; k < NQ; ++k)
-                        imgU[colo[s] + k * PL] = u[s][k];
-                }
-            wave_lds_fence();
-            // du_2[k] = sum_m D2[k][m] u[m] in registers; du_0 into imgD; du_1 over u in imgU
-            contract_dot<NQ, NQ, NPASS, BMODE>(u, du2, d2);
-            image_sweep<NQ, NPASS, 1, BMODE, true>(imgU, imgD, bi, own, d0);
-            image_sweep<NQ, NPASS, NQP, BMODE, true>(imgU, imgU, bj, own, d1);
+            T u[NPASS][NQ], dreg[NPASS][NQ];
+#include "frag/point_values_3d.inc"
             // ---- the walk over k: out_a = sum_b df_ab du_b, stored by the column's lane -------------
             T *o0 = out0 + c * (uint64_t)(EC * NQT), *o1 = out1 + c * (uint64_t)(EC * NQT),
               *o2 = out2 + c * (uint64_t)(EC * NQT);
@@ -224,7 +136,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_physderiv_wave_kernel(
 #pragma unroll
                 for (int s = 0; s < NPASS; ++s)
                 {
-                    const T x0 = a0[k % 2][s], x1 = a1[k % 2][s], x2 = du2[s][k];
+                    const T x0 = a0[k % 2][s], x1 = a1[k % 2][s], x2 = dreg[s][k];
                     T r0 = x0, r1 = x1, r2 = x2;
                     if constexpr (HASDF)
                     {
@@ -269,46 +181,18 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_physderiv_wave_kernel(
     constexpr int ES = NQ * NQP; // element stride of the point image
     static_assert(KMAP > 0, "short-lived waves only");
 
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wib  = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    T *slab        = reinterpret_cast<T *>(lds_raw) + wib * G::SLAB;
-    T *imgU        = slab; // u, then du_0
-
-    const uint64_t nchunk = (nelmt + EC - 1) / EC;
-    const ChunkIter it    = chunk_iter<KMAP, WPB, ((MEMF >> 4) & 0xfff)>(nchunk, wib);
-    if (it.count == 0)
-        return;
-
-    // the two roles of a lane per pass: column (e,i) walking j, pencil (e,j) over i
-    bool own[NPASS];
-    int colp[NPASS], colo[NPASS], ecol[NPASS], bi[NPASS];
-#pragma unroll
-    for (int s = 0; s < NPASS; ++s)
-    {
-        const int t  = s * kWave + lane;
-        own[s]       = (s + 1) * kWave <= NP || t < NP;
-        const int tc = own[s] ? t : NP - 1;
-        const int e = tc / NQ, b = tc - e * NQ;
-        ecol[s] = e;
-        colp[s] = b;          // i: offset inside a row of df / out_a
-        colo[s] = e * ES + b; // (e,i): offset of the column's j = 0 point in the image, stride NQP
-        bi[s]   = tc * NQP;   // (e,j): its i-pencil
-    }
-
-    constexpr bool AL = (MEMF & 4) && IO::ALIGN_OK;
-    typename IO::Vec st[IO::NLD];
-    chunk_fetch<IO, EC, !(MEMF & 1), AL>(st, in, it.first, nelmt, lane);
+#include "frag/wave_slab.inc"
+    T *imgU = slab; // u, then du_0
+#include "frag/wave_chunks.inc"
+#include "frag/lane_roles_2d.inc"
+#include "frag/chunk_fetch_first.inc"
 
     uint64_t c = it.first;
     for (uint64_t n = 0; n < it.count; ++n, c += it.step)
     {
-        const uint64_t left = nelmt - c * EC;
-        const int evalid    = left >= EC ? EC : (int)left;
-
-        chunk_stage<IO, AL>(st, slab, lane,
-                            IO::VEC2 ? (AL ? align_shift(in + c * IO::IN_DBL) : 0) : line_offset<T>(in + c * IO::IN_DBL));
-        wave_lds_fence();
+#include "frag/chunk_head.inc"
+#include "frag/chunk_stage.inc"
+        // the df ring, as in the 3D kernel
         const T *dc = HASDF ? df + c * (uint64_t)(EC * NCOMP * NQT) : nullptr;
         int doff[NPASS], ooff[NPASS];
         bool put[NPASS];
@@ -328,51 +212,12 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_physderiv_wave_kernel(
             for (int r = 0; r < RING; ++r)
                 load_df_slice<NPASS, NCOMP, NQ, NQT>(dv[r], dc, doff, r);
         }
-        if (n + 1 < it.count)
-            chunk_fetch<IO, EC, !(MEMF & 1), AL>(st, in, c + it.step, nelmt, lane);
-
-        // ---- forward 0: w1[(e,i)][q] = sum_p in[(e,q)][p] * B0[p][i] -------------------------------
-        {
-            T u[F::PASS0][NM], acc[F::PASS0][NQ];
-            read_pencils<NM, F::PASS0, F::P0, F::IN_STRIDE>(u, slab, lane);
-            contract<NM, NQ, F::PASS0, BMODE>(u, acc, b0);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < F::PASS0; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= F::P0 || t < F::P0)
-                {
-                    const int e = t / NM, q = t - e * NM;
-                    T *dst = slab + e * NQ * NMP + q;
-#pragma unroll
-                    for (int i = 0; i < NQ; ++i)
-                        dst[i * NMP] = acc[s][i];
-                }
-            }
-            wave_lds_fence();
-        }
+#include "frag/chunk_fetch_next.inc"
+#include "frag/forward0_2d.inc"
         // ---- forward 1 and everything at the points: lane (e,i) keeps its j-pencil in registers -----
         {
-            T u[NPASS][NQ], du1[NPASS][NQ];
-            {
-                T m[NPASS][NM];
-                read_pencils<NM, NPASS, NP, NMP>(m, slab, lane);
-                contract<NM, NQ, NPASS, BMODE>(m, u, b1);
-            }
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < NPASS; ++s)
-                if (own[s])
-                {
-#pragma unroll
-                    for (int j = 0; j < NQ; ++j)
-                        imgU[colo[s] + j * NQP] = u[s][j];
-                }
-            wave_lds_fence();
-            // du_1[j] = sum_m D1[j][m] u[m] in registers; du_0 over u in the image
-            contract_dot<NQ, NQ, NPASS, BMODE>(u, du1, d1);
-            image_sweep<NQ, NPASS, 1, BMODE, true>(imgU, imgU, bi, own, d0);
+            T u[NPASS][NQ], dreg[NPASS][NQ];
+#include "frag/point_values_2d.inc"
             // ---- the walk over j ----------------------------------------------------------------------
             T *o0 = out0 + c * (uint64_t)(EC * NQT), *o1 = out1 + c * (uint64_t)(EC * NQT);
             T a0[2][NPASS];
@@ -391,7 +236,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_physderiv_wave_kernel(
 #pragma unroll
                 for (int s = 0; s < NPASS; ++s)
                 {
-                    const T x0 = a0[j % 2][s], x1 = du1[s][j];
+                    const T x0 = a0[j % 2][s], x1 = dreg[s][j];
                     T r0 = x0, r1 = x1;
                     if constexpr (HASDF)
                     {

@@ -77,7 +77,7 @@ def main():
     ap.add_argument("units", nargs="*")
     ap.add_argument("--identical", action="store_true")
     ap.add_argument("-j", type=int, default=8)
-    a = ap.parse_args()
+    a = ap.parse_intermixed_args()  # unit names may follow the flags
     units = a.units or sorted(os.path.basename(p) for p in glob.glob(os.path.join(a.new, "csrc", "*.hip")))
     with concurrent.futures.ThreadPoolExecutor(a.j) as pool:
         jobs = {(t, u): pool.submit(kernels_of, t, u) for u in units for t in (a.parent, a.new)}
