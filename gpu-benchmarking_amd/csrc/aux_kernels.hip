@@ -480,7 +480,15 @@ struct CounterRing
     std::vector<std::pair<hipStream_t, unsigned>> eager; // stream -> slot (per-thread streams: one slot per launch)
 };
 static CounterRing g_counters[64];
-static std::mutex g_counter_mu;
+static std::mutex g_counter_mu;        // covers the rings
+static std::mutex g_counter_unit_mu[64]; // per device: one launch's acquire + reset + kernel (taken before g_counter_mu)
+
+std::mutex &counter_mutex()
+{
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    return g_counter_unit_mu[dev >= 0 && dev < 64 ? dev : 0];
+}
 
 int counter_acquire(hipStream_t s, unsigned long long **out)
 {
@@ -529,6 +537,7 @@ int counter_acquire(hipStream_t s, unsigned long long **out)
 // sf_shutdown(): graphs captured earlier must not be replayed afterwards
 int release_counters()
 {
+    std::lock_guard<std::mutex> unit(counter_mutex()); // no launch is between its acquire and its kernel
     std::lock_guard<std::mutex> lock(g_counter_mu);
     int dev = 0;
     (void)hipGetDevice(&dev);

@@ -128,13 +128,22 @@ inline int launch_quad_mfma4_impl(const QuadArgs &a, hipStream_t s)
     static_assert(lds <= 160 * 1024, "LDS slab exceeds 160 KiB");
     static_assert(DYNB == 0 || KMAP == 0, "the batch counter feeds a persistent grid");
     unsigned long long *ctr = nullptr;
+    std::unique_lock<std::mutex> unit; // held from the acquire to the launch of the kernel that draws from the counter
     if constexpr (DYNB > 0)
     {
+        // acquire + reset + launch are one enqueue unit (as scratch and launch are in bwdtrans_generic.hip): eager
+        // launches on a stream share that stream's counter, so two host threads on one stream that enqueued reset,
+        // reset, kernel, kernel would leave the second kernel a drained counter -- every wave draws "no batch" and the
+        // output is never written
+        unit = std::unique_lock<std::mutex>(counter_mutex());
         // the batch counter comes from the device's counter ring (never evicted: a pointer baked into a captured graph
         // stays valid until sf_shutdown); no counter to be had (ring exhausted, or first use inside a capture) -> the
         // same kernel with a fixed share per wave
         if (counter_acquire(s, &ctr) != SF_OK)
+        {
+            unit.unlock();
             return launch_quad_mfma4_impl<NQ, EB, WPB, MINW, GJ, KMAP, XG, SHB, 0, PEEL, SPLIT, 0>(a, s);
+        }
         // zeroed by a one-thread kernel, not a memset: under stream capture a memset node on a pointer INSIDE an
         // allocation did not zero the counter on ROCm 7.2 (the replayed grid then saw a stale ticket and exited)
         counter_reset_kernel<<<1, 8, 0, s>>>(ctr);

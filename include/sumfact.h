@@ -21,14 +21,17 @@
  *   - return value: 0 on success, a positive hipError_t, or a negative SF_E* code.  The reference
  *     reports no errors at all; nothing here aborts the process;
  *   - thread / stream safety: every entry point may be called concurrently from several host threads and on several
- *     streams of a device (sf_set_launch_hint is per calling thread).  The library's internal device memory:
+ *     streams of a device (sf_set_launch_hint is per calling thread).  Several host threads may launch on the SAME
+ *     stream (the null stream included): what one call enqueues around the library's internal memory (scratch, batch
+ *     counter, the copy of a reduction's result) stays one unit on the stream, never interleaved with that of another
+ *     thread's call.  The library's internal device memory:
  *     (i) reduction partials of sf_sumsq_* and the intermediates of the any-extent fallback (at most 1 GiB, the grid
  *     is cut down to fit) live in a scratch buffer per (device, stream; per thread for hipStreamPerThread), allocated
  *     on the first call that needs it on that stream -- that FIRST call may not be inside a stream capture;
  *     (ii) the batch counters of the persistent 2D kernels (AUTO 2D nq 25..32) live in one 512 KiB buffer per device
  *     that is allocated once and freed only by sf_shutdown(): BwdTrans launches are capture-safe from the first call
- *     (kernel and memset nodes only; inside a capture that precedes the buffer's allocation the same kernel runs
- *     with a fixed share per wave instead), and a captured graph stays replayable until sf_shutdown().
+ *     (kernel nodes only -- a kernel zeroes the counter; inside a capture that precedes the buffer's allocation the
+ *     same kernel runs with a fixed share per wave instead), and a captured graph stays replayable until sf_shutdown().
  */
 #ifndef SUMFACT_H
 #define SUMFACT_H
