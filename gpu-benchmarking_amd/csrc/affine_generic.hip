@@ -65,15 +65,12 @@ __global__ __launch_bounds__(NT) void affine_generic_kernel(
 template <int DIM, typename T>
 int launch_affine_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const AffineArgsT<T> &x, hipStream_t s)
 {
-    if (!affine_generic_built(DIM, nq[0], nq[1], nq[2]))
-        return SF_ENOTBUILT;
-    if (a.nelmt == 0)
-        return SF_OK;
-    return launch_lds_class(helm_need(DIM, nq[0], nq[1], nq[2]) <= (unsigned)kHelmSmallCap,
-                            affine_generic_kernel<T, DIM, kHelmSmallCap, 64>,
-                            affine_generic_kernel<T, DIM, kHelmLargeCap, 256>, a.nelmt, s, a.b0, a.b1, basis2(a), x.d0, x.d1,
-                            x.d2, x.qw0, x.qw1, x.qw2, x.ge, x.je, x.lam, x.je != nullptr, a.in, a.out, a.nelmt,
-                            (int)nq[0], (int)nq[1], (int)nq[2]);
+    return launch_any_extent(affine_generic_built(DIM, nq[0], nq[1], nq[2]),
+                             helm_need(DIM, nq[0], nq[1], nq[2]) <= (unsigned)kHelmSmallCap,
+                             affine_generic_kernel<T, DIM, kHelmSmallCap, 64>,
+                             affine_generic_kernel<T, DIM, kHelmLargeCap, 256>, a.nelmt, s, a.b0, a.b1, basis2(a), x.d0,
+                             x.d1, x.d2, x.qw0, x.qw1, x.qw2, x.ge, x.je, x.lam, x.je != nullptr, a.in, a.out, a.nelmt,
+                             (int)nq[0], (int)nq[1], (int)nq[2]);
 }
 template int launch_affine_generic<3, double>(const unsigned (&)[3], const HexArgs &, const AffineArgsT<double> &,
                                               hipStream_t);

@@ -1,5 +1,17 @@
-// any_extent.h -- what the any-extent kernels of iproduct_generic.hip, mass_generic.hip and helmholtz_generic.hip share:
-// the scalar FMA, the ascending strided dot product of their sweeps, and the launch of one of their two LDS classes.
+// any_extent.h -- what the any-extent kernels of iproduct_generic.hip, mass_generic.hip, helmholtz_generic.h (with
+// helmholtz_generic.hip and affine_generic.hip), physderiv_generic.hip and iprodderiv_generic.hip share: the scalar FMA,
+// the ascending strided dot product of their sweeps, and the guarded launch of one of their two LDS classes.
+// The kernel text they share is in frag/ae_*.inc, #included in place (each fragment opens with its contract):
+//   ae_prologue.inc                      the element constants
+//   ae_forward_{2d,3d}.inc               modes staged, forward sweeps p -> i, q -> j, r -> k   (mass, Helmholtz, physderiv)
+//   ae_deriv_{2d,3d}.inc                 du_a of a point                                       (Helmholtz, physderiv)
+//   ae_deriv_transposed_{2d,3d}.inc      D_a^T of a point's terms                              (Helmholtz, iprodderiv)
+//   ae_transposed_{2d,3d}.inc            transposed sweeps k -> r', j -> q', i -> p'           (mass, Helmholtz, iprodderiv)
+// The names the kernels agree on, which the fragments take from the scope: T, DIM, NT; nq0 nq1 nq2; nm0 nm1 nm2, nz, n01,
+// nqt, nmt, tid (ae_prologue.inc); b0 b1 b2, d0 d1 d2; src, dst of the element; x, the index of a loop over points; P0 ..
+// P3, the point images of the derivative kernels.  The images of a sweep are parameters: AE_* macros that the kernel
+// defines just before the #include and the fragment undefines, so that a definition left out does not compile.
+// iproduct_generic.hip sweeps in the other order and keeps its own text; only its launch is shared.
 #pragma once
 
 #include "sf_dispatch.h"
@@ -25,11 +37,16 @@ template <typename T> __device__ __forceinline__ T dot_strided(const T *u, int u
     return a;
 }
 
-// One workgroup per element up to 2^22 of them (the kernels' grid-stride loop takes the rest): the instantiation of the
-// small LDS class with 64 threads when the images fit it, that of the large class with 256 otherwise.
+// The launch of every any-extent operator: extents that are not built answer SF_ENOTBUILT, an empty batch is done.
+// Otherwise one workgroup per element up to 2^22 of them (the kernels' grid-stride loop takes the rest): the
+// instantiation of the small LDS class with 64 threads when the images fit it, that of the large class with 256 otherwise.
 template <class KS, class KL, class... A>
-inline int launch_lds_class(bool small, KS small_kern, KL large_kern, uint64_t nelmt, hipStream_t s, A... args)
+inline int launch_any_extent(bool built, bool small, KS small_kern, KL large_kern, uint64_t nelmt, hipStream_t s, A... args)
 {
+    if (!built)
+        return SF_ENOTBUILT;
+    if (nelmt == 0)
+        return SF_OK;
     const unsigned grid = nelmt < (1ull << 22) ? (unsigned)nelmt : (1u << 22);
     if (small)
         small_kern<<<grid, 64, 0, s>>>(args...);

@@ -1,7 +1,9 @@
 // helmholtz_generic.h -- the any-extent kernel body of the fused Helmholtz operator, shared by helmholtz_generic.hip (a
 // metric per point) and affine_generic.hip (constants per element).  What the kernels do, their order of operations and
 // their LDS images are described at the top of those two units; the body is that of helmholtz_generic.hip with the
-// flux-and-mass step taken out into flux_points(), which asks a policy MET:
+// flux-and-mass step taken out into flux_points(), and its sweeps and derivative steps are the fragments frag/ae_*.inc
+// (listed in any_extent.h), which mass_generic.hip, physderiv_generic.hip and iprodderiv_generic.hip include as well.
+// flux_points() asks a policy MET:
 //   MET::SCALED, MET::NCOMP   the fluxes and the mass term carry a factor q per point; metric components per point
 //   element(e, nqt)           once per element
 //   coef(x, nqt, gg)          the NCOMP coefficients of point x, in the order of the planes of g
@@ -56,43 +58,26 @@ __device__ __forceinline__ void helm_generic_body(T *lds, const T *b0, const T *
                                                   const T *d2, MET &met, const T *in, T *out, uint64_t nelmt, int nq0,
                                                   int nq1, int nq2)
 {
-    const int nm0 = nq0 - 1, nm1 = nq1 - 1, nm2 = DIM == 3 ? nq2 - 1 : 1;
-    const int nz  = DIM == 3 ? nq2 : 1;
-    const int n01 = nq0 * nq1;
-    const int nqt = n01 * nz;        // points per element
-    const int nmt = nm0 * nm1 * nm2; // modes per element
+#include "frag/ae_prologue.inc"
     T *P0 = lds, *P1 = lds + nqt, *P2 = lds + 2 * nqt, *P3 = lds + (DIM == 3 ? 3 : 2) * nqt;
-    const int tid = threadIdx.x;
     for (uint64_t e = blockIdx.x; e < nelmt; e += gridDim.x)
     {
         const T *src = in + e * (uint64_t)nmt;
         T *dst       = out + e * (uint64_t)nmt;
         met.element(e, nqt);
-        for (int x = tid; x < nmt; x += NT)
-            P1[x] = src[x];
-        __syncthreads();
         if constexpr (DIM == 2)
         {
-            // forward 0: w1[q][i] = sum_p in[q][p] * B0[p][i]
-            for (int x = tid; x < nm1 * nq0; x += NT)
-            {
-                const int i = x % nq0, q = x / nq0;
-                P2[x] = dot_strided(P1 + q * nm0, 1, b0 + i, nq0, nm0);
-            }
-            __syncthreads();
-            // forward 1: u[j][i] = sum_q w1[q][i] * B1[q][j]
+#define AE_MODES P1
+#define AE_W1 P2
+#define AE_POINTS P0
+#define AE_POINT_VALUE(s) s
+#include "frag/ae_forward_2d.inc"
+            // du_a = D_a u, to P1 ..
             for (int x = tid; x < nqt; x += NT)
             {
-                const int i = x % nq0, j = x / nq0;
-                P0[x] = dot_strided(P2 + i, nq0, b1 + j, nq1, nm1);
-            }
-            __syncthreads();
-            // du_0[j][i] = sum_m D0[i][m] u[j][m];  du_1[j][i] = sum_m D1[j][m] u[m][i]
-            for (int x = tid; x < nqt; x += NT)
-            {
-                const int i = x % nq0, j = x / nq0;
-                P1[x] = dot_strided(P0 + j * nq0, 1, d0 + i * nq0, 1, nq0);
-                P2[x] = dot_strided(P0 + i, nq0, d1 + j * nq1, 1, nq1);
+#define AE_DU0 P1[x]
+#define AE_DU1 P2[x]
+#include "frag/ae_deriv_2d.inc"
             }
             __syncthreads();
             // fluxes in place, the mass term over u (every thread touches its own points only)
@@ -101,56 +86,29 @@ __device__ __forceinline__ void helm_generic_body(T *lds, const T *b0, const T *
             // v = ((lambda w) u + D_0^T f_0) + D_1^T f_1, over the mass term
             for (int x = tid; x < nqt; x += NT)
             {
-                const int i = x % nq0, j = x / nq0;
-                const T t0 = dot_strided(P1 + j * nq0, 1, d0 + i, nq0, nq0);
-                const T t1 = dot_strided(P2 + i, nq0, d1 + j, nq1, nq1);
-                P0[x]      = (P0[x] + t0) + t1;
+#include "frag/ae_deriv_transposed_2d.inc"
+                P0[x] = (P0[x] + t0) + t1;
             }
             __syncthreads();
-            // transposed 1: t1[q'][i] = sum_j v[j][i] * B1[q'][j]
-            for (int x = tid; x < nm1 * nq0; x += NT)
-            {
-                const int i = x % nq0, q = x / nq0;
-                P1[x] = dot_strided(P0 + i, nq0, b1 + q * nq1, 1, nq1);
-            }
-            __syncthreads();
-            // transposed 0: out[q'][p'] = sum_i t1[q'][i] * B0[p'][i]
-            for (int x = tid; x < nmt; x += NT)
-            {
-                const int p = x % nm0, q = x / nm0;
-                dst[x] = dot_strided(P1 + q * nq0, 1, b0 + p * nq0, 1, nq0);
-            }
+#define AE_POINTS P0
+#define AE_T1 P1
+#include "frag/ae_transposed_2d.inc"
         }
         else
         {
-            // forward 0: w1[r][q][i] = sum_p in[r][q][p] * B0[p][i]
-            for (int x = tid; x < nq0 * nm1 * nm2; x += NT)
-            {
-                const int i = x % nq0, rq = x / nq0;
-                P0[x] = dot_strided(P1 + rq * nm0, 1, b0 + i, nq0, nm0);
-            }
-            __syncthreads();
-            // forward 1: w2[r][j][i] = sum_q w1[r][q][i] * B1[q][j]
-            for (int x = tid; x < n01 * nm2; x += NT)
-            {
-                const int i = x % nq0, rj = x / nq0, j = rj % nq1, r = rj / nq1;
-                P1[x] = dot_strided(P0 + r * nm1 * nq0 + i, nq0, b1 + j, nq1, nm1);
-            }
-            __syncthreads();
-            // forward 2: u[k][j][i] = sum_r w2[r][j][i] * B2[r][k]
+#define AE_MODES P1
+#define AE_W1 P0
+#define AE_W2 P1
+#define AE_POINTS P0
+#define AE_POINT_VALUE(s) s
+#include "frag/ae_forward_3d.inc"
+            // du_a = D_a u, to P1 ..
             for (int x = tid; x < nqt; x += NT)
             {
-                const int ji = x % n01, k = x / n01;
-                P0[x] = dot_strided(P1 + ji, n01, b2 + k, nq2, nm2);
-            }
-            __syncthreads();
-            // du_0 = D0 u along i, du_1 = D1 u along j, du_2 = D2 u along k
-            for (int x = tid; x < nqt; x += NT)
-            {
-                const int i = x % nq0, kj = x / nq0, j = kj % nq1, k = kj / nq1;
-                P1[x] = dot_strided(P0 + kj * nq0, 1, d0 + i * nq0, 1, nq0);
-                P2[x] = dot_strided(P0 + k * n01 + i, nq0, d1 + j * nq1, 1, nq1);
-                P3[x] = dot_strided(P0 + j * nq0 + i, n01, d2 + k * nq2, 1, nq2);
+#define AE_DU0 P1[x]
+#define AE_DU1 P2[x]
+#define AE_DU2 P3[x]
+#include "frag/ae_deriv_3d.inc"
             }
             __syncthreads();
             // fluxes in place, the mass term over u (every thread touches its own points only)
@@ -159,33 +117,14 @@ __device__ __forceinline__ void helm_generic_body(T *lds, const T *b0, const T *
             // v = (((lambda w) u + D_0^T f_0) + D_1^T f_1) + D_2^T f_2, over the mass term
             for (int x = tid; x < nqt; x += NT)
             {
-                const int i = x % nq0, kj = x / nq0, j = kj % nq1, k = kj / nq1;
-                const T t0 = dot_strided(P1 + kj * nq0, 1, d0 + i, nq0, nq0);
-                const T t1 = dot_strided(P2 + k * n01 + i, nq0, d1 + j, nq1, nq1);
-                const T t2 = dot_strided(P3 + j * nq0 + i, n01, d2 + k, nq2, nq2);
-                P0[x]      = ((P0[x] + t0) + t1) + t2;
+#include "frag/ae_deriv_transposed_3d.inc"
+                P0[x] = ((P0[x] + t0) + t1) + t2;
             }
             __syncthreads();
-            // transposed 2: t1[r'][j][i] = sum_k v[k][j][i] * B2[r'][k]
-            for (int x = tid; x < n01 * nm2; x += NT)
-            {
-                const int ji = x % n01, r = x / n01;
-                P1[x] = dot_strided(P0 + ji, n01, b2 + r * nq2, 1, nq2);
-            }
-            __syncthreads();
-            // transposed 1: t2[r'][q'][i] = sum_j t1[r'][j][i] * B1[q'][j]
-            for (int x = tid; x < nq0 * nm1 * nm2; x += NT)
-            {
-                const int i = x % nq0, rq = x / nq0, q = rq % nm1, r = rq / nm1;
-                P2[x] = dot_strided(P1 + r * n01 + i, nq0, b1 + q * nq1, 1, nq1);
-            }
-            __syncthreads();
-            // transposed 0: out[r'][q'][p'] = sum_i t2[r'][q'][i] * B0[p'][i]
-            for (int x = tid; x < nmt; x += NT)
-            {
-                const int p = x % nm0, rq = x / nm0;
-                dst[x] = dot_strided(P2 + rq * nq0, 1, b0 + p * nq0, 1, nq0);
-            }
+#define AE_POINTS P0
+#define AE_T1 P1
+#define AE_T2 P2
+#include "frag/ae_transposed_3d.inc"
         }
         __syncthreads(); // the next element overwrites the images
     }

@@ -60,15 +60,12 @@ __global__ __launch_bounds__(NT) void helmholtz_generic_kernel(
 template <int DIM, typename T>
 int launch_helmholtz_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const HelmArgsT<T> &x, hipStream_t s)
 {
-    if (!helmholtz_generic_built(DIM, nq[0], nq[1], nq[2]))
-        return SF_ENOTBUILT;
-    if (a.nelmt == 0)
-        return SF_OK;
-    return launch_lds_class(helm_need(DIM, nq[0], nq[1], nq[2]) <= (unsigned)kHelmSmallCap,
-                            helmholtz_generic_kernel<T, DIM, kHelmSmallCap, 64>,
-                            helmholtz_generic_kernel<T, DIM, kHelmLargeCap, 256>, a.nelmt, s, a.b0, a.b1, basis2(a), x.d0,
-                            x.d1, x.d2, x.g, x.w, x.lam, x.w != nullptr, a.in, a.out, a.nelmt, (int)nq[0], (int)nq[1],
-                            (int)nq[2]);
+    return launch_any_extent(helmholtz_generic_built(DIM, nq[0], nq[1], nq[2]),
+                             helm_need(DIM, nq[0], nq[1], nq[2]) <= (unsigned)kHelmSmallCap,
+                             helmholtz_generic_kernel<T, DIM, kHelmSmallCap, 64>,
+                             helmholtz_generic_kernel<T, DIM, kHelmLargeCap, 256>, a.nelmt, s, a.b0, a.b1, basis2(a), x.d0,
+                             x.d1, x.d2, x.g, x.w, x.lam, x.w != nullptr, a.in, a.out, a.nelmt, (int)nq[0], (int)nq[1],
+                             (int)nq[2]);
 }
 template int launch_helmholtz_generic<3, double>(const unsigned (&)[3], const HexArgs &, const HelmArgsT<double> &,
                                                  hipStream_t);

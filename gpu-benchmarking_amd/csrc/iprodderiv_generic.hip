@@ -8,9 +8,9 @@
 // Four (2D: three) LDS regions of one point image each, P0 .. P3:
 //   3D: in_0, in_1, in_2 (HBM) -> g_0, g_1, g_2 (P1, P2, P3) -> v (P0) -> t1 (P1) -> t2 (P2) -> out (HBM)
 //   2D: in_0, in_1 (HBM) -> g_0, g_1 (P1, P2) -> v (P0) -> t1 (P1) -> out (HBM)
-// The back sweeps are those of helm_generic_body (helmholtz_generic.h), restated here because that body cannot be
-// entered in the middle; the bounds and the LDS classes are shared with it.  Every buffer is read and written with scalar
-// accesses: scalar alignment is enough.  No workspace and static LDS only: every launch is a single kernel node that
+// The transposed derivatives of a point and the back sweeps are the text of helm_generic_body (helmholtz_generic.h): the
+// fragments frag/ae_deriv_transposed_*.inc and frag/ae_transposed_*.inc; the bounds and the LDS classes are shared with
+// that body too.  Every buffer is read and written with scalar accesses: scalar alignment is enough.  No workspace and static LDS only: every launch is a single kernel node that
 // needs no function attribute, capture-safe from the first call.  `df` / `w` are not dereferenced when has_df / has_w is
 // false.  Latency-bound (a barrier per sweep, one element per workgroup), not a roofline target.  Extents up to 12 per
 // direction in 3D and 32 in 2D; beyond, SF_ENOTBUILT.
@@ -27,13 +27,8 @@ __global__ __launch_bounds__(NT) void iprodderiv_generic_kernel(
     uint64_t nelmt, int nq0, int nq1, int nq2)
 {
     __shared__ T lds[CAP];
-    const int nm0 = nq0 - 1, nm1 = nq1 - 1, nm2 = DIM == 3 ? nq2 - 1 : 1;
-    const int nz  = DIM == 3 ? nq2 : 1;
-    const int n01 = nq0 * nq1;
-    const int nqt = n01 * nz;        // points per element
-    const int nmt = nm0 * nm1 * nm2; // modes per element
+#include "frag/ae_prologue.inc"
     T *P0 = lds, *P1 = lds + nqt, *P2 = lds + 2 * nqt, *P3 = lds + (DIM == 3 ? 3 : 2) * nqt;
-    const int tid = threadIdx.x;
     for (uint64_t e = blockIdx.x; e < nelmt; e += gridDim.x)
     {
         const T *f0  = in0 + e * (uint64_t)nqt, *f1 = in1 + e * (uint64_t)nqt;
@@ -64,25 +59,13 @@ __global__ __launch_bounds__(NT) void iprodderiv_generic_kernel(
             // v = D_0^T g_0 + D_1^T g_1
             for (int x = tid; x < nqt; x += NT)
             {
-                const int i = x % nq0, j = x / nq0;
-                const T t0 = dot_strided(P1 + j * nq0, 1, d0 + i, nq0, nq0);
-                const T t1 = dot_strided(P2 + i, nq0, d1 + j, nq1, nq1);
-                P0[x]      = t0 + t1;
+#include "frag/ae_deriv_transposed_2d.inc"
+                P0[x] = t0 + t1;
             }
             __syncthreads();
-            // transposed 1: t1[q'][i] = sum_j v[j][i] * B1[q'][j]
-            for (int x = tid; x < nm1 * nq0; x += NT)
-            {
-                const int i = x % nq0, q = x / nq0;
-                P1[x] = dot_strided(P0 + i, nq0, b1 + q * nq1, 1, nq1);
-            }
-            __syncthreads();
-            // transposed 0: out[q'][p'] = sum_i t1[q'][i] * B0[p'][i]
-            for (int x = tid; x < nmt; x += NT)
-            {
-                const int p = x % nm0, q = x / nm0;
-                dst[x] = dot_strided(P1 + q * nq0, 1, b0 + p * nq0, 1, nq0);
-            }
+#define AE_POINTS P0
+#define AE_T1 P1
+#include "frag/ae_transposed_2d.inc"
         }
         else
         {
@@ -111,33 +94,14 @@ __global__ __launch_bounds__(NT) void iprodderiv_generic_kernel(
             // v = (D_0^T g_0 + D_1^T g_1) + D_2^T g_2
             for (int x = tid; x < nqt; x += NT)
             {
-                const int i = x % nq0, kj = x / nq0, j = kj % nq1, k = kj / nq1;
-                const T t0 = dot_strided(P1 + kj * nq0, 1, d0 + i, nq0, nq0);
-                const T t1 = dot_strided(P2 + k * n01 + i, nq0, d1 + j, nq1, nq1);
-                const T t2 = dot_strided(P3 + j * nq0 + i, n01, d2 + k, nq2, nq2);
-                P0[x]      = (t0 + t1) + t2;
+#include "frag/ae_deriv_transposed_3d.inc"
+                P0[x] = (t0 + t1) + t2;
             }
             __syncthreads();
-            // transposed 2: t1[r'][j][i] = sum_k v[k][j][i] * B2[r'][k]
-            for (int x = tid; x < n01 * nm2; x += NT)
-            {
-                const int ji = x % n01, r = x / n01;
-                P1[x] = dot_strided(P0 + ji, n01, b2 + r * nq2, 1, nq2);
-            }
-            __syncthreads();
-            // transposed 1: t2[r'][q'][i] = sum_j t1[r'][j][i] * B1[q'][j]
-            for (int x = tid; x < nq0 * nm1 * nm2; x += NT)
-            {
-                const int i = x % nq0, rq = x / nq0, q = rq % nm1, r = rq / nm1;
-                P2[x] = dot_strided(P1 + r * n01 + i, nq0, b1 + q * nq1, 1, nq1);
-            }
-            __syncthreads();
-            // transposed 0: out[r'][q'][p'] = sum_i t2[r'][q'][i] * B0[p'][i]
-            for (int x = tid; x < nmt; x += NT)
-            {
-                const int p = x % nm0, rq = x / nm0;
-                dst[x] = dot_strided(P2 + rq * nq0, 1, b0 + p * nq0, 1, nq0);
-            }
+#define AE_POINTS P0
+#define AE_T1 P1
+#define AE_T2 P2
+#include "frag/ae_transposed_3d.inc"
         }
         __syncthreads(); // the next element overwrites the images
     }
@@ -146,16 +110,13 @@ __global__ __launch_bounds__(NT) void iprodderiv_generic_kernel(
 template <int DIM, typename T>
 int launch_iprodderiv_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const IprodDerivArgsT<T> &x, hipStream_t s)
 {
-    if (!iprodderiv_generic_built(DIM, nq[0], nq[1], nq[2]))
-        return SF_ENOTBUILT;
-    if (a.nelmt == 0)
-        return SF_OK;
     // the images and the classes of the Helmholtz fallback: 4 (2D: 3) nqt scalars
-    return launch_lds_class(helm_need(DIM, nq[0], nq[1], nq[2]) <= (unsigned)kHelmSmallCap,
-                            iprodderiv_generic_kernel<T, DIM, kHelmSmallCap, 64>,
-                            iprodderiv_generic_kernel<T, DIM, kHelmLargeCap, 256>, a.nelmt, s, a.b0, a.b1, basis2(a), x.d0,
-                            x.d1, x.d2, x.df, x.df != nullptr, x.w, x.w != nullptr, x.in0, x.in1, x.in2, a.out, a.nelmt,
-                            (int)nq[0], (int)nq[1], (int)nq[2]);
+    return launch_any_extent(iprodderiv_generic_built(DIM, nq[0], nq[1], nq[2]),
+                             helm_need(DIM, nq[0], nq[1], nq[2]) <= (unsigned)kHelmSmallCap,
+                             iprodderiv_generic_kernel<T, DIM, kHelmSmallCap, 64>,
+                             iprodderiv_generic_kernel<T, DIM, kHelmLargeCap, 256>, a.nelmt, s, a.b0, a.b1, basis2(a), x.d0,
+                             x.d1, x.d2, x.df, x.df != nullptr, x.w, x.w != nullptr, x.in0, x.in1, x.in2, a.out, a.nelmt,
+                             (int)nq[0], (int)nq[1], (int)nq[2]);
 }
 template int launch_iprodderiv_generic<3, double>(const unsigned (&)[3], const HexArgs &, const IprodDerivArgsT<double> &,
                                                   hipStream_t);

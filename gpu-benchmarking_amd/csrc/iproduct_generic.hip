@@ -6,7 +6,8 @@
 // index, sweeps i -> p, j -> q, k -> r, the order of the wave kernels.  The bases are read straight from global memory
 // (nm*nq values each, cache-resident).  No workspace: every launch is a single kernel node, capture-safe from the first
 // call.  Extents up to 16 per direction in 3D and 32 in 2D; beyond, SF_ENOTBUILT.  The sums are written out where
-// mass_generic.hip and helmholtz_generic.hip call dot_strided(): the compiler schedules the two forms differently here.
+// the fragments frag/ae_*.inc of the other any-extent kernels call dot_strided(): the compiler schedules the two forms
+// differently here, and the sweeps run in the other order, so the kernel shares only its launch (any_extent.h).
 #include "any_extent.h"
 
 namespace sf
@@ -93,15 +94,12 @@ __global__ __launch_bounds__(NT) void iprod_generic_kernel(const T *__restrict__
 
 template <int DIM, typename T> int launch_iprod_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, hipStream_t s)
 {
-    if (!iprod_generic_built(DIM, nq[0], nq[1], nq[2]))
-        return SF_ENOTBUILT;
-    if (a.nelmt == 0)
-        return SF_OK;
     const unsigned nz   = DIM == 3 ? nq[2] : 1;
     const unsigned need = nq[0] * nq[1] * nz + (nq[0] - 1) * nq[1] * nz;
-    return launch_lds_class(need <= (unsigned)kIprodSmallCap, iprod_generic_kernel<T, DIM, kIprodSmallCap, 64>,
-                            iprod_generic_kernel<T, DIM, kIprodLargeCap, 256>, a.nelmt, s, a.b0, a.b1, basis2(a), a.in,
-                            a.out, a.nelmt, (int)nq[0], (int)nq[1], (int)nq[2]);
+    return launch_any_extent(iprod_generic_built(DIM, nq[0], nq[1], nq[2]), need <= (unsigned)kIprodSmallCap,
+                             iprod_generic_kernel<T, DIM, kIprodSmallCap, 64>,
+                             iprod_generic_kernel<T, DIM, kIprodLargeCap, 256>, a.nelmt, s, a.b0, a.b1, basis2(a), a.in,
+                             a.out, a.nelmt, (int)nq[0], (int)nq[1], (int)nq[2]);
 }
 template int launch_iprod_generic<3, double>(const unsigned (&)[3], const HexArgs &, hipStream_t);
 template int launch_iprod_generic<3, float>(const unsigned (&)[3], const HexArgsT<float> &, hipStream_t);

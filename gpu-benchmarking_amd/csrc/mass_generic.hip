@@ -7,6 +7,8 @@
 // regions A and B:
 //   3D: in (B) -> w1 (A) -> w2 (B) -> weighted points (A) -> t1 (B) -> t2 (A) -> out (HBM)
 //   2D: in (A) -> w1 (B) -> weighted points (A) -> t1 (B) -> out (HBM)
+// The sweeps are the fragments frag/ae_forward_*.inc and frag/ae_transposed_*.inc, which the Helmholtz body shares; the
+// multiply by the weight is the value that the last forward sweep stores.
 // A holds nq0*nq1[*nq2] scalars (the point image is the largest it sees), B nq0*nq1*nm2 in 3D and nq0*nm1 in 2D; the
 // launcher derives both from the extents and refuses what does not fit the large class.  `in`, `w` and the bases are
 // read from global memory with scalar loads, `out` is written with scalar stores: buffers that are only 8-byte
@@ -29,12 +31,8 @@ __global__ __launch_bounds__(NT) void mass_generic_kernel(const T *__restrict__ 
                                                           int nq0, int nq1, int nq2, int sizeA)
 {
     __shared__ T lds[CAP];
-    const int nm0 = nq0 - 1, nm1 = nq1 - 1, nm2 = DIM == 3 ? nq2 - 1 : 1;
-    const int nz  = DIM == 3 ? nq2 : 1;
-    const int nqt = nq0 * nq1 * nz;  // points per element
-    const int nmt = nm0 * nm1 * nm2; // modes per element
+#include "frag/ae_prologue.inc"
     T *A = lds, *B = lds + sizeA;
-    const int tid = threadIdx.x;
     for (uint64_t e = blockIdx.x; e < nelmt; e += gridDim.x)
     {
         const T *src = in + e * (uint64_t)nmt;
@@ -42,84 +40,27 @@ __global__ __launch_bounds__(NT) void mass_generic_kernel(const T *__restrict__ 
         T *dst       = out + e * (uint64_t)nmt;
         if constexpr (DIM == 2)
         {
-            for (int x = tid; x < nmt; x += NT)
-                A[x] = src[x];
-            __syncthreads();
-            // forward 0: w1[q][i] = sum_p in[q][p] * B0[p][i]
-            for (int x = tid; x < nm1 * nq0; x += NT)
-            {
-                const int i = x % nq0, q = x / nq0;
-                B[x] = dot_strided(A + q * nm0, 1, b0 + i, nq0, nm0);
-            }
-            __syncthreads();
-            // forward 1 and weight: v[j][i] = w[j][i] * sum_q w1[q][i] * B1[q][j]
-            for (int x = tid; x < nqt; x += NT)
-            {
-                const int i = x % nq0, j = x / nq0;
-                A[x] = dot_strided(B + i, nq0, b1 + j, nq1, nm1) * wt[x];
-            }
-            __syncthreads();
-            // transposed 1: t1[q'][i] = sum_j v[j][i] * B1[q'][j]
-            for (int x = tid; x < nm1 * nq0; x += NT)
-            {
-                const int i = x % nq0, q = x / nq0;
-                B[x] = dot_strided(A + i, nq0, b1 + q * nq1, 1, nq1);
-            }
-            __syncthreads();
-            // transposed 0: out[q'][p'] = sum_i t1[q'][i] * B0[p'][i]
-            for (int x = tid; x < nmt; x += NT)
-            {
-                const int p = x % nm0, q = x / nm0;
-                dst[x] = dot_strided(B + q * nq0, 1, b0 + p * nq0, 1, nq0);
-            }
+#define AE_MODES A
+#define AE_W1 B
+#define AE_POINTS A
+#define AE_POINT_VALUE(s) s * wt[x] // the weight: v = w u
+#include "frag/ae_forward_2d.inc"
+#define AE_POINTS A
+#define AE_T1 B
+#include "frag/ae_transposed_2d.inc"
         }
         else
         {
-            const int n01 = nq0 * nq1;
-            for (int x = tid; x < nmt; x += NT)
-                B[x] = src[x];
-            __syncthreads();
-            // forward 0: w1[r][q][i] = sum_p in[r][q][p] * B0[p][i]
-            for (int x = tid; x < nq0 * nm1 * nm2; x += NT)
-            {
-                const int i = x % nq0, rq = x / nq0;
-                A[x] = dot_strided(B + rq * nm0, 1, b0 + i, nq0, nm0);
-            }
-            __syncthreads();
-            // forward 1: w2[r][j][i] = sum_q w1[r][q][i] * B1[q][j]
-            for (int x = tid; x < n01 * nm2; x += NT)
-            {
-                const int i = x % nq0, rj = x / nq0, j = rj % nq1, r = rj / nq1;
-                B[x] = dot_strided(A + r * nm1 * nq0 + i, nq0, b1 + j, nq1, nm1);
-            }
-            __syncthreads();
-            // forward 2 and weight: v[k][j][i] = w[k][j][i] * sum_r w2[r][j][i] * B2[r][k]
-            for (int x = tid; x < nqt; x += NT)
-            {
-                const int ji = x % n01, k = x / n01;
-                A[x] = dot_strided(B + ji, n01, b2 + k, nq2, nm2) * wt[x];
-            }
-            __syncthreads();
-            // transposed 2: t1[r'][j][i] = sum_k v[k][j][i] * B2[r'][k]
-            for (int x = tid; x < n01 * nm2; x += NT)
-            {
-                const int ji = x % n01, r = x / n01;
-                B[x] = dot_strided(A + ji, n01, b2 + r * nq2, 1, nq2);
-            }
-            __syncthreads();
-            // transposed 1: t2[r'][q'][i] = sum_j t1[r'][j][i] * B1[q'][j]
-            for (int x = tid; x < nq0 * nm1 * nm2; x += NT)
-            {
-                const int i = x % nq0, rq = x / nq0, q = rq % nm1, r = rq / nm1;
-                A[x] = dot_strided(B + r * n01 + i, nq0, b1 + q * nq1, 1, nq1);
-            }
-            __syncthreads();
-            // transposed 0: out[r'][q'][p'] = sum_i t2[r'][q'][i] * B0[p'][i]
-            for (int x = tid; x < nmt; x += NT)
-            {
-                const int p = x % nm0, rq = x / nm0;
-                dst[x] = dot_strided(A + rq * nq0, 1, b0 + p * nq0, 1, nq0);
-            }
+#define AE_MODES B
+#define AE_W1 A
+#define AE_W2 B
+#define AE_POINTS A
+#define AE_POINT_VALUE(s) s * wt[x] // the weight: v = w u
+#include "frag/ae_forward_3d.inc"
+#define AE_POINTS A
+#define AE_T1 B
+#define AE_T2 A
+#include "frag/ae_transposed_3d.inc"
         }
         __syncthreads(); // the next element overwrites the images
     }
@@ -143,15 +84,12 @@ static void mass_regions(int dim, unsigned nq0, unsigned nq1, unsigned nq2, unsi
 template <int DIM, typename T>
 int launch_mass_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const T *w, hipStream_t s)
 {
-    if (!mass_generic_built(DIM, nq[0], nq[1], nq[2]))
-        return SF_ENOTBUILT;
-    if (a.nelmt == 0)
-        return SF_OK;
     unsigned sizeA, sizeB;
     mass_regions(DIM, nq[0], nq[1], nq[2], sizeA, sizeB);
-    return launch_lds_class(sizeA + sizeB <= (unsigned)kMassSmallCap, mass_generic_kernel<T, DIM, kMassSmallCap, 64>,
-                            mass_generic_kernel<T, DIM, kMassLargeCap, 256>, a.nelmt, s, a.b0, a.b1, basis2(a), w, a.in,
-                            a.out, a.nelmt, (int)nq[0], (int)nq[1], (int)nq[2], (int)sizeA);
+    return launch_any_extent(mass_generic_built(DIM, nq[0], nq[1], nq[2]), sizeA + sizeB <= (unsigned)kMassSmallCap,
+                             mass_generic_kernel<T, DIM, kMassSmallCap, 64>,
+                             mass_generic_kernel<T, DIM, kMassLargeCap, 256>, a.nelmt, s, a.b0, a.b1, basis2(a), w, a.in,
+                             a.out, a.nelmt, (int)nq[0], (int)nq[1], (int)nq[2], (int)sizeA);
 }
 template int launch_mass_generic<3, double>(const unsigned (&)[3], const HexArgs &, const double *, hipStream_t);
 template int launch_mass_generic<3, float>(const unsigned (&)[3], const HexArgsT<float> &, const float *, hipStream_t);
