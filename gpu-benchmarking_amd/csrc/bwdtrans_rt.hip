@@ -2,7 +2,8 @@
 // anisotropic 3D extents up to 16 per direction (the reference takes nq0, nq1, nq2 at run time,
 // benchmark05/benchmark05.cc:291-297, 1425-1429).
 #include "bwdtrans_rt.h"
-#include "bwdtrans_wave3.h"
+#include "bwdtrans_aniso.h"
+#include "chunked_launch.h"
 #include "rtc_config.h"
 #include "sf_dispatch.h"
 
@@ -30,7 +31,7 @@ template <int NB> static int go_rt(const RtShape &sh, int wpb, size_t lds, const
     return e == hipSuccess ? SF_OK : (int)e;
 }
 
-// ---- compile-time triples (bwdtrans_wave3.h) -----------------------------------------------------------------------
+// ---- compile-time triples (bwdtrans_aniso.h) -----------------------------------------------------------------------
 // EC: chunks of about one nq = 8 element (512 points) -- the footprint the isotropic rows converged on
 template <int NQ0, int NQ1, int NQ2> struct Cfg3
 {
@@ -42,18 +43,13 @@ template <int NQ0, int NQ1, int NQ2> struct Cfg3
 
 template <int NQ0, int NQ1, int NQ2> static int go3(const HexArgs &a, hipStream_t s)
 {
-    using C              = Cfg3<NQ0, NQ1, NQ2>;
-    constexpr int WPB    = 4;
-    auto kern            = hex_wave3_kernel<NQ0, NQ1, NQ2, C::EC, WPB, C::BM, 2>;
-    constexpr size_t lds = wave3_lds_bytes<NQ0, NQ1, NQ2, C::EC, WPB>();
+    using C = Cfg3<NQ0, NQ1, NQ2>;
+    static OccCache cache = {};
+    constexpr size_t lds  = slab_lds_bytes<BwdGeom<3, C::EC, double, NQ0, NQ1, NQ2>, 4>();
     static_assert(lds <= 64 * 1024, "LDS slab");
-    const uint64_t nchunk = (a.nelmt + C::EC - 1) / C::EC;
-    const uint64_t grid   = (nchunk + WPB - 1) / WPB;
-    if (grid > 0x7fffffffull)
-        return SF_EINVAL;
-    kern<<<(unsigned)grid, kWave * WPB, lds, s>>>(a.b0, a.b1, a.b2, a.in, a.out, a.nelmt);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SF_OK : (int)e;
+    // one chunk per short-lived wave (KMAP = 1), four waves per workgroup
+    return launch_chunked<4, C::EC, 1>(hex_wave3_kernel<NQ0, NQ1, NQ2, C::EC, 4, C::BM, 2>, cache, lds, 0, s, a.nelmt, a.b0,
+                                       a.b1, a.b2, a.in, a.out, a.nelmt);
 }
 
 // The instantiated shapes: every ordering of the extents {8,8,4}, {4,8,6}, {10,6,8} (the shapes the round-2 review
@@ -64,24 +60,23 @@ template <int NQ0, int NQ1, int NQ2> static int go3(const HexArgs &a, hipStream_
     X(8, 6, 6) X(8, 8, 10) X(8, 10, 8) X(10, 8, 8) X(10, 10, 8) X(10, 8, 10) X(8, 10, 10) X(6, 6, 4) X(6, 4, 6) X(4, 6, 6)   \
     X(4, 4, 6) X(4, 6, 4) X(6, 4, 4)
 
-// the run-time specialisation's host-side configuration (rtc_config.h) restates Cfg3 and the slab of WaveGeom3: pinned
+// the run-time specialisation's host-side configuration (rtc_config.h) restates Cfg3 and the slab of BwdGeom: pinned
 // here to the template's own values for every compile-time triple
 template <int A, int B, int C> constexpr bool rtc_matches_cfg3()
 {
     constexpr RtcCfg r = rtc_cfg(3, A, B, C, 8);
     using C3           = Cfg3<A, B, C>;
-    return r.ec == C3::EC && r.bmode == C3::BM && r.wpb == 4 && r.minw == 2 && r.xg == 64 &&
-           r.slab == WaveGeom3<A, B, C, C3::EC>::SLAB_OUT && r.lds == wave3_lds_bytes<A, B, C, C3::EC, 4>();
+    using G            = BwdGeom<3, C3::EC, double, A, B, C>;
+    return r.ec == C3::EC && r.bmode == C3::BM && r.wpb == 4 && r.minw == 2 && r.xg == 64 && r.slab == G::SLAB &&
+           r.lds == slab_lds_bytes<G, 4>();
 }
-#define SF_PIN3(A, B, C) static_assert(rtc_matches_cfg3<A, B, C>(), "rtc_config.h disagrees with Cfg3 / WaveGeom3");
+#define SF_PIN3(A, B, C) static_assert(rtc_matches_cfg3<A, B, C>(), "rtc_config.h disagrees with Cfg3 / BwdGeom");
 SF_TRIPLES(SF_PIN3)
 #undef SF_PIN3
 
 // SF_ENOTBUILT: the shape is not in the table (the caller then takes the run-time-extent kernel)
 int launch_hex_wave3(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, hipStream_t s)
 {
-    if (a.nelmt == 0)
-        return SF_OK;
     const unsigned key = (nq0 << 16) | (nq1 << 8) | nq2;
     switch (key)
     {

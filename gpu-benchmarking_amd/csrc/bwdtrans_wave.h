@@ -37,6 +37,13 @@
 //  * Scalar type: every kernel is a template on T (double = the reference's only instantiation; float =
 //    the T the reference's templates allow but never instantiate).  "16-byte lane" = double2 or float4.
 //
+//  * Shared text.  Every sweep that stores in the form of Sweep below is one text, frag/sweep.inc (its scatter half
+//    alone, behind a contraction the kernel writes itself: frag/sweep_store.inc), #included in place with the sweep of
+//    the geometry, the contraction and the basis as parameters -- here, in bwdtrans_aniso.h, iproduct_wave.h and, through
+//    frag/forward*.inc and frag/transposed1_3d.inc, in the fused operators.  Written out stay the direct-store branches
+//    (OUT_ST16 / OUT_ST8), which are BwdTrans's own, and quad_wave_kernel's OUT_LDS scatter: frag/sweep_store.inc with
+//    G::Sw1 was tried there and changed the code of 62 of the 210 kernels of bwdtrans_quad.hip.
+//
 // Algorithmic HBM traffic per element: sizeof(T)*(nm^d + nq^d) bytes (in read once, out written once);
 // measured traffic 1.003x that (profiles/hbm_traffic.json).
 #pragma once
@@ -91,41 +98,73 @@ __device__ __forceinline__ double swap_adjacent(double v)
     return __hiloint2double(hi, lo);
 }
 
-template <int NQ, int EC, int DIM, typename T = double> struct WaveGeom
+// One sweep of a wave kernel, the form frag/sweep.inc runs: lane t = (e, a, b), a < A, b < B, owns one of NP pencils of
+// NIN values at stride SIN, contracts it to NOUT values and stores value o at slab[((e*NOUT + o)*A + a)*SOUT + b].
+template <int NIN_, int NOUT_, int NP_, int SIN_, int A_, int B_, int SOUT_> struct Sweep
 {
+    static constexpr int NIN = NIN_, NOUT = NOUT_, NP = NP_, SIN = SIN_, A = A_, B = B_, SOUT = SOUT_;
+    static constexpr int PASS = cdiv(NP, kWave);
+};
+
+// The geometry of a wave kernel of DIM = 2 or 3 directions: direction d contracts pencils of I<d> values to O<d> values,
+// direction 0 (the fastest index) first.  The input image and the DIM - 1 intermediates live one after another in the
+// same slab, every pencil stride padded to an odd number of scalars; the last sweep writes the output image in its final
+// layout.  BwdTrans has I = nm, O = nq (BwdGeom, WaveGeom); IProductWRTBase is the same with the two swapped (IprodGeom).
+template <int DIM, int EC, typename T, int I0, int O0, int I1, int O1, int I2 = 1, int O2 = 1> struct SweepGeom
+{
+    static_assert(DIM == 3 || (I2 == 1 && O2 == 1), "two directions: the third has length 1");
     using Scalar = T;
     using Vec    = typename VecOf<T>::type;
-    static constexpr int VW  = VecOf<T>::W; // scalars per 16-byte lane
-    static constexpr int NM  = NQ - 1;
-    static constexpr int NMP = NM | 1; // padded pencil stride (odd number of scalars)
-    static constexpr int NMT = (DIM == 3) ? NM * NM * NM : NM * NM; // modes per element
-    static constexpr int NQT = (DIM == 3) ? NQ * NQ * NQ : NQ * NQ; // points per element
-    // input pencils keep the global layout when NM is odd (already conflict-free)
-    static constexpr int IN_STRIDE = (NM % 2 == 0) ? NM + 1 : NM;
-    static constexpr int IN_DBL    = EC * NMT; // scalars per chunk in HBM
+    static constexpr int VW      = VecOf<T>::W; // scalars per 16-byte lane
+    static constexpr int IN_LEN  = I0;           // length of an input pencil in HBM
+    static constexpr int IN_ELEM = I0 * I1 * I2, OUT_ELEM = O0 * O1 * O2; // scalars per element read / written
+    // padded pencil strides (odd numbers of scalars: conflict-free; an odd length keeps the global layout)
+    static constexpr int S0 = I0 | 1, S1 = I1 | 1, S2 = I2 | 1;
+    static constexpr int IN_STRIDE = S0;
+    static constexpr int IN_DBL    = EC * IN_ELEM; // scalars per chunk in HBM
     static constexpr bool VEC2     = (IN_DBL % VW) == 0; // chunk is a whole number of 16-B lanes
-    // pencils per chunk in each sweep
-    static constexpr int P0 = (DIM == 3) ? EC * NM * NM : EC * NM; // (e,r,q) | (e,q)
-    static constexpr int P1 = (DIM == 3) ? EC * NQ * NM : EC * NQ; // (e,i,r) | (e,i)
-    static constexpr int P2 = EC * NQ * NQ;                       // (e,j,i)   (3D only)
-    static constexpr int PASS0 = cdiv(P0, kWave);
-    static constexpr int PASS1 = cdiv(P1, kWave);
-    static constexpr int PASS2 = cdiv(P2, kWave);
-    // LDS slab per wave (scalars): max over the three images that live in it, one after another
-    static constexpr int SLAB_IN = P0 * IN_STRIDE;
-    static constexpr int SLAB_W1 = P1 * NMP;
-    static constexpr int SLAB_W2 = (DIM == 3) ? P2 * NMP : 0;
+    // pencils per chunk in each sweep: 3D (e,x2,x1) -> (e,o0,x2) -> (e,o1,o0); 2D (e,x1) -> (e,o0)
+    static constexpr int P0 = EC * I2 * I1, P1 = EC * O0 * I2, P2 = EC * O1 * O0;
+    static constexpr int PASS0 = cdiv(P0, kWave), PASS1 = cdiv(P1, kWave), PASS2 = cdiv(P2, kWave);
+    using Sw0 = Sweep<I0, O0, P0, S0, I2, I1, S1>;
+    // the last sweep of either dimension stores into the output image: A = 1, SOUT = B = the points of a plane / row
+    using Sw1 = Sweep<I1, O1, P1, S1, DIM == 3 ? O0 : 1, DIM == 3 ? I2 : O0, DIM == 3 ? S2 : O0>;
+    using Sw2 = Sweep<I2, O2, P2, S2, 1, O0 * O1, O0 * O1>; // 3D only
+    // LDS slab per wave (scalars): max over the images that live in it, one after another
+    static constexpr int SLAB_IN = P0 * S0;
+    static constexpr int SLAB_W1 = P1 * S1;
+    static constexpr int SLAB_W2 = (DIM == 3) ? P2 * S2 : 0;
     static constexpr int SLAB0   = CMax<CMax<SLAB_IN, SLAB_W1>::value, SLAB_W2>::value;
-    static constexpr int OUT_DBL = EC * NQT; // scalars per chunk written to HBM
+    static constexpr int OUT_DBL = EC * OUT_ELEM; // scalars per chunk written to HBM
     // slab without / with room for the output image (OUT_LDS), kept 16-B aligned
     static constexpr int SLAB_NOOUT = (SLAB0 + VW - 1) / VW * VW;
     static constexpr int SLAB_OUT   = (CMax<SLAB0, OUT_DBL>::value + VW - 1) / VW * VW;
-    static constexpr int NBAS = (NM * NQ + VW - 1) / VW * VW;
+    static constexpr int SLAB       = SLAB_OUT; // what frag/wave_slab.inc gives a wave
     static constexpr int NLD  = VEC2 ? cdiv(IN_DBL / VW, kWave) : cdiv(IN_DBL, kWave);
     // the chunk's 16-B lanes can be shifted by up to 7 so that every wave-wide load covers whole 128-B
     // lines; free when the shifted span needs no extra staging register
     static constexpr bool ALIGN_OK = VEC2 && cdiv(IN_DBL / VW + 7, kWave) == NLD;
 };
+
+// BwdTrans with the extents taken per direction: nq<d> points from nq<d> - 1 modes (2D: NQ2 is not read)
+template <int DIM, int EC, typename T, int NQ0, int NQ1, int NQ2 = 2>
+using BwdGeom = SweepGeom<DIM, EC, T, NQ0 - 1, NQ0, NQ1 - 1, NQ1, DIM == 3 ? NQ2 - 1 : 1, DIM == 3 ? NQ2 : 1>;
+
+// the isotropic spelling, with the names the isotropic kernels use
+template <int NQ, int EC, int DIM, typename T = double> struct WaveGeom : BwdGeom<DIM, EC, T, NQ, NQ, NQ>
+{
+    static constexpr int NM  = NQ - 1;
+    static constexpr int NMP = NM | 1; // = S0 = S1 = S2
+    static constexpr int NMT = WaveGeom::IN_ELEM;  // modes per element
+    static constexpr int NQT = WaveGeom::OUT_ELEM; // points per element
+    static constexpr int NBAS = (NM * NQ + WaveGeom::VW - 1) / WaveGeom::VW * WaveGeom::VW;
+};
+
+// dynamic LDS of a workgroup of WPB waves that own G::SLAB scalars each
+template <class G, int WPB> constexpr size_t slab_lds_bytes()
+{
+    return sizeof(typename G::Scalar) * (size_t)WPB * G::SLAB;
+}
 
 // lanes to skip so that lane 0 of every load instruction sits on a 128-byte line
 __device__ __forceinline__ int align_shift(const void *p)
@@ -319,7 +358,7 @@ __device__ __forceinline__ void chunk_stage(const typename G::Vec (&st)[G::NLD],
             if (AL ? (v >= 0 && v < G::IN_DBL / VW)
                    : ((k + 1) * kWave <= G::IN_DBL / VW || v < G::IN_DBL / VW))
             {
-                if constexpr (G::IN_STRIDE == G::NM)
+                if constexpr (G::IN_STRIDE == G::IN_LEN)
                 {
                     *reinterpret_cast<V *>(slab + VW * v) = st[k];
                 }
@@ -329,7 +368,7 @@ __device__ __forceinline__ void chunk_stage(const typename G::Vec (&st)[G::NLD],
                     for (int j = 0; j < VW; ++j)
                     {
                         const int f          = VW * v + j;
-                        slab[f + f / G::NM] = st[k][j];
+                        slab[f + f / G::IN_LEN] = st[k][j];
                     }
                 }
             }
@@ -347,10 +386,10 @@ __device__ __forceinline__ void chunk_stage(const typename G::Vec (&st)[G::NLD],
                 const int f = VW * (k * kWave + lane) - sh + h;
                 if (f >= 0 && f < G::IN_DBL)
                 {
-                    if constexpr (G::IN_STRIDE == G::NM)
+                    if constexpr (G::IN_STRIDE == G::IN_LEN)
                         slab[f] = st[k][h];
                     else
-                        slab[f + f / G::NM] = st[k][h];
+                        slab[f + f / G::IN_LEN] = st[k][h];
                 }
             }
     }
@@ -557,7 +596,7 @@ __device__ __forceinline__ void chunk_fetch(typename G::Vec (&st)[G::NLD],
     if (left >= EC)
         chunk_load<G, true, NTL, AL>(st, in + c * G::IN_DBL, lane, 0);
     else
-        chunk_load<G, false, NTL, AL>(st, in + c * G::IN_DBL, lane, (int)left * G::NMT);
+        chunk_load<G, false, NTL, AL>(st, in + c * G::IN_DBL, lane, (int)left * G::IN_ELEM);
 }
 
 // Final-sweep store of one pass: lane t owns NOUT values acc[n] destined for dst[n*NSTRIDE]
@@ -727,10 +766,10 @@ __device__ __forceinline__ void block_load_stage(typename G::Scalar *slab0, cons
             {
                 const int w = f / G::IN_DBL, r = f - w * G::IN_DBL;
                 T *dst      = slab0 + w * SLAB;
-                if constexpr (G::IN_STRIDE == G::NM)
+                if constexpr (G::IN_STRIDE == G::IN_LEN)
                     dst[r] = x[k][h];
                 else
-                    dst[r + r / G::NM] = x[k][h];
+                    dst[r + r / G::IN_LEN] = x[k][h];
             }
         }
 }
@@ -745,7 +784,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_wave_kernel(
     const T *__restrict__ in, T *__restrict__ out, uint64_t nelmt)
 {
     using G          = WaveGeom<NQ, EC, 3, T>;
-    constexpr int NM = G::NM, NMP = G::NMP, NM2 = NM * NM, NQ2 = NQ * NQ;
+    constexpr int NM = G::NM, NMP = G::NMP, NQ2 = NQ * NQ;
     static_assert(OUTM != OUT_ST16 || (NQ % 2 == 0 && sizeof(T) == 8),
                   "paired 16-byte stores need even nq and fp64");
     constexpr int SLAB = slab_doubles<G, OUTM>();
@@ -802,48 +841,15 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_wave_kernel(
         }
 
         // ---- direction 0: w1[(e,i,r)][q] = sum_p in[(e,r,q)][p] * B0[p][i] ----------------------
-        {
-            T u[G::PASS0][NM], acc[G::PASS0][NQ];
-            read_pencils<NM, G::PASS0, G::P0, G::IN_STRIDE>(u, slab, lane);
-            contract<NM, NQ, G::PASS0, BMODE>(u, acc, bs[0]);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < G::PASS0; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= G::P0 || t < G::P0)
-                {
-                    const int e = t / NM2, rq = t - e * NM2, r = rq / NM, q = rq - r * NM;
-                    T *dst = slab + (e * NQ * NM + r) * NMP + q;
-#pragma unroll
-                    for (int i = 0; i < NQ; ++i)
-                        dst[i * NM * NMP] = acc[s][i];
-                }
-            }
-            wave_lds_fence();
-        }
+#define SWEEP G::Sw0
+#define SWEEP_CONTRACT contract
+#define SWEEP_BASIS bs[0]
+#include "frag/sweep.inc"
         // ---- direction 1: w2[(e,j,i)][r] = sum_q w1[(e,i,r)][q] * B1[q][j] ----------------------
-        {
-            T u[G::PASS1][NM], acc[G::PASS1][NQ];
-            read_pencils<NM, G::PASS1, G::P1, NMP>(u, slab, lane);
-            contract<NM, NQ, G::PASS1, BMODE>(u, acc, bs[1]);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < G::PASS1; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= G::P1 || t < G::P1)
-                {
-                    const int e = t / (NQ * NM), ir = t - e * (NQ * NM), i = ir / NM,
-                              r = ir - i * NM;
-                    T *dst = slab + (e * NQ2 + i) * NMP + r;
-#pragma unroll
-                    for (int j = 0; j < NQ; ++j)
-                        dst[j * NQ * NMP] = acc[s][j];
-                }
-            }
-            wave_lds_fence();
-        }
+#define SWEEP G::Sw1
+#define SWEEP_CONTRACT contract
+#define SWEEP_BASIS bs[1]
+#include "frag/sweep.inc"
         // ---- direction 2: out[e][k][(j,i)] = sum_r w2[(e,j,i)][r] * B2[r][k] --------------------
         {
             T u[G::PASS2][NM], acc[G::PASS2][NQ];
@@ -852,21 +858,8 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_wave_kernel(
             T *oc = out + c * (uint64_t)(EC * G::NQT);
             if constexpr (OUTM == OUT_LDS)
             {
-                wave_lds_fence();
-#pragma unroll
-                for (int s = 0; s < G::PASS2; ++s)
-                {
-                    const int t = s * kWave + lane;
-                    if ((s + 1) * kWave <= G::P2 || t < G::P2)
-                    {
-                        const int e = t / NQ2, pl = t - e * NQ2;
-                        T *dst = slab + e * G::NQT + pl;
-#pragma unroll
-                        for (int k = 0; k < NQ; ++k)
-                            dst[k * NQ2] = acc[s][k];
-                    }
-                }
-                wave_lds_fence();
+#define SWEEP G::Sw2
+#include "frag/sweep_store.inc"
                 chunk_flush<G, !(MEMF & 2), (MEMF & 8) != 0>(slab, oc, evalid * G::NQT, lane);
             }
             else
@@ -932,26 +925,10 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_wave_kernel(
             chunk_fetch<G, EC, !(MEMF & 1), AL>(st, in, c + it.step, nelmt, lane);
 
         // ---- direction 0: w[(e,i)][q] = sum_p in[(e,q)][p] * B0[p][i] ---------------------------
-        {
-            T u[G::PASS0][NM], acc[G::PASS0][NQ];
-            read_pencils<NM, G::PASS0, G::P0, G::IN_STRIDE>(u, slab, lane);
-            contract<NM, NQ, G::PASS0, BMODE>(u, acc, bs[0]);
-            wave_lds_fence();
-#pragma unroll
-            for (int s = 0; s < G::PASS0; ++s)
-            {
-                const int t = s * kWave + lane;
-                if ((s + 1) * kWave <= G::P0 || t < G::P0)
-                {
-                    const int e = t / NM, q = t - e * NM;
-                    T *dst = slab + e * NQ * NMP + q;
-#pragma unroll
-                    for (int i = 0; i < NQ; ++i)
-                        dst[i * NMP] = acc[s][i];
-                }
-            }
-            wave_lds_fence();
-        }
+#define SWEEP G::Sw0
+#define SWEEP_CONTRACT contract
+#define SWEEP_BASIS bs[0]
+#include "frag/sweep.inc"
         // ---- direction 1: out[e][j][i] = sum_q w[(e,i)][q] * B1[q][j] ---------------------------
         {
             T u[G::PASS1][NM], acc[G::PASS1][NQ];

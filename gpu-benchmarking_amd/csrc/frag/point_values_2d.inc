@@ -1,7 +1,7 @@
 // frag/point_values_2d.inc -- last forward sweep of a quad, q -> j, into registers, and the two derivatives of u.
 // Expects: T, NM, NQ, NQP, NMP, NP, NPASS, BMODE; b1 (nm x nq), d0, d1 (nq x nq); slab, imgU, lane; the lane roles
 //          (frag/lane_roles_2d.inc); u[NPASS][NQ] and dreg[NPASS][NQ], declared by the kernel.
-// Slab before: w1[(e,i)][q] (frag/forward0_2d.inc).  After: imgU = du_0 (index (e nq + j) NQP + i), fenced.
+// Slab before: w1[(e,i)][q] (frag/forward0.inc).  After: imgU = du_0 (index (e nq + j) NQP + i), fenced.
 // Registers of the column's lane (e,i): u = the point values, dreg = du_1, both over j.
             {
                 T m[NPASS][NM];

@@ -14,7 +14,7 @@ template <int DIM, int NQ, int EC, int WPB, int BMODE, int MINW, int KMAP, int M
 static int launch_iprod(const ArgsT<DIM, T> &a, hipStream_t s)
 {
     static OccCache cache = {};
-    constexpr size_t lds = iprod_lds_bytes<NQ, EC, DIM, WPB, T>();
+    constexpr size_t lds = slab_lds_bytes<IprodGeom<NQ, EC, DIM, T>, WPB>();
     static_assert(lds <= 160 * 1024, "LDS slab exceeds 160 KiB");
     static_assert(KMAP > 0, "short-lived waves: the grid covers the batch");
     if constexpr (DIM == 3)

@@ -35,11 +35,15 @@
 // it were written out (helper functions changed the code of tuned instantiations, DESIGN s9 item 7).  Every fragment
 // opens with its contract: what it computes, the names it expects in scope and declares, the slab before and after.
 // The names the kernels agree on: G the geometry whose SLAB the wave owns, M the MassGeom (transposed half, output), F
-// the WaveGeom (forward half), IO the chunk I/O view; NP / NPASS the point columns per chunk and their passes.  A
+// the WaveGeom (forward half), IO the chunk I/O view (IN_LEN, IN_ELEM, IN_DBL, IN_STRIDE, NLD, OUT_DBL, VEC2, ALIGN_OK:
+// a SweepGeom has them, MassIo takes them from F and M); NP / NPASS the point columns per chunk and their passes.  A
 // kernel below reads as its own lines between the includes:
 //   wave_slab, wave_chunks, chunk_fetch_first | per chunk: chunk_head, chunk_stage, [the weight loads],
-//   chunk_fetch_next, forward0_{3d,2d}, forward1_3d, [last forward sweep, weight, first transposed sweep],
+//   chunk_fetch_next, forward0, forward1_3d, [last forward sweep, weight, first transposed sweep],
 //   transposed1_3d, transposed0 (which ends with chunk_flush and the closing fence).
+// forward0, forward1_3d and transposed1_3d are instances of frag/sweep.inc, the one sweep text of the wave kernels
+// (bwdtrans_wave.h): each names its Sweep (F::Sw0, F::Sw1, M::SwT1), its contraction and its basis.  The kernels that
+// have one chunk per wave and no loop (bwdtrans_aniso.h) open with wave_slab, wave_one_chunk.
 #pragma once
 
 #include "iproduct_wave.h"
@@ -61,6 +65,7 @@ template <int NQ, int EC, int DIM, typename T = double> struct MassGeom
     static constexpr int PT1 = (DIM == 3) ? EC * NM * NM : EC * NM; // pencils over i, read by the sweep i -> p'
     static constexpr int PASST2 = cdiv(PT2 > 0 ? PT2 : 1, kWave);
     static constexpr int PASST1 = cdiv(PT1, kWave);
+    using SwT1 = Sweep<NQ, NM, PT2, NQP, 1, NQ, NQP>; // the sweep j -> q' (3D only): (e,r') in the place of e
     static constexpr int SLAB_T = CMax<PT2, PT1>::value * NQP;
     static constexpr int OUT_DBL = EC * NMT; // scalars per chunk written to HBM
     static constexpr int SLAB =
@@ -68,13 +73,14 @@ template <int NQ, int EC, int DIM, typename T = double> struct MassGeom
     static_assert(SLAB <= IprodGeom<NQ, EC, DIM, T>::SLAB, "the fused slab stays within the IProductWRTBase slab");
 };
 
-// The view that the chunk I/O of bwdtrans_wave.h takes of the geometry: the input side of BwdTrans on both ends.
+// The view that the chunk I/O of bwdtrans_wave.h takes of the geometry: the input side of BwdTrans on both ends.  (A
+// SweepGeom is its own view; this one joins the forward half's input to the transposed half's output.)
 template <class G> struct MassIo
 {
     using F      = typename G::F;
     using Scalar = typename G::Scalar;
     using Vec    = typename G::Vec;
-    static constexpr int VW = G::VW, NM = G::NM, NMT = G::NMT, IN_DBL = F::IN_DBL, IN_STRIDE = F::IN_STRIDE;
+    static constexpr int VW = G::VW, IN_LEN = F::IN_LEN, IN_ELEM = F::IN_ELEM, IN_DBL = F::IN_DBL, IN_STRIDE = F::IN_STRIDE;
     static constexpr int NLD = F::NLD, OUT_DBL = G::OUT_DBL;
     static constexpr bool VEC2 = F::VEC2, ALIGN_OK = F::ALIGN_OK;
 };
@@ -119,7 +125,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_mass_wave_kernel(
     using G          = M; // the slab is the mass slab
     using F          = typename M::F;
     using IO         = MassIo<M>;
-    constexpr int NM = M::NM, NMP = F::NMP, NQP = M::NQP, NM2 = NM * NM, NQ2 = NQ * NQ;
+    constexpr int NM = M::NM, NMP = F::NMP, NQP = M::NQP, NQ2 = NQ * NQ;
     constexpr int NPASS = F::PASS2, NP = F::P2; // the point columns (e,j,i)
     static_assert(OUTM == OUT_LDS, "the output (nm^3 per element) leaves through the LDS stream");
     static_assert(KMAP > 0, "short-lived waves only");
@@ -139,7 +145,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_mass_wave_kernel(
         T wv[NPASS][NQ];
         load_weights<NQ, NPASS, NP, NQ2>(wv, w + c * (uint64_t)(EC * M::NQT), evalid, lane);
 #include "frag/chunk_fetch_next.inc"
-#include "frag/forward0_3d.inc"
+#include "frag/forward0.inc"
 #include "frag/forward1_3d.inc"
         // ---- at the points (forward 2, the weight, transposed 2): lane (e,j,i) keeps its k-pencil in registers ----
         //      v[k] = w[e][k][j][i] * sum_r w2[(e,j,i)][r] * B2[r][k];  t2[(e,r',i)][j] = sum_k v[k] * B2[r'][k]
@@ -210,7 +216,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_mass_wave_kernel(
         T wv[NPASS][NQ];
         load_weights<NQ, NPASS, NP, NQ>(wv, w + c * (uint64_t)(EC * M::NQT), evalid, lane);
 #include "frag/chunk_fetch_next.inc"
-#include "frag/forward0_2d.inc"
+#include "frag/forward0.inc"
         // ---- at the points (forward 1, the weight, transposed 1): lane (e,i) keeps its j-pencil in registers ----
         //      v[j] = w[e][j][i] * sum_q w1[(e,i)][q] * B1[q][j];  t1[(e,q')][i] = sum_j v[j] * B1[q'][j]
         {

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_physderiv_wave_kernel(
     using M          = typename G::M;
     using F          = typename G::F;
     using IO         = MassIo<M>;
-    constexpr int NM = G::NM, NMP = F::NMP, NQP = G::NQP, NM2 = NM * NM, NQ2 = NQ * NQ, NQT = NQ2 * NQ;
+    constexpr int NM = G::NM, NMP = F::NMP, NQP = G::NQP, NQ2 = NQ * NQ, NQT = NQ2 * NQ;
     constexpr int NPASS = G::NPASS, NP = G::NP, RING = G::RING, NCOMP = 9;
     constexpr int PL = NQ * NQP, ES = NQ * PL; // plane and element stride of a point image
     static_assert(KMAP > 0, "short-lived waves only");
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_physderiv_wave_kernel(
                 load_df_slice<NPASS, NCOMP, NQ2, NQT>(dv[r], dc, doff, r);
         }
 #include "frag/chunk_fetch_next.inc"
-#include "frag/forward0_3d.inc"
+#include "frag/forward0.inc"
 #include "frag/forward1_3d.inc"
         // ---- forward 2 and everything at the points: lane (e,j,i) keeps its k-pencil in registers ---
         {
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_physderiv_wave_kernel(
                 load_df_slice<NPASS, NCOMP, NQ, NQT>(dv[r], dc, doff, r);
         }
 #include "frag/chunk_fetch_next.inc"
-#include "frag/forward0_2d.inc"
+#include "frag/forward0.inc"
         // ---- forward 1 and everything at the points: lane (e,i) keeps its j-pencil in registers -----
         {
             T u[NPASS][NQ], dreg[NPASS][NQ];

@@ -1,9 +1,8 @@
 // rtc.hip -- load / launch half of the run-time specialisation: sf_specialise() compiles (once per process, through
-// rtc_compile.cc) and loads (once per device) the wave-per-chunk kernel of bwdtrans_wave3.h / bwdtrans_wave2.h for the
+// rtc_compile.cc) and loads (once per device) the wave-per-chunk kernel of bwdtrans_aniso.h for the
 // extents a caller names; AUTO then launches it for shapes the compiled tables miss.  Nothing here compiles or loads
 // behind a launch: a launch only finds what sf_specialise() made ready.
-#include "bwdtrans_wave2.h"
-#include "bwdtrans_wave3.h"
+#include "bwdtrans_aniso.h"
 #include "rtc_compile.h"
 #include "sf_dispatch.h"
 
@@ -22,13 +21,15 @@ template <int A, int B, int S> constexpr bool rtc_pins2()
 {
     constexpr RtcCfg c = rtc_cfg(2, A, B, 0, S);
     using T            = typename std::conditional<S == 8, double, float>::type;
-    return c.slab == WaveGeom2<A, B, c.ec, T>::SLAB_OUT && c.lds == wave2_lds_bytes<A, B, c.ec, c.wpb, T>();
+    using G            = BwdGeom<2, c.ec, T, A, B>;
+    return c.slab == G::SLAB && c.lds == slab_lds_bytes<G, c.wpb>();
 }
 template <int A, int B, int C, int S> constexpr bool rtc_pins3()
 {
     constexpr RtcCfg c = rtc_cfg(3, A, B, C, S);
     using T            = typename std::conditional<S == 8, double, float>::type;
-    return c.slab == WaveGeom3<A, B, C, c.ec, T>::SLAB_OUT && c.lds == wave3_lds_bytes<A, B, C, c.ec, c.wpb, T>();
+    using G            = BwdGeom<3, c.ec, T, A, B, C>;
+    return c.slab == G::SLAB && c.lds == slab_lds_bytes<G, c.wpb>();
 }
 static_assert(kRtcBasisSmem == BASIS_SMEM && kRtcBasisCols == BASIS_SMEM_COLS, "basis modes");
 static_assert(rtc_pins2<4, 9, 8>() && rtc_pins2<16, 3, 8>() && rtc_pins2<12, 20, 8>() && rtc_pins2<23, 5, 8>() &&

@@ -173,7 +173,7 @@ int rtc_compile(const RtcKey &k, const std::string &arch, RtcCode *out)
         names[i] = kRtcHeaderNames[i], texts[i] = kRtcHeaderTexts[i];
     for (int i = 0; i < kNumStandIns; ++i)
         names[kRtcNumHeaders + i] = kStandInNames[i], texts[kRtcNumHeaders + i] = kStandInTexts[i];
-    const char *src = k.dim == 3 ? "#include \"bwdtrans_wave3.h\"\n" : "#include \"bwdtrans_wave2.h\"\n";
+    const char *src = "#include \"bwdtrans_aniso.h\"\n";
     const std::string expr = rtc_name_expression(k);
     const std::vector<std::string> opts = rtc_options(arch);
     std::vector<const char *> argv;

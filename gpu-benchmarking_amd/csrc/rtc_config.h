@@ -1,7 +1,6 @@
 // rtc_config.h -- launch configuration of the run-time specialised wave kernels (rtc.hip): which template arguments
 // a shape gets and how much dynamic LDS its launch needs.  Plain C++ (no HIP): the host restates, with run-time
-// constexpr functions, what Cfg3 (bwdtrans_rt.hip) and WaveGeom3 / WaveGeom2 (bwdtrans_wave3.h / bwdtrans_wave2.h)
-// compute at compile time.  bwdtrans_rt.hip and rtc.hip pin the two against each other with static_asserts, so the
+// constexpr functions, what Cfg3 (bwdtrans_rt.hip) and BwdGeom (bwdtrans_wave.h) compute at compile time.  bwdtrans_rt.hip and rtc.hip pin the two against each other with static_asserts, so the
 // host and the device cannot disagree on the slab size.
 #pragma once
 
@@ -31,12 +30,12 @@ constexpr int kRtcBasisSmem = 1, kRtcBasisCols = 2; // BASIS_SMEM / BASIS_SMEM_C
 struct RtcCfg
 {
     int ec, wpb, bmode, minw, xg;
-    int slab;   // scalars per wave (WaveGeom*::SLAB_OUT)
+    int slab;   // scalars per wave (BwdGeom::SLAB)
     size_t lds; // dynamic LDS bytes of one workgroup
     bool ok;    // false: the slab of one wave exceeds kRtcMaxLds
 };
 
-// WaveGeom3<NQ0, NQ1, NQ2, EC, T>::SLAB_OUT, vw = scalars per 16-byte lane
+// BwdGeom<3, EC, T, NQ0, NQ1, NQ2>::SLAB, vw = scalars per 16-byte lane
 constexpr int rtc_slab3(int nq0, int nq1, int nq2, int ec, int vw)
 {
     const int nm0 = nq0 - 1, nm1 = nq1 - 1, nm2 = nq2 - 1;
@@ -45,7 +44,7 @@ constexpr int rtc_slab3(int nq0, int nq1, int nq2, int ec, int vw)
     return (rtc_max(slab0, ec * nq0 * nq1 * nq2) + vw - 1) / vw * vw;
 }
 
-// WaveGeom2<NQ0, NQ1, EC, T>::SLAB_OUT
+// BwdGeom<2, EC, T, NQ0, NQ1>::SLAB
 constexpr int rtc_slab2(int nq0, int nq1, int ec, int vw)
 {
     const int nm0 = nq0 - 1, nm1 = nq1 - 1;

@@ -35,8 +35,9 @@ def aggregate_gdofs(total_elements, nm_tot, steps, max_elapsed_s):
 
 
 KERNEL_SOURCES = ("bwdtrans_wave.h", "wave_table.h", "bwdtrans_hex.hip", "bwdtrans_quad.hip",
-                  "bwdtrans_mfma.h", "bwdtrans_mfma4.h", "sf_common.h", "wave_launch.h",
-                  "bwdtrans_wave3.h", "bwdtrans_rt.h", "bwdtrans_rt.hip", "bwdtrans_hmfma4.h")
+                  "bwdtrans_mfma.h", "bwdtrans_mfma4.h", "sf_common.h", "wave_launch.h", "chunked_launch.h",
+                  "bwdtrans_aniso.h", "bwdtrans_rt.h", "bwdtrans_rt.hip", "bwdtrans_hmfma4.h",
+                  "frag/sweep.inc", "frag/sweep_store.inc")
 
 
 def kernel_source_hash(root):

@@ -104,8 +104,10 @@ def test_rtc_check_matches_the_aot_instantiation(pkg):
 def test_rtc_source_hash_is_the_hash_of_the_current_headers(pkg):
     """The library embeds the kernel headers at build time; the hash it prints must be that of the files as they are."""
     files = [("sf_common.h", "csrc/sf_common.h"), ("bwdtrans_wave.h", "csrc/bwdtrans_wave.h"),
-             ("bwdtrans_wave3.h", "csrc/bwdtrans_wave3.h"), ("bwdtrans_wave2.h", "csrc/bwdtrans_wave2.h"),
-             ("../../include/sumfact.h", "../include/sumfact.h")]
+             ("bwdtrans_aniso.h", "csrc/bwdtrans_aniso.h")]
+    files += [(f"frag/{f}.inc", f"csrc/frag/{f}.inc")
+              for f in ("wave_slab", "wave_one_chunk", "chunk_head", "sweep", "sweep_store")]
+    files += [("../../include/sumfact.h", "../include/sumfact.h")]
     x = 0xcbf29ce484222325
     for name, path in files:
         with open(os.path.join(PKG, path), "rb") as f:
