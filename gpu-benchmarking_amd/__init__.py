@@ -21,4 +21,5 @@ from .bwdtrans import (  # noqa: F401
     helmholtz_hex, helmholtz_quad, affine_helmholtz_hex, affine_helmholtz_quad,
     physderiv_hex, physderiv_quad,
     iprodderiv_hex, iprodderiv_quad, physderiv_autograd,
+    diag_tables, diag_helmholtz_hex, diag_helmholtz_quad,
 )

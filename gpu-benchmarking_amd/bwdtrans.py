@@ -71,9 +71,11 @@ def quad_wsp_doubles(nq, nelmt):
 # family without one; whether float32 quietly takes the AUTO route for any `variant` (BwdTrans) or refuses all but "auto";
 # BwdTrans only: wsp_need(nelmt) -> {variant: numel of the caller-owned workspace it needs}; out_parts: the number of
 # separate output arrays of the C call (1: `out` is one flat tensor; d: `out` is a (d, n) tensor or a sequence of d tensors);
-# inp_parts: the same for the input arrays (1: `inp` is one flat tensor; d: a (d, n) tensor or a sequence of d tensors).
+# inp_parts: the same for the input arrays (1: `inp` is one flat tensor; d: a (d, n) tensor or a sequence of d tensors; 0:
+# the C call has no input array -- `inp` is then the operand that sizes the batch, `anchor`(points per element) values per
+# element, listed among the extras and passed there only).
 _Family = collections.namedtuple("_Family", "stem inp_points out_points extras lam f32_ignores_variant wsp_need out_parts "
-                                 "inp_parts", defaults=(lambda nelmt, nqt: [], None, False, None, 1, 1))
+                                 "inp_parts anchor", defaults=(lambda nelmt, nqt: [], None, False, None, 1, 1, None))
 
 
 def _output_parts(what, out, parts, numel, inp):
@@ -125,7 +127,7 @@ def _input_parts(what, inp, parts):
 
 def _operator_call(what, fam, nq, bases, inp, out, variant, stream, wsp=None):
     """The one call path of bwdtrans_* / iproduct_* / mass_* / helmholtz_* / affine_helmholtz_* / physderiv_* /
-    iprodderiv_*: sizes, dtypes and devices are checked here (before any library call), pointers, alignment and overlap in
+    iprodderiv_* / diag_helmholtz_*: sizes, dtypes and devices are checked here (before any library call), pointers, alignment and overlap in
     the C ABI."""
     nq = tuple(int(x) for x in nq)
     ins = None
@@ -138,10 +140,15 @@ def _operator_call(what, fam, nq, bases, inp, out, variant, stream, wsp=None):
     if nmt <= 0:
         raise capi.SumfactError(capi.SF_EINVAL, what)
     n_in, n_out = nqt if fam.inp_points else nmt, nqt if fam.out_points else nmt
+    if fam.inp_parts == 0:
+        if not isinstance(inp, torch.Tensor):
+            raise TypeError(f"{what}: the operand that sizes the batch must be a tensor")
+        n_in = fam.anchor(nqt)
     nelmt = inp.numel() // n_in
     if nelmt * n_in != inp.numel():
-        raise ValueError(f"{what}: in.numel() is not a multiple of the {'points' if fam.inp_points else 'modes'} per "
-                         f"element ({n_in})")
+        raise ValueError(f"{what}: {'in' if fam.inp_parts else 'the operand that sizes the batch'}.numel() is not a "
+                         f"multiple of the {'values' if not fam.inp_parts else 'points' if fam.inp_points else 'modes'} "
+                         f"per element ({n_in})")
     if fam.out_parts > 1:
         out, outs = _output_parts(what, out, fam.out_parts, nelmt * n_out, inp)
     else:
@@ -167,10 +174,10 @@ def _operator_call(what, fam, nq, bases, inp, out, variant, stream, wsp=None):
     ptrs = [None if t is None else _dev_ptr(t, name, dtype) for name, t, _, _ in operands]
     if lam is not None:
         ptrs.append(ctypes.c_double(lam))
-    if ins is None:
-        ptrs.append(_dev_ptr(inp, "in", dtype))
-    else:
+    if ins is not None:
         ptrs += [_dev_ptr(t, f"in{a}", dtype) for a, t in enumerate(ins)]
+    elif fam.inp_parts:
+        ptrs.append(_dev_ptr(inp, "in", dtype))
     if fam.wsp_need is not None and not f32:
         ptrs.append(None if wsp is None else _dev_ptr(wsp, "wsp", dtype))
     with torch.cuda.device(inp.device):
@@ -333,6 +340,61 @@ def iprodderiv_quad(nq, basis0, basis1, deriv0, deriv1, df, w, inp, out=None, va
     planes of df (or None), one of w (or None), inp a (2, n) tensor or a sequence of two flat tensors."""
     return _operator_call("iprodderiv_quad", _iprodderiv(nq, (deriv0, deriv1), df, w), nq, (basis0, basis1), inp, out,
                           variant, stream)
+
+
+def diag_tables(nq_d, basis, deriv, stream=None):
+    """The three tables of one direction for diag_helmholtz_*: with E[p][i] = sum_m deriv[i][m] basis[p][m] (the
+    derivative of mode p at point i), a flat tensor tab[t][p][i], t = 0, 1, 2, of basis * basis, E * basis and E * E: 3 nm nq
+    values, on basis's device, in one small kernel.  They depend on the order only: build them once."""
+    nq_d = int(nq_d)
+    if nq_d < 2:
+        raise capi.SumfactError(capi.SF_EINVAL, "diag_tables")
+    if not isinstance(basis, torch.Tensor) or basis.dtype not in (torch.float64, torch.float32):
+        raise TypeError("diag_tables: basis must be a float64 or float32 tensor")
+    if basis.numel() != (nq_d - 1) * nq_d:
+        raise ValueError(f"diag_tables: basis has {basis.numel()} values, not {(nq_d - 1) * nq_d}")
+    _check_operands("diag_tables", [("deriv", deriv, nq_d * nq_d, False)], basis)
+    f32 = basis.dtype == torch.float32
+    ptrs = [_dev_ptr(basis, "basis", basis.dtype), _dev_ptr(deriv, "deriv", basis.dtype)]
+    tab = torch.empty(3 * (nq_d - 1) * nq_d, dtype=basis.dtype, device=basis.device)
+    with torch.cuda.device(basis.device):
+        rc = (capi.lib().sf_diag_tables_f32 if f32 else capi.lib().sf_diag_tables_f64)(
+            nq_d, *ptrs, _dev_ptr(tab, "tab", basis.dtype), _stream(stream, basis.device))
+    capi.check(rc, "sf_diag_tables")
+    return tab
+
+
+def _diag(what, nq, bases, derivs, g, w, lam, out, variant, stream, tabs):
+    nq = tuple(int(q) for q in nq)
+    ncomp = len(nq) * (len(nq) + 1) // 2
+    if tabs is None:
+        if any(q < 2 for q in nq):
+            raise capi.SumfactError(capi.SF_EINVAL, what)
+        tabs = [diag_tables(q, b, d, stream) for q, b, d in zip(nq, bases, derivs)]
+    tabs = tuple(tabs)
+    if len(tabs) != len(nq):
+        raise ValueError(f"{what}: tabs holds {len(tabs)} tensors, not {len(nq)}")
+    fam = _Family("diag_helmholtz", False, False, lambda nelmt, nqt: _per_direction("tab", tabs, lambda q: 3 * (q - 1) * q, nq) + [
+        ("g", g, nelmt * ncomp * nqt, False), ("w", w, nelmt * nqt, True)], lam, inp_parts=0, anchor=lambda nqt: ncomp * nqt)
+    return _operator_call(what, fam, nq, (), g, out, variant, stream)
+
+
+def diag_helmholtz_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, g, w, lam, out=None, variant="auto", stream=None,
+                       tabs=None):
+    """The diagonal of helmholtz_hex's operator, per element, in one kernel on g's device: out[e][r][q][p] =
+    (B^T [lam diag(w_e) + sum_ab D_a^T diag(G_ab,e) D_b] B)[rqp][rqp] -- what a Jacobi preconditioner or a Chebyshev smoother
+    needs.  The bases, derivative matrices, g, w (or None with lam == 0) and lam of helmholtz_hex; out holds nm0*nm1*nm2
+    modes per element and may not overlap g, w or a table.  tabs: the three tensors of diag_tables(nq_d, basis_d, deriv_d),
+    built here when None; when given, the bases and derivative matrices are not looked at.  float64 takes variant
+    "auto", "wave" or "generic"; float32 the AUTO route.  A plain function: no autograd."""
+    return _diag("diag_helmholtz_hex", nq, (basis0, basis1, basis2), (deriv0, deriv1, deriv2), g, w, lam, out, variant,
+                 stream, tabs)
+
+
+def diag_helmholtz_quad(nq, basis0, basis1, deriv0, deriv1, g, w, lam, out=None, variant="auto", stream=None, tabs=None):
+    """The diagonal of helmholtz_quad's operator: g[e][c][j][i] with c = 0..2 for (00, 01, 11), w[e][j][i] or None with
+    lam == 0; tabs: the two tensors of diag_tables, built here when None."""
+    return _diag("diag_helmholtz_quad", nq, (basis0, basis1), (deriv0, deriv1), g, w, lam, out, variant, stream, tabs)
 
 
 class _BwdTrans(torch.autograd.Function):

@@ -43,20 +43,22 @@ SYMBOLS = {
     "sf_bwdtrans_specialised": (_i, [_i, _u, _u, _u, _i, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sf_last_specialise_log": (ctypes.c_char_p, []),
     "sf_shutdown": (_i, []),
+    "sf_diag_tables_f64": (_i, [_u, _vp, _vp, _vp, _vp]),
+    "sf_diag_tables_f32": (_i, [_u, _vp, _vp, _vp, _vp]),
 }
 
 
 def _operator_symbols():
-    """sf_<stem>_{hex,quad}_{f64,f64_variant,f32} of the seven operator families: [variant,] the extents, nelmt, the pointer
-    operands in front of `in` (so many per direction, so many per call), [lambda,] in (or one input per direction),
-    [BwdTrans _variant: wsp,] out (or one output per direction), stream."""
-    rows = {"bwdtrans": (1, 0, False, False, False), "iproduct": (1, 0, False, False, False),
-            "mass": (1, 1, False, False, False), "helmholtz": (2, 2, True, False, False),
-            "affine_helmholtz": (3, 2, True, False, False), "physderiv": (2, 1, False, True, False),
-            "iprodderiv": (2, 2, False, False, True)}
-    for stem, (per_direction, per_call, has_lambda, out_per_direction, in_per_direction) in rows.items():
+    """sf_<stem>_{hex,quad}_{f64,f64_variant,f32} of the eight operator families: [variant,] the extents, nelmt, the pointer
+    operands in front of `in` (so many per direction, so many per call), [lambda,] in (or one input per direction, or none:
+    diag_helmholtz reads only its operands), [BwdTrans _variant: wsp,] out (or one output per direction), stream."""
+    rows = {"bwdtrans": (1, 0, False, False, 1), "iproduct": (1, 0, False, False, 1),
+            "mass": (1, 1, False, False, 1), "helmholtz": (2, 2, True, False, 1),
+            "affine_helmholtz": (3, 2, True, False, 1), "physderiv": (2, 1, False, True, 1),
+            "iprodderiv": (2, 2, False, False, "per direction"), "diag_helmholtz": (1, 2, True, False, 0)}
+    for stem, (per_direction, per_call, has_lambda, out_per_direction, inputs) in rows.items():
         for shape, dim in (("hex", 3), ("quad", 2)):
-            ins = [_vp] * (dim if in_per_direction else 1)
+            ins = [_vp] * (dim if inputs == "per direction" else inputs)
             outs = [_vp] * (dim if out_per_direction else 1)
             tail = [_vp] * (per_direction * dim + per_call) + ([ctypes.c_double] if has_lambda else []) + ins + outs + [_vp]
             for sfx in ("f64", "f64_variant", "f32"):

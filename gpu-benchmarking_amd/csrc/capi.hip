@@ -1,12 +1,13 @@
 // capi.hip -- the extern "C" boundary of libsumfact.so (declared in include/sumfact.h).
 // Validation + dispatch only: every operator entry point forwards to one template <int DIM, typename T> function below
-// (bwdtrans, iprod, mass, helmholtz, affine, physderiv, iprodderiv), which validates, builds ArgsT<DIM, T> and routes to the launchers that
+// (bwdtrans, iprod, mass, helmholtz, affine, physderiv, iprodderiv, diag), which validates, builds ArgsT<DIM, T> and routes to the launchers that
 // sf_dispatch.h declares.  Kernels live in bwdtrans_hex.hip / bwdtrans_quad.hip / bwdtrans_rt.hip /
 // bwdtrans_generic.hip / aux_kernels.hip, IProductWRTBase in iproduct.hip / iproduct_generic.hip, the fused mass
 // operator in mass.hip / mass_f32.hip / mass_generic.hip, the fused Helmholtz operator in helmholtz.hip /
 // helmholtz_f32.hip / helmholtz_generic.hip, its affine-element form in affine.hip / affine_f32.hip / affine_generic.hip,
 // BwdTrans fused with the physical-space gradient in physderiv.hip / physderiv_f32.hip / physderiv_generic.hip, its
-// transpose IProductWRTDerivBase in iprodderiv.hip / iprodderiv_f32.hip / iprodderiv_generic.hip.
+// transpose IProductWRTDerivBase in iprodderiv.hip / iprodderiv_f32.hip / iprodderiv_generic.hip, the diagonal of the
+// Helmholtz operator in diag.hip / diag_f32.hip / diag_generic.hip.
 #include "sf_dispatch.h"
 
 #include <cstdio>
@@ -321,6 +322,51 @@ static int iprodderiv(int variant, const unsigned (&nq)[3], size_t nelmt, const 
         variant, nq, iprodderiv_generic_built(DIM, nq[0], nq[1], nq[2]), iprodderiv_wave_built(DIM, nq[0]), out, out,
         [&] { return launch_iprodderiv_wave<DIM, T>(nq[0], a, x, s); },
         [&] { return launch_iprodderiv_generic<DIM, T>(nq, a, x, s); });
+}
+
+// ---- the diagonal of the fused Helmholtz operator: one validation and routing for both dimensions and scalar types ------
+// The order of sf_helmholtz_* without `in`: the table triples of sf_diag_tables_* stand where the bases do, `w` is looked
+// at only when lambda != 0, `out` is the only 16-byte stream of the wave kernels.
+template <int DIM, typename T>
+static int diag(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&tab)[3], const T *g, const T *w,
+                double lambda, T *out, void *stream)
+{
+    const bool has_w = lambda != 0.0; // false for NaN too, which is refused with the nulls
+    const int rc     = validate(range_ok<DIM>(variant, nq), nelmt,
+                                {tab[0], tab[1], DIM == 3 ? tab[2] : tab[0], g, out, has_w ? w : g}, sizeof(T),
+                                lambda - lambda == 0.0);
+    if (rc != kProceed)
+        return rc;
+    // the output may not overlap what the call reads
+    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
+    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
+    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
+    if (overlaps(out, modes_bytes, g, (DIM == 3 ? 6 : 3) * points_bytes) || (has_w && overlaps(out, modes_bytes, w, points_bytes)))
+        return SF_EINVAL;
+    for (int d = 0; d < DIM; ++d)
+        if (overlaps(out, modes_bytes, tab[d], sizeof(T) * 3 * (nq[d] - 1) * nq[d]))
+            return SF_EINVAL;
+    const hipStream_t s = (hipStream_t)stream;
+    const auto a        = make_args<DIM, T>(tab, nullptr, nullptr, out, nelmt); // the tables in the place of the bases
+    const DiagArgsT<T> x{g, has_w ? w : nullptr, (T)lambda};                    // lambda is rounded to T here, once
+    return route<DIM>(
+        variant, nq, diag_generic_built(DIM, nq[0], nq[1], nq[2]), diag_wave_built(DIM, nq[0]), out, out,
+        [&] { return launch_diag_wave<DIM, T>(nq[0], a, x, s); }, [&] { return launch_diag_generic<DIM, T>(nq, a, x, s); });
+}
+
+// the tables of one direction: range, nulls, scalar alignment, `tab` overlapping an input, then the one kernel
+template <typename T> static int diag_tables(unsigned nq, const T *basis, const T *deriv, T *tab, void *stream)
+{
+    if (nq < 2 || nq > 1024)
+        return SF_EINVAL;
+    if (!basis || !deriv || !tab)
+        return SF_EINVAL;
+    if (!aligned(basis, sizeof(T)) || !aligned(deriv, sizeof(T)) || !aligned(tab, sizeof(T)))
+        return SF_EALIGN;
+    const size_t nb = sizeof(T) * (nq - 1) * nq;
+    if (overlaps(tab, 3 * nb, basis, nb) || overlaps(tab, 3 * nb, deriv, sizeof(T) * nq * nq))
+        return SF_EINVAL;
+    return launch_diag_tables<T>(nq, basis, deriv, tab, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -704,6 +750,56 @@ int sf_iprodderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float
 {
     return iprodderiv<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
                                 {deriv0, deriv1, nullptr}, df, w, {in0, in1, nullptr}, out, stream);
+}
+
+// ---- the diagonal of the fused Helmholtz operator: Jacobi preconditioner, Chebyshev smoother, diagonal scaling ----------
+int sf_diag_tables_f64(unsigned nq, const double *basis, const double *deriv, double *tab, void *stream)
+{
+    return diag_tables<double>(nq, basis, deriv, tab, stream);
+}
+
+int sf_diag_tables_f32(unsigned nq, const float *basis, const float *deriv, float *tab, void *stream)
+{
+    return diag_tables<float>(nq, basis, deriv, tab, stream);
+}
+
+int sf_diag_helmholtz_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *tab0,
+                                      const double *tab1, const double *tab2, const double *g, const double *w,
+                                      double lambda, double *out, void *stream)
+{
+    return diag<3, double>(variant, {nq0, nq1, nq2}, nelmt, {tab0, tab1, tab2}, g, w, lambda, out, stream);
+}
+
+int sf_diag_helmholtz_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *tab0, const double *tab1,
+                              const double *tab2, const double *g, const double *w, double lambda, double *out,
+                              void *stream)
+{
+    return diag<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {tab0, tab1, tab2}, g, w, lambda, out, stream);
+}
+
+int sf_diag_helmholtz_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *tab0,
+                                       const double *tab1, const double *g, const double *w, double lambda, double *out,
+                                       void *stream)
+{
+    return diag<2, double>(variant, {nq0, nq1, 0u}, nelmt, {tab0, tab1, nullptr}, g, w, lambda, out, stream);
+}
+
+int sf_diag_helmholtz_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *tab0, const double *tab1,
+                               const double *g, const double *w, double lambda, double *out, void *stream)
+{
+    return diag<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {tab0, tab1, nullptr}, g, w, lambda, out, stream);
+}
+
+int sf_diag_helmholtz_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *tab0, const float *tab1,
+                              const float *tab2, const float *g, const float *w, double lambda, float *out, void *stream)
+{
+    return diag<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {tab0, tab1, tab2}, g, w, lambda, out, stream);
+}
+
+int sf_diag_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *tab0, const float *tab1,
+                               const float *g, const float *w, double lambda, float *out, void *stream)
+{
+    return diag<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {tab0, tab1, nullptr}, g, w, lambda, out, stream);
 }
 
 int sf_sumsq_f32(const float *x, size_t n, double *result_host, void *stream)

@@ -157,6 +157,24 @@ template <int DIM, typename T>
 int launch_iprodderiv_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const IprodDerivArgsT<T> &x, hipStream_t s);
 bool iprodderiv_wave_built(int dim, unsigned nq);
 bool iprodderiv_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
+// The diagonal of the fused Helmholtz operator, diag(B^T [lambda diag(w) + sum_ab D_a^T diag(G_ab) D_b] B) (diag.hip /
+// diag_f32.hip: the wave kernels of diag_wave.h, the Helmholtz table; diag_generic.hip: any extents up to 12 per direction
+// in 3D and 32 in 2D, and the kernel that forms the tables).  There is no input array: b0 .. b2 of the BwdTrans arguments
+// are the table triples tab_d[t][p][i] of sf_diag_tables_*, `in` is not used.  Beyond them: the metric planes, the mass
+// weight (null: lambda == 0, never read) and lambda in the scalar type.
+template <typename T> struct DiagArgsT
+{
+    const T *g, *w;
+    T lam;
+};
+template <int DIM, typename T>
+int launch_diag_wave(unsigned nq, const ArgsT<DIM, T> &a, const DiagArgsT<T> &x, hipStream_t s);
+template <int DIM, typename T>
+int launch_diag_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const DiagArgsT<T> &x, hipStream_t s);
+bool diag_wave_built(int dim, unsigned nq);
+bool diag_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
+// tab[t][p][i], t = 0, 1, 2: B o B, E o B, E o E with E[p][i] = sum_m deriv[i*nq + m] basis[p*nq + m]; one kernel
+template <typename T> int launch_diag_tables(unsigned nq, const T *basis, const T *deriv, T *tab, hipStream_t s);
 int sumsq_f32_blocking(const float *x, size_t n, double *result_host, hipStream_t s);
 int fill_sincos_f32(float *in, size_t nelmt, size_t nm_tot, hipStream_t s);
 int fill_basis_f32(float *b, size_t nm, size_t nq, hipStream_t s);

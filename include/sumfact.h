@@ -571,6 +571,81 @@ int sf_iprodderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float
                            const float *deriv0, const float *deriv1, const float *df, const float *w,
                            const float *in0, const float *in1, float *out, void *stream);
 
+/*
+ * The DIAGONAL of the fused Helmholtz operator of sf_helmholtz_*, per element:
+ *   diag_e = diag( B^T [ lambda diag(w_e) + sum_a sum_b D_a^T diag(G_ab,e) D_b ] B )
+ * what a Jacobi preconditioner, a Chebyshev smoother or a diagonal scaling of a matrix-free Poisson / Helmholtz /
+ * implicit-diffusion solve needs next to the operator itself, in ONE kernel: per element the call reads the
+ * (1 + d(d+1)/2) nq^d metric scalars of sf_helmholtz_* (one plane fewer with lambda == 0) and writes nm^d modes; applying
+ * the operator to nm^d unit vectors costs nm^d launches and nm^d times that traffic.  Two calls:
+ *
+ * sf_diag_tables_*: the tables of ONE direction, once per order (they depend on the basis and the derivative matrix only).
+ *   With E[p][i] = sum_m deriv[i*nq + m] * basis[p*nq + m], the derivative of mode p at point i, the call writes
+ *   tab[t][p][i], t = 0, 1, 2:  T^0 = B o B,  T^1 = E o B,  T^2 = E o E  (elementwise products), each row-major nm x nq
+ *   like a basis: 3 nm nq scalars, caller-owned.  Rounding: E is an ascending sum over m, the first product a multiply,
+ *   then FMAs; every table entry is a single product.  One small kernel, no allocation, capture-safe.  Validation, before
+ *   any HIP call: nq < 2 or nq > 1024: SF_EINVAL; a null pointer: SF_EINVAL; a pointer not scalar-aligned: SF_EALIGN;
+ *   `tab` overlapping `basis` or `deriv` as byte ranges: SF_EINVAL.
+ *
+ * sf_diag_helmholtz_*: with tab_d the table triple of direction d,
+ *   3D: out[e][r][q][p] = sum_kji lambda w[e][k][j][i] T0^0[p][i] T1^0[q][j] T2^0[r][k]
+ *                       + sum_c f_c sum_kji g[e][c][k][j][i] T0^{s0}[p][i] T1^{s1}[q][j] T2^{s2}[r][k]
+ *   2D: the same without k and r.  For the plane c = (a, b) of g: s_d = [d == a] + [d == b] is the table of direction d,
+ *   f_c = 1 if a == b, else 2 (the symmetric pair is stored once).  Seven terms in 3D, four in 2D.
+ * Layout: g and w exactly as in sf_helmholtz_* (g[e][c][k][j][i], component order 3D (00, 01, 02, 11, 12, 22), 2D (00,
+ * 01, 11); w[e][k][j][i]); g may be indefinite.  out: nm0*nm1[*nm2] modes per element, p fastest, the layout of the
+ * output of sf_iproduct_*.  If lambda == 0, `w` may be NULL: it is then never read (nor validated), and the call moves one
+ * plane less.  lambda is a double in every entry point, rounded to the scalar type once, before the launch.
+ * Why tables in memory: the kernels take their one-dimensional operands as wave-uniform scalar-register rows straight
+ * from global memory; forming B o B or E o B inside a sweep would cost a vector multiply per FMA.
+ * Order of operations (it defines the rounding; every sum in ascending index, the first product a multiply, then FMAs;
+ * each image below is a sum of its own, merges are additions; the wave kernels and the fallback follow it alike):
+ *   3D, the planes in the order of g, c = 0 .. 5, contraction order k -> r, j -> q, i -> p:
+ *   1. k -> r: A_c[r][j][i] = sum_k g_c[k][j][i] T2^{s2}[r][k]; A_1, A_2, A_4 (the off-diagonal planes) are doubled, which
+ *      is exact; if lambda != 0: A_5 = A_5 + sum_k (lambda w[k][j][i]) T2^0[r][k]      -- six images, one merge
+ *   2. j -> q: S_c[r][q][i] = sum_j A_c[r][j][i] T1^{s1}[q][j], merged by the direction-0 table in the order of the planes:
+ *      B^2 = S_0,  B^1 = S_1 + S_2,  B^0 = (S_3 + S_4) + S_5                           -- three images, three merges
+ *   3. i -> p: out[r][q][p] = (sum_i B^0 T0^0[p][i] + sum_i B^1 T0^1[p][i]) + sum_i B^2 T0^2[p][i]       -- two merges
+ *   2D, contraction order j -> q, i -> p:
+ *   1. j -> q: B^0[q][i] = sum_j g_2 T1^2[q][j] (if lambda != 0: + sum_j (lambda w) T1^0[q][j]),
+ *      B^1 = 2 sum_j g_1 T1^1[q][j],  B^2 = sum_j g_0 T1^0[q][j]
+ *   2. i -> p: as step 3 above.
+ * Routes, through the same dispatch as the other operators: SF_VARIANT_AUTO runs the wave kernel for the isotropic orders
+ * of its table (3D nq 2..8, 2D nq 2..16: the table of sf_helmholtz_*, no row left out) when `out` is 16-byte aligned, else
+ * GENERIC; SF_VARIANT_WAVE returns SF_ENOTBUILT off that table and SF_EALIGN unless `out` is 16-byte aligned;
+ * SF_VARIANT_GENERIC (one workgroup per element, latency-bound) takes any extents up to 12 per direction in 3D and 32 in 2D
+ * -- 3D nq 9..12, all anisotropic shapes and an `out` that is only scalar-aligned take it; any other variant SF_ENOTBUILT,
+ * extents beyond those bounds SF_ENOTBUILT.  g, w and the tables are read one scalar per lane or as scalar operands and
+ * need only scalar alignment on every route.
+ * Validation, before any HIP call, in this order: (1) an extent < 2 or a variant outside [0, SF_NUM_VARIANTS):
+ * SF_EINVAL; (2) nelmt == 0: SF_OK; (3) a null table, g or out, a null w with lambda != 0, or a lambda that is not finite:
+ * SF_EINVAL; (4) any of them (w only if lambda != 0) not scalar-aligned: SF_EALIGN; (5) `out` overlapping `g`, (if
+ * lambda != 0) `w`, or any of the tables, compared as byte ranges of their full sizes: SF_EINVAL; (6) extents beyond the
+ * fallback's bounds: SF_ENOTBUILT; (7) an unsupported variant: SF_ENOTBUILT.  The inputs may overlap each other (all are
+ * only read).
+ * No internal workspace and no allocation: every call is a single kernel node, capture-safe from the process's first
+ * call, thread-safe as the rest.
+ */
+int sf_diag_tables_f64(unsigned nq, const double *basis, const double *deriv, double *tab, void *stream);
+int sf_diag_tables_f32(unsigned nq, const float *basis, const float *deriv, float *tab, void *stream);
+int sf_diag_helmholtz_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                              const double *tab0, const double *tab1, const double *tab2,
+                              const double *g, const double *w, double lambda, double *out, void *stream);
+int sf_diag_helmholtz_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                                      const double *tab0, const double *tab1, const double *tab2,
+                                      const double *g, const double *w, double lambda, double *out, void *stream);
+int sf_diag_helmholtz_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *tab0, const double *tab1,
+                               const double *g, const double *w, double lambda, double *out, void *stream);
+int sf_diag_helmholtz_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *tab0,
+                                       const double *tab1, const double *g, const double *w, double lambda,
+                                       double *out, void *stream);
+/* T = float (AUTO route; every array 4-byte aligned; lambda stays a double) */
+int sf_diag_helmholtz_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *tab0,
+                              const float *tab1, const float *tab2, const float *g, const float *w, double lambda,
+                              float *out, void *stream);
+int sf_diag_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *tab0, const float *tab1,
+                               const float *g, const float *w, double lambda, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
