@@ -22,4 +22,5 @@ from .bwdtrans import (  # noqa: F401
     physderiv_hex, physderiv_quad,
     iprodderiv_hex, iprodderiv_quad, physderiv_autograd,
     diag_tables, diag_helmholtz_hex, diag_helmholtz_quad,
+    GsMap, gs_setup, global_to_local, assemble, gs,
 )

@@ -397,6 +397,95 @@ def diag_helmholtz_quad(nq, basis0, basis1, deriv0, deriv1, g, w, lam, out=None,
     return _diag("diag_helmholtz_quad", nq, (basis0, basis1), (deriv0, deriv1), g, w, lam, out, variant, stream, tabs)
 
 
+class GsMap:
+    """What gs_setup returns: the local-to-global map `l2g` (int32, nlocal entries) and its inverted index `rows` (nglobal
+    words) / `perm` (nlocal words), all on one device.  rows / perm are opaque: only the library reads them."""
+
+    def __init__(self, l2g, rows, perm, nlocal, nglobal):
+        self.l2g, self.rows, self.perm, self.nlocal, self.nglobal = l2g, rows, perm, nlocal, nglobal
+
+
+def gs_setup(l2g, nglobal, stream=None):
+    """Invert the local-to-global map once (blocking): l2g[i] is the global degree of freedom of local coefficient i, a
+    negative entry a coefficient that belongs to none; every entry must be < nglobal (else SumfactError SF_EINVAL).
+    Returns the GsMap that global_to_local, assemble and gs take."""
+    nglobal = int(nglobal)
+    if not (isinstance(l2g, torch.Tensor) and l2g.dtype == torch.int32):
+        raise TypeError("gs_setup: l2g must be an int32 tensor")
+    if nglobal < 0:
+        raise ValueError("gs_setup: nglobal is negative")
+    l2g = l2g.reshape(-1)
+    nlocal = l2g.numel()
+    rows = torch.zeros(nglobal, dtype=torch.int32, device=l2g.device)    # a map of no coefficients: rows of none
+    perm = torch.empty(nlocal, dtype=torch.int32, device=l2g.device)
+    with torch.cuda.device(l2g.device):
+        rc = capi.lib().sf_gs_setup(nlocal, nglobal, _dev_ptr(l2g, "l2g", torch.int32), _dev_ptr(rows, "rows", torch.int32),
+                                    _dev_ptr(perm, "perm", torch.int32), _stream(stream, l2g.device))
+    capi.check(rc, "sf_gs_setup")
+    return GsMap(l2g, rows, perm, nlocal, nglobal)
+
+
+def _gs_map(what, gsmap):
+    if not isinstance(gsmap, GsMap):
+        raise TypeError(f"{what}: gsmap must come from gs_setup")
+
+
+def _gs_values(what, gsmap, values, sign):
+    """The checks of the gather-scatter calls before the library sees a pointer: `values` is (name, tensor, numel) of the
+    float64 / float32 arrays, the first of which sets dtype and device; sign, if given, has nlocal values of that dtype.
+    Returns (suffix of the symbol, dtype, pointer of sign or None)."""
+    first = values[0][1]
+    if not isinstance(first, torch.Tensor) or first.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"{what}: {values[0][0]} must be a float64 or float32 tensor")
+    if first.device != gsmap.l2g.device:
+        raise ValueError(f"{what}: {values[0][0]} is on {first.device}, the map is on {gsmap.l2g.device}")
+    _check_operands(what, [(name, t, need, False) for name, t, need in values] + [("sign", sign, gsmap.nlocal, True)], first)
+    return _sfx(first.dtype), first.dtype, None if sign is None else _dev_ptr(sign, "sign", first.dtype)
+
+
+def global_to_local(gsmap, glob, sign=None, out=None, stream=None):
+    """Q: out[i] = sign[i] * glob[l2g[i]], 0 where l2g[i] < 0 (Nektar++'s AssemblyMap::GlobalToLocal).  glob holds nglobal
+    values, out and sign nlocal; sign None: all +1."""
+    _gs_map("global_to_local", gsmap)
+    if out is None and isinstance(glob, torch.Tensor):
+        out = torch.empty(gsmap.nlocal, dtype=glob.dtype, device=glob.device)
+    sfx, dtype, sp = _gs_values("global_to_local", gsmap, [("glob", glob, gsmap.nglobal), ("out", out, gsmap.nlocal)], sign)
+    with torch.cuda.device(glob.device):
+        rc = getattr(capi.lib(), "sf_global_to_local_" + sfx)(
+            gsmap.nlocal, _dev_ptr(gsmap.l2g, "l2g", torch.int32), sp, _dev_ptr(glob, "glob", dtype),
+            _dev_ptr(out, "out", dtype), _stream(stream, glob.device))
+    capi.check(rc, "sf_global_to_local")
+    return out
+
+
+def assemble(gsmap, local, sign=None, out=None, stream=None):
+    """Q^T: out[g] = sum of sign[i] * local[i] over the local coefficients of g, added in ascending i (Nektar++'s
+    AssemblyMap::Assemble); 0 for a g with none.  No float atomics: bitwise reproducible.  Every out[g] is written."""
+    _gs_map("assemble", gsmap)
+    if out is None and isinstance(local, torch.Tensor):
+        out = torch.empty(gsmap.nglobal, dtype=local.dtype, device=local.device)
+    sfx, dtype, sp = _gs_values("assemble", gsmap, [("local", local, gsmap.nlocal), ("out", out, gsmap.nglobal)], sign)
+    with torch.cuda.device(local.device):
+        rc = getattr(capi.lib(), "sf_assemble_" + sfx)(
+            gsmap.nglobal, _dev_ptr(gsmap.rows, "rows", torch.int32), _dev_ptr(gsmap.perm, "perm", torch.int32), sp,
+            _dev_ptr(local, "local", dtype), _dev_ptr(out, "out", dtype), _stream(stream, local.device))
+    capi.check(rc, "sf_assemble")
+    return out
+
+
+def gs(gsmap, local, sign=None, stream=None):
+    """Q Q^T in place: local[i] <- sign[i] * sum_j sign[j] * local[j] over the coefficients that share l2g[i], the sum in
+    assemble's order; coefficients with l2g[i] < 0 or alone on their degree of freedom stay as they are.  Returns local."""
+    _gs_map("gs", gsmap)
+    sfx, dtype, sp = _gs_values("gs", gsmap, [("local", local, gsmap.nlocal)], sign)
+    with torch.cuda.device(local.device):
+        rc = getattr(capi.lib(), "sf_gs_" + sfx)(
+            gsmap.nglobal, _dev_ptr(gsmap.rows, "rows", torch.int32), _dev_ptr(gsmap.perm, "perm", torch.int32), sp,
+            _dev_ptr(local, "local", dtype), _stream(stream, local.device))
+    capi.check(rc, "sf_gs")
+    return local
+
+
 class _BwdTrans(torch.autograd.Function):
     """AUTO BwdTrans forward; its input gradient is IProductWRTBase of the output gradient (the exact transpose)."""
 

@@ -45,7 +45,12 @@ SYMBOLS = {
     "sf_shutdown": (_i, []),
     "sf_diag_tables_f64": (_i, [_u, _vp, _vp, _vp, _vp]),
     "sf_diag_tables_f32": (_i, [_u, _vp, _vp, _vp, _vp]),
+    "sf_gs_setup": (_i, [_sz, _sz, _vp, _vp, _vp, _vp]),
 }
+for _sfx in ("f64", "f32"):     # the gather-scatter apply calls: count, index arrays, sign, values, stream
+    SYMBOLS[f"sf_global_to_local_{_sfx}"] = (_i, [_sz, _vp, _vp, _vp, _vp, _vp])
+    SYMBOLS[f"sf_assemble_{_sfx}"] = (_i, [_sz, _vp, _vp, _vp, _vp, _vp, _vp])
+    SYMBOLS[f"sf_gs_{_sfx}"] = (_i, [_sz, _vp, _vp, _vp, _vp, _vp])
 
 
 def _operator_symbols():

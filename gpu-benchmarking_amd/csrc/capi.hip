@@ -7,7 +7,8 @@
 // helmholtz_f32.hip / helmholtz_generic.hip, its affine-element form in affine.hip / affine_f32.hip / affine_generic.hip,
 // BwdTrans fused with the physical-space gradient in physderiv.hip / physderiv_f32.hip / physderiv_generic.hip, its
 // transpose IProductWRTDerivBase in iprodderiv.hip / iprodderiv_f32.hip / iprodderiv_generic.hip, the diagonal of the
-// Helmholtz operator in diag.hip / diag_f32.hip / diag_generic.hip.
+// Helmholtz operator in diag.hip / diag_f32.hip / diag_generic.hip, the gather-scatter between local coefficients and
+// global degrees of freedom in gs.hip.
 #include "sf_dispatch.h"
 
 #include <cstdio>
@@ -367,6 +368,54 @@ template <typename T> static int diag_tables(unsigned nq, const T *basis, const 
     if (overlaps(tab, 3 * nb, basis, nb) || overlaps(tab, 3 * nb, deriv, sizeof(T) * nq * nq))
         return SF_EINVAL;
     return launch_diag_tables<T>(nq, basis, deriv, tab, (hipStream_t)stream);
+}
+
+// ---- gather-scatter: the checks of the four calls, in the order include/sumfact.h documents --------------------------
+// counts beyond 2^31 - 1 (SF_EINVAL), a count of zero (SF_OK), a null among `ptrs` (SF_EINVAL), an index array that is not
+// 4-byte aligned or a value array that is not `align`-aligned (SF_EALIGN); `sign` may be null
+constexpr size_t kGsMaxCount = 0x7fffffffull;
+static int gs_validate(size_t n0, size_t n1, std::initializer_list<const void *> index, size_t align,
+                       std::initializer_list<const void *> values, const void *sign)
+{
+    if (n0 > kGsMaxCount || n1 > kGsMaxCount)
+        return SF_EINVAL;
+    if (n0 == 0 || n1 == 0)
+        return SF_OK;
+    for (const void *p : index)
+        if (!p)
+            return SF_EINVAL;
+    for (const void *p : values)
+        if (!p)
+            return SF_EINVAL;
+    for (const void *p : index)
+        if (!aligned(p, sizeof(int32_t)))
+            return SF_EALIGN;
+    for (const void *p : values)
+        if (!aligned(p, align))
+            return SF_EALIGN;
+    return aligned(sign, align) ? kProceed : (int)SF_EALIGN;
+}
+
+template <typename T>
+static int global_to_local(size_t nlocal, const int32_t *l2g, const T *sign, const T *global, T *local, void *stream)
+{
+    const int rc = gs_validate(nlocal, 1, {l2g}, sizeof(T), {global, local}, sign);
+    return rc != kProceed ? rc : launch_global_to_local<T>(nlocal, l2g, sign, global, local, (hipStream_t)stream);
+}
+
+template <typename T>
+static int assemble(size_t nglobal, const int32_t *rows, const int32_t *perm, const T *sign, const T *local, T *global,
+                    void *stream)
+{
+    const int rc = gs_validate(nglobal, 1, {rows, perm}, sizeof(T), {local, global}, sign);
+    return rc != kProceed ? rc : launch_assemble<T>(nglobal, rows, perm, sign, local, global, (hipStream_t)stream);
+}
+
+template <typename T>
+static int gs(size_t nglobal, const int32_t *rows, const int32_t *perm, const T *sign, T *local, void *stream)
+{
+    const int rc = gs_validate(nglobal, 1, {rows, perm}, sizeof(T), {local}, sign);
+    return rc != kProceed ? rc : launch_gs<T>(nglobal, rows, perm, sign, local, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -800,6 +849,47 @@ int sf_diag_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const f
                                const float *g, const float *w, double lambda, float *out, void *stream)
 {
     return diag<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {tab0, tab1, nullptr}, g, w, lambda, out, stream);
+}
+
+// ---- gather-scatter: Q, Q^T and Q Q^T of a local-to-global map, and the setup that inverts the map --------------------
+int sf_gs_setup(size_t nlocal, size_t nglobal, const int32_t *l2g, int32_t *rows, int32_t *perm, void *stream)
+{
+    const int rc = gs_validate(nlocal, nglobal, {l2g, rows, perm}, sizeof(int32_t), {}, nullptr);
+    return rc != kProceed ? rc : gs_setup(nlocal, nglobal, l2g, rows, perm, (hipStream_t)stream);
+}
+
+int sf_global_to_local_f64(size_t nlocal, const int32_t *l2g, const double *sign, const double *global, double *local,
+                           void *stream)
+{
+    return global_to_local<double>(nlocal, l2g, sign, global, local, stream);
+}
+
+int sf_global_to_local_f32(size_t nlocal, const int32_t *l2g, const float *sign, const float *global, float *local,
+                           void *stream)
+{
+    return global_to_local<float>(nlocal, l2g, sign, global, local, stream);
+}
+
+int sf_assemble_f64(size_t nglobal, const int32_t *rows, const int32_t *perm, const double *sign, const double *local,
+                    double *global, void *stream)
+{
+    return assemble<double>(nglobal, rows, perm, sign, local, global, stream);
+}
+
+int sf_assemble_f32(size_t nglobal, const int32_t *rows, const int32_t *perm, const float *sign, const float *local,
+                    float *global, void *stream)
+{
+    return assemble<float>(nglobal, rows, perm, sign, local, global, stream);
+}
+
+int sf_gs_f64(size_t nglobal, const int32_t *rows, const int32_t *perm, const double *sign, double *local, void *stream)
+{
+    return gs<double>(nglobal, rows, perm, sign, local, stream);
+}
+
+int sf_gs_f32(size_t nglobal, const int32_t *rows, const int32_t *perm, const float *sign, float *local, void *stream)
+{
+    return gs<float>(nglobal, rows, perm, sign, local, stream);
 }
 
 int sf_sumsq_f32(const float *x, size_t n, double *result_host, void *stream)

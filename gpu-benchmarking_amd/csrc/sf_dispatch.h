@@ -47,7 +47,7 @@ int matvec(unsigned M, unsigned N, const double *A, const double *x, double *y, 
 int fill_matvec(double *A, double *x, unsigned M, unsigned N, hipStream_t s);
 int release_workspaces();
 // internal scratch buffer of (current device, stream, kind), at least `bytes` long; kinds: 0 reductions, 1 BwdTrans
-// intermediates.  Hold scratch_mutex() from the acquire to the end of the enqueue sequence that uses the buffer.
+// intermediates, 2 the gather-scatter setup.  Hold scratch_mutex() from the acquire to the end of the enqueue sequence that uses the buffer.
 int scratch_acquire(hipStream_t s, int kind, size_t bytes, void **out);
 std::recursive_mutex &scratch_mutex();
 // 8-byte batch counter for one launch of a persistent kernel on `s` (zero it with a one-thread kernel in front of the
@@ -175,6 +175,16 @@ bool diag_wave_built(int dim, unsigned nq);
 bool diag_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
 // tab[t][p][i], t = 0, 1, 2: B o B, E o B, E o E with E[p][i] = sum_m deriv[i*nq + m] basis[p*nq + m]; one kernel
 template <typename T> int launch_diag_tables(unsigned nq, const T *basis, const T *deriv, T *tab, hipStream_t s);
+// Gather-scatter (gs.hip): the setup that inverts a local-to-global map into rows / perm (blocking; integer atomics, a
+// three-kernel scan, scratch kind 2) and the three apply launches, one kernel each; sign null: all +1.
+int gs_setup(size_t nlocal, size_t nglobal, const int32_t *l2g, int32_t *rows, int32_t *perm, hipStream_t s);
+template <typename T>
+int launch_global_to_local(size_t nlocal, const int32_t *l2g, const T *sign, const T *global, T *local, hipStream_t s);
+template <typename T>
+int launch_assemble(size_t nglobal, const int32_t *rows, const int32_t *perm, const T *sign, const T *local, T *global,
+                    hipStream_t s);
+template <typename T>
+int launch_gs(size_t nglobal, const int32_t *rows, const int32_t *perm, const T *sign, T *local, hipStream_t s);
 int sumsq_f32_blocking(const float *x, size_t n, double *result_host, hipStream_t s);
 int fill_sincos_f32(float *in, size_t nelmt, size_t nm_tot, hipStream_t s);
 int fill_basis_f32(float *b, size_t nm, size_t nq, hipStream_t s);

@@ -646,6 +646,53 @@ int sf_diag_helmholtz_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t n
 int sf_diag_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *tab0, const float *tab1,
                                const float *g, const float *w, double lambda, float *out, void *stream);
 
+/*
+ * GATHER-SCATTER between the element-local coefficients the operators above work on and the global degrees of freedom
+ * of a continuous-Galerkin space: with Q the nlocal x nglobal matrix of a local-to-global map, global_to_local applies
+ * Q, assemble Q^T and gs Q Q^T, so that  A = Q^T blockdiag(H_e) Q  is  global_to_local -> sf_helmholtz_* -> assemble,
+ * and the Jacobi diagonal is assemble(sf_diag_helmholtz_*).  Replaces Nektar++'s AssemblyMap::GlobalToLocal, ::Assemble
+ * and ::UniversalAssemble round an operator evaluation.  The library numbers nothing: the caller passes the map.
+ *
+ * The map.  l2g[i], i = 0 .. nlocal-1, is the global degree of freedom of local coefficient i (i = e * nm^d + ..., the
+ *   layout of the operators' `in`).  A negative entry: the coefficient belongs to no global degree of freedom (a
+ *   constrained / Dirichlet coefficient).  Entries must be < nglobal.
+ * The sign.  `sign` may be NULL: all +1.  Otherwise sign[i] is +1 or -1 (Nektar++'s localToGlobalSign), in the scalar
+ *   type of the values; products with it are exact.
+ * global_to_local:  local[i] = sign[i] * global[l2g[i]];  local[i] = 0 where l2g[i] < 0.  Every local[i] is written.
+ * assemble:  global[g] = sum of sign[i] * local[i] over { i : l2g[i] == g }, the terms added in ASCENDING i, starting
+ *   from the first term, one rounding per addition; a g with no local coefficient gets 0.  Every one of the nglobal
+ *   outputs is written (no zeroing beforehand).  No float atomics: the result is bitwise reproducible.
+ * gs:  local[i] <- sign[i] * sum_j sign[j] * local[j] over { j : l2g[j] == l2g[i] }, the sum in the order of assemble, in
+ *   place.  Coefficients with l2g[i] < 0 are left untouched, and so are those alone on their global degree of freedom
+ *   (sign^2 = 1).  The lists are disjoint, which is what makes the update in place safe.
+ *
+ * sf_gs_setup inverts the map once: it writes `rows` (nglobal words) and `perm` (nlocal words), caller-owned, the
+ *   inverted index that assemble and gs walk -- CSR by global degree of freedom, the local indices of a row ascending.
+ *   The content is opaque but deterministic: two calls on one map write the same bytes.  It is BLOCKING (it synchronises
+ *   `stream`, like sf_sumsq_f64), takes the stream's internal scratch (not stream-capture safe) and returns SF_EINVAL if
+ *   any l2g[i] >= nglobal; nothing is then written out of range and rows / perm are unusable.  A row is summed by one
+ *   lane: rows far longer than a finite-element mesh produces (a few dozen entries) are correct but slow, in the setup
+ *   and in assemble / gs.
+ * The three apply calls are asynchronous, stateless, allocate nothing, are thread-safe and capture-safe (one kernel node
+ *   each).  local, global and sign may not overlap each other, nor the index arrays.
+ * Limits and validation, before any HIP call, in this order: (1) nlocal or nglobal > 2^31 - 1: SF_EINVAL; (2) a count of
+ *   zero (setup: either; global_to_local: nlocal; assemble, gs: nglobal): SF_OK, nothing launched, nothing written;
+ *   (3) a null pointer (sign excepted): SF_EINVAL; (4) a pointer not aligned to its own scalar (4 bytes for the int32_t
+ *   arrays and float, 8 for double): SF_EALIGN.  Anything scalar-aligned works, at the same speed: the kernels access
+ *   one scalar per lane, consecutive lanes on consecutive scalars.
+ */
+int sf_gs_setup(size_t nlocal, size_t nglobal, const int32_t *l2g, int32_t *rows, int32_t *perm, void *stream);
+int sf_global_to_local_f64(size_t nlocal, const int32_t *l2g, const double *sign, const double *global, double *local,
+                           void *stream);
+int sf_global_to_local_f32(size_t nlocal, const int32_t *l2g, const float *sign, const float *global, float *local,
+                           void *stream);
+int sf_assemble_f64(size_t nglobal, const int32_t *rows, const int32_t *perm, const double *sign, const double *local,
+                    double *global, void *stream);
+int sf_assemble_f32(size_t nglobal, const int32_t *rows, const int32_t *perm, const float *sign, const float *local,
+                    float *global, void *stream);
+int sf_gs_f64(size_t nglobal, const int32_t *rows, const int32_t *perm, const double *sign, double *local, void *stream);
+int sf_gs_f32(size_t nglobal, const int32_t *rows, const int32_t *perm, const float *sign, float *local, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
