@@ -14,7 +14,7 @@ it is missing.
 """
 from . import capi, logfmt, shard  # noqa: F401
 from .bwdtrans import (  # noqa: F401
-    bwdtrans_hex, bwdtrans_quad, sumsq, fill_sincos, fill_basis, fill_random, fill_l2norm,
+    bwdtrans_hex, bwdtrans_hex_mfma4, bwdtrans_quad, sumsq, fill_sincos, fill_basis, fill_random, fill_l2norm,
     stream_copy, device_info, interleave64, bwdtrans_hex_interleaved, fill_vecadd, vector_add, fill_matvec, matvec, hex_wsp_doubles, quad_wsp_doubles, VARIANTS,
     specialise, specialisation_state, specialise_log, bwdtrans_specialised,
     iproduct_hex, iproduct_quad, bwdtrans_autograd, mass_hex, mass_quad,

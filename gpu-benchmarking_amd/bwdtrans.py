@@ -195,6 +195,31 @@ def bwdtrans_hex(nq, basis0, basis1, basis2, inp, out=None, variant="auto", wsp=
     return _operator_call("bwdtrans_hex", fam, nq, (basis0, basis1, basis2), inp, out, variant, stream, wsp)
 
 
+def bwdtrans_hex_mfma4(nq, basis0, basis1, basis2, inp, direct, out=None, stream=None):
+    """For tests and tuning: bwdtrans_hex((nq,) * 3, ..., variant="mfma4") in float64 with the kernel's output path named
+    -- direct false: the element is assembled in LDS and streamed out flat; true: the accumulators of the third sweep are
+    stored as they are.  variant="mfma4" and "auto" choose per order."""
+    what, nq = "bwdtrans_hex_mfma4", int(nq)
+    if nq < 2:
+        raise capi.SumfactError(capi.SF_EINVAL, what)
+    if not isinstance(inp, torch.Tensor):
+        raise TypeError(f"{what}: in must be a tensor")
+    nmt, nqt = (nq - 1) ** 3, nq ** 3
+    nelmt = inp.numel() // nmt
+    if nelmt * nmt != inp.numel():
+        raise ValueError(f"{what}: in.numel() is not a multiple of the modes per element ({nmt})")
+    if out is None:
+        out = torch.empty(nelmt * nqt, dtype=inp.dtype, device=inp.device)
+    operands = [(f"basis{d}", b, (nq - 1) * nq, False) for d, b in enumerate((basis0, basis1, basis2))]
+    operands += [("in", inp, nelmt * nmt, False), ("out", out, nelmt * nqt, False)]
+    _check_operands(what, operands, inp)
+    with torch.cuda.device(inp.device):
+        rc = capi.lib().sf_bwdtrans_hex_f64_mfma4(int(bool(direct)), nq, nelmt, *(_dev_ptr(t, name) for name, t, _, _ in operands),
+                                                  _stream(stream, inp.device))
+    capi.check(rc, what)
+    return out
+
+
 def bwdtrans_quad(nq, basis0, basis1, inp, out=None, variant="auto", wsp=None, stream=None):
     """out[e][j][i] = sum_qp in[e][q][p] B0[p][i] B1[q][j] on inp's device."""
     fam = _Family("bwdtrans", False, True, f32_ignores_variant=True,

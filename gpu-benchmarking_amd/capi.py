@@ -28,6 +28,7 @@ SYMBOLS = {
     "sf_stream_copy_f64": (_i, [_vp, _vp, _sz, _vp]),
     "sf_bwdtrans_hex_f64_interleaved": (_i, [_u, _u, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sf_interleave64_f64": (_i, [_vp, _vp, _sz, _sz, _i, _vp]),
+    "sf_bwdtrans_hex_f64_mfma4": (_i, [_i, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sf_sumsq_f32": (_i, [_vp, _sz, ctypes.POINTER(ctypes.c_double), _vp]),
     "sf_fill_sincos_f32": (_i, [_vp, _sz, _sz, _vp]),
     "sf_fill_basis_f32": (_i, [_vp, _sz, _sz, _vp]),

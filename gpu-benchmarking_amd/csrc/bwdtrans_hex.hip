@@ -5,8 +5,6 @@
 #include "wave_launch.h"
 #include "wave_table.h"
 
-#include <cstdlib>
-
 namespace sf
 {
 
@@ -155,28 +153,32 @@ template <> int launch_bwd_mfma<3, double>(unsigned nq, const HexArgs &a, hipStr
 // peeled onto the vector pipe, 279 without (283-287)   15: 271 peeled, 274 not (290-292)   16: 319 = 0.72 with the
 // accumulators stored directly and unpadded W2 rows (five workgroups per CU), 310 through the LDS output image (290-307).
 // AUTO runs it at nq 12, 14 and 16 (hex_auto_kernel()).
-template <int NQ> static int go_mfma4(const HexArgs &a, hipStream_t s)
+// direct: the accumulators of sweep 3 are stored directly (whole 128-byte lines only where nq is a multiple of 4 and `out`
+// is 128-byte aligned); else the element is assembled in LDS and leaves as one flat stream
+template <int NQ> static int go_mfma4(bool direct, const HexArgs &a, hipStream_t s)
 {
-    // SF_HEX_MFMA4_CFG is a development knob, read at every call (1: output through an LDS image, 3: accumulators stored
-    // directly -- whole 128-byte lines only where nq is a multiple of 4 and `out` is 128-byte aligned)
-    const char *env = getenv("SF_HEX_MFMA4_CFG");
-    const int cfg   = env ? atoi(env) : (NQ == 16 ? 3 : 1);
-    if (cfg == 3)
+    if (direct)
         return launch_hex_mfma4<NQ, 1, 2, 1, 64, true>(a, s);
     return launch_hex_mfma4<NQ, 1, (NQ == 12 ? 1 : 2), 1, 64>(a, s);
 }
 
-template <> int launch_bwd_mfma4<3, double>(unsigned nq, const HexArgs &a, hipStream_t s)
+int launch_hex_mfma4_path(bool direct, unsigned nq, const HexArgs &a, hipStream_t s)
 {
     switch (nq)
     {
-    case 12: return go_mfma4<12>(a, s);
-    case 13: return go_mfma4<13>(a, s);
-    case 14: return go_mfma4<14>(a, s);
-    case 15: return go_mfma4<15>(a, s);
-    case 16: return go_mfma4<16>(a, s);
+    case 12: return go_mfma4<12>(direct, a, s);
+    case 13: return go_mfma4<13>(direct, a, s);
+    case 14: return go_mfma4<14>(direct, a, s);
+    case 15: return go_mfma4<15>(direct, a, s);
+    case 16: return go_mfma4<16>(direct, a, s);
     default: return SF_ENOTBUILT;
     }
+}
+
+// the measured best output path per order: direct at nq = 16 only
+template <> int launch_bwd_mfma4<3, double>(unsigned nq, const HexArgs &a, hipStream_t s)
+{
+    return launch_hex_mfma4_path(nq == 16, nq, a, s);
 }
 
 // the measured best matrix-core kernel above the wave kernel's table
@@ -221,26 +223,19 @@ template <int NQ> static int go_f32(const HexArgsT<float> &a, hipStream_t s)
 {
     if constexpr (NQ == 2)
         return launch_stream(hex_nq2_stream_f32_kernel, a.nelmt * 2, s, a.b0, a.b1, a.b2, a.in, a.out, a.nelmt);
-    if constexpr (NQ >= 12)
+    // fp32 matrix-core kernel (hex_mfma_kernel, T = float: v_mfma_f32_16x16x4_f32) from nq = 13, where it is ahead of
+    // the vector kernel (the candidates are cases of tools/sf_tune_f32; profiles/r03/f32_hex_mfma_configurations.log;
+    // 131 072 elements, fraction of the fp32 HBM roofline, vector kernel in brackets): 13 0.594 (0.518)  14 0.590 (0.552)
+    // 15 0.676 (0.524)  16 0.705 (0.549); nq = 12 stays on the vector kernel (0.605 against 0.508).
+    if constexpr (NQ >= 15)
+        return launch_hex_mfma<NQ, 1, 1, 1, 1, 64, float>(a, s);
+    else if constexpr (NQ >= 13)
+        return launch_hex_mfma<NQ, 1, 1, 2, 1, 64, float>(a, s); // two waves per SIMD
+    else
     {
-        // fp32 matrix-core kernel (hex_mfma_kernel, T = float: v_mfma_f32_16x16x4_f32) from nq = 13, where it is ahead of
-        // the vector kernel (tools/experiments/f32_hex_cfg.py, profiles/r03/f32_hex_mfma_configurations.log; 131 072
-        // elements, fraction of the fp32 HBM roofline, vector kernel in brackets): 13 0.594 (0.518)  14 0.590 (0.552)
-        // 15 0.676 (0.524)  16 0.705 (0.549); nq = 12 stays on the vector kernel (0.605 against 0.508).
-        // SF_F32_HEX_CFG is a development knob (0: vector kernel).
-        constexpr int best = NQ == 12 ? 0 : (NQ <= 14 ? 2 : 1);
-        static const int cfg = getenv("SF_F32_HEX_CFG") ? atoi(getenv("SF_F32_HEX_CFG")) : best;
-        switch (cfg)
-        {
-        case 1: return launch_hex_mfma<NQ, 1, 1, 1, 1, 64, float>(a, s);
-        case 2: return launch_hex_mfma<NQ, 1, 1, 2, 1, 64, float>(a, s);
-        case 3: return launch_hex_mfma<NQ, 1, 2, 2, 1, 64, float>(a, s);
-        case 4: return launch_hex_mfma<NQ, 2, 1, 1, 1, 64, float>(a, s);
-        default: break;
-        }
+        using C = HexCfgF32<NQ>;
+        return launch_hex_wave<NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, C::OUT, C::MF, float>(a, s);
     }
-    using C = HexCfgF32<NQ>;
-    return launch_hex_wave<NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, C::OUT, C::MF, float>(a, s);
 }
 
 // What AUTO runs in 3D for T = float: the vector kernel up to nq = 12, the fp32 matrix-core kernel at 13..16

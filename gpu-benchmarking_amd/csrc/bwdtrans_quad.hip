@@ -4,8 +4,6 @@
 #include "wave_launch.h"
 #include "wave_table.h"
 
-#include <cstdlib>
-
 namespace sf
 {
 
@@ -80,25 +78,15 @@ template <int NQ> static int go_f32(const QuadArgsT<float> &a, hipStream_t s)
     {
         // v_mfma_f32_16x16x4_f32 (bwdtrans_mfma.h, T = float): two-element chunks, LDS-staged line-aligned output where the
         // rows are not whole lines, two waves per SIMD, XCD runs
-        // per order the best of tools/experiments/f32_mfma_cfg.sh over two boxes (profiles/r03/f32_mfma_configurations*.log;
+        // per order the best of five candidates (cases of tools/sf_tune_f32) over two boxes (profiles/r03/f32_mfma_configurations*.log;
         // fraction of the fp32 HBM roofline at 1 Mi elements, vector kernel in brackets): 25 0.54-0.57 (0.51)
         // 26 0.53-0.54 (0.51)  27 0.56-0.57 (0.50)  28 0.57 (0.52)  29 0.60-0.61 (0.52)  30 0.57-0.58 (0.52)
         // 31 0.61-0.62 (0.51)  32 0.64 (0.42); at nq 17..24 the vector kernel stays ahead (second log)
-        constexpr int best = NQ == 25 ? 3 : ((NQ == 28 || NQ == 32) ? 2 : ((NQ == 26 || NQ == 30 || NQ == 31) ? 4 : (NQ == 27 ? 0 : 1)));
-        static const int cfg = getenv("SF_F32_MFMA_CFG") ? atoi(getenv("SF_F32_MFMA_CFG")) : best; // development knob
-        switch (cfg)
-        {
-        case 1: return launch_quad_mfma<NQ, 2, 4, 4, 2, (NQ != 32), 64, float>(a, s);
-        case 2: return launch_quad_mfma<NQ, 4, 4, 2, 1, (NQ != 32), 64, float>(a, s);
-        case 3: return launch_quad_mfma<NQ, 4, 4, 4, 1, (NQ != 32), 64, float>(a, s);
-        case 4: return launch_quad_mfma<NQ, 2, 4, 4, 1, (NQ != 32), 64, float>(a, s);
-        case 5:
-        {
-            using C = QuadCfgF32<NQ>;
-            return launch_quad_wave<NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, C::OUT, C::MF, float>(a, s);
-        }
-        default: return launch_quad_mfma<NQ, 2, 4, 2, 2, (NQ != 32), 64, float>(a, s);
-        }
+        // (EC, MINW, KMAP): 25 (4, 4, 1)  26, 30, 31 (2, 4, 1)  27 (2, 2, 2)  28, 32 (4, 2, 1)  29 (2, 4, 2)
+        constexpr int EC = (NQ == 25 || NQ == 28 || NQ == 32) ? 4 : 2;
+        constexpr int MW = (NQ == 27 || NQ == 28 || NQ == 32) ? 2 : 4;
+        constexpr int KM = (NQ == 27 || NQ == 29) ? 2 : 1;
+        return launch_quad_mfma<NQ, EC, 4, MW, KM, (NQ != 32), 64, float>(a, s);
     }
     else
     {

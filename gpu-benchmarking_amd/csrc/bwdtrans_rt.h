@@ -124,12 +124,16 @@ template <> struct SRow<6>
     }
 };
 
-// columns [N0, N0 + D) of acc[g][n] = sum_{m < nm} u[g][m] * B[m][n] for the G pencils a lane owns in this group of
-// passes, ascending m, the first product starts the sum.  Rows go through a two-deep ring: wait for row m, request row
-// m + 1, run row m's FMAs (all G pencils: a row is fetched once per group, not once per pass) on top of the request.
-template <int NB, int G, int N0, int D>
-__device__ __forceinline__ void contract_rt_cols(const double (&u)[G][NB - 1], double (&acc)[G][NB],
-                                                 __amdgpu_buffer_rsrc_t rsrc, int nm, int nq, int ng)
+// columns [N0, N0 + D) of acc[n] = sum_{m < nm} u[m] * B[m][n] for the pencil a lane owns in this pass, ascending m, the
+// first product starts the sum.  Rows go through a two-deep ring: wait for row m, request row m + 1, run row m's FMAs on
+// top of the request.
+// One pencil per lane and pass.  Measured: groups of 2-4 passes that share a fetched row, with the chunk sized to fill
+// them, are SLOWER than one pass with one-pass chunks at every shape AUTO sends here (8x8x8: 0.27-0.32 of the roofline
+// against 0.52; the larger LDS images and the per-pass guards cost more than the shared rows give back), and help only
+// above nq = 12, where the block kernel is ahead anyway (profiles/r03/anisotropic_shapes.log).
+template <int NB, int N0, int D>
+__device__ __forceinline__ void contract_rt_cols(const double (&u)[NB - 1], double (&acc)[NB], __amdgpu_buffer_rsrc_t rsrc,
+                                                 int nm, int nq)
 {
     SRow<D> b[2];
     b[0].issue(rsrc, 8 * N0);
@@ -143,39 +147,24 @@ __device__ __forceinline__ void contract_rt_cols(const double (&u)[G][NB - 1], d
                 b[(m + 1) % 2].issue(rsrc, 8 * ((m + 1) * nq + N0));
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int g = 0; g < G; ++g)
-                if (g < ng) // wave-uniform: passes of this group that hold pencils
-                {
-#pragma unroll
-                    for (int n = 0; n < D; ++n)
-                        acc[g][N0 + n] = (m == 0) ? u[g][0] * b[0].get(n) : fma_t(u[g][m], b[m % 2].get(n), acc[g][N0 + n]);
-                }
+            for (int n = 0; n < D; ++n)
+                acc[N0 + n] = (m == 0) ? u[0] * b[0].get(n) : fma_t(u[m], b[m % 2].get(n), acc[N0 + n]);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
 }
 
-template <int NB, int G>
-__device__ __forceinline__ void contract_rt(const double (&u)[G][NB - 1], double (&acc)[G][NB], __amdgpu_buffer_rsrc_t rsrc,
-                                            int nm, int nq, int ng)
+template <int NB>
+__device__ __forceinline__ void contract_rt(const double (&u)[NB - 1], double (&acc)[NB], __amdgpu_buffer_rsrc_t rsrc, int nm,
+                                            int nq)
 {
     if constexpr (NB <= 8)
-        contract_rt_cols<NB, G, 0, NB>(u, acc, rsrc, nm, nq, ng);
+        contract_rt_cols<NB, 0, NB>(u, acc, rsrc, nm, nq);
     else
     {
-        contract_rt_cols<NB, G, 0, 8>(u, acc, rsrc, nm, nq, ng);
-        contract_rt_cols<NB, G, 8, NB - 8>(u, acc, rsrc, nm, nq, ng);
+        contract_rt_cols<NB, 0, 8>(u, acc, rsrc, nm, nq);
+        contract_rt_cols<NB, 8, NB - 8>(u, acc, rsrc, nm, nq);
     }
-}
-
-// pencils a lane handles per group of passes (a basis row is fetched once per group).  Measured: groups of 2-4 passes
-// with the chunk sized to fill them are SLOWER than one pass per group with one-pass chunks at every shape AUTO sends
-// here (8x8x8: 0.27-0.32 of the roofline against 0.52; the larger LDS images and the per-pass guards cost more than the
-// shared rows give back), and help only above nq = 12, where the block kernel is ahead anyway
-// (profiles/r03/anisotropic_shapes.log).
-constexpr int rt_group(int nb)
-{
-    return 1;
 }
 
 template <int NB, typename T>
@@ -184,6 +173,38 @@ __device__ __forceinline__ void read_pencil_rt(T (&u)[NB - 1], const T *pencil, 
 #pragma unroll
     for (int m = 0; m < NB - 1; ++m)
         u[m] = (m < nm) ? pencil[m] : T(0);
+}
+
+// where a pencil's results go: the first one and the distance between two of them (doubles)
+struct RtDst
+{
+    double *p;
+    int stride;
+};
+
+// One sweep: the `np` pencils of the image `src` (pencil stride `ss`, nm values each) times the basis behind `rsrc`, 64
+// pencils per pass; the nq results of pencil t go where dst_of(t) says.  Lanes beyond the last pencil compute a copy of
+// it and store nothing.
+template <int NB, class DstOf>
+__device__ __forceinline__ void sweep_rt(const double *src, int ss, int nm, int nq, __amdgpu_buffer_rsrc_t rsrc, int np,
+                                         int lane, DstOf dst_of)
+{
+    for (int t0 = 0; t0 < np; t0 += kWave)
+    {
+        double u[NB - 1], acc[NB];
+        const int t = t0 + lane, tc = t < np ? t : np - 1;
+        read_pencil_rt<NB>(u, src + tc * ss, nm);
+        contract_rt<NB>(u, acc, rsrc, nm, nq);
+        const RtDst d = dst_of(tc);
+        if (t < np)
+        {
+#pragma unroll
+            for (int k = 0; k < NB; ++k)
+                if (k < nq)
+                    d.p[k * d.stride] = acc[k];
+        }
+    }
+    wave_lds_fence();
 }
 
 template <int NB, int XG = 64>
@@ -256,120 +277,21 @@ __global__ __launch_bounds__(256) void hex_wave_rt_kernel(const RtShape sh, cons
     const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc((void *)b0, 0, 8 * sh.nm0 * sh.nq0, kRsrcWord3);
     const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc((void *)b1, 0, 8 * sh.nm1 * sh.nq1, kRsrcWord3);
     const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc((void *)b2, 0, 8 * sh.nm2 * sh.nq2, kRsrcWord3);
-    constexpr int G = rt_group(NB);
     // ---- direction 0: w1[(e,i,r)][q] = sum_p in[(e,r,q)][p] * B0[p][i]          image A -> image B -----------------
-    {
-        const int np = evalid * nm12;
-        for (int t0 = 0; t0 < np; t0 += G * kWave)
-        {
-            T u[G][NB - 1], acc[G][NB];
-            int tc[G];
-            const int ng = (np - t0 + kWave - 1) / kWave; // passes of this group that hold pencils (wave-uniform)
-#pragma unroll
-            for (int g = 0; g < G; ++g)
-            {
-                if (g >= ng)
-                    continue;
-                const int t = t0 + g * kWave + lane;
-                tc[g]       = t < np ? t : np - 1;
-                read_pencil_rt<NB>(u[g], imga + tc[g] * sh.s0, sh.nm0);
-            }
-            contract_rt<NB, G>(u, acc, r0, sh.nm0, sh.nq0, ng);
-#pragma unroll
-            for (int g = 0; g < G; ++g)
-            {
-                if (g >= ng)
-                    continue;
-                const int t = t0 + g * kWave + lane;
-                const int e = div_magic(tc[g], sh.m_nm12), rq = tc[g] - e * nm12, r = div_magic(rq, sh.m_nm1),
-                          q = rq - r * sh.nm1;
-                T *dst = imgb + ((e * sh.nq0) * sh.nm2 + r) * sh.s1 + q;
-                if (t < np)
-                {
-#pragma unroll
-                    for (int k = 0; k < NB; ++k)
-                        if (k < sh.nq0)
-                            dst[k * sh.nm2 * sh.s1] = acc[g][k];
-                }
-            }
-        }
-        wave_lds_fence();
-    }
+    sweep_rt<NB>(imga, sh.s0, sh.nm0, sh.nq0, r0, evalid * nm12, lane, [&](int t) {
+        const int e = div_magic(t, sh.m_nm12), rq = t - e * nm12, r = div_magic(rq, sh.m_nm1), q = rq - r * sh.nm1;
+        return RtDst{imgb + ((e * sh.nq0) * sh.nm2 + r) * sh.s1 + q, sh.nm2 * sh.s1};
+    });
     // ---- direction 1: w2[(e,j,i)][r] = sum_q w1[(e,i,r)][q] * B1[q][j]          image B -> image A -----------------
-    {
-        const int np = evalid * nq0nm2;
-        for (int t0 = 0; t0 < np; t0 += G * kWave)
-        {
-            T u[G][NB - 1], acc[G][NB];
-            int tc[G];
-            const int ng = (np - t0 + kWave - 1) / kWave; // passes of this group that hold pencils (wave-uniform)
-#pragma unroll
-            for (int g = 0; g < G; ++g)
-            {
-                if (g >= ng)
-                    continue;
-                const int t = t0 + g * kWave + lane;
-                tc[g]       = t < np ? t : np - 1;
-                read_pencil_rt<NB>(u[g], imgb + tc[g] * sh.s1, sh.nm1);
-            }
-            contract_rt<NB, G>(u, acc, r1, sh.nm1, sh.nq1, ng);
-#pragma unroll
-            for (int g = 0; g < G; ++g)
-            {
-                if (g >= ng)
-                    continue;
-                const int t = t0 + g * kWave + lane;
-                const int e = div_magic(tc[g], sh.m_nq0nm2), ir = tc[g] - e * nq0nm2, i = div_magic(ir, sh.m_nm2),
-                          r = ir - i * sh.nm2;
-                T *dst = imga + ((e * sh.nq1) * sh.nq0 + i) * sh.s2 + r;
-                if (t < np)
-                {
-#pragma unroll
-                    for (int k = 0; k < NB; ++k)
-                        if (k < sh.nq1)
-                            dst[k * sh.nq0 * sh.s2] = acc[g][k];
-                }
-            }
-        }
-        wave_lds_fence();
-    }
+    sweep_rt<NB>(imgb, sh.s1, sh.nm1, sh.nq1, r1, evalid * nq0nm2, lane, [&](int t) {
+        const int e = div_magic(t, sh.m_nq0nm2), ir = t - e * nq0nm2, i = div_magic(ir, sh.m_nm2), r = ir - i * sh.nm2;
+        return RtDst{imga + ((e * sh.nq1) * sh.nq0 + i) * sh.s2 + r, sh.nq0 * sh.s2};
+    });
     // ---- direction 2: out[e][k][(j,i)] = sum_r w2[(e,j,i)][r] * B2[r][k]        image A -> image B (final layout) --
-    {
-        const int np = evalid * nq01;
-        for (int t0 = 0; t0 < np; t0 += G * kWave)
-        {
-            T u[G][NB - 1], acc[G][NB];
-            int tc[G];
-            const int ng = (np - t0 + kWave - 1) / kWave; // passes of this group that hold pencils (wave-uniform)
-#pragma unroll
-            for (int g = 0; g < G; ++g)
-            {
-                if (g >= ng)
-                    continue;
-                const int t = t0 + g * kWave + lane;
-                tc[g]       = t < np ? t : np - 1;
-                read_pencil_rt<NB>(u[g], imga + tc[g] * sh.s2, sh.nm2);
-            }
-            contract_rt<NB, G>(u, acc, r2, sh.nm2, sh.nq2, ng);
-#pragma unroll
-            for (int g = 0; g < G; ++g)
-            {
-                if (g >= ng)
-                    continue;
-                const int t = t0 + g * kWave + lane;
-                const int e = div_magic(tc[g], sh.m_nq01), pl = tc[g] - e * nq01;
-                T *dst = imgb + e * sh.nqt + pl;
-                if (t < np)
-                {
-#pragma unroll
-                    for (int k = 0; k < NB; ++k)
-                        if (k < sh.nq2)
-                            dst[k * nq01] = acc[g][k];
-                }
-            }
-        }
-        wave_lds_fence();
-    }
+    sweep_rt<NB>(imga, sh.s2, sh.nm2, sh.nq2, r2, evalid * nq01, lane, [&](int t) {
+        const int e = div_magic(t, sh.m_nq01), pl = t - e * nq01;
+        return RtDst{imgb + e * sh.nqt + pl, nq01};
+    });
     // ---- image B -> HBM: one flat stream on the 16-byte word grid of the chunk's output -------------------------------
     {
         T *dst        = out + c * (uint64_t)sh.ec * sh.nqt;

@@ -7,8 +7,6 @@
 #include "rtc_config.h"
 #include "sf_dispatch.h"
 
-#include <cstdlib>
-
 namespace sf
 {
 
@@ -113,8 +111,6 @@ int launch_hex_rt(unsigned nq0, unsigned nq1, unsigned nq2, const HexArgs &a, hi
     // chunks that fill the 64 lanes in the widest sweep (nq0 nq1 pencils per element); larger chunks measured slower
     // (their LDS images cost more occupancy than the shared basis rows give back)
     int ec = 64 / (sh.nq0 * sh.nq1);
-    if (const char *env = getenv("SF_RT_EC")) // development knob (tools/aniso_bench.py)
-        ec = atoi(env);
     ec = ec < 1 ? 1 : (ec > 16 ? 16 : ec);
     int off_b = 0;
     while (ec > 1 && images(ec, &off_b) > 2048)

@@ -233,10 +233,6 @@ template <typename T> __device__ __forceinline__ int line_offset(const void *p)
 {
     return __builtin_amdgcn_readfirstlane((int)(((uintptr_t)p / sizeof(T)) & (128 / sizeof(T) - 1)));
 }
-__device__ __forceinline__ int line_offset_f64(const void *p)
-{
-    return line_offset<double>(p);
-}
 
 template <int NMAX, typename T> constexpr int word_grid_regs()
 {
@@ -270,13 +266,6 @@ __device__ __forceinline__ void chunk_load_any(typename VecOf<T>::type (&st)[NRE
         }
         st[k] = x;
     }
-}
-
-template <int NMAX, int NREG>
-__device__ __forceinline__ void chunk_load_any_f64(double2_t (&st)[NREG], const double *__restrict__ src,
-                                                   int lane, int nvalid)
-{
-    chunk_load_any<NMAX, NREG, double>(st, src, lane, nvalid);
 }
 
 // A chunk loop requests chunk n+1 (loads into the staging registers), computes chunk n and stores it, then loops.
@@ -669,12 +658,6 @@ __device__ __forceinline__ void flush_any(const T *img, T *__restrict__ dst, int
                     dst[d0 + h] = img[d0 + h];
         }
     }
-}
-
-template <int NMAX>
-__device__ __forceinline__ void flush_any_f64(const double *img, double *__restrict__ dst, int nout, int lane)
-{
-    flush_any<NMAX, double>(img, dst, nout, lane);
 }
 
 // OUT_LDS epilogue: the slab holds the chunk's output in final layout; stream `nout` scalars to HBM

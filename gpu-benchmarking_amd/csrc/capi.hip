@@ -460,6 +460,19 @@ int sf_bwdtrans_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, 
     return bwdtrans<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, nullptr, out, stream);
 }
 
+// SF_VARIANT_MFMA4's leg of bwdtrans<3, double> with the output path named instead of chosen per order
+int sf_bwdtrans_hex_f64_mfma4(int direct, unsigned nq, size_t nelmt, const double *basis0, const double *basis1,
+                              const double *basis2, const double *in, double *out, void *stream)
+{
+    const int pre = validate(range_ok<3>(SF_VARIANT_MFMA4, {nq, nq, nq}), nelmt, {basis0, basis1, basis2, in, out}, sizeof(double));
+    if (pre != kProceed)
+        return pre;
+    if (!aligned(in, 16) || !aligned(out, 16))
+        return SF_EALIGN;
+    const HexArgs a{basis0, basis1, basis2, in, nullptr, out, (uint64_t)nelmt};
+    return launch_hex_mfma4_path(direct != 0, nq, a, (hipStream_t)stream);
+}
+
 int sf_bwdtrans_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
                                  const double *basis1, const double *in, double *wsp, double *out, void *stream)
 {

@@ -25,6 +25,9 @@ inline int launch_rc()
 template <int DIM, typename T> int launch_bwd_wave(unsigned nq, const ArgsT<DIM, T> &a, hipStream_t s);
 template <int DIM, typename T> int launch_bwd_mfma(unsigned nq, const ArgsT<DIM, T> &a, hipStream_t s);
 template <int DIM, typename T> int launch_bwd_mfma4(unsigned nq, const ArgsT<DIM, T> &a, hipStream_t s);
+// the 3D 4x4x4_4b kernel with its output path named: the element assembled in LDS and streamed out flat, or (direct) the
+// sweep-3 accumulators stored as they are; launch_bwd_mfma4<3, double> picks per order (sf_bwdtrans_hex_f64_mfma4)
+int launch_hex_mfma4_path(bool direct, unsigned nq, const HexArgs &a, hipStream_t s);
 // what SF_VARIANT_AUTO runs for an isotropic order on 16-byte-aligned in / out: the measured best kernel of the order,
 // then whatever else is built for it (SF_ENOTBUILT: nothing is); double and float
 template <int DIM, typename T> int launch_bwd_iso_auto(unsigned nq, const ArgsT<DIM, T> &a, hipStream_t s);

@@ -11,7 +11,7 @@
 namespace sf
 {
 
-// zeroes the eight ticket counters of a launch's 64-byte slot (one device-wide counter, or one per XCD)
+// zeroes a launch's 64-byte slot of the counter ring (eight words; the kernel's batch counter is the first)
 static __global__ void counter_reset_kernel(unsigned long long *ctr)
 {
     __hip_atomic_store(ctr + threadIdx.x, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -49,12 +49,11 @@ inline int launch_quad_mfma(const QuadArgsT<T> &a, hipStream_t s, int grid_overr
                                          grid_override, s, a.nelmt, a.b0, a.b1, a.in, a.out, a.nelmt);
 }
 
-template <int NQ, int EB, int WPB, int MINW, int GJ, int KMAP, int XG, bool SHB, int DYNB, bool PEEL = true, bool SPLIT = false,
-          int XR = 0>
+template <int NQ, int EB, int WPB, int MINW, int GJ, int KMAP, int XG, bool SHB, int DYNB, bool PEEL = true>
 inline int launch_quad_mfma4_impl(const QuadArgs &a, hipStream_t s)
 {
     static OccCache cache = {};
-    auto kern            = quad_mfma4_kernel<NQ, EB, WPB, MINW, GJ, KMAP, XG, SHB, DYNB, PEEL, SPLIT, false, false, XR>;
+    auto kern            = quad_mfma4_kernel<NQ, EB, WPB, MINW, GJ, KMAP, XG, SHB, DYNB, PEEL>;
     constexpr size_t lds = mfma4_lds_bytes<NQ, EB, WPB, SHB>();
     static_assert(lds <= 160 * 1024, "LDS slab exceeds 160 KiB");
     static_assert(DYNB == 0 || KMAP == 0, "the batch counter feeds a persistent grid");
@@ -73,7 +72,7 @@ inline int launch_quad_mfma4_impl(const QuadArgs &a, hipStream_t s)
         if (counter_acquire(s, &ctr) != SF_OK)
         {
             unit.unlock();
-            return launch_quad_mfma4_impl<NQ, EB, WPB, MINW, GJ, KMAP, XG, SHB, 0, PEEL, SPLIT, 0>(a, s);
+            return launch_quad_mfma4_impl<NQ, EB, WPB, MINW, GJ, KMAP, XG, SHB, 0, PEEL>(a, s);
         }
         // zeroed by a one-thread kernel, not a memset: under stream capture a memset node on a pointer INSIDE an
         // allocation did not zero the counter on ROCm 7.2 (the replayed grid then saw a stale ticket and exited)
@@ -85,17 +84,17 @@ inline int launch_quad_mfma4_impl(const QuadArgs &a, hipStream_t s)
 
 // SHBONLY: the configuration only fits the LDS with one basis copy (b0 == b1)
 template <int NQ, int EB, int WPB, int MINW, int GJ, int KMAP, int XG = 0, bool SHBONLY = false, int DYNB = 0,
-          bool PEEL = true, bool SPLIT = false, int XR = 0>
+          bool PEEL = true>
 inline int launch_quad_mfma4(const QuadArgs &a, hipStream_t s)
 {
     if (a.nelmt == 0)
         return SF_OK;
     if (a.b0 == a.b1)
-        return launch_quad_mfma4_impl<NQ, EB, WPB, MINW, GJ, KMAP, XG, true, DYNB, PEEL, SPLIT, XR>(a, s);
+        return launch_quad_mfma4_impl<NQ, EB, WPB, MINW, GJ, KMAP, XG, true, DYNB, PEEL>(a, s);
     if constexpr (SHBONLY)
         return SF_ENOTBUILT;
     else
-        return launch_quad_mfma4_impl<NQ, EB, WPB, MINW, GJ, KMAP, XG, false, DYNB, PEEL, SPLIT, XR>(a, s);
+        return launch_quad_mfma4_impl<NQ, EB, WPB, MINW, GJ, KMAP, XG, false, DYNB, PEEL>(a, s);
 }
 
 template <int NQ, int EC, int WPB, int MINW, int KMAP, int XG = 0, typename T = double>

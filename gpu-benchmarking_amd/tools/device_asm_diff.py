@@ -2,7 +2,7 @@
 """Compare the gfx950 device code of two source trees, kernel by kernel: the check of a refactor that must not change
 what a kernel does.
 
-    python3 tools/device_asm_diff.py PARENT_TREE NEW_TREE [--identical] [-j N] [unit ...]
+    python3 tools/device_asm_diff.py PARENT_TREE NEW_TREE [--identical | --by-content] [-j N] [unit ...]
 
 PARENT_TREE / NEW_TREE: two copies of gpu-benchmarking_amd/ (the directories that hold csrc/).  unit: file names under
 csrc/ (default: every csrc/*.hip of NEW_TREE).  Each unit of each tree is compiled to device assembly with the flags of the
@@ -14,6 +14,11 @@ buffer_*, flat_*, scratch_*); the occupancy remark; the LDS size.  Scratch size 
 the parent's kernel already has some, not above the parent's.
 Recorded (a table row for every kernel where one moved): VGPRs, SGPRs, s_waitcnt count, instruction count.
 With --identical the sha256 of every kernel's text must be equal instead (units that the change does not touch).
+With --by-content kernels are matched by text, not by name (a change that removes kernels, which renumbers the local
+labels of every later kernel of the unit, or template parameters, which renames a kernel): the function index in local
+labels (.LBB<f>_<n>, .LJTI<f>_<n>, ...) and the kernel's own name are normalised before hashing, and every kernel of the
+new tree must then equal one kernel of the parent's unit, each parent kernel serving once.  Parent kernels left without
+a partner are listed by demangled name; the exit status is 0 when every new kernel found one.
 """
 import argparse
 import collections
@@ -32,6 +37,13 @@ REMARK = re.compile(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[-Rpass")
 EQUAL = ("Occupancy", "LDS Size")
 ZERO = ("ScratchSize", "VGPRs Spill", "SGPRs Spill")
 RECORD = ("VGPRs", "TotalSGPRs", "s_waitcnt", "insts")
+LABEL = re.compile(r"(\.L[A-Za-z_]+|\bBB)\d+_(\d+)")  # .LBB12_3 and, in comments, BB12_3: drop the function index
+
+
+def content_sha(name, text):
+    """sha256 of a kernel's text with its own name, the function index of local labels and column padding normalised."""
+    body = LABEL.sub(r"\1_\2", "\n".join(text).replace(name, "KERNEL"))
+    return hashlib.sha256(re.sub(r"[ \t]+", " ", body).encode()).hexdigest()
 
 
 def kernels_of(tree, unit):
@@ -61,6 +73,7 @@ def kernels_of(tree, unit):
                    if t and not t.startswith(".") and not t.endswith(":")]
             k = dict(res.get(cur, {}))
             k["sha"] = hashlib.sha256("\n".join(text).encode()).hexdigest()
+            k["csha"] = content_sha(cur, text)
             k["must"] = collections.Counter(o for o in ops if MUST.match(o))
             k["s_waitcnt"] = sum(o.startswith("s_waitcnt") for o in ops)
             k["insts"] = len(ops)
@@ -70,12 +83,42 @@ def kernels_of(tree, unit):
     return out
 
 
+def demangled(names):
+    out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
+    return [re.sub(r"^void sf::", "", d).split("(")[0] for d in out]
+
+
+def by_content(unit, old, new):
+    """Pair every kernel of `new` with one of `old` of equal normalised text; returns the number left without one."""
+    free = collections.defaultdict(list)
+    for n in sorted(old):
+        free[old[n]["csha"]].append(n)
+    lone = []
+    for n in sorted(new, key=lambda n: (n not in old, n)):  # kernels that kept their name take their namesake first
+        pool = free[new[n]["csha"]]
+        if n in pool:
+            pool.remove(n)
+        elif pool:
+            pool.pop(0)
+        else:
+            lone.append(n)
+    for d in demangled(lone):
+        print(f"FAIL {unit}: {d}: equals no kernel of the parent tree")
+    rest = sorted(n for pool in free.values() for n in pool)
+    for d in demangled(rest):
+        print(f"parent only {unit}: {d}")
+    print(f"== {unit}: parent {len(old)} kernels, new {len(new)}, {len(new) - len(lone)} equal a parent kernel by content, "
+          f"{len(rest)} only in the parent, {len(lone)} FAILED")
+    return len(lone)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("parent")
     ap.add_argument("new")
     ap.add_argument("units", nargs="*")
     ap.add_argument("--identical", action="store_true")
+    ap.add_argument("--by-content", action="store_true")
     ap.add_argument("-j", type=int, default=8)
     a = ap.parse_intermixed_args()  # unit names may follow the flags
     units = a.units or sorted(os.path.basename(p) for p in glob.glob(os.path.join(a.new, "csrc", "*.hip")))
@@ -84,11 +127,12 @@ def main():
     bad = 0
     for u in units:
         old, new = jobs[(a.parent, u)].result(), jobs[(a.new, u)].result()
+        if a.by_content:
+            bad += by_content(u, old, new)
+            continue
         names = sorted(set(old) | set(new))
-        dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
         same = moved = fail = 0
-        for n, d in zip(names, dem):
-            short = re.sub(r"^void sf::", "", d).split("(")[0]
+        for n, short in zip(names, demangled(names)):
             if n not in old or n not in new:
                 print(f"FAIL {u}: {short}: only in the {'new' if n in new else 'parent'} tree")
                 fail += 1

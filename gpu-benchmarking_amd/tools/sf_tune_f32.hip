@@ -1,6 +1,7 @@
 // sf_tune_f32.hip -- configuration sweep of the T = float instantiations (development tool).
 #include "../csrc/sf_dispatch.h"
 #include "../csrc/wave_launch.h"
+#include "../csrc/wave_table.h"
 #include "tune_guard.h"
 
 #include <algorithm>
@@ -89,6 +90,32 @@ void quad_case(const QuadArgsT<float> &a)
         [&]() { return launch_quad_wave<NQ, EC, WPB, BM, MW, KM, OUT, MEMF, float>(a, 0); });
 }
 
+// fp32 matrix-core kernel (bwdtrans_mfma.h, T = float): the candidates AUTO's fp32 rows were picked from
+// (bwdtrans_quad.hip / bwdtrans_hex.hip go_f32; profiles/r03/f32_mfma_configurations*.log, f32_hex_mfma_configurations.log)
+template <int NQ, int EC, int WPB, int MW, int KM, bool OUTL, int XG> void quad_mfma_case(const QuadArgsT<float> &a)
+{
+    char label[96];
+    std::snprintf(label, sizeof label, "quad f32 nq%d mfma EC%d WPB%d MW%d K%d outl%d xg%d", NQ, EC, WPB, MW, KM, (int)OUTL, XG);
+    const double nm = NQ - 1;
+    if (!tune::fits(label, sizeof(float) * a.nelmt * tune::ipow(NQ - 1, 2), sizeof(float) * a.nelmt * tune::ipow(NQ, 2),
+                    sizeof(float) * (NQ - 1) * NQ))
+        return;
+    run(label, a.nelmt * nm * nm, a.nelmt * 4.0 * (nm * nm + (double)NQ * NQ), a.out, a.nelmt * (size_t)NQ * NQ,
+        [&]() { return launch_quad_mfma<NQ, EC, WPB, MW, KM, OUTL, XG, float>(a, 0); });
+}
+
+template <int NQ, int EC, int WPB, int MW, int KM, int XG> void hex_mfma_case(const HexArgsT<float> &a)
+{
+    char label[96];
+    std::snprintf(label, sizeof label, "hex f32 nq%d mfma EC%d WPB%d MW%d K%d xg%d", NQ, EC, WPB, MW, KM, XG);
+    const double nm = NQ - 1;
+    if (!tune::fits(label, sizeof(float) * a.nelmt * tune::ipow(NQ - 1, 3), sizeof(float) * a.nelmt * tune::ipow(NQ, 3),
+                    sizeof(float) * (NQ - 1) * NQ))
+        return;
+    run(label, a.nelmt * nm * nm * nm, a.nelmt * 4.0 * (nm * nm * nm + (double)NQ * NQ * NQ), a.out,
+        a.nelmt * (size_t)NQ * NQ * NQ, [&]() { return launch_hex_mfma<NQ, EC, WPB, MW, KM, XG, float>(a, 0); });
+}
+
 int main(int argc, char **argv)
 {
     const size_t nelmt = argc > 1 ? (size_t)std::atoll(argv[1]) : (size_t)1 << 20;
@@ -96,8 +123,10 @@ int main(int argc, char **argv)
     CK(hipEventCreate(&g_e0));
     CK(hipEventCreate(&g_e1));
     constexpr int NQ = 8, NM = 7;
-    // buffers hold the LARGEST case below: hex nq 8 (343 in / 512 out per element) and quad nq 24 (529 / 576)
-    constexpr size_t kMaxIn = 529, kMaxOut = 576, kMaxBasis = 23 * 24;
+    // buffers hold the LARGEST case below: hex nq 8 (343 in / 512 out per element) and quad nq 32 (961 / 1024); the hex
+    // nq 12..16 cases (3375 / 4096 at nq 16) run on an eighth of the elements
+    constexpr size_t kMaxIn = 961, kMaxOut = 1024, kMaxBasis = 31 * 32;
+    static_assert(8 * kMaxIn >= 15 * 15 * 15 && 8 * kMaxOut >= 16 * 16 * 16, "hex nq 16 on nelmt / 8 elements must fit");
     static_assert(kMaxIn >= NM * NM * NM && kMaxOut >= NQ * NQ * NQ, "hex nq 8 must fit");
     float *b, *in, *out;
     CK(hipMalloc((void **)&b, sizeof(float) * NM * NQ));
@@ -175,6 +204,43 @@ int main(int argc, char **argv)
         ODD(5, 48, BASIS_SMEM, 4, 0) ODD(7, 36, BASIS_SMEM, 4, 8) ODD(9, 28, BASIS_SMEM, 4, 8)
         ODD(11, 20, BASIS_SMEM_COLS, 2, 8)
 #undef ODD
+    }
+    // 2D nq 25..32: the matrix-core configurations against the vector kernel's table row
+    for (int rep = 0; rep < 2; ++rep)
+    {
+#define QM(NQ)                                                                                     \
+    {                                                                                              \
+        using C = QuadCfgF32<NQ>;                                                                  \
+        static_assert((NQ - 1) * NQ <= kMaxBasis, "basis buffer");                                 \
+        fill_basis_f32(b2, NQ - 1, NQ, 0);                                                         \
+        QuadArgsT<float> qq{b2, b2, in, nullptr, out, nelmt};                                      \
+        quad_case<NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, C::OUT, C::MF>(qq);                      \
+        quad_mfma_case<NQ, 2, 4, 2, 2, (NQ != 32), 64>(qq);                                        \
+        quad_mfma_case<NQ, 2, 4, 4, 2, (NQ != 32), 64>(qq);                                        \
+        quad_mfma_case<NQ, 4, 4, 2, 1, (NQ != 32), 64>(qq);                                        \
+        quad_mfma_case<NQ, 4, 4, 4, 1, (NQ != 32), 64>(qq);                                        \
+        quad_mfma_case<NQ, 2, 4, 4, 1, (NQ != 32), 64>(qq);                                        \
+    }
+        QM(25) QM(26) QM(27) QM(28) QM(29) QM(30) QM(31) QM(32)
+#undef QM
+    }
+    // 3D nq 12..16, on nelmt / 8 elements: the matrix-core configurations against the vector kernel's table row
+    for (int rep = 0; rep < 2; ++rep)
+    {
+#define HM(NQ)                                                                                     \
+    {                                                                                              \
+        using C = HexCfgF32<NQ>;                                                                   \
+        static_assert((NQ - 1) * NQ <= kMaxBasis, "basis buffer");                                 \
+        fill_basis_f32(b2, NQ - 1, NQ, 0);                                                         \
+        HexArgsT<float> hh{b2, b2, b2, in, nullptr, out, nelmt / 8};                               \
+        hex_case<NQ, C::EC, C::WPB, C::BM, C::MW, C::KM, C::OUT, C::MF>(hh);                       \
+        hex_mfma_case<NQ, 1, 1, 1, 1, 64>(hh);                                                     \
+        hex_mfma_case<NQ, 1, 1, 2, 1, 64>(hh);                                                     \
+        hex_mfma_case<NQ, 1, 2, 2, 1, 64>(hh);                                                     \
+        hex_mfma_case<NQ, 2, 1, 1, 1, 64>(hh);                                                     \
+    }
+        HM(12) HM(13) HM(14) HM(15) HM(16)
+#undef HM
     }
     return 0;
 }

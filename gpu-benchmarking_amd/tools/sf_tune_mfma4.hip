@@ -8,7 +8,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <string>
 #include <vector>
 
 #ifndef TUNE_NQ
@@ -93,7 +92,7 @@ template <class F> static void run(const char *label, const QuadArgs &a, F launc
     std::fflush(stdout);
 }
 
-template <int EB, int WPB, int MW, int GJ, int K, int XG, int DYNB = 0, bool PEEL = true, bool SPLIT = false, int XR = 0>
+template <int EB, int WPB, int MW, int GJ, int K, int XG, int DYNB = 0, bool PEEL = true>
 static void m4(const QuadArgs &a)
 {
     constexpr int NQ = TUNE_NQ;
@@ -107,49 +106,18 @@ static void m4(const QuadArgs &a)
     else if constexpr (mfma4_lds_bytes<NQ, EB, WPB>() <= 160 * 1024)
     {
         char label[96];
-        std::snprintf(label, sizeof label, "quad nq%d MFMA4 EB%d WPB%d MW%d GJ%d K%d xg%d dyn%d%s xr%d lds %zu", NQ, EB, WPB, MW, GJ, K,
-                      XG, DYNB, PEEL ? (SPLIT ? " split" : "") : " nopeel", XR, mfma4_lds_bytes<NQ, EB, WPB>());
-        run(label, a, [&]() { return launch_quad_mfma4<NQ, EB, WPB, MW, GJ, K, XG, false, DYNB, PEEL, SPLIT, XR>(a, 0); });
-    }
-}
-
-// ST ticket counters in lines of their own (quad_mfma4_kernel's ST): small batches without the one-line atomic limit
-template <int EB, int WPB, int MW, int DYNB, int ST, int GW = 0> static void m4s(const QuadArgs &a)
-{
-    constexpr int NQ = TUNE_NQ;
-    constexpr size_t lds = mfma4_lds_bytes<NQ, EB, WPB, true>();
-    if constexpr (lds <= 160 * 1024)
-    {
-        auto kern = quad_mfma4_kernel<NQ, EB, WPB, MW, 4, 0, 0, true, DYNB, true, false, false, false, 0, ST>;
-        if (lds > 48 * 1024)
-            CK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int bpc = 0, cus = 0;
-        CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kern, kWave * WPB, lds));
-        CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
-        const uint64_t nchunk = (a.nelmt + EB - 1) / EB, need = (nchunk + WPB - 1) / WPB;
-        uint64_t grid         = (uint64_t)(GW > 0 ? GW : bpc) * cus;
-        if (grid > need)
-            grid = need;
-        static unsigned long long *ctr = nullptr;
-        if (!ctr)
-            CK(hipMalloc((void **)&ctr, 128 * 64));
-        char label[96];
-        std::snprintf(label, sizeof label, "quad nq%d MFMA4 EB%d WPB%d MW%d K0 dyn%d striped%d (%d wg/CU) lds %zu", NQ, EB, WPB, MW, DYNB,
-                      ST, GW > 0 ? GW : bpc, lds);
-        run(label, a, [&]() {
-            (void)hipMemsetAsync(ctr, 0, 128 * 64, 0);
-            kern<<<(unsigned)grid, kWave * WPB, lds>>>(a.b0, a.b1, a.in, a.out, a.nelmt, ctr, nullptr);
-            return (int)hipGetLastError();
-        });
+        std::snprintf(label, sizeof label, "quad nq%d MFMA4 EB%d WPB%d MW%d GJ%d K%d xg%d dyn%d%s lds %zu", NQ, EB, WPB, MW, GJ, K,
+                      XG, DYNB, PEEL ? "" : " nopeel", mfma4_lds_bytes<NQ, EB, WPB>());
+        run(label, a, [&]() { return launch_quad_mfma4<NQ, EB, WPB, MW, GJ, K, XG, false, DYNB, PEEL>(a, 0); });
     }
 }
 
 // shader-clock time per phase of the chunk loop (quad_mfma4_kernel with STAMP): persistent grid fed by the batch counter,
 // or one chunk per wave
-template <int EB, int WPB, int MW, int K, int XG, int DYNB, bool EFL = false> static void phases(const QuadArgs &a)
+template <int EB, int WPB, int MW, int K, int XG, int DYNB> static void phases(const QuadArgs &a)
 {
     constexpr int NQ = TUNE_NQ;
-    auto kern        = quad_mfma4_kernel<NQ, EB, WPB, MW, 4, K, XG, true, DYNB, true, false, true, EFL>;
+    auto kern        = quad_mfma4_kernel<NQ, EB, WPB, MW, 4, K, XG, true, DYNB, true, true>;
     constexpr size_t lds = mfma4_lds_bytes<NQ, EB, WPB, true>();
     if (lds > 48 * 1024)
         CK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -192,9 +160,9 @@ template <int EB, int WPB, int MW, int K, int XG, int DYNB, bool EFL = false> st
     CK(hipFree(dres));
     std::printf("(stamped launch: %.3f ms, max|d| %.2e) ", ms, hres);
     const double n = (double)host[5];
-    std::printf("phases%s nq%d EB%d WPB%d MW%d K%d dyn%d (%d blocks/CU): shader clocks per chunk: stage+issue %.0f | step 1 %.0f | "
+    std::printf("phases nq%d EB%d WPB%d MW%d K%d dyn%d (%d blocks/CU): shader clocks per chunk: stage+issue %.0f | step 1 %.0f | "
                 "step 2 %.0f | flush %.0f | wait next %.0f | sum %.0f (%llu chunks)\n",
-                EFL ? " [stores per j group]" : "", NQ, EB, WPB, MW, K, DYNB, bpc, host[0] / n, host[1] / n, host[2] / n, host[3] / n, host[4] / n,
+                NQ, EB, WPB, MW, K, DYNB, bpc, host[0] / n, host[1] / n, host[2] / n, host[3] / n, host[4] / n,
                 (host[0] + host[1] + host[2] + host[3] + host[4]) / n, host[5]);
 }
 
@@ -223,37 +191,11 @@ int main(int argc, char **argv)
                 NQ, nelmt, g_reps);
     run("generic block/LDS (reference result)", a, [&]() { return launch_bwd_generic<2, double>(SF_VARIANT_BLOCK_LDS, {NQ, NQ, 0u}, a, 0); },
         true);
-    if (argc > 3 && std::string(argv[3]) == "striped")
-    {
-        for (int rep = 0; rep < 2; ++rep)
-        {
-            m4<2, 4, 2, 4, 0, 0, 4>(a);
-            m4<2, 4, 2, 4, 0, 0, 8>(a);
-            m4s<2, 4, 2, 4, 1>(a); // the single counter through this launcher
-            m4s<2, 4, 2, 4, 16>(a);
-            m4s<2, 4, 2, 2, 16>(a);
-            m4s<2, 4, 2, 1, 16>(a);
-            m4s<2, 4, 2, 1, 64>(a);
-            m4s<2, 4, 2, 2, 64>(a);
-            m4s<2, 4, 2, 1, 8>(a);
-            m4s<4, 4, 1, 1, 16>(a);
-            m4s<4, 4, 1, 2, 16>(a);
-            m4s<4, 4, 1, 1, 64>(a);
-            m4s<1, 4, 4, 1, 64>(a);
-            m4s<1, 4, 4, 2, 64>(a);
-            m4s<1, 4, 3, 1, 64>(a);
-        }
-        return 0;
-    }
     phases<2, 4, 2, 0, 0, 4>(a);
     phases<2, 4, 2, 1, 64, 0>(a);
     phases<2, 4, 2, 2, 64, 0>(a);
     phases<1, 4, 4, 1, 64, 0>(a);
     phases<4, 4, 1, 0, 0, 4>(a);
-    phases<2, 4, 2, 0, 0, 4, true>(a);
-    phases<2, 4, 2, 1, 64, 0, true>(a);
-    phases<2, 4, 2, 2, 64, 0, true>(a);
-    phases<1, 4, 4, 1, 64, 0, true>(a);
     if (argc > 3) // phases only
         return 0;
     for (int rep = 0; rep < 2; ++rep)
@@ -265,18 +207,8 @@ int main(int argc, char **argv)
         m4<2, 4, 2, 4, 0, 0>(a);
         m4<2, 4, 2, 4, 0, 0, 4>(a);
         m4<2, 4, 2, 4, 0, 0, 4, false>(a); // the same without the peeled k remainder (differs at nm = 1, 2 mod 4 only)
-        m4<2, 4, 2, 4, 0, 0, 4, true, true>(a); // ... with the unpaired i tile's spare blocks splitting the q tiles (odd tile counts)
-        m4<2, 4, 2, 4, 1, 64, 0, true, true>(a);
-        m4<2, 4, 2, 4, 2, 64, 0, true, true>(a);
         m4<2, 4, 2, 4, 1, 64, 0, false>(a);
         m4<2, 4, 2, 4, 0, 0, 8>(a);
-        // batch tickets per XCD: runs of 4 / 16 / 64 neighbouring batches on one XCD
-        m4<2, 4, 2, 4, 0, 0, 4, true, false, 4>(a);
-        m4<2, 4, 2, 4, 0, 0, 4, true, false, 16>(a);
-        m4<2, 4, 2, 4, 0, 0, 4, true, false, 64>(a);
-        m4<2, 4, 2, 4, 0, 0, 2, true, false, 32>(a);
-        m4<2, 4, 2, 4, 0, 0, 1, true, false, 64>(a);
-        m4<4, 4, 1, 4, 0, 0, 4, true, false, 16>(a);
         m4<2, 8, 2, 4, 0, 0, 8>(a);
         m4<4, 4, 1, 4, 0, 0>(a);
         m4<4, 4, 1, 4, 0, 0, 4>(a);

@@ -97,6 +97,15 @@ int sf_bwdtrans_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigne
                                 const double *basis2, const double *in, double *wsp, double *out,
                                 void *stream);
 
+/* For tests and tuning: the SF_VARIANT_MFMA4 kernel of the isotropic order nq with its output path named.  direct == 0
+ * assembles the element in LDS and streams it out flat; direct != 0 stores the accumulators of the third sweep as they
+ * are.  SF_VARIANT_AUTO and SF_VARIANT_MFMA4 keep choosing the path per order (direct at nq = 16 only).  For the same
+ * arguments it answers what sf_bwdtrans_hex_f64_variant(SF_VARIANT_MFMA4, nq, nq, nq, ..., wsp = NULL, ...) answers: the
+ * same validation, SF_EALIGN unless in / out are 16-byte aligned, SF_ENOTBUILT (before any HIP call) outside nq 12..16. */
+int sf_bwdtrans_hex_f64_mfma4(int direct, unsigned nq, size_t nelmt, const double *basis0,
+                              const double *basis1, const double *basis2, const double *in,
+                              double *out, void *stream);
+
 /*
  * 2D quad BwdTrans: out[e][j][i] = sum_q sum_p in[e][q][p] B0[p][i] B1[q][j].
  * Replaces BwdTransQuadKernel_QP_1D<<<blocks, threads, smem>>>(nm0,nm1,nmTot,nq0,nq1,nelmt,

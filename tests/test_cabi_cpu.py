@@ -56,6 +56,34 @@ def test_argument_validation_without_gpu(pkg):
     assert lib.sf_bwdtrans_hex_f64(8, 8, 8, 4, 0x1000, 0x1000, 0x1000, 0x1001, 0x2000, None) == -2
 
 
+def test_hex_mfma4_export_validates_as_the_variant_without_gpu(pkg):
+    """sf_bwdtrans_hex_f64_mfma4 answers what sf_bwdtrans_hex_f64_variant(SF_VARIANT_MFMA4, nq, nq, nq, ...) answers,
+    whichever output path is named -- and, off the kernel's table, before any HIP call."""
+    lib = pkg.capi.lib()
+    mfma4 = pkg.VARIANTS["mfma4"]
+    A = 0x10000  # 16-byte-aligned dummies, never dereferenced
+    cases = [  # nq, nelmt, (basis0, basis1, basis2, in, out), expected code
+        (1, 10, (A, A, A, A, A), pkg.capi.SF_EINVAL),
+        (12, 0, (None, None, None, None, None), pkg.capi.SF_OK),
+        (12, 4, (A, A, None, A, A), pkg.capi.SF_EINVAL),            # a null among the pointers
+        (12, 4, (A, A, A, A + 1, A), pkg.capi.SF_EALIGN),           # an odd address
+        (11, 4, (A, A, A, A, A), pkg.capi.SF_ENOTBUILT),            # off the table
+        (12, 4, (A, A, A, A + 8, A), pkg.capi.SF_EALIGN),           # `in` only 8-byte aligned
+    ]
+    for nq, nelmt, (b0, b1, b2, x, out), want in cases:
+        assert lib.sf_bwdtrans_hex_f64_variant(mfma4, nq, nq, nq, nelmt, b0, b1, b2, x, None, out, None) == want, (nq, nelmt)
+        for direct in (0, 1):
+            assert lib.sf_bwdtrans_hex_f64_mfma4(direct, nq, nelmt, b0, b1, b2, x, out, None) == want, (direct, nq, nelmt)
+
+
+def test_library_reads_no_environment_variable():
+    """The kernels' configuration is what the source says: no file under csrc/ reads the environment."""
+    csrc = os.path.join(ROOT, "gpu-benchmarking_amd", "csrc")
+    for dirpath, _, files in os.walk(csrc):
+        for f in files:
+            assert "getenv" not in open(os.path.join(dirpath, f)).read(), f
+
+
 def test_product_never_imports_oracle():
     """The product path must not route through the oracle (or any CPU fallback)."""
     pkg_dir = os.path.join(ROOT, "gpu-benchmarking_amd")

@@ -109,26 +109,31 @@ def test_hex_mfma_parity_all_orders(sf, oracle, nq):
             assert err <= TOL, (nq, nelmt, err)
 
 
+def _hex_mfma4_legs(sf, nq, bs, x, out_of=lambda: None):
+    """(label, output) of one input through the 4x4x4 kernel: both output paths by name, and SF_VARIANT_MFMA4's choice."""
+    yield "lds", sf.bwdtrans_hex_mfma4(nq, *bs, x, False, out=out_of())
+    yield "direct", sf.bwdtrans_hex_mfma4(nq, *bs, x, True, out=out_of())
+    yield "mfma4", sf.bwdtrans_hex((nq,) * 3, *bs, x, out=out_of(), variant="mfma4")
+
+
 @pytest.mark.parametrize("nq", range(12, 17))
 def test_hex_mfma4_parity_all_orders(sf, oracle, nq):
-    """3D kernel on v_mfma_f64_4x4x4_4b (csrc/bwdtrans_hmfma4.h; AUTO runs it at nq 12 and 16): every order it is built
-    for, both output paths, ragged element counts, plus more elements than the grid has waves with distinct bases per
+    """3D kernel on v_mfma_f64_4x4x4_4b (csrc/bwdtrans_hmfma4.h; AUTO runs it at nq 12, 14 and 16): every order it is
+    built for, both output paths (output through an LDS image / accumulators stored directly) and the path
+    SF_VARIANT_MFMA4 picks, ragged element counts, plus more elements than the grid has waves with distinct bases per
     direction."""
-    import os
-    try:
-        for cfg in ("1", "3"):  # output through an LDS image / accumulators stored directly
-            os.environ["SF_HEX_MFMA4_CFG"] = cfg
-            for nelmt in (1, 2, 3, 7, 64, 129, 600):
-                err = _hex_case(sf, oracle, (nq,) * 3, nelmt, "mfma4", seed=nelmt + nq)
-                assert err <= TOL, (cfg, nq, nelmt, err)
-            nelmt = 5003
+    for nelmt in (1, 2, 3, 7, 64, 129, 600, 5003):
+        seed = nelmt + nq
+        if nelmt == 5003:
             bs = [sf.fill_random((nq - 1) * nq, 11 + d) for d in range(3)]
             x = sf.fill_random(nelmt * (nq - 1) ** 3, 5 + nq)
-            got = sf.bwdtrans_hex((nq,) * 3, *bs, x, variant="mfma4")
-            ref = oracle.bwdtrans_hex((nq,) * 3, nelmt, *[_np(b) for b in bs], _np(x))
-            assert oracle.rel_err(_np(got), ref) <= TOL, cfg
-    finally:
-        os.environ.pop("SF_HEX_MFMA4_CFG", None)
+        else:
+            bs = [sf.fill_random((nq - 1) * nq, 100 + d + seed) for d in range(3)]
+            x = sf.fill_random(nelmt * (nq - 1) ** 3, seed)
+        ref = oracle.bwdtrans_hex((nq,) * 3, nelmt, *[_np(b) for b in bs], _np(x))
+        for leg, got in _hex_mfma4_legs(sf, nq, bs, x):
+            err = oracle.rel_err(_np(got), ref)
+            assert err <= TOL, (leg, nq, nelmt, err)
 
 
 RT_SHAPES = [(8, 8, 4), (4, 8, 6), (10, 6, 8), (2, 2, 2), (2, 16, 3), (16, 2, 2), (3, 2, 5), (7, 7, 7), (5, 9, 13),
@@ -456,29 +461,26 @@ def test_hex_matrix_core_orders_line_offsets_and_guard_bands(sf, oracle, torch_m
     """3D nq 12..16 through AUTO (hex_mfma4_kernel at 12 / 14 / 16 -- nq 16 stores its accumulators directly --,
     hex_mfma_kernel at 13 / 15) and through both output paths of the 4x4x4 kernel: every 16-byte-multiple offset of `in`
     and `out` inside a 128-byte line gives the oracle's result, and nothing is written before or after the output view."""
-    import os
     GUARD = 32
     nmt, nqt = (nq - 1) ** 3, nq ** 3
     bs = [sf.fill_random((nq - 1) * nq, 60 + d) for d in range(3)]
-    try:
-        for variant, cfg in (("auto", None), ("mfma4", "1"), ("mfma4", "3")):
-            if cfg is None:
-                os.environ.pop("SF_HEX_MFMA4_CFG", None)
-            else:
-                os.environ["SF_HEX_MFMA4_CFG"] = cfg
-            for nelmt, off_in, off_out in ((131, 2, 0), (300, 6, 4), (77, 10, 14), (64, 0, 8), (5, 12, 2)):
-                xbuf = sf.fill_random(nelmt * nmt + 16, 7 * nq + nelmt)
-                x = xbuf[off_in:off_in + nelmt * nmt]
-                obuf = torch_mod.full((nelmt * nqt + 2 * GUARD,), -7.0, dtype=torch_mod.float64, device="cuda")
-                out = obuf[GUARD + off_out - 16:GUARD + off_out - 16 + nelmt * nqt]
-                sf.bwdtrans_hex((nq,) * 3, *bs, x, out=out, variant=variant)
-                ref = oracle.bwdtrans_hex((nq,) * 3, nelmt, *[_np(b) for b in bs], _np(x).copy())
-                assert oracle.rel_err(_np(out), ref) <= TOL, (variant, cfg, nq, nelmt, off_in, off_out)
-                head = obuf[:GUARD + off_out - 16]
-                tail = obuf[GUARD + off_out - 16 + nelmt * nqt:]
-                assert bool((head == -7.0).all()) and bool((tail == -7.0).all()), (variant, cfg, nq, nelmt)
-    finally:
-        os.environ.pop("SF_HEX_MFMA4_CFG", None)
+    for nelmt, off_in, off_out in ((131, 2, 0), (300, 6, 4), (77, 10, 14), (64, 0, 8), (5, 12, 2)):
+        xbuf = sf.fill_random(nelmt * nmt + 16, 7 * nq + nelmt)
+        x = xbuf[off_in:off_in + nelmt * nmt]
+        ref = oracle.bwdtrans_hex((nq,) * 3, nelmt, *[_np(b) for b in bs], _np(x).copy())
+        obufs = []
+
+        def view():
+            obufs.append(torch_mod.full((nelmt * nqt + 2 * GUARD,), -7.0, dtype=torch_mod.float64, device="cuda"))
+            return obufs[-1][GUARD + off_out - 16:GUARD + off_out - 16 + nelmt * nqt]
+
+        legs = [("auto", sf.bwdtrans_hex((nq,) * 3, *bs, x, out=view(), variant="auto"))]
+        legs += _hex_mfma4_legs(sf, nq, bs, x, view)
+        for (leg, out), obuf in zip(legs, obufs):
+            assert oracle.rel_err(_np(out), ref) <= TOL, (leg, nq, nelmt, off_in, off_out)
+            head = obuf[:GUARD + off_out - 16]
+            tail = obuf[GUARD + off_out - 16 + nelmt * nqt:]
+            assert bool((head == -7.0).all()) and bool((tail == -7.0).all()), (leg, nq, nelmt)
 
 
 @pytest.mark.parametrize("dim,nq", [(3, 8), (3, 10), (3, 5), (3, 13), (2, 16), (2, 20), (2, 28), (2, 9)])
