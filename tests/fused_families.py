@@ -36,7 +36,7 @@ import numpy as np
 
 from affine_ref import affine_eval, affine_excess, affine_n, ref_affine
 from helm_ref import COMPONENTS, helm_excess, helm_n, helmholtz_f64, ref_helmholtz
-from iprod_ref import U64, elementwise_excess, gamma, iprod_f64, ref_iprod, unit_roundoff  # noqa: F401
+from iprod_ref import U64, elementwise_excess, f64_factor, gamma, iprod_f64, ref_iprod, unit_roundoff  # noqa: F401
 from iprodderiv_ref import iprodderiv_excess, iprodderiv_f64, iprodderiv_n, ref_iprodderiv
 from mass_ref import mass_excess, mass_f64, mass_n, ref_mass
 from physderiv_ref import physderiv_excess, physderiv_f64, physderiv_n, ref_physderiv
@@ -322,12 +322,9 @@ class Problem:
         return self.fam.excess(got, ref, absref, self.nq, unit_roundoff(self.dtype_name), factor=factor)
 
     def f64_factor(self):
-        """The factor on gamma_N(u) absref64 for a result of unit roundoff u against the fp64 reference.  The result is
-        within gamma_N(u) and the reference within gamma_N(u64) of the truth, both times the exact absolute operator, and
-        that is at most (1 + gamma_N) absref64: (1 + gamma_N(u64) / gamma_N(u)) (1 + gamma_N(u)).  For an fp64 result this
-        is the 2 (1 + gamma_N) of the families' large-batch tests; for a float32 one it is 1 + 2e-9 times (1 + gamma_N)."""
-        n, u = self.fam.n(self.nq), unit_roundoff(self.dtype_name)
-        return (1 + gamma(n, U64) / gamma(n, u)) * (1 + gamma(n, u))
+        """The factor on gamma_N(u) absref64 for a result of unit roundoff u against the fp64 reference: iprod_ref.f64_factor
+        at the family's N."""
+        return f64_factor(self.fam.n(self.nq), unit_roundoff(self.dtype_name))
 
 
 def excess_over_slices(p, outs, present, step, lo=0):

@@ -23,6 +23,14 @@ def unit_roundoff(dtype_name):
     return U32 if dtype_name == "float32" else U64
 
 
+def f64_factor(n, u):
+    """The factor on gamma_n(u) absref64 for a result of unit roundoff u against an fp64 reference of the same n.  The
+    result is within gamma_n(u) and the reference within gamma_n(u64) of the truth, both times the exact absolute operator,
+    and that is at most (1 + gamma_n) absref64: (1 + gamma_n(u64) / gamma_n(u)) (1 + gamma_n(u)).  For an fp64 result this
+    is the 2 (1 + gamma_n) of the families' large-batch tests; for a float32 one it is 1 + 2e-9 times (1 + gamma_n)."""
+    return (1 + gamma(n, U64) / gamma(n, u)) * (1 + gamma(n, u))
+
+
 def _sweeps(nq, nelmt, bases, x, dt):
     """Sweeps in dtype dt; x holds nelmt * prod(nq) points, bases are nm x nq row-major."""
     nq = tuple(int(q) for q in nq)

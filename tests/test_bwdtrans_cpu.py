@@ -1,10 +1,16 @@
 """CPU-side checks of the BwdTrans entry points (include/sumfact.h sf_bwdtrans_*): the return code of every path that
 ends before a HIP call -- the validation order, the variant range, and what each explicit variant answers for extents
-off its table or for 8-byte-aligned buffers -- the Python wrappers' size checks, and the binding's signatures."""
+off its table or for 8-byte-aligned buffers -- the Python wrappers' size checks, and the binding's signatures; and the
+long-double reference and elementwise bound of tests/bwd_ref.py: against a dense contraction, against the pinned oracle,
+against deliberately wrong contractions, and against an error that the batch-maximum criterion cannot see."""
 import ctypes
+import math
 import os
 
+import numpy as np
 import pytest
+
+import bwd_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "gpu-benchmarking_amd")
@@ -154,6 +160,186 @@ def test_bwdtrans_python_checks_sizes_without_gpu(pkg):
         hx((8, 8, 8), b, b, b, x3, variant="block-glb", wsp=torch.zeros(pkg.hex_wsp_doubles((8, 8, 8), 2) - 1, dtype=f64))
     with pytest.raises(ValueError):
         qd((8, 8), b, b, x2, variant="block-glb", wsp=torch.zeros(pkg.quad_wsp_doubles((8, 8), 2) - 1, dtype=f64))
+
+
+# ---- tests/bwd_ref.py: the long-double reference and the elementwise bound of tests/test_gpu_bwdtrans_bounds.py ---------
+def _host_case(oracle, nq, nelmt, seed):
+    """Seeded per-value-distinct data, distinct bases per direction (the generator of the GPU tests)."""
+    bs = [oracle.fill_random((q - 1) * q, 500 + 7 * seed + d) for d, q in enumerate(nq)]
+    return bs, oracle.fill_random(nelmt * int(np.prod([q - 1 for q in nq])), 10 + seed)
+
+
+def _oracle_bwd(oracle, nq, nelmt, bs, x):
+    return (oracle.bwdtrans_hex if len(nq) == 3 else oracle.bwdtrans_quad)(tuple(nq), nelmt, *bs, x)
+
+
+@pytest.mark.parametrize("nq", [(2, 2, 2), (3, 5, 4), (4, 9), (2, 7)], ids=lambda s: "x".join(map(str, s)))
+def test_reference_is_the_dense_kronecker_contraction(oracle, nq):
+    """The sweeps of ref_bwdtrans against one einsum over all modes at once, both in long double: they differ by the
+    rounding of two long-double evaluations, gamma_{prod nm + N}(2^-64) absref at the most."""
+    ld, nelmt = np.longdouble, 5
+    bs, x = _host_case(oracle, nq, nelmt, 1)
+    ref, absref = bwd_ref.ref_bwdtrans(nq, nelmt, bs, x)
+    nm = [q - 1 for q in nq]
+    b = [np.asarray(v, dtype=ld).reshape(m, q) for v, m, q in zip(bs, nm, nq)]
+    if len(nq) == 3:
+        dense = np.einsum("erqp,pi,qj,rk->ekji", np.asarray(x, dtype=ld).reshape(nelmt, nm[2], nm[1], nm[0]), *b)
+        dabs = np.einsum("erqp,pi,qj,rk->ekji", np.abs(np.asarray(x, dtype=ld)).reshape(nelmt, nm[2], nm[1], nm[0]),
+                         *[np.abs(v) for v in b])
+    else:
+        dense = np.einsum("eqp,pi,qj->eji", np.asarray(x, dtype=ld).reshape(nelmt, nm[1], nm[0]), *b)
+        dabs = np.einsum("eqp,pi,qj->eji", np.abs(np.asarray(x, dtype=ld)).reshape(nelmt, nm[1], nm[0]),
+                         *[np.abs(v) for v in b])
+    assert ref.dtype == ld and absref.dtype == ld and ref.shape == (nelmt * int(np.prod(nq)),)
+    n_ld = int(np.prod(nm)) + bwd_ref.bwd_n(nq)
+    assert bwd_ref.bwd_excess(dense.reshape(-1), ref, absref, nq, 2.0 ** -64, factor=n_ld / bwd_ref.bwd_n(nq)) <= 1.0
+    assert np.all(np.abs(dabs.reshape(-1) - absref) <= 2.0 ** -60 * absref) and np.all(absref > 0)
+    f64, abs64 = bwd_ref.bwd_f64(nq, nelmt, bs, x)
+    assert f64.dtype == np.float64 and bwd_ref.bwd_excess(f64, ref, absref, nq, bwd_ref.U64) <= 1.0
+    assert np.all(np.abs(abs64 - absref) <= bwd_ref.gamma(bwd_ref.bwd_n(nq), bwd_ref.U64) * absref)
+
+
+def test_bwd_n_counts_one_rounding_per_term_of_each_sweep():
+    assert bwd_ref.bwd_n((8, 8, 8)) == 21 and bwd_ref.bwd_n((2, 2, 2)) == 3 and bwd_ref.bwd_n((3, 5, 4)) == 9
+    assert bwd_ref.bwd_n((32, 32)) == 62 and bwd_ref.bwd_n((4, 9)) == 11
+    # the factor against fp64 sweeps is the one the fused families use (fused_families.Problem.f64_factor)
+    g = bwd_ref.gamma(21, bwd_ref.U64)
+    assert bwd_ref.bwd_f64_factor((8, 8, 8), bwd_ref.U64) == 2 * (1 + g)
+    assert abs(bwd_ref.bwd_f64_factor((8, 8, 8), bwd_ref.U32) - (1 + bwd_ref.gamma(21, bwd_ref.U32))) <= 1e-8
+
+
+def test_bwd_excess_refuses_nan_and_errors_under_a_zero_bound():
+    ref, absref = np.array([1.0, 0.0, -2.0]), np.array([1.0, 0.0, 2.0])
+    assert bwd_ref.bwd_excess(ref, ref, absref, (3, 3), bwd_ref.U64) == 0.0
+    assert bwd_ref.bwd_excess(np.array([1.0, 1e-300, -2.0]), ref, absref, (3, 3), bwd_ref.U64) == math.inf
+    assert bwd_ref.bwd_excess(np.array([1.0, 0.0, np.nan]), ref, absref, (3, 3), bwd_ref.U64) == math.inf
+    one = bwd_ref.gamma(4, bwd_ref.U64)                                   # N = 4: an error of exactly the bound passes
+    assert bwd_ref.bwd_excess(np.array([1.0 + one, 0.0, -2.0]), ref, absref, (3, 3), bwd_ref.U64) <= 1.0
+    assert bwd_ref.bwd_excess(np.array([1.0 + 3 * one, 0.0, -2.0]), ref, absref, (3, 3), bwd_ref.U64) > 1.0
+    assert bwd_ref.bwd_excess(np.array([1.0 + 3 * one, 0.0, -2.0]), ref, absref, (3, 3), bwd_ref.U64, factor=4.0) <= 1.0
+
+
+ORACLE_SHAPES = [(2, 2, 2), (3, 5, 4), (8, 8, 8), (5, 9, 13), (16, 16, 16), (2, 2), (4, 9), (2, 7), (16, 16), (32, 32)]
+
+
+@pytest.mark.parametrize("nq", ORACLE_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_oracle_is_within_the_elementwise_bound(oracle, nq):
+    """The pinned oracle (fp64 sweeps in C) lies within gamma_N(2^-53) absref of the long-double reference, element by
+    element: the reference and the oracle state the same operation, and the bound holds for a correct fp64 evaluation."""
+    nelmt = 7
+    bs, x = _host_case(oracle, nq, nelmt, 2)
+    ref, absref = bwd_ref.ref_bwdtrans(nq, nelmt, bs, x)
+    q = bwd_ref.bwd_excess(_oracle_bwd(oracle, nq, nelmt, bs, x), ref, absref, nq, bwd_ref.U64)
+    print(f"oracle {nq}: max |err| / (gamma_N absref) = {q:.3g}")
+    assert q <= 1.0, (nq, q)
+
+
+def _transposed(b, q):
+    """The nm x nq basis read as if it had been stored nq x nm."""
+    return np.ascontiguousarray(np.asarray(b).reshape(q - 1, q).T).reshape(-1)
+
+
+def _mode_dropped(b, q, m):
+    out = np.array(b, dtype=np.float64).reshape(q - 1, q)
+    out[m] = 0.0
+    return out.reshape(-1)
+
+
+@pytest.mark.parametrize("nq,wrong", [
+    ((3, 5, 5), lambda bs, nq: [bs[0], bs[2], bs[1]]),                    # the bases of two directions swapped
+    ((5, 4, 5), lambda bs, nq: [bs[2], bs[1], bs[0]]),
+    ((3, 5, 4), lambda bs, nq: [bs[0], _transposed(bs[1], nq[1]), bs[2]]),  # one basis transposed
+    ((4, 9), lambda bs, nq: [_transposed(bs[0], nq[0]), bs[1]]),
+    ((3, 5, 4), lambda bs, nq: [bs[0], bs[1], _mode_dropped(bs[2], nq[2], 1)]),   # one mode dropped from one sweep
+    ((4, 9), lambda bs, nq: [bs[0], _mode_dropped(bs[1], nq[1], 7)]),
+], ids=["swap12-3x5x5", "swap02-5x4x5", "transposed1-3x5x4", "transposed0-4x9", "mode-dropped2-3x5x4", "mode-dropped1-4x9"])
+def test_the_bound_tells_a_wrong_contraction_from_a_right_one(oracle, nq, wrong):
+    nelmt = 3
+    bs, x = _host_case(oracle, nq, nelmt, 3)
+    ref, absref = bwd_ref.ref_bwdtrans(nq, nelmt, bs, x)
+    bad, _ = bwd_ref.ref_bwdtrans(nq, nelmt, wrong(bs, nq), x)
+    assert bwd_ref.bwd_excess(ref, ref, absref, nq, bwd_ref.U64) == 0.0
+    assert bwd_ref.bwd_excess(bad, ref, absref, nq, bwd_ref.U64) > 1.0
+    assert bwd_ref.bwd_excess(bad, ref, absref, nq, bwd_ref.U32) > 1.0
+
+
+def test_an_error_the_batch_maximum_hides_fails_the_elementwise_bound(oracle):
+    """Why the elementwise bound: 1000 gamma_N absref added to the single smallest entry of a correct result still meets
+    the criterion of tests/test_gpu_parity.py, max |got - oracle| / max |oracle| <= 1e-12, and fails bwd_excess."""
+    nq, nelmt = (3, 3, 3), 200
+    bs, x = _host_case(oracle, nq, nelmt, 4)
+    good = _oracle_bwd(oracle, nq, nelmt, bs, x)
+    ref, absref = bwd_ref.ref_bwdtrans(nq, nelmt, bs, x)
+    assert bwd_ref.bwd_excess(good, ref, absref, nq, bwd_ref.U64) <= 1.0
+    bad = good.copy()
+    at = int(np.argmin(np.abs(good)))
+    bad[at] += 1e3 * bwd_ref.gamma(bwd_ref.bwd_n(nq), bwd_ref.U64) * float(absref[at])
+    assert bad[at] != good[at]
+    assert oracle.rel_err(bad, good) <= 1e-12                              # the old criterion passes
+    q = bwd_ref.bwd_excess(bad, ref, absref, nq, bwd_ref.U64)
+    print(f"hidden error at entry {at}: rel_err = {oracle.rel_err(bad, good):.3g}, excess = {q:.3g}")
+    assert q > 1.0                                                         # the new bound fails
+
+
+def test_kernel_rows_mirror_the_launchers():
+    """tests/bwd_kernels.py restates the (EC, WPB) of the launchers beside the wave table.  Reads source text, literal lines
+    included: a failure after a reformat or a rename in csrc that changes no behaviour only means "update the mirror".  It
+    guards the batch sizes of tests/test_gpu_bwdtrans_bounds.py."""
+    import bwd_kernels as bk
+    quad, hexa, rt, gen = (bk.source(n) for n in ("bwdtrans_quad.hip", "bwdtrans_hex.hip", "bwdtrans_rt.hip",
+                                                  "bwdtrans_generic.hip"))
+    for text, lines in (
+        (quad, ("static constexpr int EC = (QuadCfg<NQ>::EC / 4 + 1) / 2 * 2 < 2 ? 2 : (QuadCfg<NQ>::EC / 4 + 1) / 2 * 2;",
+                "return launch_quad_wave<NQ, QuadSmall<NQ>::EC, 1, C::BM, C::MW, 1, C::OUT>(a, s);",
+                "constexpr uint64_t per_block = (uint64_t)C::EC * C::WPB * (C::KM > 0 ? C::KM : 1);",
+                "if (a.nelmt < 2 * per_block * (uint64_t)device_info().num_cu)",
+                "constexpr int EC = (NQ >= 13 && NQ <= 15) ? 4 : 2;", "constexpr bool mid = NQ >= 25 && NQ <= 31;",
+                "return launch_quad_mfma<NQ, EC, (mid ? 2 : 4),", "constexpr int kQuadF32MfmaFrom = 25;",
+                "constexpr int EC = (NQ == 25 || NQ == 28 || NQ == 32) ? 4 : 2;",
+                "return launch_quad_mfma<NQ, EC, 4, MW, KM, (NQ != 32), 64, float>(a, s);",
+                "if constexpr (NQ <= 22 || NQ == 24)", "return launch_quad_mfma4<NQ, 2, 4, 2, 4, 1, 64>(a, s);",
+                "return launch_quad_mfma4<NQ, 2, 4, 2, 4, 2, 64>(a, s);", "else if constexpr (NQ <= 27)",
+                "return launch_quad_mfma4<NQ, 4, 4, 1, 4, 0, 0, false, 8>(a, s);",
+                "return launch_quad_mfma4<NQ, 2, 4, 2, 4, 0, 0, false, 4>(a, s);", "const uint64_t nv = nelmt * 2;")),
+        (hexa, ("static constexpr int EC  = HexCfg<NQ>::EC == 1 ? 1",
+                ": ((HexCfg<NQ>::EC / 4 + 1) / 2 * 2 < 2 ? 2 : (HexCfg<NQ>::EC / 4 + 1) / 2 * 2);",
+                "return launch_hex_wave<NQ, HexSmall<NQ>::EC, 1, C::BM, C::MW, 1, HexSmall<NQ>::OUT>(a, s);",
+                "constexpr uint64_t per_block = (uint64_t)C::EC * C::WPB * (C::KM > 0 ? C::KM : 1);",
+                "if (a.nelmt < 2 * per_block * (uint64_t)device_info().num_cu)",
+                "if constexpr (NQ <= 10)", "return launch_hex_mfma<NQ, 2, 2, 2, 1>(a, s);",
+                "constexpr int WPB = NQ == 11 ? 4 : 1;", "return launch_hex_mfma<NQ, 1, WPB, MW, 1, 64>(a, s);",
+                "return launch_hex_mfma4<NQ, 1, 2, 1, 64, true>(a, s);",
+                "return launch_hex_mfma4<NQ, 1, (NQ == 12 ? 1 : 2), 1, 64>(a, s);",
+                "return launch_hex_mfma<NQ, 1, 1, 1, 1, 64, float>(a, s);", "else if constexpr (NQ >= 13)",
+                "return launch_hex_mfma<NQ, 1, 1, 2, 1, 64, float>(a, s);", "const uint64_t nv = nelmt * 4;")),
+        (rt, ("static constexpr int EC  = 512 / NQT < 1 ? 1 : (512 / NQT > 8 ? 8 : 512 / NQT);",
+              "return launch_chunked<4, C::EC, 1>(hex_wave3_kernel<NQ0, NQ1, NQ2, C::EC, 4, C::BM, 2>,",
+              "int ec = 64 / (sh.nq0 * sh.nq1);", "ec = ec < 1 ? 1 : (ec > 16 ? 16 : ec);",
+              "while (ec > 1 && images(ec, &off_b) > 2048)",
+              "const int za = (ec * (in_img > w2 ? in_img : w2) + 1) & ~1, zb = (ec * (w1 > sh.nqt ? w1 : sh.nqt) + 1) & ~1;",
+              "while (wpb > 1 && basis + sizeof(double) * (size_t)wpb * sh.slab > 64 * 1024)")),
+        (gen, ("const unsigned bs     = hinted_block(128, 0xffffffffu);",
+               "unsigned grid      = hinted_grid(a.nelmt, cap);"))):
+        for line in lines:
+            assert line in text, line
+    assert bk.wave_rows(3, 8, "float64") == [(1, 8), (1, 1)] and bk.wave_rows(3, 3, "float64") == [(14, 2), (4, 1)]
+    assert bk.wave_rows(2, 7, "float64") == [(6, 4), (2, 1)] and bk.wave_rows(2, 24, "float64") == [(2, 4), (2, 1)]
+    assert bk.wave_rows(2, 7, "float32") == [(16, 4)] and bk.wave_rows(2, 20, "float32") == [(8, 4)]
+    assert bk.wave_rows(2, 17, "float32") == [(6, 4)] and bk.wave_rows(3, 9, "float32") == [(4, 2)]
+    assert bk.wave_km(3, 8) == 1 and bk.wave_km(2, 32) == 2 and bk.tuned_from(3, 8, 256) == 4096
+    assert bk.tuned_from(3, 3, 256) == 14336 and bk.tuned_from(2, 3, 256) == 86016 and bk.tuned_from(2, 32, 256) == 8192
+    assert bk.wave_rows(3, 2, "float64") == [(64, 1)] and bk.wave_rows(2, 2, "float32") == [(256, 1)]
+    assert bk.f32_auto_rows(3, 12) == ("wave", [(1, 4)]) and bk.f32_auto_rows(3, 13) == ("mfma", [(1, 1)])
+    assert bk.f32_auto_rows(2, 24) == ("wave", [(4, 4)]) and bk.f32_auto_rows(2, 25) == ("mfma", [(4, 4)])
+    assert bk.triple_row((8, 8, 4)) == (2, 4) and bk.triple_row((4, 4, 6)) == (5, 4) and bk.triple_row((10, 10, 8)) == (1, 4)
+    assert bk.rt_row((3, 5, 4)) == (4, 4) and bk.rt_row((2, 2, 2)) == (16, 4) and bk.rt_row((16, 16, 16)) == (1, 1)
+    assert bk.ragged_counts([(4, 4)]) == [1, 3, 5, 17, 35] and bk.ragged_counts([(1, 1)]) == [1, 2, 5]
+    # the fused families read the same fp64 rows and fp32 pins through their own mirror
+    import fused_families as ff
+    tables = bk.wave_tables()
+    assert {n: tables["hex64"][n] for n in ff.HEX64} == ff.HEX64 and {n: tables["quad64"][n] for n in ff.QUAD64} == ff.QUAD64
+    assert all(tables["hex32"][n] == ff.table_row(3, n, "float32") for n in ff.HEX64)
+    assert all(tables["quad32"][n] == ff.table_row(2, n, "float32") for n in ff.QUAD64)
 
 
 def test_bwdtrans_binding_signatures(pkg):
