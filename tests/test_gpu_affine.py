@@ -1,8 +1,9 @@
-"""GPU tests of the fused Helmholtz operator on affine elements (include/sumfact.h sf_affine_helmholtz_*): every wave
-order through AUTO, ragged counts, the any-extent fallback, refusals, scalar-aligned views, guard values around `out` with
-ge / je / qw between NaN bands, the Laplacian without je, every ge component on its own, the mass limit, agreement with
-sf_helmholtz_* on expanded planes, the null-space and energy identities on affine geometry, symmetry, a 20 011-element
-batch, stream capture and two streams in flight.
+"""GPU tests of the fused Helmholtz operator on affine elements (include/sumfact.h sf_affine_helmholtz_*) that are the
+family's own: scalar-aligned views, the Laplacian that never reads je, every ge component on its own, the mass limit,
+agreement with sf_helmholtz_* on expanded planes, the null-space and energy identities on affine geometry, symmetry, a
+20 011-element batch and refused overlaps.  install() adds the family's cases of the parametrised tests the fused
+families share (tests/fused_common.py: every wave order through AUTO, ragged counts, the fallback, explicit variants,
+guard bands); refusals, stream capture and two streams in flight are tests/test_gpu_fused_common.py.
 
 Reference and bound: tests/affine_ref.py.  Elementwise |gpu - ref| <= gamma_N' * absref against a long-double reference
 on the expanded planes, N' = helm_n(nq) + d, u = 2^-53 (fp64) or 2^-24 (fp32).  Data: seeded, distinct per element and
@@ -10,41 +11,21 @@ per value, uniform in [-1, 1) -- the signs of qw, ge and je included, so ge is n
 once per problem; a run on fewer elements takes a prefix of the same arrays and is compared with the prefix of it.
 """
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from affine_ref import (affine_excess, affine_geometry, affine_n, exact_energy_affine, expand, gll_affine_setup,
                         ref_affine)
+from fused_common import install
+from fused_families import BY_NAME, case_id, sf, to_host, torch_mod  # noqa: F401
 from helm_ref import COMPONENTS, U64, gamma, symmetry_bound, unit_roundoff
 from mass_ref import mass_excess, mass_n, ref_mass
 
 pytestmark = pytest.mark.gpu
+install(globals(), BY_NAME["affine"])
 
-WAVE_ORDERS = [(3, n) for n in range(2, 9)] + [(2, n) for n in range(2, 17)]
-RAGGED = [1, 2, 3, 5, 13, 15, 63, 65, 127, 257, 1001]
-FALLBACK = [(6, 6, 12), (3, 5, 4), (2, 3, 2), (9, 9, 9), (12, 12, 12), (4, 9), (16, 3), (32, 32), (23, 5)]
 LAM = 0.75
-
-
-@pytest.fixture(scope="module")
-def sf():
-    import __graft_entry__ as ge
-    return ge.load_package()
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available(), "the GPU tests need a GPU"
-    return torch
-
-
-def _np(t):
-    return None if t is None else t.detach().cpu().numpy()
 
 
 def _nmt(nq):
@@ -53,10 +34,6 @@ def _nmt(nq):
 
 def _ncomp(nq):
     return len(COMPONENTS[len(nq)])
-
-
-def _ids(v):
-    return "x".join(map(str, v)) if isinstance(v, tuple) else str(v)
 
 
 class Problem:
@@ -87,118 +64,33 @@ class Problem:
 
     def ref(self, lam=LAM):
         if lam not in self._refs:
-            self._refs[lam] = ref_affine(self.nq, self.nelmt, [_np(b) for b in self.bs], [_np(d) for d in self.ds],
-                                         [_np(q) for q in self.qs], _np(self.ge), _np(self.je) if lam != 0 else None, lam,
-                                         _np(self.x))
+            self._refs[lam] = ref_affine(self.nq, self.nelmt, [to_host(b) for b in self.bs], [to_host(d) for d in self.ds],
+                                         [to_host(q) for q in self.qs], to_host(self.ge), to_host(self.je) if lam != 0 else None, lam,
+                                         to_host(self.x))
         return self._refs[lam]
 
     def check(self, got, what, lam=LAM, n=None):
         n = self.nelmt if n is None else n
         ref, absref = self.ref(lam)
         ref, absref = ref[:n * self.nmt], absref[:n * self.nmt]
-        q = affine_excess(_np(got), ref, absref, self.nq, unit_roundoff(self.dtype_name))
+        q = affine_excess(to_host(got), ref, absref, self.nq, unit_roundoff(self.dtype_name))
         print(f"{what}: {self.nq} {self.dtype_name} nelmt={n} lam={lam}: max |err| / (gamma_N' absref) = {q:.3g}")
         assert q <= 1.0, (what, self.nq, self.dtype_name, n, q)
         assert float(np.max(np.abs(ref))) > 0
 
     def check_other(self, got, what, lam, **data):
         """Against a reference of its own, for a run with some array replaced (host copies given by name)."""
-        a = {"bs": [_np(b) for b in self.bs], "ds": [_np(d) for d in self.ds], "qs": [_np(q) for q in self.qs],
-             "ge": _np(self.ge), "je": _np(self.je) if lam != 0 else None, "x": _np(self.x)}
+        a = {"bs": [to_host(b) for b in self.bs], "ds": [to_host(d) for d in self.ds], "qs": [to_host(q) for q in self.qs],
+             "ge": to_host(self.ge), "je": to_host(self.je) if lam != 0 else None, "x": to_host(self.x)}
         a.update(data)
         ref, absref = ref_affine(self.nq, self.nelmt, a["bs"], a["ds"], a["qs"], a["ge"], a["je"], lam, a["x"])
-        q = affine_excess(_np(got), ref, absref, self.nq, unit_roundoff(self.dtype_name))
+        q = affine_excess(to_host(got), ref, absref, self.nq, unit_roundoff(self.dtype_name))
         print(f"{what}: {self.nq} {self.dtype_name} nelmt={self.nelmt} lam={lam}: max |err| / (gamma_N' absref) = {q:.3g}")
         assert q <= 1.0, (what, self.nq, self.dtype_name, q)
         assert float(np.max(np.abs(ref))) > 0
 
 
-@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
-@pytest.mark.parametrize("dim,nq", WAVE_ORDERS, ids=[f"{d}d-nq{n}" for d, n in WAVE_ORDERS])
-def test_auto_every_wave_order(sf, torch_mod, dim, nq, dtype_name):
-    p = Problem(sf, torch_mod, (nq,) * dim, 403, dtype_name, nq)
-    got = p.run()
-    lap = p.run(lam=0.0)
-    torch_mod.cuda.synchronize()
-    p.check(got, "auto")
-    p.check(lap, "auto laplacian", lam=0.0)
-    if dtype_name == "float64":
-        # AUTO runs the wave kernel here: the same bits as the explicit variant
-        wave, wlap = p.run(variant="wave"), p.run(lam=0.0, variant="wave")
-        torch_mod.cuda.synchronize()
-        assert torch_mod.equal(got, wave) and torch_mod.equal(lap, wlap)
-
-
-# where the lane -> element map can go wrong: many elements per wave in two passes (3D nq 2, 3), two elements (nq 5),
-# one element and uniform constants (nq 6, 7, 8), the 2D chunk sizes, and the shrunk fp32 rows
-RAGGED_SHAPES = [((2, 2, 2), "float64"), ((3, 3, 3), "float64"), ((5, 5, 5), "float64"), ((6, 6, 6), "float64"),
-                 ((7, 7, 7), "float64"), ((8, 8, 8), "float64"),
-                 ((3, 3), "float64"), ((8, 8), "float64"), ((12, 12), "float64"), ((16, 16), "float64"),
-                 ((6, 6, 6), "float32"), ((13, 13), "float32")]
-
-
-@pytest.mark.parametrize("nq,dtype_name", RAGGED_SHAPES, ids=[_ids(s) + "-" + d for s, d in RAGGED_SHAPES])
-def test_ragged_counts(sf, torch_mod, nq, dtype_name):
-    """The last chunk is partial, or the whole batch is smaller than one chunk.  Every count runs on a prefix of one
-    problem's arrays and is compared with the prefix of its reference (reads past the end of ge / je are the business of
-    the NaN bands of the guard test)."""
-    p = Problem(sf, torch_mod, nq, max(RAGGED), dtype_name, 3)
-    for lam in (LAM, 0.0):
-        outs = [(n, p.run(lam=lam, n=n)) for n in RAGGED]
-        torch_mod.cuda.synchronize()
-        for n, got in outs:
-            assert got.numel() == n * p.nmt
-            p.check(got, "ragged", lam=lam, n=n)
-
-
-@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
-@pytest.mark.parametrize("nq", FALLBACK, ids=_ids)
-def test_fallback_shapes(sf, torch_mod, nq, dtype_name):
-    p = Problem(sf, torch_mod, nq, 150, dtype_name, 70)
-    for lam in (LAM, 0.0):
-        for n in (1, 37, 150):
-            got = p.run(lam=lam, n=n)
-            torch_mod.cuda.synchronize()
-            p.check(got, "fallback", lam=lam, n=n)
-            if dtype_name == "float64":
-                gen = p.run(lam=lam, n=n, variant="generic")
-                torch_mod.cuda.synchronize()
-                assert torch_mod.equal(got, gen)
-
-
-@pytest.mark.parametrize("nq", [(8, 8, 8), (5, 5, 5), (12, 12), (9, 9)], ids=_ids)
-def test_explicit_wave_and_generic(sf, torch_mod, nq):
-    """Both routes of an order of the table against the same reference."""
-    p = Problem(sf, torch_mod, nq, 333, "float64", 9)
-    for variant in ("wave", "generic"):
-        for lam in (LAM, 0.0):
-            got = p.run(lam=lam, variant=variant)
-            torch_mod.cuda.synchronize()
-            p.check(got, variant, lam=lam)
-
-
-def test_refusals(sf, torch_mod):
-    """Extents outside the fallback's bounds, WAVE off the table, variants without a fused kernel: SF_ENOTBUILT."""
-    def rc_of(nq, **kw):
-        p = Problem(sf, torch_mod, nq, 3, "float64", 2)
-        with pytest.raises(sf.capi.SumfactError) as ei:
-            p.run(**kw)
-        return ei.value.rc
-    assert rc_of((13, 4, 4)) == sf.capi.SF_ENOTBUILT
-    assert rc_of((4, 4, 13), variant="generic") == sf.capi.SF_ENOTBUILT
-    assert rc_of((33, 5)) == sf.capi.SF_ENOTBUILT
-    assert rc_of((5, 33)) == sf.capi.SF_ENOTBUILT
-    assert rc_of((9, 9, 9), variant="wave") == sf.capi.SF_ENOTBUILT
-    assert rc_of((6, 6, 12), variant="wave") == sf.capi.SF_ENOTBUILT
-    assert rc_of((17, 17), variant="wave") == sf.capi.SF_ENOTBUILT
-    assert rc_of((8, 8, 8), variant="mfma") == sf.capi.SF_ENOTBUILT
-    p32 = Problem(sf, torch_mod, (13, 4, 4), 3, "float32", 2)
-    with pytest.raises(sf.capi.SumfactError) as ei:
-        p32.run()
-    assert ei.value.rc == sf.capi.SF_ENOTBUILT
-
-
-@pytest.mark.parametrize("nq", [(8, 8, 8), (5, 5, 5), (8, 8), (11, 11)], ids=_ids)
+@pytest.mark.parametrize("nq", [(8, 8, 8), (5, 5, 5), (8, 8), (11, 11)], ids=case_id)
 def test_scalar_aligned_views(sf, torch_mod, nq):
     """in or out at a scalar offset: correct through the fallback, WAVE answers SF_EALIGN.  ge / je / qw at odd scalar
     offsets: still the wave kernel, bit-equal to WAVE.  Guards on both sides of out are untouched."""
@@ -237,36 +129,7 @@ def test_scalar_aligned_views(sf, torch_mod, nq):
                     assert torch_mod.equal(wave, o)     # ge, je and qw need only scalar alignment on the wave route
 
 
-GUARD = [((2, 2, 2), 33), ((3, 3, 3), 1001), ((6, 6, 6), 129), ((8, 8, 8), 65), ((5, 5), 4099), ((16, 16), 127),
-         ((6, 6, 12), 13), ((9, 9, 9), 15)]
-
-
-@pytest.mark.parametrize("nq,nelmt", GUARD, ids=[_ids(s) for s, _ in GUARD])
-def test_guard_values_around_out_and_nan_around_the_inputs(sf, torch_mod, nq, nelmt):
-    """`out` sits between two guard bands (16-byte aligned, so the wave kernels run): only its own values change.  ge,
-    je and each qw_d are views inside larger buffers filled with NaN on both sides: a value read from outside that
-    reached a result would show as a NaN in `out`."""
-    for dtype_name, pad in (("float64", 64), ("float32", 128)):
-        dtype = getattr(torch_mod, dtype_name)
-        p = Problem(sf, torch_mod, nq, nelmt, dtype_name, 5)
-
-        def banded(t):
-            buf = torch_mod.full((t.numel() + 2 * pad,), float("nan"), dtype=dtype, device="cuda")
-            buf[pad:pad + t.numel()] = t
-            return buf[pad:pad + t.numel()]
-
-        ge, je, qs = banded(p.ge), banded(p.je), [banded(q) for q in p.qs]
-        for lam in (LAM, 0.0):
-            obuf = torch_mod.full((nelmt * p.nmt + 2 * pad,), -3.5, dtype=dtype, device="cuda")
-            o = obuf[pad:pad + nelmt * p.nmt]
-            p.run(lam=lam, ge=ge, je=je if lam != 0 else None, qs=qs, out=o)
-            torch_mod.cuda.synchronize()
-            assert bool((obuf[:pad] == -3.5).all()) and bool((obuf[pad + nelmt * p.nmt:] == -3.5).all()), dtype_name
-            assert not bool(torch_mod.isnan(o).any()), dtype_name
-            p.check(o, "guard", lam=lam)
-
-
-@pytest.mark.parametrize("nq", [(8, 8, 8), (5, 5, 5), (12, 12), (3, 3), (6, 6, 12), (23, 5)], ids=_ids)
+@pytest.mark.parametrize("nq", [(8, 8, 8), (5, 5, 5), (12, 12), (3, 3), (6, 6, 12), (23, 5)], ids=case_id)
 def test_laplacian_never_reads_je(sf, torch_mod, nq):
     """lambda == 0 with je=None equals lambda == 0 with a NaN-filled je, bit for bit, in both precisions."""
     for dtype_name in ("float64", "float32"):
@@ -279,7 +142,7 @@ def test_laplacian_never_reads_je(sf, torch_mod, nq):
         p.check(none, "laplacian", lam=0.0)
 
 
-@pytest.mark.parametrize("nq", [(8, 8, 8), (5, 5, 5), (6, 4, 5), (12, 12), (4, 9)], ids=_ids)
+@pytest.mark.parametrize("nq", [(8, 8, 8), (5, 5, 5), (6, 4, 5), (12, 12), (4, 9)], ids=case_id)
 def test_each_ge_component_alone(sf, torch_mod, nq):
     """One-hot components: pins the component order and that an off-diagonal component enters both (a,b) and (b,a)."""
     p = Problem(sf, torch_mod, nq, 67, "float64", 41)
@@ -289,13 +152,13 @@ def test_each_ge_component_alone(sf, torch_mod, nq):
         ge = ge.reshape(-1)
         got = p.run(lam=0.0, ge=ge)
         torch_mod.cuda.synchronize()
-        p.check_other(got, f"component {COMPONENTS[len(nq)][c]}", 0.0, ge=_np(ge))
+        p.check_other(got, f"component {COMPONENTS[len(nq)][c]}", 0.0, ge=to_host(ge))
         assert float(got.abs().max()) > 0
 
 
 @pytest.mark.parametrize("nq,dtype_name", [((8, 8, 8), "float64"), ((4, 4, 4), "float32"), ((12, 12), "float64"),
                                            ((7, 7), "float32"), ((6, 6, 12), "float64"), ((4, 9), "float64")],
-                         ids=lambda v: _ids(v))
+                         ids=lambda v: case_id(v))
 def test_mass_limit(sf, torch_mod, nq, dtype_name):
     """ge = 0, lambda = 1 is the mass operator with w = je (x) qw: against tests/mass_ref.py on the w expanded in long
     double.  mass_ref counts one rounding for the weight (N = 2 sum nq + 1); here the weight takes d + 1 -- d - 1 for q,
@@ -304,17 +167,17 @@ def test_mass_limit(sf, torch_mod, nq, dtype_name):
     p = Problem(sf, torch_mod, nq, 131, dtype_name, 31)
     got = p.run(lam=1.0, ge=torch_mod.zeros_like(p.ge))
     torch_mod.cuda.synchronize()
-    _, w = expand(nq, p.nelmt, [_np(q) for q in p.qs], np.zeros(p.nelmt * p.nc), _np(p.je))
-    ref, absref = ref_mass(nq, p.nelmt, [_np(b) for b in p.bs], w, _np(p.x))
+    _, w = expand(nq, p.nelmt, [to_host(q) for q in p.qs], np.zeros(p.nelmt * p.nc), to_host(p.je))
+    ref, absref = ref_mass(nq, p.nelmt, [to_host(b) for b in p.bs], w, to_host(p.x))
     u = unit_roundoff(dtype_name)
     n = mass_n(nq)
-    q = mass_excess(_np(got), ref, absref, nq, u, factor=gamma(n + len(nq), u) / gamma(n, u))
+    q = mass_excess(to_host(got), ref, absref, nq, u, factor=gamma(n + len(nq), u) / gamma(n, u))
     print(f"mass limit {nq} {dtype_name}: max |err| / (gamma_{n + len(nq)} absref) = {q:.3g}")
     assert q <= 1.0 and float(np.max(np.abs(ref))) > 0
 
 
 @pytest.mark.parametrize("nq,dtype_name", [((8, 8, 8), "float64"), ((5, 5, 5), "float32"), ((12, 12), "float64"),
-                                           ((6, 6, 12), "float64"), ((9, 9), "float32")], ids=lambda v: _ids(v))
+                                           ((6, 6, 12), "float64"), ((9, 9), "float32")], ids=lambda v: case_id(v))
 def test_agrees_with_helmholtz_on_expanded_planes(sf, torch_mod, nq, dtype_name):
     """sf_helmholtz_* on g and w expanded on the device in working precision, and sf_affine_helmholtz_*: both inside the
     bound of the same long-double reference."""
@@ -334,7 +197,7 @@ def test_agrees_with_helmholtz_on_expanded_planes(sf, torch_mod, nq, dtype_name)
 
 
 def _dots(a, b, nelmt):
-    a, b = _np(a).reshape(nelmt, -1), _np(b).reshape(nelmt, -1)
+    a, b = to_host(a).reshape(nelmt, -1), to_host(b).reshape(nelmt, -1)
     return [math.fsum(a[e] * b[e]) for e in range(nelmt)]
 
 
@@ -357,7 +220,7 @@ def test_affine_geometry_null_space_and_energy(sf, torch_mod, dim, nq):
     yc = f(ext, *tb, *td, *tq, tge, None, 0.0, dev(const.reshape(-1)))
     torch_mod.cuda.synchronize()
     ref, absref = ref_affine(ext, nelmt, bases, derivs, qws, ge, None, 0.0, const.reshape(-1))
-    q = affine_excess(_np(yc), ref, absref, ext, U64)
+    q = affine_excess(to_host(yc), ref, absref, ext, U64)
     print(f"null space {ext}: max |A 1| = {float(yc.abs().max()):.3e}, excess {q:.3g}")
     assert q <= 1.0
     assert float(np.max(np.abs(np.asarray(ref, dtype=np.float64)))) <= gamma(affine_n(ext), U64) * float(np.max(absref))
@@ -366,7 +229,7 @@ def test_affine_geometry_null_space_and_energy(sf, torch_mod, dim, nq):
     yabs = f(ext, *[b.abs() for b in tb], *[d.abs() for d in td], *tq, tge.abs(), None, 0.0, x.abs())
     torch_mod.cuda.synchronize()
     got, slack = _dots(y, x, nelmt), _dots(yabs, x.abs(), nelmt)
-    xs = _np(x).reshape(nelmt, -1)
+    xs = to_host(x).reshape(nelmt, -1)
     fac = symmetry_bound(ext, U64)
     worst = 0.0
     for e in range(nelmt):
@@ -377,7 +240,7 @@ def test_affine_geometry_null_space_and_energy(sf, torch_mod, dim, nq):
     assert worst <= 1.0
 
 
-@pytest.mark.parametrize("nq", [(8, 8, 8), (12, 12), (6, 6, 12)], ids=_ids)
+@pytest.mark.parametrize("nq", [(8, 8, 8), (12, 12), (6, 6, 12)], ids=case_id)
 def test_symmetry(sf, torch_mod, nq):
     """|<A x, y> - <x, A y>| <= symmetry_bound * sum_e <|A||x|, |y|>_e for an indefinite ge and weights of both signs."""
     nelmt = 257
@@ -404,8 +267,8 @@ def test_batch_of_20011_hex8(sf, torch_mod):
     sample = np.unique(np.concatenate((rng.choice(nelmt - 3, 64, replace=False), [nelmt - 3, nelmt - 2, nelmt - 1])))
     assert len(sample) == 67
     idx = torch_mod.tensor(sample, device="cuda")
-    pick = lambda t, n: _np(t.view(nelmt, n)[idx].reshape(-1))      # noqa: E731
-    ref, absref = ref_affine(nq, len(sample), [_np(b) for b in p.bs], [_np(d) for d in p.ds], [_np(q) for q in p.qs],
+    pick = lambda t, n: to_host(t.view(nelmt, n)[idx].reshape(-1))      # noqa: E731
+    ref, absref = ref_affine(nq, len(sample), [to_host(b) for b in p.bs], [to_host(d) for d in p.ds], [to_host(q) for q in p.qs],
                              pick(p.ge, p.nc), pick(p.je, 1), LAM, pick(p.x, p.nmt))
     worst = affine_excess(pick(y, p.nmt), ref, absref, nq, U64)
     print(f"20011 elements ({len(sample)} sampled): max |err| / (gamma_N' absref) = {worst:.3g}")
@@ -413,87 +276,6 @@ def test_batch_of_20011_hex8(sf, torch_mod):
     again = p.run()
     torch_mod.cuda.synchronize()
     assert torch_mod.equal(y, again)
-
-
-@pytest.mark.parametrize("nq,nelmt", [((8, 8, 8), 2003), ((9, 9), 5003), ((6, 6, 12), 301), ((3, 3, 3), 1001)],
-                         ids=lambda v: _ids(v))
-def test_captured_graph_replay_matches_eager(sf, torch_mod, nq, nelmt):
-    p = Problem(sf, torch_mod, nq, nelmt, "float64", 11)
-    for lam in (LAM, 0.0):
-        eager = p.run(lam=lam)
-        o = torch_mod.zeros(nelmt * p.nmt, dtype=torch_mod.float64, device="cuda")
-        torch_mod.cuda.synchronize()
-        side = torch_mod.cuda.Stream()
-        side.wait_stream(torch_mod.cuda.current_stream())
-        g = torch_mod.cuda.CUDAGraph()
-        with torch_mod.cuda.stream(side):
-            with torch_mod.cuda.graph(g, stream=side):
-                p.run(lam=lam, out=o, stream=side)
-        torch_mod.cuda.current_stream().wait_stream(side)
-        g.replay()
-        torch_mod.cuda.synchronize()
-        assert torch_mod.equal(o, eager)
-        assert float(o.abs().max()) > 0
-
-
-FIRST_CALL_CAPTURED = r"""
-import sys
-import torch
-sys.path.insert(0, sys.argv[1])
-import __graft_entry__ as ge
-sf = ge.load_package()
-for nq, nelmt in (((8, 8, 8), 1001), ((6, 6, 12), 301), ((9, 9), 2001), ((23, 5), 301)):
-    f = sf.affine_helmholtz_hex if len(nq) == 3 else sf.affine_helmholtz_quad
-    dim = len(nq)
-    bs = [sf.fill_random((q - 1) * q, 40 + d) for d, q in enumerate(nq)]
-    ds = [sf.fill_random(q * q, 50 + d) for d, q in enumerate(nq)]
-    qs = [sf.fill_random(q, 60 + d) for d, q in enumerate(nq)]
-    nmo = 1
-    for q in nq:
-        nmo = nmo * (q - 1)
-    x = sf.fill_random(nelmt * nmo, 41)
-    ge_ = sf.fill_random(nelmt * dim * (dim + 1) // 2, 43)
-    je = sf.fill_random(nelmt, 42)
-    o = torch.zeros(nelmt * nmo, dtype=torch.float64, device="cuda")
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    gr = torch.cuda.CUDAGraph()
-    with torch.cuda.stream(side):
-        with torch.cuda.graph(gr, stream=side):
-            f(nq, *bs, *ds, *qs, ge_, je, 0.5, x, out=o, stream=side)     # the process's first call of this route
-    torch.cuda.current_stream().wait_stream(side)
-    gr.replay()
-    torch.cuda.synchronize()
-    eager = f(nq, *bs, *ds, *qs, ge_, je, 0.5, x)
-    torch.cuda.synchronize()
-    assert torch.equal(o, eager), nq
-    assert float(o.abs().max()) > 0, nq
-print("first calls captured")
-"""
-
-
-def test_first_call_inside_a_capture():
-    """Capture-safe from the first call: a fresh child process whose first call of each route (3D wave, 3D fallback, 2D
-    wave, 2D fallback) is inside a stream capture; the replay equals an eager call made afterwards."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", FIRST_CALL_CAPTURED, root], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "first calls captured" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-
-
-def test_two_streams_in_flight(sf, torch_mod):
-    """Two problems enqueued on two streams before either is waited for."""
-    jobs = [((7, 7, 7), 1501), ((12, 12), 4001)]
-    streams = [torch_mod.cuda.Stream(), torch_mod.cuda.Stream()]
-    probs = [Problem(sf, torch_mod, nq, nelmt, "float64", nelmt % 97) for nq, nelmt in jobs]
-    torch_mod.cuda.synchronize()
-    outs = []
-    for p, st in zip(probs, streams):
-        with torch_mod.cuda.stream(st):
-            outs.append(p.run(stream=st))
-    torch_mod.cuda.synchronize()
-    for p, o in zip(probs, outs):
-        p.check(o, "stream job")
 
 
 def test_overlap_is_refused(sf, torch_mod):

@@ -1,9 +1,10 @@
-"""GPU tests of the diagonal of the fused Helmholtz operator (include/sumfact.h sf_diag_helmholtz_*, sf_diag_tables_*):
-every wave order through AUTO, ragged counts (the chunk tails), the any-extent fallback, scalar-aligned views, guard
-values around `out` with `g`, `w` and the tables between NaN bands, the Laplacian without `w`, the operator itself as the
-witness (sf_helmholtz_* applied to every unit vector), the Gauss-Lobatto closed form, the tables alone, several XCD
-windows, `g` past 2^32 scalars, stream capture from the process's first call, two streams in flight and four host threads
-on one stream.
+"""GPU tests of the diagonal of the fused Helmholtz operator (include/sumfact.h sf_diag_helmholtz_*, sf_diag_tables_*)
+that are the family's own: scalar-aligned views of out, g, w and the tables, the Laplacian that never reads `w`, the
+operator itself as the witness (sf_helmholtz_* applied to every unit vector), the Gauss-Lobatto closed form, the tables
+alone, several XCD windows, `g` past 2^32 scalars, four host threads on one stream and refused overlaps.  install() adds
+the family's cases of the parametrised tests the fused families share (tests/fused_common.py: every wave order through
+AUTO, ragged counts, the fallback, explicit variants, guard bands); refusals, stream capture and two streams in flight
+are tests/test_gpu_fused_common.py.
 
 Reference and bound: tests/diag_ref.py.  Elementwise |gpu - ref| <= gamma_N * absref against a long-double reference,
 gamma_N = N u / (1 - N u), N = 3 sum nq_d + d + 2 + (6 | 3), u = 2^-53 (fp64) or 2^-24 (fp32); where long double would be
@@ -13,53 +14,24 @@ Data: sf.fill_random, seeded, per-value distinct; g uniform in (-1, 1) and so no
 """
 import ctypes
 import gc
-import os
-import subprocess
-import sys
 import threading
 
 import numpy as np
 import pytest
 
 from diag_ref import diag_excess, diag_f64, diag_n, gll_exact_diag, ref_diag, tables, tables_excess
+from fused_common import install
+from fused_families import BY_NAME, case_id, sf, sizes, to_host, torch_mod  # noqa: F401
 from helm_ref import COMPONENTS, U64, gamma, gll_setup, helm_n, ref_helmholtz, unit_roundoff
 
 pytestmark = pytest.mark.gpu
+install(globals(), BY_NAME["diag"])
 
-WAVE_ORDERS = [(3, n) for n in range(2, 9)] + [(2, n) for n in range(2, 17)]
-RAGGED = [1, 2, 3, 5, 13, 15, 63, 65, 127, 257, 1001]
-FALLBACK = [(6, 6, 12), (3, 5, 4), (12, 10, 11), (2, 3, 2), (9, 9, 9), (11, 11, 11), (12, 12, 12), (4, 9), (16, 3),
-            (32, 32), (23, 5)]
 LAM = 0.75
-
-
-@pytest.fixture(scope="module")
-def sf():
-    import __graft_entry__ as ge
-    return ge.load_package()
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available(), "the GPU tests need a GPU"
-    return torch
-
-
-def _np(t):
-    return None if t is None else t.detach().cpu().numpy()
-
-
-def _sizes(nq):
-    return int(np.prod([q - 1 for q in nq])), int(np.prod(nq))
 
 
 def _ncomp(nq):
     return len(COMPONENTS[len(nq)])
-
-
-def _ids(v):
-    return "x".join(map(str, v)) if isinstance(v, tuple) else str(v)
 
 
 class Problem:
@@ -68,13 +40,13 @@ class Problem:
     def __init__(self, sf, torch_mod, nq, nelmt, dtype_name, seed):
         dtype = getattr(torch_mod, dtype_name)
         self.nq, self.nelmt, self.dtype_name = tuple(nq), nelmt, dtype_name
-        _, nqt = _sizes(nq)
+        _, nqt = sizes(nq)
         self.bs = [sf.fill_random((q - 1) * q, 500 + 7 * seed + d, dtype=dtype) for d, q in enumerate(nq)]
         self.ds = [sf.fill_random(q * q, 600 + 7 * seed + d, dtype=dtype) for d, q in enumerate(nq)]
         self.g = sf.fill_random(nelmt * _ncomp(nq) * nqt, 8000 + seed, dtype=dtype)
         self.w = sf.fill_random(nelmt * nqt, 7000 + seed, dtype=dtype)
         self.tabs = [sf.diag_tables(q, b, d) for q, b, d in zip(nq, self.bs, self.ds)]
-        self.host = ([_np(b) for b in self.bs], [_np(d) for d in self.ds])
+        self.host = ([to_host(b) for b in self.bs], [to_host(d) for d in self.ds])
 
     def run(self, sf, lam=LAM, **kw):
         g = kw.pop("g", self.g)
@@ -86,10 +58,10 @@ class Problem:
     def excess(self, got, lam=LAM, g=None, w="self"):
         g = self.g if g is None else g
         w = self.w if isinstance(w, str) else w
-        nelmt = g.numel() // (_ncomp(self.nq) * _sizes(self.nq)[1])
-        ref, absref = ref_diag(self.nq, nelmt, *self.host, _np(g), _np(w), lam)
+        nelmt = g.numel() // (_ncomp(self.nq) * sizes(self.nq)[1])
+        ref, absref = ref_diag(self.nq, nelmt, *self.host, to_host(g), to_host(w), lam)
         assert float(np.max(np.abs(ref))) > 0
-        return diag_excess(_np(got), ref, absref, self.nq, unit_roundoff(self.dtype_name))
+        return diag_excess(to_host(got), ref, absref, self.nq, unit_roundoff(self.dtype_name))
 
     def check(self, got, what, lam=LAM, g=None, w="self"):
         q = self.excess(got, lam, g, w)
@@ -100,100 +72,24 @@ class Problem:
 def f64_excess(p, got, lam=LAM, lo=0, n=None):
     """max |got - fp64 numpy| / ((gamma_N(u) + gamma_N(u64)) (1 + gamma_N(u64)) absref64) over elements lo .. lo + n."""
     n = p.nelmt if n is None else n
-    nmt, nqt = _sizes(p.nq)
+    nmt, nqt = sizes(p.nq)
     nc = _ncomp(p.nq)
-    g = _np(p.g[lo * nc * nqt:(lo + n) * nc * nqt]).astype(np.float64)
-    w = _np(p.w[lo * nqt:(lo + n) * nqt]).astype(np.float64) if lam != 0 else None
+    g = to_host(p.g[lo * nc * nqt:(lo + n) * nc * nqt]).astype(np.float64)
+    w = to_host(p.w[lo * nqt:(lo + n) * nqt]).astype(np.float64) if lam != 0 else None
     out64, abs64 = diag_f64(p.nq, n, [b.astype(np.float64) for b in p.host[0]], [d.astype(np.float64) for d in p.host[1]],
                             g, w, lam)
     gu, g64 = gamma(diag_n(p.nq), unit_roundoff(p.dtype_name)), gamma(diag_n(p.nq), U64)
-    return diag_excess(_np(got[lo * nmt:(lo + n) * nmt]), out64, abs64, p.nq, unit_roundoff(p.dtype_name),
+    return diag_excess(to_host(got[lo * nmt:(lo + n) * nmt]), out64, abs64, p.nq, unit_roundoff(p.dtype_name),
                        factor=(gu + g64) * (1 + g64) / gu)
 
 
-@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
-@pytest.mark.parametrize("dim,nq", WAVE_ORDERS, ids=[f"{d}d-nq{n}" for d, n in WAVE_ORDERS])
-def test_auto_every_wave_order(sf, torch_mod, dim, nq, dtype_name):
-    p = Problem(sf, torch_mod, (nq,) * dim, 403, dtype_name, nq)
-    got = p.run(sf)
-    torch_mod.cuda.synchronize()
-    p.check(got, "auto")
-    lap = p.run(sf, lam=0.0, w=None)
-    torch_mod.cuda.synchronize()
-    p.check(lap, "auto laplacian", lam=0.0, w=None)
-    if dtype_name == "float64":
-        # AUTO runs the wave kernel here: the same bits as the explicit variant
-        wave = p.run(sf, variant="wave")
-        torch_mod.cuda.synchronize()
-        assert torch_mod.equal(got, wave)
-
-
-RAGGED_SHAPES = [((2, 2, 2), "float64"), ((3, 3, 3), "float64"), ((4, 4, 4), "float64"), ((6, 6, 6), "float64"),
-                 ((7, 7, 7), "float64"), ((8, 8, 8), "float64"),
-                 ((3, 3), "float64"), ((7, 7), "float64"), ((8, 8), "float64"), ((12, 12), "float64"),
-                 ((16, 16), "float64"),
-                 ((3, 3, 3), "float32"), ((8, 8, 8), "float32"), ((13, 13), "float32")]
-
-
-@pytest.mark.parametrize("nq,dtype_name", RAGGED_SHAPES, ids=[_ids(s) + "-" + d for s, d in RAGGED_SHAPES])
-def test_ragged_counts(sf, torch_mod, nq, dtype_name):
-    """The last chunk is partial (1 .. EC - 1 elements of it exist), or the whole batch is smaller than one chunk; g and w
-    end where the batch ends."""
-    for nelmt in RAGGED:
-        p = Problem(sf, torch_mod, nq, nelmt, dtype_name, nelmt % 101)
-        got = p.run(sf)
-        torch_mod.cuda.synchronize()
-        p.check(got, "ragged")
-
-
-@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
-@pytest.mark.parametrize("nq", FALLBACK, ids=_ids)
-def test_fallback_shapes(sf, torch_mod, nq, dtype_name):
-    for nelmt in (1, 37, 150):
-        p = Problem(sf, torch_mod, nq, nelmt, dtype_name, 70 + nelmt)
-        got = p.run(sf)
-        torch_mod.cuda.synchronize()
-        p.check(got, "fallback")
-        if dtype_name == "float64":
-            gen = p.run(sf, variant="generic")
-            torch_mod.cuda.synchronize()
-            assert torch_mod.equal(got, gen)
-            with pytest.raises(sf.capi.SumfactError) as ei:
-                p.run(sf, variant="wave")
-            assert ei.value.rc == sf.capi.SF_ENOTBUILT
-    lap = p.run(sf, lam=0.0, w=None)
-    torch_mod.cuda.synchronize()
-    p.check(lap, "fallback laplacian", lam=0.0, w=None)
-
-
-def test_extents_beyond_the_fallback(sf, torch_mod):
-    big = Problem(sf, torch_mod, (13, 4, 4), 2, "float64", 2)
-    for variant in ("auto", "generic", "wave"):
-        with pytest.raises(sf.capi.SumfactError) as ei:
-            big.run(sf, variant=variant)
-        assert ei.value.rc == sf.capi.SF_ENOTBUILT
-    p = Problem(sf, torch_mod, (8, 8, 8), 5, "float64", 2)
-    with pytest.raises(sf.capi.SumfactError) as ei:
-        p.run(sf, variant="mfma")
-    assert ei.value.rc == sf.capi.SF_ENOTBUILT
-
-
-@pytest.mark.parametrize("nq", [(8, 8, 8), (5, 5, 5), (12, 12), (9, 9)], ids=_ids)
-def test_explicit_wave_and_generic(sf, torch_mod, nq):
-    p = Problem(sf, torch_mod, nq, 777, "float64", 9)
-    for variant in ("wave", "generic"):
-        got = p.run(sf, variant=variant)
-        torch_mod.cuda.synchronize()
-        p.check(got, variant)
-
-
-@pytest.mark.parametrize("nq", [(8, 8, 8), (7, 7, 7), (8, 8), (11, 11)], ids=_ids)
+@pytest.mark.parametrize("nq", [(8, 8, 8), (7, 7, 7), (8, 8), (11, 11)], ids=case_id)
 def test_scalar_aligned_views(sf, torch_mod, nq):
     """Scalar-aligned views of out, g, w and the tables.  AUTO is correct through the fallback when out lacks 16-byte
     alignment (guards on both sides of out untouched, variant "wave" refuses with SF_EALIGN), and stays on the wave
     kernel, bit for bit, when only g / w / the tables do."""
     nelmt = 133
-    nmt, nqt = _sizes(nq)
+    nmt, nqt = sizes(nq)
     nc = _ncomp(nq)
     cases = (("float64", ((1, 0, 0, 0), (0, 1, 1, 1), (3, 1, 3, 1))), ("float32", ((2, 0, 0, 0), (0, 1, 3, 1), (1, 3, 1, 3))))
     for dtype_name, offsets in cases:
@@ -235,39 +131,7 @@ def test_scalar_aligned_views(sf, torch_mod, nq):
                 assert torch_mod.equal(o, aligned)      # the same kernel, the same bits, wherever the inputs sit
 
 
-GUARD = [((3, 3, 3), 1001), ((6, 6, 6), 129), ((7, 7, 7), 257), ((8, 8, 8), 65), ((2, 2, 2), 33), ((5, 5), 4099),
-         ((13, 13), 1000), ((16, 16), 127), ((6, 6, 12), 13), ((23, 5), 14), ((9, 9, 9), 15)]
-
-
-@pytest.mark.parametrize("nq,nelmt", GUARD, ids=[_ids(s) for s, _ in GUARD])
-def test_guard_values_around_out_and_nan_around_the_inputs(sf, torch_mod, nq, nelmt):
-    """`out` sits between two guard bands (16-byte aligned, so the wave kernels run): only its own values change.  `g`, `w`
-    and the tables are views inside larger buffers filled with NaN on both sides: a value read from outside that reached a
-    result would show as a NaN in `out`."""
-    nmt, nqt = _sizes(nq)
-    nc = _ncomp(nq)
-    for dtype_name, pad in (("float64", 64), ("float32", 128)):
-        dtype = getattr(torch_mod, dtype_name)
-        p = Problem(sf, torch_mod, nq, nelmt, dtype_name, 5)
-
-        def banded(t):
-            buf = torch_mod.full((t.numel() + 2 * pad,), float("nan"), dtype=dtype, device="cuda")
-            buf[pad:pad + t.numel()] = t
-            return buf[pad:pad + t.numel()]
-
-        g, w, tabs = banded(p.g), banded(p.w), [banded(t) for t in p.tabs]
-        obuf = torch_mod.full((nelmt * nmt + 2 * pad,), -3.5, dtype=dtype, device="cuda")
-        o = obuf[pad:pad + nelmt * nmt]
-        for lam, ww in ((LAM, w), (0.0, None)):
-            o.fill_(-3.5)
-            p.run(sf, lam=lam, g=g, w=ww, tabs=tabs, out=o)
-            torch_mod.cuda.synchronize()
-            assert bool((obuf[:pad] == -3.5).all()) and bool((obuf[pad + nelmt * nmt:] == -3.5).all()), dtype_name
-            assert not bool(torch_mod.isnan(o).any()), dtype_name
-            p.check(o, "guard", lam=lam, w=None if ww is None else p.w)
-
-
-@pytest.mark.parametrize("nq", [(8, 8, 8), (5, 5, 5), (12, 12), (3, 3), (6, 6, 12), (23, 5)], ids=_ids)
+@pytest.mark.parametrize("nq", [(8, 8, 8), (5, 5, 5), (12, 12), (3, 3), (6, 6, 12), (23, 5)], ids=case_id)
 def test_laplacian_never_reads_w(sf, torch_mod, nq):
     """lambda == 0 with w=None equals lambda == 0 with a NaN-filled w, bit for bit, in both precisions."""
     for dtype_name in ("float64", "float32"):
@@ -280,11 +144,11 @@ def test_laplacian_never_reads_w(sf, torch_mod, nq):
         p.check(none, "laplacian", lam=0.0, w=None)
 
 
-@pytest.mark.parametrize("nq,nelmt", [((4, 4, 4), 67), ((6, 6), 131)], ids=lambda v: _ids(v))
+@pytest.mark.parametrize("nq,nelmt", [((4, 4, 4), 67), ((6, 6), 131)], ids=lambda v: case_id(v))
 def test_the_operator_itself_is_the_witness(sf, torch_mod, nq, nelmt):
     """sf_helmholtz_* applied to the unit vector e_m in every element, entry m collected: the diagonal, within the sum of
     the two families' bounds (each result is within its own gamma_N absref of the same exact number)."""
-    nmt, _ = _sizes(nq)
+    nmt, _ = sizes(nq)
     p = Problem(sf, torch_mod, nq, nelmt, "float64", 3)
     helm = sf.helmholtz_hex if len(nq) == 3 else sf.helmholtz_quad
     for lam, w in ((LAM, p.w), (0.0, None)):
@@ -297,12 +161,12 @@ def test_the_operator_itself_is_the_witness(sf, torch_mod, nq, nelmt):
             x[:, m] = 1.0
             y = helm(nq, *p.bs, *p.ds, p.g, w, lam, x.reshape(-1))
             col[:, m] = y.view(nelmt, nmt)[:, m]
-            _, ha = ref_helmholtz(nq, nelmt, *p.host, _np(p.g), _np(w), lam, _np(x.reshape(-1)))
+            _, ha = ref_helmholtz(nq, nelmt, *p.host, to_host(p.g), to_host(w), lam, to_host(x.reshape(-1)))
             habs[:, m] = np.asarray(ha).reshape(nelmt, nmt)[:, m]
         torch_mod.cuda.synchronize()
-        _, dabs = ref_diag(nq, nelmt, *p.host, _np(p.g), _np(w), lam)
+        _, dabs = ref_diag(nq, nelmt, *p.host, to_host(p.g), to_host(w), lam)
         bound = gamma(diag_n(nq), U64) * np.asarray(dabs).reshape(-1) + gamma(helm_n(nq), U64) * habs.reshape(-1)
-        err = np.abs(_np(diag).astype(np.longdouble) - _np(col.reshape(-1)).astype(np.longdouble))
+        err = np.abs(to_host(diag).astype(np.longdouble) - to_host(col.reshape(-1)).astype(np.longdouble))
         worst = float(np.max(err / bound))
         print(f"witness {nq} lam={lam}: max |diag - (A e_m)_m| / (sum of the bounds) = {worst:.3g}")
         assert worst <= 1.0 and float(diag.abs().max()) > 0
@@ -323,14 +187,14 @@ def test_gll_closed_form(sf, torch_mod, dim, nq):
         got = f(ext, *tb, *td, tg, ww, lam)                              # tabs=None: the tables are built on the way
         torch_mod.cuda.synchronize()
         ref, absref = ref_diag(ext, nelmt, bases, derivs, g, hw, lam)
-        q = diag_excess(_np(got), ref, absref, ext, U64)
+        q = diag_excess(to_host(got), ref, absref, ext, U64)
         exact = np.tile(gll_exact_diag(nq, dim, lam), nelmt)
         scale = float(np.max(np.abs(exact)))
         e_ref = float(np.max(np.abs(np.asarray(ref, dtype=np.float64) - exact))) / scale
         slack = gamma(diag_n(ext), U64) * np.asarray(absref, dtype=np.float64) + 1e-12 * scale
         print(f"gll {ext} lam={lam}: excess {q:.3g}; reference against the closed form {e_ref:.3g} of max |exact| = {scale:.4g}")
         assert q <= 1.0 and e_ref <= 1e-12
-        assert bool(np.all(np.abs(_np(got) - exact) <= slack))
+        assert bool(np.all(np.abs(to_host(got) - exact) <= slack))
 
 
 @pytest.mark.parametrize("dtype_name", ["float64", "float32"])
@@ -344,7 +208,7 @@ def test_diag_tables(sf, torch_mod, dtype_name):
         tab = sf.diag_tables(nq, b, d)
         torch_mod.cuda.synchronize()
         assert tab.numel() == 3 * (nq - 1) * nq
-        q = tables_excess(_np(tab), tables(nq, _np(b), _np(d)), tables(nq, _np(b), _np(d), absolute=True), nq,
+        q = tables_excess(to_host(tab), tables(nq, to_host(b), to_host(d)), tables(nq, to_host(b), to_host(d), absolute=True), nq,
                           unit_roundoff(dtype_name))
         print(f"tables nq {nq} {dtype_name}: max |err| / (gamma_{2 * nq + 1} abstab) = {q:.3g}")
         assert q <= 1.0 and float(tab.abs().max()) > 0
@@ -355,7 +219,7 @@ WINDOWS = [((8, 8, 8), {"float64": (1, 8), "float32": (2, 8)}), ((16, 16), {"flo
 
 
 @pytest.mark.parametrize("dtype_name", ["float64", "float32"])
-@pytest.mark.parametrize("nq,rows", WINDOWS, ids=[_ids(s) for s, _ in WINDOWS])
+@pytest.mark.parametrize("nq,rows", WINDOWS, ids=[case_id(s) for s, _ in WINDOWS])
 def test_several_xcd_windows(sf, torch_mod, nq, rows, dtype_name):
     """Workgroups are renumbered in windows of 8 * 64 = 512: four full windows' worth of elements plus 3, so that the grid
     ends in a partial window and a ragged chunk.  The whole output against the fp64 numpy form, in slices."""
@@ -378,7 +242,7 @@ def test_streams_past_2_to_the_32_scalars(sf, torch_mod):
     """fp32 3D nq 8 with g just past 2^32 scalars (the index arithmetic is in scalars): windows of 300 elements against
     the long-double reference at the head, across the elements that hold scalar 2^31 and 2^32 of g, and at the tail."""
     nq, win = (8, 8, 8), 300
-    nmt, nqt = _sizes(nq)
+    nmt, nqt = sizes(nq)
     per_g = 6 * nqt
     nelmt = (1 << 32) // per_g + 1 + 333
     nelmt += 1 - nelmt % 2                                    # odd: a ragged last chunk (EC = 2) in a partial workgroup
@@ -400,9 +264,9 @@ def test_streams_past_2_to_the_32_scalars(sf, torch_mod):
         worst = 0.0
         for lo in (0, e31 - win // 2, e32 - win // 2, nelmt - win):
             assert 0 <= lo and lo + win <= nelmt
-            ref, absref = ref_diag(nq, win, *p.host, _np(p.g[lo * per_g:(lo + win) * per_g]),
-                                   _np(p.w[lo * nqt:(lo + win) * nqt]), LAM)
-            q = diag_excess(_np(out[lo * nmt:(lo + win) * nmt]), ref, absref, nq, unit_roundoff("float32"))
+            ref, absref = ref_diag(nq, win, *p.host, to_host(p.g[lo * per_g:(lo + win) * per_g]),
+                                   to_host(p.w[lo * nqt:(lo + win) * nqt]), LAM)
+            q = diag_excess(to_host(out[lo * nmt:(lo + win) * nmt]), ref, absref, nq, unit_roundoff("float32"))
             print(f"past 2^32: elements {lo} .. {lo + win}: max |err| / (gamma_N absref) = {q:.3g}")
             worst = max(worst, q)
         assert worst <= 1.0
@@ -411,72 +275,6 @@ def test_streams_past_2_to_the_32_scalars(sf, torch_mod):
             t.untyped_storage().resize_(0)
         gc.collect()
         torch_mod.cuda.empty_cache()
-
-
-FIRST_CALL_CAPTURED = r"""
-import sys
-import torch
-sys.path.insert(0, sys.argv[1])
-import __graft_entry__ as ge
-sf = ge.load_package()
-for nq, nelmt in (((8, 8, 8), 5001), ((6, 6, 12), 301), ((9, 9), 2001), ((23, 5), 301)):
-    f = sf.diag_helmholtz_hex if len(nq) == 3 else sf.diag_helmholtz_quad
-    dim = len(nq)
-    bs = [sf.fill_random((q - 1) * q, 40 + d) for d, q in enumerate(nq)]
-    ds = [sf.fill_random(q * q, 50 + d) for d, q in enumerate(nq)]
-    npt, nmo = 1, 1
-    for q in nq:
-        npt, nmo = npt * q, nmo * (q - 1)
-    g = sf.fill_random(nelmt * npt * dim * (dim + 1) // 2, 43)
-    w = sf.fill_random(nelmt * npt, 42)
-    o = torch.zeros(nelmt * nmo, dtype=torch.float64, device="cuda")
-    tabs = [torch.zeros(3 * (q - 1) * q, dtype=torch.float64, device="cuda") for q in nq]
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    gr = torch.cuda.CUDAGraph()
-    with torch.cuda.stream(side):
-        with torch.cuda.graph(gr, stream=side):
-            # the process's first calls of the tables kernel and of this route: the tables and the diagonal in one graph
-            built = [sf.diag_tables(q, b, d, stream=side) for q, b, d in zip(nq, bs, ds)]
-            for t, b in zip(tabs, built):
-                t.copy_(b)
-            f(nq, *bs, *ds, g, w, 0.5, out=o, stream=side, tabs=tabs)
-    torch.cuda.current_stream().wait_stream(side)
-    gr.replay()
-    torch.cuda.synchronize()
-    eager = f(nq, *bs, *ds, g, w, 0.5)
-    torch.cuda.synchronize()
-    assert torch.equal(o, eager), nq
-    assert float(o.abs().max()) > 0, nq
-print("first calls captured")
-"""
-
-
-def test_first_call_inside_a_capture():
-    """Capture-safe from the first call: a fresh child process whose first call of each route (3D wave, 3D fallback, 2D
-    wave, 2D fallback) and of the tables kernel is inside a stream capture; the replay equals an eager call made
-    afterwards."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", FIRST_CALL_CAPTURED, root], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "first calls captured" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-
-
-def test_two_streams_in_flight(sf, torch_mod):
-    """Two problems enqueued on two streams before either is waited for; each against the fp64 numpy form."""
-    jobs = [((7, 7, 7), 30011), ((12, 12), 100003)]
-    streams = [torch_mod.cuda.Stream(), torch_mod.cuda.Stream()]
-    probs = [Problem(sf, torch_mod, nq, nelmt, "float64", nelmt % 97) for nq, nelmt in jobs]
-    torch_mod.cuda.synchronize()
-    outs = []
-    for p, st in zip(probs, streams):
-        with torch_mod.cuda.stream(st):
-            outs.append(p.run(sf, stream=st))
-    torch_mod.cuda.synchronize()
-    for p, o in zip(probs, outs):
-        q = max(f64_excess(p, o, lo=lo, n=min(8192, p.nelmt - lo)) for lo in range(0, p.nelmt, 8192))
-        print(f"stream job {p.nq}: {q:.3g}")
-        assert q <= 1.0, p.nq
 
 
 def test_four_host_threads_on_one_stream(sf, torch_mod):
@@ -498,7 +296,7 @@ def test_four_host_threads_on_one_stream(sf, torch_mod):
     ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
     outs, calls = [], []
     for p in probs:
-        n = p.nelmt * _sizes(p.nq)[0]
+        n = p.nelmt * sizes(p.nq)[0]
         stride = (n + 31) // 32 * 32                     # rows start 256-byte aligned, as fresh allocations would
         o = torch.full((launches, stride), float("nan"), dtype=torch.float64, device="cuda")
         outs.append(o[:, :n])

@@ -22,22 +22,9 @@ test_one_past_each_bound: SF_ENOTBUILT.
 import pytest
 
 import fused_families as ff
-from fused_families import FAMILIES, Problem, case_id, excess_over_slices
+from fused_families import FAMILIES, Problem, case_id, excess_over_slices, sf, torch_mod  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def sf():
-    import __graft_entry__ as ge
-    return ge.load_package()
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available(), "the GPU tests need a GPU"
-    return torch
 
 
 def _nan_outs(torch_mod, fam, nq, nelmt, dtype_name, off=0):

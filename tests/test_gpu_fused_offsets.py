@@ -21,25 +21,12 @@ and in fp64 the explicit "wave" call is not refused and gives the bits of AUTO.
 """
 import pytest
 
-from fused_families import SCALAR, VEC, WAVE_CASES, Problem, wave_ids, wave_row
+from fused_families import SCALAR, VEC, WAVE_CASES, Banded, Problem, sf, torch_mod, wave_ids, wave_row  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -3.5
 VEC_BYTES = (16, 48, 80, 112, 0)
-
-
-@pytest.fixture(scope="module")
-def sf():
-    import __graft_entry__ as ge
-    return ge.load_package()
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available(), "the GPU tests need a GPU"
-    return torch
 
 
 def ragged_count(ec, wpb):
@@ -50,25 +37,6 @@ def ragged_count(ec, wpb):
         n += 1
     assert 257 <= n <= 1031
     return n
-
-
-class Banded:
-    """A view of `n` scalars at `off` scalars into a line of a line-aligned buffer, two lines of `fill` on either side."""
-
-    def __init__(self, torch_mod, dtype, n, off, fill):
-        line = 128 // torch_mod.empty(0, dtype=dtype).element_size()
-        self.fill, self.lo, self.hi = fill, 2 * line + off, 2 * line + off + n
-        self.buf = torch_mod.empty(self.hi + 2 * line, dtype=dtype, device="cuda")
-        assert self.buf.data_ptr() % 128 == 0
-        self.reset()
-        self.view = self.buf[self.lo:self.hi]
-
-    def reset(self):
-        self.buf.fill_(self.fill)
-
-    def bands_intact(self, torch_mod):
-        bands = torch_mod.cat([self.buf[:self.lo], self.buf[self.hi:]])
-        return bool(torch_mod.isnan(bands).all()) if self.fill != self.fill else bool((bands == self.fill).all())
 
 
 @pytest.mark.parametrize("dtype_name", ["float64", "float32"])

@@ -27,25 +27,12 @@ import gc
 import numpy as np
 import pytest
 
-from fused_families import (FAMILIES, WAVE_CASES, Problem, case_id, excess_over_slices, sizes, to_host, wave_ids,
-                            wave_row)
+from fused_families import (FAMILIES, WAVE_CASES, Problem, case_id, excess_over_slices, sf, sizes, to_host,  # noqa: F401
+                            torch_mod, wave_ids, wave_row)
 
 pytestmark = pytest.mark.gpu
 
 WINDOW = 512                  # workgroups per renumbering window: 8 XCDs * XG = 64 (csrc/wave_table.h XG64)
-
-
-@pytest.fixture(scope="module")
-def sf():
-    import __graft_entry__ as ge
-    return ge.load_package()
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available(), "the GPU tests need a GPU"
-    return torch
 
 
 def batch_for_windows(dim, nq, ec, wpb):

@@ -1,51 +1,28 @@
 """GPU tests of IProductWRTDerivBase (include/sumfact.h sf_iprodderiv_*), out = sum_b B^T D_b^T (w sum_a df_ab f_a) in
-one kernel: every wave order through AUTO with and without df and w, ragged counts, the any-extent fallback, variant
-routing, scalar-aligned input views, guard words around the output with NaN around every input, df / w never read when
-None, every plane of df on its own, adjointness to sf_physderiv_* on the device, composition against sf_helmholtz_*,
-physderiv_autograd, the three input forms, stream capture (also as a process's first call), two streams in flight and
-a 20 011-element batch.
+one kernel, that are the family's own: an 8-byte-aligned `out`, scalar-aligned input views, df / w never read when None,
+identity planes and a unit weight, every plane of df on its own, adjointness to sf_physderiv_* on the device,
+composition against sf_helmholtz_*, physderiv_autograd, the three input forms, a 20 011-element batch and refused
+overlaps.  install() adds the family's cases of the parametrised tests the fused families share (tests/fused_common.py:
+every wave order through AUTO, ragged counts, the fallback, explicit variants, guard bands); refusals, stream capture
+and two streams in flight are tests/test_gpu_fused_common.py.
 
 Reference and bound: tests/iprodderiv_ref.py.  Elementwise |gpu - ref| <= gamma_N * absref against a long-double
 reference, gamma_N = N u / (1 - N u), N = sum nq_d + max nq_d + 2 d, u = 2^-53 (fp64) or 2^-24 (fp32).
 Data: seeded, per-value distinct (sf.fill_random); df and w uniform in (-1, 1), so every component and sign is exercised.
 """
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from fused_common import install
+from fused_families import BY_NAME, case_id, sf, sizes, to_host, torch_mod  # noqa: F401
 from helm_ref import COMPONENTS, helm_n, ref_helmholtz
 from iprodderiv_ref import (U64, gamma, iprodderiv_excess, iprodderiv_f64, iprodderiv_n, ref_iprodderiv, unit_roundoff)
 from physderiv_ref import physderiv_n, ref_physderiv
 
 pytestmark = pytest.mark.gpu
+install(globals(), BY_NAME["iprodderiv"])
 
-WAVE_ORDERS = [(3, n) for n in range(2, 9)] + [(2, n) for n in range(2, 17)]
-FALLBACK = [(9, 9, 9), (11, 11, 11), (6, 6, 12), (3, 5, 4), (12, 10, 8), (20, 20), (4, 9), (23, 5), (32, 32)]
-NULLS = [(True, True), (False, True), (True, False), (False, False)]
-
-
-@pytest.fixture(scope="module")
-def sf():
-    import __graft_entry__ as ge
-    return ge.load_package()
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available(), "the GPU tests need a GPU"
-    return torch
-
-
-def _np(t):
-    return None if t is None else t.detach().cpu().numpy()
-
-
-def _sizes(nq):
-    return int(np.prod([q - 1 for q in nq])), int(np.prod(nq))
 
 
 class Problem:
@@ -54,7 +31,7 @@ class Problem:
     def __init__(self, sf, torch_mod, nq, nelmt, dtype_name, seed):
         dtype = getattr(torch_mod, dtype_name)
         self.nq, self.nelmt, self.dtype_name, self.dim = tuple(nq), nelmt, dtype_name, len(nq)
-        nmt, nqt = _sizes(nq)
+        nmt, nqt = sizes(nq)
         self.bs = [sf.fill_random((q - 1) * q, 500 + 7 * seed + d, dtype=dtype) for d, q in enumerate(nq)]
         self.ds = [sf.fill_random(q * q, 600 + 7 * seed + d, dtype=dtype) for d, q in enumerate(nq)]
         self.df = sf.fill_random(nelmt * self.dim ** 2 * nqt, 8000 + seed, dtype=dtype)
@@ -77,96 +54,25 @@ class Problem:
         df = self.df if isinstance(df, str) else df
         w = self.w if isinstance(w, str) else w
         f = self.f if f is None else f
-        rows = [_np(r) for r in f]
-        return ref_iprodderiv(self.nq, self.nelmt, [_np(b) for b in self.bs], [_np(d) for d in self.ds], _np(df), _np(w),
+        rows = [to_host(r) for r in f]
+        return ref_iprodderiv(self.nq, self.nelmt, [to_host(b) for b in self.bs], [to_host(d) for d in self.ds], to_host(df), to_host(w),
                               rows)
 
     def check(self, got, what, ref=None, **kw):
         ref, absref = self.reference(**kw) if ref is None else ref
         assert float(np.max(np.abs(ref))) > 0
-        got = _np(got)
+        got = to_host(got)
         assert got.shape == ref.shape, (got.shape, ref.shape)
         q = iprodderiv_excess(got, ref, absref, self.nq, unit_roundoff(self.dtype_name))
         print(f"{what}: {self.nq} {self.dtype_name} nelmt={self.nelmt}: max |err| / (gamma_N absref) = {q:.3g}")
         assert q <= 1.0, (what, self.nq, self.dtype_name, self.nelmt, q)
 
 
-def _ids(v):
-    return "x".join(map(str, v)) if isinstance(v, tuple) else str(v)
-
-
-@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
-@pytest.mark.parametrize("dim,nq", WAVE_ORDERS, ids=[f"{d}d-nq{n}" for d, n in WAVE_ORDERS])
-def test_auto_every_wave_order(sf, torch_mod, dim, nq, dtype_name):
-    """One element, 97 elements (3 EC + 1 for every row with EC <= 32: ragged last chunks, the two-pass rows, the partly
-    filled waves of 3D nq 5 / 6 / 7, the 2D EC override from nq 9) and, for the 2D rows with longer chunks (EC up to 256
-    at nq 2 in fp32), 769; each with and without df and w."""
-    for nelmt in (1, 97) + ((769,) if dim == 2 and nq <= 4 else ()):
-        p = Problem(sf, torch_mod, (nq,) * dim, nelmt, dtype_name, nq)
-        for has_df, has_w in NULLS:
-            kw = dict(df=p.df if has_df else None, w=p.w if has_w else None)
-            got = p.run(sf, **kw)
-            torch_mod.cuda.synchronize()
-            assert tuple(got.shape) == (nelmt * (nq - 1) ** dim,)
-            p.check(got, f"auto df={has_df} w={has_w}", **kw)
-            if dtype_name == "float64":
-                # AUTO runs the wave kernel here: the same bits as the explicit variant
-                wave = p.run(sf, variant="wave", **kw)
-                torch_mod.cuda.synchronize()
-                assert torch_mod.equal(got, wave)
-
-
-@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
-@pytest.mark.parametrize("nq", FALLBACK, ids=_ids)
-def test_fallback_shapes(sf, torch_mod, nq, dtype_name):
-    for nelmt in (5, 33):
-        p = Problem(sf, torch_mod, nq, nelmt, dtype_name, 70 + nelmt)
-        got = p.run(sf)
-        torch_mod.cuda.synchronize()
-        p.check(got, "fallback")
-        if dtype_name == "float64":
-            gen = p.run(sf, variant="generic")
-            torch_mod.cuda.synchronize()
-            assert torch_mod.equal(got, gen)
-    for has_df, has_w in NULLS[1:]:
-        kw = dict(df=p.df if has_df else None, w=p.w if has_w else None)
-        got = p.run(sf, **kw)
-        torch_mod.cuda.synchronize()
-        p.check(got, f"fallback df={has_df} w={has_w}", **kw)
-
-
-@pytest.mark.parametrize("nq", [(8, 8, 8), (5, 5, 5), (12, 12), (9, 9)], ids=_ids)
-def test_explicit_wave_and_generic(sf, torch_mod, nq):
-    """Each explicit variant inside the bound of the reference (which serves both)."""
-    p = Problem(sf, torch_mod, nq, 67, "float64", 9)
-    for has_df, has_w in NULLS:
-        kw = dict(df=p.df if has_df else None, w=p.w if has_w else None)
-        ref = p.reference(**kw)
-        for variant in ("wave", "generic"):
-            got = p.run(sf, variant=variant, **kw)
-            torch_mod.cuda.synchronize()
-            p.check(got, f"{variant} df={has_df} w={has_w}", ref=ref)
-
-
-def test_variants_off_the_table(sf, torch_mod):
-    p = Problem(sf, torch_mod, (9, 9, 9), 5, "float64", 2)
-    for variant in ("wave", "mfma", "mfma4", "thread", "block-lds", "block-glb", "wave-rt"):
-        with pytest.raises(sf.capi.SumfactError) as ei:
-            p.run(sf, variant=variant)
-        assert ei.value.rc == sf.capi.SF_ENOTBUILT, variant
-    for nq in ((6, 6, 12), (17, 17), (4, 9)):                      # anisotropic, or above the 2D table
-        q = Problem(sf, torch_mod, nq, 5, "float64", 2)
-        with pytest.raises(sf.capi.SumfactError) as ei:
-            q.run(sf, variant="wave")
-        assert ei.value.rc == sf.capi.SF_ENOTBUILT, nq
-    big = Problem(sf, torch_mod, (13, 4, 4), 2, "float64", 2)
-    with pytest.raises(sf.capi.SumfactError) as ei:
-        big.run(sf)
-    assert ei.value.rc == sf.capi.SF_ENOTBUILT
-    # an 8-byte-aligned out: WAVE refuses it, AUTO takes the fallback and is correct
+def test_wave_refuses_an_eight_byte_aligned_out(sf, torch_mod):
+    """An 8-byte-aligned out: WAVE refuses it, AUTO takes the fallback and is correct."""
     for nq in ((8, 8, 8), (12, 12)):
         p = Problem(sf, torch_mod, nq, 19, "float64", 3)
-        nmt, _ = _sizes(nq)
+        nmt, _ = sizes(nq)
         obuf = torch_mod.full((19 * nmt + 8,), 7.25, dtype=torch_mod.float64, device="cuda")
         out = obuf[1:1 + 19 * nmt]
         assert out.data_ptr() % 16 == 8
@@ -181,12 +87,12 @@ def test_variants_off_the_table(sf, torch_mod):
         p.check(out, "auto on an 8-byte-aligned out")
 
 
-@pytest.mark.parametrize("nq", [(8, 8, 8), (7, 7, 7), (3, 3, 3), (8, 8), (11, 11)], ids=_ids)
+@pytest.mark.parametrize("nq", [(8, 8, 8), (7, 7, 7), (3, 3, 3), (8, 8), (11, 11)], ids=case_id)
 def test_scalar_aligned_input_views(sf, torch_mod, nq):
     """Every in_a, df and w offset by one scalar (not 16-byte aligned), out 16-byte aligned: the inputs need scalar
     alignment only, so variant "wave" runs, AUTO gives its bits, and both sit inside the bound."""
     nelmt, dim = 45, len(nq)
-    _, nqt = _sizes(nq)
+    _, nqt = sizes(nq)
     n = nelmt * nqt
     for dtype_name in ("float64", "float32"):
         dtype = getattr(torch_mod, dtype_name)
@@ -209,45 +115,7 @@ def test_scalar_aligned_input_views(sf, torch_mod, nq):
             assert torch_mod.equal(got, wave)
 
 
-# (shape, EC of the fp64 row, EC of the fp32 row): the chunk lengths of csrc/iprodderiv_launch.h
-GUARD = [((8, 8, 8), 1, 2), ((7, 7, 7), 1, 2), ((6, 6, 6), 1, 3), ((3, 3, 3), 14, 14), ((16, 16), 4, 4), ((9, 9), 4, 8),
-         ((2, 2), 128, 256)]
-
-
-@pytest.mark.parametrize("nq,ec64,ec32", GUARD, ids=[_ids(s) for s, _, _ in GUARD])
-def test_guard_words_around_out_and_nan_around_every_input(sf, torch_mod, nq, ec64, ec32):
-    """`out` is carved from a larger buffer with guard words on both sides (16-byte aligned, so the wave kernels run):
-    only its own values change.  Every in_a, df and w is a view with NaN immediately before and after it: a value read
-    from outside that reached a result would show as a NaN.  Counts 1, EC + 1 and 2 EC - 1."""
-    dim = len(nq)
-    nmt, nqt = _sizes(nq)
-    for dtype_name, ec in (("float64", ec64), ("float32", ec32)):
-        dtype = getattr(torch_mod, dtype_name)
-        pad = 64 if dtype_name == "float64" else 128
-
-        def nan_view(t):
-            buf = torch_mod.full((t.numel() + 2 * pad,), float("nan"), dtype=dtype, device="cuda")
-            buf[pad:pad + t.numel()] = t
-            return buf[pad:pad + t.numel()]
-
-        for nelmt in sorted({1, ec + 1, max(1, 2 * ec - 1)}):
-            p = Problem(sf, torch_mod, nq, nelmt, dtype_name, 5)
-            fs = [nan_view(p.f[a]) for a in range(dim)]
-            df, w = nan_view(p.df), nan_view(p.w)
-            obuf = torch_mod.full((nelmt * nmt + 2 * pad,), -3.5, dtype=dtype, device="cuda")
-            out = obuf[pad:pad + nelmt * nmt]
-            for has_df, has_w in NULLS:
-                obuf.fill_(-3.5)
-                kw = dict(df=df if has_df else None, w=w if has_w else None)
-                p.run(sf, f=fs, out=out, **kw)
-                torch_mod.cuda.synchronize()
-                assert bool((obuf[:pad] == -3.5).all()) and bool((obuf[pad + nelmt * nmt:] == -3.5).all()), \
-                    (dtype_name, nelmt, has_df, has_w)
-                assert bool(torch_mod.isfinite(obuf).all()), (dtype_name, nelmt, has_df, has_w)
-                p.check(out, f"guard df={has_df} w={has_w}", f=fs, **kw)
-
-
-@pytest.mark.parametrize("nq", [(8, 8, 8), (5, 5, 5), (12, 12), (6, 6, 12), (23, 5)], ids=_ids)
+@pytest.mark.parametrize("nq", [(8, 8, 8), (5, 5, 5), (12, 12), (6, 6, 12), (23, 5)], ids=case_id)
 def test_df_and_w_are_never_read_when_none(sf, torch_mod, nq):
     """df=None / w=None with no such buffer in existence (the problem's own are freed first; what stands beside them is
     a NaN-filled array of size 1): the result is finite and equals the reference, on wave and fallback shapes, in both
@@ -265,12 +133,12 @@ def test_df_and_w_are_never_read_when_none(sf, torch_mod, nq):
 
 
 @pytest.mark.parametrize("nq,dtype_name", [((8, 8, 8), "float64"), ((7, 7), "float32"), ((6, 6, 12), "float64"),
-                                           ((9, 9, 9), "float32"), ((12, 12), "float64")], ids=lambda v: _ids(v))
+                                           ((9, 9, 9), "float32"), ((12, 12), "float64")], ids=lambda v: case_id(v))
 def test_identity_planes_and_unit_weight(sf, torch_mod, nq, dtype_name):
     """Identity planes of df give the values of df=None within the bound; a w of all ones is bit-identical to w=None
     (1 * t is exact)."""
     dim = len(nq)
-    _, nqt = _sizes(nq)
+    _, nqt = sizes(nq)
     p = Problem(sf, torch_mod, nq, 37, dtype_name, 51)
     ident = torch_mod.zeros_like(p.df).view(p.nelmt, dim, dim, nqt)
     for a in range(dim):
@@ -287,12 +155,12 @@ def test_identity_planes_and_unit_weight(sf, torch_mod, nq, dtype_name):
         assert float(b.abs().max()) > 0
 
 
-@pytest.mark.parametrize("nq", [(8, 8, 8), (6, 4, 5), (12, 12), (4, 9)], ids=_ids)
+@pytest.mark.parametrize("nq", [(8, 8, 8), (6, 4, 5), (12, 12), (4, 9)], ids=case_id)
 def test_each_plane_alone(sf, torch_mod, nq):
     """One plane of df all ones, the others zero: out = B^T D_b^T (w f_a) for the plane c = a d + b.  A transposed
     a d + b would take another input and another derivative; the reference tells."""
     dim = len(nq)
-    _, nqt = _sizes(nq)
+    _, nqt = sizes(nq)
     p = Problem(sf, torch_mod, nq, 21, "float64", 41)
     seen = []
     for c in range(dim * dim):
@@ -302,14 +170,14 @@ def test_each_plane_alone(sf, torch_mod, nq):
         got = p.run(sf, df=df)
         torch_mod.cuda.synchronize()
         p.check(got, f"plane {c}", df=df)
-        seen.append(_np(got))
+        seen.append(to_host(got))
     for c in range(dim * dim):
         for c2 in range(c):
             assert not np.array_equal(seen[c], seen[c2]), (c, c2)
 
 
 @pytest.mark.parametrize("dtype_name", ["float64", "float32"])
-@pytest.mark.parametrize("nq", [(8, 8, 8), (5, 5, 5), (16, 16), (6, 6, 12)], ids=_ids)
+@pytest.mark.parametrize("nq", [(8, 8, 8), (5, 5, 5), (16, 16), (6, 6, 12)], ids=case_id)
 def test_adjoint_of_physderiv_on_the_device(sf, torch_mod, nq, dtype_name):
     """<physderiv(x), f> against <x, iprodderiv(df, None, f)>, both products of the device results formed on the host in
     long double: the difference is at most (gamma_Nphys + gamma_N) times the inner product of absolute values,
@@ -321,17 +189,17 @@ def test_adjoint_of_physderiv_on_the_device(sf, torch_mod, nq, dtype_name):
         grad = p.physderiv(sf, df=df)
         div = p.run(sf, df=df, w=None)
         torch_mod.cuda.synchronize()
-        f, x = _np(p.f).astype(ld), _np(p.x).astype(ld)
-        lhs = np.sum(_np(grad).astype(ld) * f)
-        rhs = np.sum(x * _np(div).astype(ld))
-        _, gabs = ref_physderiv(nq, p.nelmt, [_np(b) for b in p.bs], [_np(d) for d in p.ds], _np(df), _np(p.x))
+        f, x = to_host(p.f).astype(ld), to_host(p.x).astype(ld)
+        lhs = np.sum(to_host(grad).astype(ld) * f)
+        rhs = np.sum(x * to_host(div).astype(ld))
+        _, gabs = ref_physderiv(nq, p.nelmt, [to_host(b) for b in p.bs], [to_host(d) for d in p.ds], to_host(df), to_host(p.x))
         bound = (gamma(physderiv_n(nq), u) + gamma(iprodderiv_n(nq), u)) * np.sum(gabs * np.abs(f))
         print(f"adjoint {nq} {dtype_name} df={'yes' if df is not None else 'None'}: |lhs - rhs| = "
               f"{float(abs(lhs - rhs)):.3e}, bound {float(bound):.3e}")
         assert abs(lhs - rhs) <= bound and abs(lhs) > 0
 
 
-@pytest.mark.parametrize("nq", [(8, 8, 8), (12, 12)], ids=_ids)
+@pytest.mark.parametrize("nq", [(8, 8, 8), (12, 12)], ids=case_id)
 def test_composition_is_the_helmholtz_operator(sf, torch_mod, nq):
     """iprodderiv(df, w, physderiv(df, x)) against helmholtz(g, None, 0, x) with g_ab = w sum_c df_ca df_cb built on the
     host (long double, rounded once).  Both approximate the same exact operator: the composition within
@@ -339,10 +207,10 @@ def test_composition_is_the_helmholtz_operator(sf, torch_mod, nq):
     Helmholtz kernel within its own gamma_Nhelm absref; their difference is at most the sum of the two bounds."""
     ld = np.longdouble
     dim = len(nq)
-    _, nqt = _sizes(nq)
+    _, nqt = sizes(nq)
     p = Problem(sf, torch_mod, nq, 23, "float64", 61)
-    dd = _np(p.df).astype(ld).reshape(p.nelmt, dim * dim, nqt)
-    ww = _np(p.w).astype(ld).reshape(p.nelmt, nqt)
+    dd = to_host(p.df).astype(ld).reshape(p.nelmt, dim * dim, nqt)
+    ww = to_host(p.w).astype(ld).reshape(p.nelmt, nqt)
     g = np.empty((p.nelmt, len(COMPONENTS[dim]), nqt), dtype=ld)
     gabs = np.empty_like(g)
     for c, (a, b) in enumerate(COMPONENTS[dim]):
@@ -352,18 +220,18 @@ def test_composition_is_the_helmholtz_operator(sf, torch_mod, nq):
     comp = p.run(sf, f=p.physderiv(sf))
     helm = (sf.helmholtz_hex if dim == 3 else sf.helmholtz_quad)(nq, *p.bs, *p.ds, g64, None, 0.0, p.x)
     torch_mod.cuda.synchronize()
-    bases, derivs = [_np(b) for b in p.bs], [_np(d) for d in p.ds]
-    _, habs = ref_helmholtz(nq, p.nelmt, bases, derivs, _np(g64), None, 0.0, _np(p.x))
+    bases, derivs = [to_host(b) for b in p.bs], [to_host(d) for d in p.ds]
+    _, habs = ref_helmholtz(nq, p.nelmt, bases, derivs, to_host(g64), None, 0.0, to_host(p.x))
     # the composition on absolute values is the Helmholtz operator on |B|, |D|, |x| with the metric of absolute values
-    _, cabs = ref_helmholtz(nq, p.nelmt, bases, derivs, gabs.reshape(-1), None, 0.0, _np(p.x))
+    _, cabs = ref_helmholtz(nq, p.nelmt, bases, derivs, gabs.reshape(-1), None, 0.0, to_host(p.x))
     bound = gamma(physderiv_n(nq) + iprodderiv_n(nq) + 1, U64) * cabs + gamma(helm_n(nq), U64) * habs
-    err = np.abs(_np(comp).astype(ld) - _np(helm).astype(ld))
+    err = np.abs(to_host(comp).astype(ld) - to_host(helm).astype(ld))
     q = float(np.max(err / bound))
     print(f"composition {nq}: max |iprodderiv(physderiv) - helmholtz| / (sum of bounds) = {q:.3g}")
     assert q <= 1.0 and float(helm.abs().max()) > 0
 
 
-@pytest.mark.parametrize("nq", [(8, 8, 8), (9, 9)], ids=_ids)
+@pytest.mark.parametrize("nq", [(8, 8, 8), (9, 9)], ids=case_id)
 def test_physderiv_autograd(sf, torch_mod, nq):
     """.backward() of (out * f).sum() gives exactly iprodderiv_*(df, None, f); constants that require grad are refused."""
     p = Problem(sf, torch_mod, nq, 31, "float64", 71)
@@ -385,7 +253,7 @@ def test_physderiv_autograd(sf, torch_mod, nq):
         sf.physderiv_autograd(nq, [p.bs[0].clone().requires_grad_()] + p.bs[1:], p.ds, p.df, p.x)
 
 
-@pytest.mark.parametrize("nq", [(7, 7, 7), (8, 8, 8), (9, 9), (4, 9)], ids=_ids)
+@pytest.mark.parametrize("nq", [(7, 7, 7), (8, 8, 8), (9, 9), (4, 9)], ids=case_id)
 def test_input_forms(sf, torch_mod, nq):
     """The (d, n) tensor physderiv_* returns (rows 256-byte aligned, the whole not contiguous for these odd n, taken
     without a copy), a sequence of d tensors and a contiguous (d n) tensor give bit-identical results."""
@@ -400,108 +268,15 @@ def test_input_forms(sf, torch_mod, nq):
     p.check(a, "input forms", f=grad)
 
 
-@pytest.mark.parametrize("nq,nelmt", [((8, 8, 8), 20011), ((9, 9), 5003)], ids=lambda v: _ids(v))
-def test_captured_graph_replay_matches_eager(sf, torch_mod, nq, nelmt):
-    p = Problem(sf, torch_mod, nq, nelmt, "float64", 11)
-    eager = p.run(sf)
-    o = torch_mod.zeros_like(eager)
-    torch_mod.cuda.synchronize()
-    side = torch_mod.cuda.Stream()
-    side.wait_stream(torch_mod.cuda.current_stream())
-    g = torch_mod.cuda.CUDAGraph()
-    with torch_mod.cuda.stream(side):
-        with torch_mod.cuda.graph(g, stream=side):
-            p.run(sf, out=o, stream=side)
-    torch_mod.cuda.current_stream().wait_stream(side)
-    g.replay()
-    torch_mod.cuda.synchronize()
-    assert torch_mod.equal(o, eager)
-    assert float(o.abs().max()) > 0
-
-
-FIRST_CALL_CAPTURED = r"""
-import sys
-import torch
-sys.path.insert(0, sys.argv[1])
-import __graft_entry__ as ge
-sf = ge.load_package()
-for nq, nelmt in (((8, 8, 8), 1001), ((6, 6, 12), 101), ((9, 9), 1002), ((23, 5), 101)):
-    f = sf.iprodderiv_hex if len(nq) == 3 else sf.iprodderiv_quad
-    dim = len(nq)
-    bs = [sf.fill_random((q - 1) * q, 40 + d) for d, q in enumerate(nq)]
-    ds = [sf.fill_random(q * q, 50 + d) for d, q in enumerate(nq)]
-    npt, nmo = 1, 1
-    for q in nq:
-        npt, nmo = npt * q, nmo * (q - 1)
-    x = sf.fill_random(dim * nelmt * npt, 41).view(dim, nelmt * npt)
-    df = sf.fill_random(nelmt * npt * dim * dim, 43)
-    w = sf.fill_random(nelmt * npt, 44)
-    o = torch.zeros(nelmt * nmo, dtype=torch.float64, device="cuda")
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    gr = torch.cuda.CUDAGraph()
-    with torch.cuda.stream(side):
-        with torch.cuda.graph(gr, stream=side):
-            f(nq, *bs, *ds, df, w, x, out=o, stream=side)     # the process's first call of this route
-    torch.cuda.current_stream().wait_stream(side)
-    gr.replay()
-    torch.cuda.synchronize()
-    eager = f(nq, *bs, *ds, df, w, x)
-    torch.cuda.synchronize()
-    assert torch.equal(o, eager), nq
-    assert float(o.abs().max()) > 0, nq
-print("first calls captured")
-"""
-
-
-def test_first_call_inside_a_capture():
-    """Capture-safe from the first call: a fresh child process whose first fused call of each route (3D wave, 3D
-    fallback, 2D wave, 2D fallback) is inside a stream capture; the replay equals an eager call made afterwards."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", FIRST_CALL_CAPTURED, root], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "first calls captured" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-
-
-def _sampled_excess(torch_mod, p, got, sample):
-    """The excess of the elements `sample` of a batch against the long-double reference of just those."""
-    dim = p.dim
-    nmt, nqt = _sizes(p.nq)
-    idx = torch_mod.tensor(sample, device="cuda")
-    pick = lambda t, n: _np(t.reshape(p.nelmt, n)[idx].reshape(-1))      # noqa: E731
-    ref, absref = ref_iprodderiv(p.nq, len(sample), [_np(b) for b in p.bs], [_np(d) for d in p.ds],
-                                 pick(p.df, dim * dim * nqt), pick(p.w, nqt), [pick(p.f[a], nqt) for a in range(dim)])
-    return iprodderiv_excess(pick(got, nmt), ref, absref, p.nq, U64)
-
-
-def test_two_streams_in_flight(sf, torch_mod):
-    """Two problems enqueued on two streams before either is waited for; a seeded sample of each against the reference."""
-    jobs = [((7, 7, 7), 3011), ((12, 12), 10003)]
-    streams = [torch_mod.cuda.Stream(), torch_mod.cuda.Stream()]
-    probs = [Problem(sf, torch_mod, nq, nelmt, "float64", nelmt % 97) for nq, nelmt in jobs]
-    torch_mod.cuda.synchronize()
-    outs = []
-    for p, st in zip(probs, streams):
-        with torch_mod.cuda.stream(st):
-            outs.append(p.run(sf, stream=st))
-    torch_mod.cuda.synchronize()
-    rng = np.random.default_rng(7)
-    for p, o in zip(probs, outs):
-        sample = np.unique(np.concatenate(([0, 1, p.nelmt - 2, p.nelmt - 1], rng.integers(0, p.nelmt, 256))))
-        q = _sampled_excess(torch_mod, p, o, sample)
-        print(f"stream job {p.nq}: {q:.3g}")
-        assert q <= 1.0, p.nq
-
-
 def test_larger_batch_hex8(sf, torch_mod):
     """20 011 elements at 3D nq = 8 against the fp64 reference (numpy matmuls); a second run is bit-identical."""
     nq, nelmt = (8, 8, 8), 20011
     p = Problem(sf, torch_mod, nq, nelmt, "float64", 8)
     y = p.run(sf)
     torch_mod.cuda.synchronize()
-    ref, absref = iprodderiv_f64(nq, nelmt, [_np(b) for b in p.bs], [_np(d) for d in p.ds], _np(p.df), _np(p.w),
-                                 [_np(r) for r in p.f])
-    worst = iprodderiv_excess(_np(y), ref, absref, nq, U64)
+    ref, absref = iprodderiv_f64(nq, nelmt, [to_host(b) for b in p.bs], [to_host(d) for d in p.ds], to_host(p.df), to_host(p.w),
+                                 [to_host(r) for r in p.f])
+    worst = iprodderiv_excess(to_host(y), ref, absref, nq, U64)
     print(f"larger batch: max |err| / (gamma_{iprodderiv_n(nq)} absref) = {worst:.3g}")
     assert worst <= 1.0
     again = p.run(sf)
