@@ -21,6 +21,8 @@ from .bwdtrans import (  # noqa: F401
     helmholtz_hex, helmholtz_quad, affine_helmholtz_hex, affine_helmholtz_quad,
     physderiv_hex, physderiv_quad,
     iprodderiv_hex, iprodderiv_quad, physderiv_autograd,
+    affine_physderiv_hex, affine_physderiv_quad, affine_iprodderiv_hex, affine_iprodderiv_quad,
+    affine_physderiv_autograd,
     diag_tables, diag_helmholtz_hex, diag_helmholtz_quad,
     GsMap, gs_setup, global_to_local, assemble, gs,
 )

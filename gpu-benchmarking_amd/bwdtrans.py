@@ -127,7 +127,7 @@ def _input_parts(what, inp, parts):
 
 def _operator_call(what, fam, nq, bases, inp, out, variant, stream, wsp=None):
     """The one call path of bwdtrans_* / iproduct_* / mass_* / helmholtz_* / affine_helmholtz_* / physderiv_* /
-    iprodderiv_* / diag_helmholtz_*: sizes, dtypes and devices are checked here (before any library call), pointers, alignment and overlap in
+    iprodderiv_* / affine_physderiv_* / affine_iprodderiv_* / diag_helmholtz_*: sizes, dtypes and devices are checked here (before any library call), pointers, alignment and overlap in
     the C ABI."""
     nq = tuple(int(x) for x in nq)
     ins = None
@@ -367,6 +367,59 @@ def iprodderiv_quad(nq, basis0, basis1, deriv0, deriv1, df, w, inp, out=None, va
                           variant, stream)
 
 
+def _affine_physderiv(nq, derivs, dfe):
+    d = len(nq)
+    return _Family("aff_physderiv", False, True, lambda nelmt, nqt: _per_direction("deriv", derivs, lambda q: q * q, nq) + [
+        ("dfe", dfe, nelmt * d * d, False)], out_parts=d)
+
+
+def affine_physderiv_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, dfe, inp, out=None, variant="auto",
+                         stream=None):
+    """physderiv_hex on affine elements in one kernel, on inp's device: out[a][e][k][j][i] = sum_b dfe[e][3 a + b]
+    du_b[e][k][j][i], with dfe[e][c] the nine constants of the element's inverse Jacobian, c = 3 a + b for d xi_b / d x_a
+    (the order of the planes of physderiv_hex's df; required).  Bit for bit physderiv_hex on planes filled with the
+    constants.  The bases, derivative matrices, inp, out and variants of physderiv_hex.  A plain function: no autograd."""
+    return _operator_call("affine_physderiv_hex", _affine_physderiv(nq, (deriv0, deriv1, deriv2), dfe), nq,
+                          (basis0, basis1, basis2), inp, out, variant, stream)
+
+
+def affine_physderiv_quad(nq, basis0, basis1, deriv0, deriv1, dfe, inp, out=None, variant="auto", stream=None):
+    """physderiv_quad on affine elements: out[a][e][j][i] = sum_b dfe[e][2 a + b] du_b[e][j][i], four constants per
+    element, a (2, nelmt * nq0*nq1) result."""
+    return _operator_call("affine_physderiv_quad", _affine_physderiv(nq, (deriv0, deriv1), dfe), nq, (basis0, basis1), inp,
+                          out, variant, stream)
+
+
+def _affine_iprodderiv(nq, derivs, qws, dfe, je):
+    d = len(nq)
+    unweighted = je is None             # the quadrature weights are then never read and may be None as well
+    return _Family("aff_iprodderiv", True, False, lambda nelmt, nqt: (
+        _per_direction("deriv", derivs, lambda q: q * q, nq)
+        + [(f"qw{i}", t, int(q), unweighted) for i, (t, q) in enumerate(zip(qws, nq))]
+        + [("dfe", dfe, nelmt * d * d, False), ("je", je, nelmt, True)]), inp_parts=d)
+
+
+def affine_iprodderiv_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, qw0, qw1, qw2, dfe, je, inp, out=None,
+                          variant="auto", stream=None):
+    """iprodderiv_hex on affine elements in one kernel, the transpose of affine_physderiv_hex: with g_b = (je[e] qw2[k]
+    (qw1[j] qw0[i])) sum_a dfe[e][3 a + b] inp[a] per point, out[e][r][q][p] = sum_b (B^T D_b^T g_b)[e][r][q][p].  qw_d
+    the one-dimensional quadrature weights and je[e] = |det J| as in affine_helmholtz_hex, dfe as in affine_physderiv_hex
+    (required).  je=None: no weight at all, je and qw_d are never read (qw_d may then be None too) -- the exact transpose
+    of affine_physderiv_hex.  With je, bit for bit iprodderiv_hex on df planes filled with the constants and w = je *
+    (qw2 * (qw1 * qw0)).  inp, out and variants as iprodderiv_hex.  A plain function: no autograd."""
+    return _operator_call("affine_iprodderiv_hex",
+                          _affine_iprodderiv(nq, (deriv0, deriv1, deriv2), (qw0, qw1, qw2), dfe, je), nq,
+                          (basis0, basis1, basis2), inp, out, variant, stream)
+
+
+def affine_iprodderiv_quad(nq, basis0, basis1, deriv0, deriv1, qw0, qw1, dfe, je, inp, out=None, variant="auto",
+                           stream=None):
+    """iprodderiv_quad on affine elements: g_b = (je[e] qw1[j] qw0[i]) sum_a dfe[e][2 a + b] inp[a]; four constants per
+    element, je[e] or None (then qw_d are never read)."""
+    return _operator_call("affine_iprodderiv_quad", _affine_iprodderiv(nq, (deriv0, deriv1), (qw0, qw1), dfe, je), nq,
+                          (basis0, basis1), inp, out, variant, stream)
+
+
 def diag_tables(nq_d, basis, deriv, stream=None):
     """The three tables of one direction for diag_helmholtz_*: with E[p][i] = sum_m deriv[i][m] basis[p][m] (the
     derivative of mode p at point i), a flat tensor tab[t][p][i], t = 0, 1, 2, of basis * basis, E * basis and E * E: 3 nm nq
@@ -569,6 +622,41 @@ def physderiv_autograd(nq, bases, derivs, df, inp):
         raise ValueError("physderiv_autograd: the bases, the derivative matrices and df are constants; detach them (no "
                          "gradient flows to them)")
     return _PhysDeriv.apply(inp, nq, df, *bases, *derivs)
+
+
+class _AffinePhysDeriv(torch.autograd.Function):
+    """AUTO affine_physderiv_* forward; its input gradient is affine_iprodderiv_*(dfe, je=None, grad_out) (the exact
+    transpose)."""
+
+    @staticmethod
+    def forward(ctx, inp, nq, dfe, *mats):
+        ctx.nq, ctx.shape = nq, inp.shape
+        ctx.save_for_backward(*mats, dfe)
+        x = inp.contiguous()
+        return affine_physderiv_hex(nq, *mats, dfe, x) if len(nq) == 3 else affine_physderiv_quad(nq, *mats, dfe, x)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        saved = ctx.saved_tensors
+        mats, dfe, d = saved[:-1], saved[-1], len(ctx.nq)
+        g = grad_out if grad_out.shape[1] <= 1 or grad_out.stride(1) == 1 else grad_out.contiguous()
+        f = affine_iprodderiv_hex if d == 3 else affine_iprodderiv_quad
+        return (f(ctx.nq, *mats, *(None,) * d, dfe, None, g).reshape(ctx.shape), None, None) + (None,) * len(mats)
+
+
+def affine_physderiv_autograd(nq, bases, derivs, dfe, inp):
+    """affine_physderiv_* (AUTO) with a backward pass: the gradient with respect to `inp` is affine_iprodderiv_*(dfe,
+    je=None, grad_out), enqueued on the current stream.  The bases, the derivative matrices and dfe are constants: one
+    that requires grad is refused.  Returns the (d, n) output of affine_physderiv_*."""
+    nq, bases, derivs = tuple(int(x) for x in nq), tuple(bases), tuple(derivs)
+    if len(nq) not in (2, 3) or len(bases) != len(nq) or len(derivs) != len(nq):
+        raise ValueError("affine_physderiv_autograd: 2 or 3 extents, one basis and one derivative matrix per extent")
+    if not isinstance(dfe, torch.Tensor):
+        raise TypeError("affine_physderiv_autograd: dfe must be a tensor")
+    if any(t.requires_grad for t in bases + derivs + (dfe,)):
+        raise ValueError("affine_physderiv_autograd: the bases, the derivative matrices and dfe are constants; detach "
+                         "them (no gradient flows to them)")
+    return _AffinePhysDeriv.apply(inp, nq, dfe, *bases, *derivs)
 
 
 def _spec_args(nq, dtype):

@@ -55,13 +55,14 @@ for _sfx in ("f64", "f32"):     # the gather-scatter apply calls: count, index a
 
 
 def _operator_symbols():
-    """sf_<stem>_{hex,quad}_{f64,f64_variant,f32} of the eight operator families: [variant,] the extents, nelmt, the pointer
+    """sf_<stem>_{hex,quad}_{f64,f64_variant,f32} of the ten operator families: [variant,] the extents, nelmt, the pointer
     operands in front of `in` (so many per direction, so many per call), [lambda,] in (or one input per direction, or none:
     diag_helmholtz reads only its operands), [BwdTrans _variant: wsp,] out (or one output per direction), stream."""
     rows = {"bwdtrans": (1, 0, False, False, 1), "iproduct": (1, 0, False, False, 1),
             "mass": (1, 1, False, False, 1), "helmholtz": (2, 2, True, False, 1),
             "affine_helmholtz": (3, 2, True, False, 1), "physderiv": (2, 1, False, True, 1),
-            "iprodderiv": (2, 2, False, False, "per direction"), "diag_helmholtz": (1, 2, True, False, 0)}
+            "iprodderiv": (2, 2, False, False, "per direction"), "diag_helmholtz": (1, 2, True, False, 0),
+            "aff_physderiv": (2, 1, False, True, 1), "aff_iprodderiv": (3, 2, False, False, "per direction")}
     for stem, (per_direction, per_call, has_lambda, out_per_direction, inputs) in rows.items():
         for shape, dim in (("hex", 3), ("quad", 2)):
             ins = [_vp] * (dim if inputs == "per direction" else inputs)

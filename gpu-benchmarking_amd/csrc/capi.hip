@@ -1,12 +1,13 @@
 // capi.hip -- the extern "C" boundary of libsumfact.so (declared in include/sumfact.h).
 // Validation + dispatch only: every operator entry point forwards to one template <int DIM, typename T> function below
-// (bwdtrans, iprod, mass, helmholtz, affine, physderiv, iprodderiv, diag), which validates, builds ArgsT<DIM, T> and routes to the launchers that
+// (bwdtrans, iprod, mass, helmholtz, affine, physderiv, iprodderiv, affine_physderiv, affine_iprodderiv, diag), which validates, builds ArgsT<DIM, T> and routes to the launchers that
 // sf_dispatch.h declares.  Kernels live in bwdtrans_hex.hip / bwdtrans_quad.hip / bwdtrans_rt.hip /
 // bwdtrans_generic.hip / aux_kernels.hip, IProductWRTBase in iproduct.hip / iproduct_generic.hip, the fused mass
 // operator in mass.hip / mass_f32.hip / mass_generic.hip, the fused Helmholtz operator in helmholtz.hip /
 // helmholtz_f32.hip / helmholtz_generic.hip, its affine-element form in affine.hip / affine_f32.hip / affine_generic.hip,
 // BwdTrans fused with the physical-space gradient in physderiv.hip / physderiv_f32.hip / physderiv_generic.hip, its
-// transpose IProductWRTDerivBase in iprodderiv.hip / iprodderiv_f32.hip / iprodderiv_generic.hip, the diagonal of the
+// transpose IProductWRTDerivBase in iprodderiv.hip / iprodderiv_f32.hip / iprodderiv_generic.hip, the affine-element forms
+// of those two in affine_deriv.hip / affine_deriv_f32.hip / affine_deriv_generic.hip, the diagonal of the
 // Helmholtz operator in diag.hip / diag_f32.hip / diag_generic.hip, the gather-scatter between local coefficients and
 // global degrees of freedom in gs.hip.
 #include "sf_dispatch.h"
@@ -67,7 +68,7 @@ static ArgsT<DIM, T> make_args(const T *const (&b)[3], const T *in, T *wsp, T *o
         return {b[0], b[1], in, wsp, out, (uint64_t)nelmt};
 }
 
-// The shared tail of sf_iproduct_*, sf_mass_*, sf_helmholtz_*, sf_affine_helmholtz_*, sf_physderiv_* and sf_iprodderiv_*: AUTO takes the wave kernel for an isotropic order of
+// The shared tail of sf_iproduct_*, sf_mass_*, sf_helmholtz_*, sf_affine_helmholtz_*, sf_physderiv_*, sf_iprodderiv_* and their affine forms: AUTO takes the wave kernel for an isotropic order of
 // its table (`wave_built`) when in / out are 16-byte aligned, and the any-extent kernel otherwise.
 template <int DIM, class Wave, class Generic>
 static int route(int variant, const unsigned (&nq)[3], bool generic_built, bool wave_built, const void *in,
@@ -323,6 +324,76 @@ static int iprodderiv(int variant, const unsigned (&nq)[3], size_t nelmt, const 
         variant, nq, iprodderiv_generic_built(DIM, nq[0], nq[1], nq[2]), iprodderiv_wave_built(DIM, nq[0]), out, out,
         [&] { return launch_iprodderiv_wave<DIM, T>(nq[0], a, x, s); },
         [&] { return launch_iprodderiv_generic<DIM, T>(nq, a, x, s); });
+}
+
+// ---- the gradient on affine elements: one validation and routing for both dimensions and scalar types ------------------
+// The order of sf_physderiv_*, with the d*d constants per element dfe in the place of df; dfe is required.
+template <int DIM, typename T>
+static int affine_physderiv(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3],
+                            const T *const (&d)[3], const T *dfe, const T *in, T *const (&out)[3], void *stream)
+{
+    const int rc = validate(range_ok<DIM>(variant, nq), nelmt,
+                            {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], in, out[0], out[1],
+                             DIM == 3 ? out[2] : out[0], dfe},
+                            sizeof(T));
+    if (rc != kProceed)
+        return rc;
+    // an output may not overlap what the call reads per element or another output
+    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
+    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
+    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
+    uintptr_t out_bits        = 0; // 16-byte aligned exactly when every output is
+    for (int a = 0; a < DIM; ++a)
+    {
+        if (overlaps(out[a], points_bytes, in, modes_bytes) || overlaps(out[a], points_bytes, dfe, sizeof(T) * nelmt * DIM * DIM))
+            return SF_EINVAL;
+        for (int c = 0; c < a; ++c)
+            if (overlaps(out[a], points_bytes, out[c], points_bytes))
+                return SF_EINVAL;
+        out_bits |= (uintptr_t)out[a];
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    const auto a        = make_args<DIM, T>(b, in, nullptr, nullptr, nelmt);
+    const AffinePhysDerivArgsT<T> x{d[0], d[1], d[2], dfe, out[0], out[1], out[2]};
+    return route<DIM>(
+        variant, nq, affine_deriv_generic_built(DIM, nq[0], nq[1], nq[2]), affine_deriv_wave_built(DIM, nq[0]), in,
+        (const void *)out_bits, [&] { return launch_affine_physderiv_wave<DIM, T>(nq[0], a, x, s); },
+        [&] { return launch_affine_physderiv_generic<DIM, T>(nq, a, x, s); });
+}
+
+// ---- the weak divergence on affine elements: one validation and routing for both dimensions and scalar types -----------
+// The order of sf_iprodderiv_*, with dfe (required) in the place of df and the quadrature weights and je in the place of
+// w: `je` and every `qw` are looked at only when je is not null.  Only `out` is a 16-byte stream of the wave kernels.
+template <int DIM, typename T>
+static int affine_iprodderiv(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3],
+                             const T *const (&d)[3], const T *const (&qw)[3], const T *dfe, const T *je,
+                             const T *const (&in)[3], T *out, void *stream)
+{
+    const bool has_w = je != nullptr;
+    const int rc     = validate(range_ok<DIM>(variant, nq), nelmt,
+                                {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], in[0], in[1],
+                                 DIM == 3 ? in[2] : in[0], out, dfe, has_w ? qw[0] : dfe, has_w ? qw[1] : dfe,
+                                 has_w && DIM == 3 ? qw[2] : dfe, has_w ? je : dfe},
+                                sizeof(T));
+    if (rc != kProceed)
+        return rc;
+    // the output may not overlap what the call reads per element
+    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
+    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
+    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
+    for (int a = 0; a < DIM; ++a)
+        if (overlaps(out, modes_bytes, in[a], points_bytes))
+            return SF_EINVAL;
+    if (overlaps(out, modes_bytes, dfe, sizeof(T) * nelmt * DIM * DIM) || (has_w && overlaps(out, modes_bytes, je, sizeof(T) * nelmt)))
+        return SF_EINVAL;
+    const hipStream_t s = (hipStream_t)stream;
+    const auto a        = make_args<DIM, T>(b, nullptr, nullptr, out, nelmt);
+    const AffineIprodDerivArgsT<T> x{d[0],  d[1], d[2], has_w ? qw[0] : nullptr, has_w ? qw[1] : nullptr,
+                                     has_w ? qw[2] : nullptr, dfe, je, in[0], in[1], in[2]};
+    return route<DIM>(
+        variant, nq, affine_deriv_generic_built(DIM, nq[0], nq[1], nq[2]), affine_deriv_wave_built(DIM, nq[0]), out, out,
+        [&] { return launch_affine_iprodderiv_wave<DIM, T>(nq[0], a, x, s); },
+        [&] { return launch_affine_iprodderiv_generic<DIM, T>(nq, a, x, s); });
 }
 
 // ---- the diagonal of the fused Helmholtz operator: one validation and routing for both dimensions and scalar types ------
@@ -812,6 +883,120 @@ int sf_iprodderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float
 {
     return iprodderiv<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
                                 {deriv0, deriv1, nullptr}, df, w, {in0, in1, nullptr}, out, stream);
+}
+
+// ---- the gradient on affine elements: d*d constants per element in the place of the planes --------------------------------
+int sf_aff_physderiv_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                                        const double *basis0, const double *basis1, const double *basis2,
+                                        const double *deriv0, const double *deriv1, const double *deriv2,
+                                        const double *dfe, const double *in, double *out0, double *out1, double *out2,
+                                        void *stream)
+{
+    return affine_physderiv<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
+                                       dfe, in, {out0, out1, out2}, stream);
+}
+
+int sf_aff_physderiv_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
+                                const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
+                                const double *deriv2, const double *dfe, const double *in, double *out0, double *out1,
+                                double *out2, void *stream)
+{
+    return affine_physderiv<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
+                                       {deriv0, deriv1, deriv2}, dfe, in, {out0, out1, out2}, stream);
+}
+
+int sf_aff_physderiv_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                                         const double *basis1, const double *deriv0, const double *deriv1,
+                                         const double *dfe, const double *in, double *out0, double *out1, void *stream)
+{
+    return affine_physderiv<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
+                                       dfe, in, {out0, out1, nullptr}, stream);
+}
+
+int sf_aff_physderiv_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                                 const double *deriv0, const double *deriv1, const double *dfe, const double *in,
+                                 double *out0, double *out1, void *stream)
+{
+    return affine_physderiv<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
+                                       {deriv0, deriv1, nullptr}, dfe, in, {out0, out1, nullptr}, stream);
+}
+
+int sf_aff_physderiv_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
+                                const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
+                                const float *deriv2, const float *dfe, const float *in, float *out0, float *out1,
+                                float *out2, void *stream)
+{
+    return affine_physderiv<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
+                                      {deriv0, deriv1, deriv2}, dfe, in, {out0, out1, out2}, stream);
+}
+
+int sf_aff_physderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
+                                 const float *deriv0, const float *deriv1, const float *dfe, const float *in, float *out0,
+                                 float *out1, void *stream)
+{
+    return affine_physderiv<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
+                                      {deriv0, deriv1, nullptr}, dfe, in, {out0, out1, nullptr}, stream);
+}
+
+// ---- the weak divergence on affine elements: the transpose of the gradient above, weighted by je (x) qw -------------------
+int sf_aff_iprodderiv_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                                         const double *basis0, const double *basis1, const double *basis2,
+                                         const double *deriv0, const double *deriv1, const double *deriv2,
+                                         const double *qw0, const double *qw1, const double *qw2, const double *dfe,
+                                         const double *je, const double *in0, const double *in1, const double *in2,
+                                         double *out, void *stream)
+{
+    return affine_iprodderiv<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
+                                        {qw0, qw1, qw2}, dfe, je, {in0, in1, in2}, out, stream);
+}
+
+int sf_aff_iprodderiv_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
+                                 const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
+                                 const double *deriv2, const double *qw0, const double *qw1, const double *qw2,
+                                 const double *dfe, const double *je, const double *in0, const double *in1,
+                                 const double *in2, double *out, void *stream)
+{
+    return affine_iprodderiv<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
+                                        {deriv0, deriv1, deriv2}, {qw0, qw1, qw2}, dfe, je, {in0, in1, in2}, out, stream);
+}
+
+int sf_aff_iprodderiv_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                                          const double *basis1, const double *deriv0, const double *deriv1,
+                                          const double *qw0, const double *qw1, const double *dfe, const double *je,
+                                          const double *in0, const double *in1, double *out, void *stream)
+{
+    return affine_iprodderiv<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
+                                        {qw0, qw1, nullptr}, dfe, je, {in0, in1, nullptr}, out, stream);
+}
+
+int sf_aff_iprodderiv_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                                  const double *deriv0, const double *deriv1, const double *qw0, const double *qw1,
+                                  const double *dfe, const double *je, const double *in0, const double *in1, double *out,
+                                  void *stream)
+{
+    return affine_iprodderiv<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
+                                        {deriv0, deriv1, nullptr}, {qw0, qw1, nullptr}, dfe, je, {in0, in1, nullptr}, out,
+                                        stream);
+}
+
+int sf_aff_iprodderiv_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
+                                 const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
+                                 const float *deriv2, const float *qw0, const float *qw1, const float *qw2,
+                                 const float *dfe, const float *je, const float *in0, const float *in1, const float *in2,
+                                 float *out, void *stream)
+{
+    return affine_iprodderiv<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
+                                       {deriv0, deriv1, deriv2}, {qw0, qw1, qw2}, dfe, je, {in0, in1, in2}, out, stream);
+}
+
+int sf_aff_iprodderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
+                                  const float *deriv0, const float *deriv1, const float *qw0, const float *qw1,
+                                  const float *dfe, const float *je, const float *in0, const float *in1, float *out,
+                                  void *stream)
+{
+    return affine_iprodderiv<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
+                                       {deriv0, deriv1, nullptr}, {qw0, qw1, nullptr}, dfe, je, {in0, in1, nullptr}, out,
+                                       stream);
 }
 
 // ---- the diagonal of the fused Helmholtz operator: Jacobi preconditioner, Chebyshev smoother, diagonal scaling ----------

@@ -160,6 +160,34 @@ template <int DIM, typename T>
 int launch_iprodderiv_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const IprodDerivArgsT<T> &x, hipStream_t s);
 bool iprodderiv_wave_built(int dim, unsigned nq);
 bool iprodderiv_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
+// The gradient and the weak divergence on affine elements, df_ab = dfe[e][a*d + b] at every point and w_e = je[e] (x) qw
+// (affine_deriv.hip / affine_deriv_f32.hip: the wave kernels of affine_deriv_wave.h, the Helmholtz table;
+// affine_deriv_generic.hip: any extents up to 12 per direction in 3D and 32 in 2D).  The gradient takes what
+// sf_physderiv_* takes with the d*d constants of every element in the place of the planes (required); the weak divergence
+// what sf_iprodderiv_* takes with dfe, the one-dimensional quadrature weights and je (null: no weight, je and qw_d never
+// read).  One pair of `built` answers serves both operators.
+template <typename T> struct AffinePhysDerivArgsT
+{
+    const T *d0, *d1, *d2, *dfe;
+    T *out0, *out1, *out2;
+};
+template <typename T> struct AffineIprodDerivArgsT
+{
+    const T *d0, *d1, *d2, *qw0, *qw1, *qw2, *dfe, *je;
+    const T *in0, *in1, *in2;
+};
+template <int DIM, typename T>
+int launch_affine_physderiv_wave(unsigned nq, const ArgsT<DIM, T> &a, const AffinePhysDerivArgsT<T> &x, hipStream_t s);
+template <int DIM, typename T>
+int launch_affine_physderiv_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const AffinePhysDerivArgsT<T> &x,
+                                    hipStream_t s);
+template <int DIM, typename T>
+int launch_affine_iprodderiv_wave(unsigned nq, const ArgsT<DIM, T> &a, const AffineIprodDerivArgsT<T> &x, hipStream_t s);
+template <int DIM, typename T>
+int launch_affine_iprodderiv_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const AffineIprodDerivArgsT<T> &x,
+                                     hipStream_t s);
+bool affine_deriv_wave_built(int dim, unsigned nq);
+bool affine_deriv_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
 // The diagonal of the fused Helmholtz operator, diag(B^T [lambda diag(w) + sum_ab D_a^T diag(G_ab) D_b] B) (diag.hip /
 // diag_f32.hip: the wave kernels of diag_wave.h, the Helmholtz table; diag_generic.hip: any extents up to 12 per direction
 // in 3D and 32 in 2D, and the kernel that forms the tables).  There is no input array: b0 .. b2 of the BwdTrans arguments

@@ -581,6 +581,126 @@ int sf_iprodderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float
                            const float *in0, const float *in1, float *out, void *stream);
 
 /*
+ * sf_physderiv_* on AFFINE elements (parallelepipeds, parallelograms: a constant Jacobian per element): sf_aff_physderiv_*
+ * (the prefix sf_affine_ names the Helmholtz family of sf_affine_helmholtz_* alone; these two families take sf_aff_).
+ *   u = B x_e,   du_b = D_b u,   out_a[e][k][j][i] = sum_b dfe[e][a*d + b] * du_b[e][k][j][i],   a = 0 .. d-1
+ * The inverse Jacobian is d*d constants per element where sf_physderiv_* streams d*d planes: per element the call moves
+ * nm^d + d nq^d + d*d scalars, and the caller stores d*d scalars per element where it stored d*d nq^d.
+ * Layout: basis_d, deriv_d, `in` and out_a exactly as in sf_physderiv_*.  dfe[e][c]: d*d scalars per element, component
+ * order c = a*d + b for d xi_b / d x_a -- the order of the planes of df; NOT symmetric.  dfe is required: the
+ * reference-space derivatives are sf_physderiv_* with df == NULL.
+ * Summation order: steps 1-3 of sf_physderiv_* with df_ab replaced by the element's constant (b ascending, the first
+ * product a multiply, then FMAs).  On a route the result is therefore BIT FOR BIT that of sf_physderiv_* on the same
+ * route with planes filled with the constants, in fp64 and in fp32.
+ * Routes, as sf_physderiv_*: SF_VARIANT_AUTO runs the fused wave kernel for the isotropic orders of its table (3D nq
+ * 2..8, 2D nq 2..16) when `in` and every out_a are 16-byte aligned, else GENERIC; SF_VARIANT_WAVE returns SF_ENOTBUILT
+ * off that table and SF_EALIGN unless `in` and every out_a are 16-byte aligned; SF_VARIANT_GENERIC (one workgroup per
+ * element, latency-bound) takes any extents up to 12 per direction in 3D and 32 in 2D -- 3D nq 9..11 and all
+ * anisotropic shapes take it; any other variant SF_ENOTBUILT, extents beyond those bounds SF_ENOTBUILT.  dfe, the bases
+ * and the derivative matrices need only scalar alignment on every route.
+ * Validation, before any HIP call, in this order: (1) an extent < 2 or a variant outside [0, SF_NUM_VARIANTS):
+ * SF_EINVAL; (2) nelmt == 0: SF_OK; (3) a null basis, deriv, dfe, in or out_a: SF_EINVAL; (4) any of them not
+ * scalar-aligned: SF_EALIGN; (5) any out_a overlapping `in`, `dfe` or another out_b, compared as byte ranges of their
+ * full sizes: SF_EINVAL; (6) extents beyond the fallback's bounds: SF_ENOTBUILT; (7) an unsupported variant:
+ * SF_ENOTBUILT.
+ * NOT in-place safe: an output that overlaps an input or another output is refused, not undefined; the inputs may overlap
+ * each other (all are only read).
+ * No internal workspace and no allocation: every call is a single kernel node, capture-safe from the process's first
+ * call.
+ */
+int sf_aff_physderiv_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                                const double *basis0, const double *basis1, const double *basis2,
+                                const double *deriv0, const double *deriv1, const double *deriv2,
+                                const double *dfe, const double *in,
+                                double *out0, double *out1, double *out2, void *stream);
+int sf_aff_physderiv_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                                        const double *basis0, const double *basis1, const double *basis2,
+                                        const double *deriv0, const double *deriv1, const double *deriv2,
+                                        const double *dfe, const double *in,
+                                        double *out0, double *out1, double *out2, void *stream);
+int sf_aff_physderiv_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                                 const double *basis1, const double *deriv0, const double *deriv1,
+                                 const double *dfe, const double *in, double *out0, double *out1, void *stream);
+int sf_aff_physderiv_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt,
+                                         const double *basis0, const double *basis1, const double *deriv0,
+                                         const double *deriv1, const double *dfe, const double *in,
+                                         double *out0, double *out1, void *stream);
+/* T = float (AUTO route; every array 4-byte aligned) */
+int sf_aff_physderiv_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
+                                const float *basis1, const float *basis2, const float *deriv0,
+                                const float *deriv1, const float *deriv2, const float *dfe, const float *in,
+                                float *out0, float *out1, float *out2, void *stream);
+int sf_aff_physderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0,
+                                 const float *basis1, const float *deriv0, const float *deriv1,
+                                 const float *dfe, const float *in, float *out0, float *out1, void *stream);
+
+/*
+ * sf_iprodderiv_* on AFFINE elements, the weak divergence with a constant Jacobian per element and the exact transpose
+ * of sf_aff_physderiv_*.  With f_a = in_a[e][k][j][i], a = 0 .. d-1:
+ *   t_b = sum_a dfe[e][a*d + b] * f_a                                   (per point; b = 0 .. d-1, a ascending)
+ *   q   = qw2[k] * (qw1[j] * qw0[i])                                    (2D: qw1[j] * qw0[i])
+ *   g_b = (je[e] * q) * t_b
+ *   out[e][r][q][p] = sum_b (B^T D_b^T g_b)[e][r][q][p]
+ * Per element the call moves d nq^d + nm^d + d*d + 1 scalars where sf_iprodderiv_* moves (d*d + d + 1) nq^d + nm^d.
+ * Layout: basis_d, deriv_d, in_a and out exactly as in sf_iprodderiv_*.  qw_d: the nq_d one-dimensional quadrature
+ * weights of direction d, as in sf_affine_helmholtz_*.  dfe[e][c]: the d*d constants of sf_aff_physderiv_*, the
+ * same array in the same order c = a*d + b; the sum here runs over the ROW index a.  je[e]: one scalar per element
+ * (|det J_e|), as in sf_affine_helmholtz_*.  dfe is required.
+ * If je is NULL no weight is applied at all: je and every qw_d are then never read (nor validated), and the call is bit
+ * for bit the algebraic transpose of sf_aff_physderiv_* on the same dfe.  With je given, the result is BIT FOR BIT
+ * that of sf_iprodderiv_* on the same route with df planes filled with the constants and the weight plane expanded in
+ * the working precision with exactly the association above, w = je * (qw2 * (qw1 * qw0)).
+ * Summation order: steps 1-4 of sf_iprodderiv_* with df_ab replaced by the element's constant and w by (je_e q).
+ * Routes, as sf_iprodderiv_*: SF_VARIANT_AUTO runs the fused wave kernel for the isotropic orders of its table (3D nq
+ * 2..8, 2D nq 2..16) when `out` is 16-byte aligned, else GENERIC; SF_VARIANT_WAVE returns SF_ENOTBUILT off that table and
+ * SF_EALIGN unless `out` is 16-byte aligned; SF_VARIANT_GENERIC (one workgroup per element, latency-bound) takes any
+ * extents up to 12 per direction in 3D and 32 in 2D -- 3D nq 9..11 and all anisotropic shapes take it; any other variant
+ * SF_ENOTBUILT, extents beyond those bounds SF_ENOTBUILT.  Only `out` needs 16-byte alignment for the wave route; every
+ * in_a, dfe, je, qw_d, the bases and the derivative matrices need only scalar alignment on every route.
+ * Validation, before any HIP call, in this order: (1) an extent < 2 or a variant outside [0, SF_NUM_VARIANTS):
+ * SF_EINVAL; (2) nelmt == 0: SF_OK; (3) a null basis, deriv, dfe, in_a or out, or -- only when je is not null -- a null
+ * qw_d: SF_EINVAL; (4) any of them (je, qw_d only when je is not null) not scalar-aligned: SF_EALIGN; (5) `out`
+ * overlapping any in_a, `dfe` or `je`, compared as byte ranges of their full sizes: SF_EINVAL; (6) extents beyond the
+ * fallback's bounds: SF_ENOTBUILT; (7) an unsupported variant: SF_ENOTBUILT.
+ * NOT in-place safe: an output that overlaps an input is refused, not undefined; the inputs may overlap each other (all
+ * are only read).
+ * No internal workspace and no allocation: every call is a single kernel node, capture-safe from the process's first
+ * call.
+ */
+int sf_aff_iprodderiv_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                                 const double *basis0, const double *basis1, const double *basis2,
+                                 const double *deriv0, const double *deriv1, const double *deriv2,
+                                 const double *qw0, const double *qw1, const double *qw2,
+                                 const double *dfe, const double *je,
+                                 const double *in0, const double *in1, const double *in2, double *out, void *stream);
+int sf_aff_iprodderiv_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                                         const double *basis0, const double *basis1, const double *basis2,
+                                         const double *deriv0, const double *deriv1, const double *deriv2,
+                                         const double *qw0, const double *qw1, const double *qw2,
+                                         const double *dfe, const double *je,
+                                         const double *in0, const double *in1, const double *in2, double *out,
+                                         void *stream);
+int sf_aff_iprodderiv_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                                  const double *basis1, const double *deriv0, const double *deriv1,
+                                  const double *qw0, const double *qw1, const double *dfe, const double *je,
+                                  const double *in0, const double *in1, double *out, void *stream);
+int sf_aff_iprodderiv_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt,
+                                          const double *basis0, const double *basis1, const double *deriv0,
+                                          const double *deriv1, const double *qw0, const double *qw1,
+                                          const double *dfe, const double *je, const double *in0,
+                                          const double *in1, double *out, void *stream);
+/* T = float (AUTO route; every array 4-byte aligned) */
+int sf_aff_iprodderiv_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
+                                 const float *basis1, const float *basis2, const float *deriv0,
+                                 const float *deriv1, const float *deriv2, const float *qw0, const float *qw1,
+                                 const float *qw2, const float *dfe, const float *je, const float *in0,
+                                 const float *in1, const float *in2, float *out, void *stream);
+int sf_aff_iprodderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0,
+                                  const float *basis1, const float *deriv0, const float *deriv1,
+                                  const float *qw0, const float *qw1, const float *dfe, const float *je,
+                                  const float *in0, const float *in1, float *out, void *stream);
+
+/*
  * The DIAGONAL of the fused Helmholtz operator of sf_helmholtz_*, per element:
  *   diag_e = diag( B^T [ lambda diag(w_e) + sum_a sum_b D_a^T diag(G_ab,e) D_b ] B )
  * what a Jacobi preconditioner, a Chebyshev smoother or a diagonal scaling of a matrix-free Poisson / Helmholtz /
