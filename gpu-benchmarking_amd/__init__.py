@@ -25,4 +25,5 @@ from .bwdtrans import (  # noqa: F401
     affine_physderiv_autograd,
     diag_tables, diag_helmholtz_hex, diag_helmholtz_quad,
     GsMap, gs_setup, global_to_local, assemble, gs,
+    geom_hex, geom_quad, geom_affine_hex, geom_affine_quad, GEOM_OUTPUTS,
 )

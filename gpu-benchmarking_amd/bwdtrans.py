@@ -475,6 +475,116 @@ def diag_helmholtz_quad(nq, basis0, basis1, deriv0, deriv1, g, w, lam, out=None,
     return _diag("diag_helmholtz_quad", nq, (basis0, basis1), (deriv0, deriv1), g, w, lam, out, variant, stream, tabs)
 
 
+GEOM_OUTPUTS = ("df", "w", "g", "detj")
+
+
+def _geom_call(what, nq, bases, derivs, qws, x, names, per, out, variant, stream):
+    """The one call path of geom_* and geom_affine_*: sizes, dtypes and devices are checked here (before any library
+    call), pointers, alignment and overlap in the C ABI.  names: the outputs asked for, a subset of the keys of `per`
+    (name -> scalars per element, in the order of the C signature); out: None or a dict name -> flat tensor (a name that
+    is asked for and missing is allocated); variant None: the call has none (the affine form).  Returns the dict of the
+    outputs asked for."""
+    nq = tuple(int(q) for q in nq)
+    d = len(nq)
+    xs = _input_parts(what, x, d)
+    inp = xs[0]
+    nmt = 1
+    for q in nq:
+        nmt *= q - 1
+    if nmt <= 0:
+        raise capi.SumfactError(capi.SF_EINVAL, what)
+    nelmt = inp.numel() // nmt
+    if nelmt * nmt != inp.numel():
+        raise ValueError(f"{what}: x_a.numel() is not a multiple of the modes per element ({nmt})")
+    names = tuple(names)
+    for name in names:
+        if name not in per:
+            raise ValueError(f"{what}: unknown output {name!r}; the outputs are {tuple(per)}")
+    if not names:
+        raise capi.SumfactError(capi.SF_EINVAL, what)
+    outs = dict(out or {})
+    for name in outs:
+        if name not in names:
+            raise ValueError(f"{what}: out holds {name!r}, which is not asked for")
+    for name in names:
+        if outs.get(name) is None:
+            outs[name] = torch.empty(nelmt * per[name], dtype=inp.dtype, device=inp.device)
+    need_q = qws is not None and any(n in names for n in ("w", "g"))
+    operands = [(f"basis{a}", b, (q - 1) * q, False) for a, (b, q) in enumerate(zip(bases, nq))]
+    operands += _per_direction("deriv", derivs, lambda q: q * q, nq)
+    if qws is not None:
+        operands += [(f"qw{a}", t if need_q else None, int(q), not need_q) for a, (t, q) in enumerate(zip(qws, nq))]
+    _check_operands(what, operands + [(name, outs[name], nelmt * per[name], False) for name in names], inp)
+    f32 = inp.dtype == torch.float32
+    dtype = torch.float32 if f32 else torch.float64
+    head = ()
+    if variant is None:
+        fn = getattr(capi.lib(), f"sf_{what}_{'f32' if f32 else 'f64'}")
+    else:
+        v = _variant(variant)
+        if f32 and v != VARIANTS["auto"]:
+            raise ValueError(f"{what}: float32 has the AUTO route only")
+        fn = getattr(capi.lib(), f"sf_{what}_{'f32' if f32 else 'f64_variant'}")
+        head = () if f32 else (v,)
+    ptrs = [None if t is None else _dev_ptr(t, name, dtype) for name, t, _, _ in operands]
+    ptrs += [_dev_ptr(t, f"x{a}", dtype) for a, t in enumerate(xs)]
+    ptrs += [_dev_ptr(outs[name], name, dtype) if name in names else None for name in per]
+    with torch.cuda.device(inp.device):
+        rc = fn(*head, *nq, nelmt, *ptrs, _stream(stream, inp.device))
+    capi.check(rc, what)
+    return {name: outs[name] for name in names}
+
+
+def _geom(what, nq, bases, derivs, qws, x, outputs, out, variant, stream):
+    d = len(nq)
+    nqt = 1
+    for q in nq:
+        nqt *= int(q)
+    per = {"df": d * d * nqt, "w": nqt, "g": d * (d + 1) // 2 * nqt, "detj": nqt}
+    return _geom_call(what, nq, bases, derivs, qws, x, outputs, per, out, variant, stream)
+
+
+def geom_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, qw0, qw1, qw2, x, outputs=GEOM_OUTPUTS, out=None,
+             variant="auto", stream=None):
+    """The geometric factors of isoparametric hexahedra from their modal coordinates, in one kernel on x's device.  x: a
+    (3, nelmt * nm0*nm1*nm2) tensor with contiguous rows or a sequence of three flat tensors, coordinate a of every element
+    in the layout of bwdtrans_hex's input, expanded in the bases of bwdtrans_hex; deriv_d as in helmholtz_hex; qw_d the
+    one-dimensional quadrature weights (looked at only when "w" or "g" is asked for; may be None otherwise).  Returns a
+    dict of flat tensors with the keys of `outputs`: "df" (nine planes per element, c = 3 a + b for d xi_b / d x_a: what
+    physderiv_hex / iprodderiv_hex take), "w" (|det J| qw2[k] qw1[j] qw0[i]) and "g" (six planes, 00 01 02 11 12 22: what
+    helmholtz_hex / diag_helmholtz_hex take), "detj" (the signed determinant).  out: a dict name -> flat tensor for the
+    outputs the caller owns.  No output may overlap x or another output.  float64 takes variant "auto", "wave" or
+    "generic"; float32 the AUTO route.  A plain function: no autograd."""
+    return _geom("geom_hex", nq, (basis0, basis1, basis2), (deriv0, deriv1, deriv2), (qw0, qw1, qw2), x, outputs, out,
+                 variant, stream)
+
+
+def geom_quad(nq, basis0, basis1, deriv0, deriv1, qw0, qw1, x, outputs=GEOM_OUTPUTS, out=None, variant="auto", stream=None):
+    """The geometric factors of isoparametric quadrilaterals: x holds two coordinates, "df" four planes (c = 2 a + b), "g"
+    three (00 01 11), w = |det J| qw1[j] qw0[i]."""
+    return _geom("geom_quad", nq, (basis0, basis1), (deriv0, deriv1), (qw0, qw1), x, outputs, out, variant, stream)
+
+
+def _geom_affine(what, nq, bases, derivs, x, stream):
+    d = len(nq)
+    per = {"dfe": d * d, "ge": d * (d + 1) // 2, "je": 1}
+    got = _geom_call(what, nq, bases, derivs, None, x, tuple(per), per, None, None, stream)
+    return got["dfe"], got["ge"], got["je"]
+
+
+def geom_affine_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, x, stream=None):
+    """geom_hex for elements known to be affine: the same formulas at the point (0, 0, 0) of every element.  Returns
+    (dfe, ge, je), the per-element constants of affine_physderiv_hex / affine_iprodderiv_hex (dfe[e][3 a + b]) and of
+    affine_helmholtz_hex (ge[e][c] = je sum_x dfe dfe, je[e] = |det J|); dfe and je equal point 0 of geom_hex bit for bit.
+    Any extents the "generic" route of geom_hex takes; float64 and float32.  A plain function: no autograd."""
+    return _geom_affine("geom_affine_hex", nq, (basis0, basis1, basis2), (deriv0, deriv1, deriv2), x, stream)
+
+
+def geom_affine_quad(nq, basis0, basis1, deriv0, deriv1, x, stream=None):
+    """geom_affine_hex in 2D: dfe[e][2 a + b], ge[e][c] with c = 0..2 for (00, 01, 11), je[e]."""
+    return _geom_affine("geom_affine_quad", nq, (basis0, basis1), (deriv0, deriv1), x, stream)
+
+
 class GsMap:
     """What gs_setup returns: the local-to-global map `l2g` (int32, nlocal entries) and its inverted index `rows` (nglobal
     words) / `perm` (nlocal words), all on one device.  rows / perm are opaque: only the library reads them."""

@@ -76,6 +76,21 @@ def _operator_symbols():
 
 SYMBOLS.update(_operator_symbols())
 
+
+def _geom_symbols():
+    """sf_geom_{hex,quad}_{f64,f64_variant,f32}: [variant,] the extents, nelmt, basis / deriv / qw per direction, x_a per
+    direction, df, w, g, detj, stream; sf_geom_affine_{hex,quad}_{f64,f32}: the same without variant and qw, with dfe, ge,
+    je."""
+    for shape, dim in (("hex", 3), ("quad", 2)):
+        for sfx in ("f64", "f64_variant", "f32"):
+            head = [_i] if sfx == "f64_variant" else []
+            yield f"sf_geom_{shape}_{sfx}", (_i, head + [_u] * dim + [_sz] + [_vp] * (4 * dim + 4) + [_vp])
+        for sfx in ("f64", "f32"):
+            yield f"sf_geom_affine_{shape}_{sfx}", (_i, [_u] * dim + [_sz] + [_vp] * (3 * dim + 3) + [_vp])
+
+
+SYMBOLS.update(_geom_symbols())
+
 _lib = None
 
 

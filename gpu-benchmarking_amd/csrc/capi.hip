@@ -9,7 +9,9 @@
 // transpose IProductWRTDerivBase in iprodderiv.hip / iprodderiv_f32.hip / iprodderiv_generic.hip, the affine-element forms
 // of those two in affine_deriv.hip / affine_deriv_f32.hip / affine_deriv_generic.hip, the diagonal of the
 // Helmholtz operator in diag.hip / diag_f32.hip / diag_generic.hip, the gather-scatter between local coefficients and
-// global degrees of freedom in gs.hip.
+// global degrees of freedom in gs.hip, the geometric factors from element coordinates (geom, geom_affine below; their
+// launchers are declared in geom_args.h) in geom.hip / geom_f32.hip / geom_generic.hip.
+#include "geom_args.h"
 #include "sf_dispatch.h"
 
 #include <cstdio>
@@ -439,6 +441,90 @@ template <typename T> static int diag_tables(unsigned nq, const T *basis, const 
     if (overlaps(tab, 3 * nb, basis, nb) || overlaps(tab, 3 * nb, deriv, sizeof(T) * nq * nq))
         return SF_EINVAL;
     return launch_diag_tables<T>(nq, basis, deriv, tab, (hipStream_t)stream);
+}
+
+// ---- the geometric factors from element coordinates: one validation and routing for both dimensions and scalar types ----
+// The order of sf_physderiv_*, with DIM coordinate streams of modes in the place of `in` and four outputs, each looked at
+// only when it is not null (all four null: refused with the nulls); the quadrature weights are looked at only when w or
+// g is asked for.  Every x_a and every output that is asked for is a 16-byte stream of the wave kernels.
+template <int DIM, typename T>
+static int geom(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *const (&d)[3],
+                const T *const (&qw)[3], const T *const (&x)[3], T *df, T *w, T *g, T *detj, void *stream)
+{
+    const bool has_q = w || g;
+    const T *some    = df ? df : (w ? w : (g ? g : detj)); // an output that is asked for, null if none is
+    const int rc     = validate(range_ok<DIM>(variant, nq), nelmt,
+                                {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], x[0], x[1],
+                                 DIM == 3 ? x[2] : x[0], some, has_q ? qw[0] : x[0], has_q ? qw[1] : x[0],
+                                 has_q && DIM == 3 ? qw[2] : x[0], df ? df : some, w ? w : some, g ? g : some,
+                                 detj ? detj : some},
+                                sizeof(T));
+    if (rc != kProceed)
+        return rc;
+    // an output may not overlap a coordinate stream or another output
+    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
+    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
+    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
+    const T *const out[4]     = {df, w, g, detj};
+    const size_t out_bytes[4] = {DIM * DIM * points_bytes, points_bytes, DIM * (DIM + 1) / 2 * points_bytes, points_bytes};
+    uintptr_t in_bits = 0, out_bits = 0; // 16-byte aligned exactly when every stream is
+    for (int a = 0; a < DIM; ++a)
+        in_bits |= (uintptr_t)x[a];
+    for (int o = 0; o < 4; ++o)
+    {
+        if (!out[o])
+            continue;
+        for (int a = 0; a < DIM; ++a)
+            if (overlaps(out[o], out_bytes[o], x[a], modes_bytes))
+                return SF_EINVAL;
+        for (int p = 0; p < o; ++p)
+            if (out[p] && overlaps(out[o], out_bytes[o], out[p], out_bytes[p]))
+                return SF_EINVAL;
+        out_bits |= (uintptr_t)out[o];
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    const auto a        = make_args<DIM, T>(b, nullptr, nullptr, nullptr, nelmt);
+    const GeomArgsT<T> ga{d[0], d[1], d[2], has_q ? qw[0] : nullptr, has_q ? qw[1] : nullptr, has_q ? qw[2] : nullptr,
+                          x[0], x[1], x[2], df, w, g, detj};
+    return route<DIM>(
+        variant, nq, geom_generic_built(DIM, nq[0], nq[1], nq[2]), geom_wave_built(DIM, nq[0]), (const void *)in_bits,
+        (const void *)out_bits, [&] { return launch_geom_wave<DIM, T>(nq[0], a, ga, s); },
+        [&] { return launch_geom_generic<DIM, T>(nq, a, ga, s); });
+}
+
+// The affine form: the order of sf_geom_* without a variant and without quadrature weights; one small kernel for any
+// extents the fallback takes.
+template <int DIM, typename T>
+static int geom_affine(const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *const (&d)[3],
+                       const T *const (&x)[3], T *dfe, T *ge, T *je, void *stream)
+{
+    const T *some = dfe ? dfe : (ge ? ge : je);
+    const int rc  = validate(range_ok<DIM>(SF_VARIANT_AUTO, nq), nelmt,
+                             {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], x[0], x[1],
+                              DIM == 3 ? x[2] : x[0], some, dfe ? dfe : some, ge ? ge : some, je ? je : some},
+                             sizeof(T));
+    if (rc != kProceed)
+        return rc;
+    const size_t mz           = DIM == 3 ? nq[2] - 1 : 1;
+    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
+    const T *const out[3]     = {dfe, ge, je};
+    const size_t out_bytes[3] = {sizeof(T) * nelmt * DIM * DIM, sizeof(T) * nelmt * (DIM * (DIM + 1) / 2), sizeof(T) * nelmt};
+    for (int o = 0; o < 3; ++o)
+    {
+        if (!out[o])
+            continue;
+        for (int a = 0; a < DIM; ++a)
+            if (overlaps(out[o], out_bytes[o], x[a], modes_bytes))
+                return SF_EINVAL;
+        for (int p = 0; p < o; ++p)
+            if (out[p] && overlaps(out[o], out_bytes[o], out[p], out_bytes[p]))
+                return SF_EINVAL;
+    }
+    if (!geom_generic_built(DIM, nq[0], nq[1], nq[2]))
+        return SF_ENOTBUILT;
+    const auto a = make_args<DIM, T>(b, nullptr, nullptr, nullptr, nelmt);
+    const GeomArgsT<T> ga{d[0], d[1], d[2], nullptr, nullptr, nullptr, x[0], x[1], x[2], dfe, je, ge, nullptr};
+    return launch_geom_affine<DIM, T>(nq, a, ga, (hipStream_t)stream);
 }
 
 // ---- gather-scatter: the checks of the four calls, in the order include/sumfact.h documents --------------------------
@@ -1047,6 +1133,93 @@ int sf_diag_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const f
                                const float *g, const float *w, double lambda, float *out, void *stream)
 {
     return diag<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {tab0, tab1, nullptr}, g, w, lambda, out, stream);
+}
+
+// ---- the geometric factors df, w, g, detj from the modal coordinates of every element -----------------------------------
+int sf_geom_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
+                            const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
+                            const double *deriv2, const double *qw0, const double *qw1, const double *qw2, const double *x0,
+                            const double *x1, const double *x2, double *df, double *w, double *g, double *detj, void *stream)
+{
+    return geom<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
+                           {qw0, qw1, qw2}, {x0, x1, x2}, df, w, g, detj, stream);
+}
+
+int sf_geom_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0, const double *basis1,
+                    const double *basis2, const double *deriv0, const double *deriv1, const double *deriv2,
+                    const double *qw0, const double *qw1, const double *qw2, const double *x0, const double *x1,
+                    const double *x2, double *df, double *w, double *g, double *detj, void *stream)
+{
+    return geom<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
+                           {qw0, qw1, qw2}, {x0, x1, x2}, df, w, g, detj, stream);
+}
+
+int sf_geom_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                             const double *basis1, const double *deriv0, const double *deriv1, const double *qw0,
+                             const double *qw1, const double *x0, const double *x1, double *df, double *w, double *g,
+                             double *detj, void *stream)
+{
+    return geom<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
+                           {qw0, qw1, nullptr}, {x0, x1, nullptr}, df, w, g, detj, stream);
+}
+
+int sf_geom_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                     const double *deriv0, const double *deriv1, const double *qw0, const double *qw1, const double *x0,
+                     const double *x1, double *df, double *w, double *g, double *detj, void *stream)
+{
+    return geom<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
+                           {qw0, qw1, nullptr}, {x0, x1, nullptr}, df, w, g, detj, stream);
+}
+
+int sf_geom_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
+                    const float *basis2, const float *deriv0, const float *deriv1, const float *deriv2, const float *qw0,
+                    const float *qw1, const float *qw2, const float *x0, const float *x1, const float *x2, float *df,
+                    float *w, float *g, float *detj, void *stream)
+{
+    return geom<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
+                          {qw0, qw1, qw2}, {x0, x1, x2}, df, w, g, detj, stream);
+}
+
+int sf_geom_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
+                     const float *deriv0, const float *deriv1, const float *qw0, const float *qw1, const float *x0,
+                     const float *x1, float *df, float *w, float *g, float *detj, void *stream)
+{
+    return geom<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
+                          {qw0, qw1, nullptr}, {x0, x1, nullptr}, df, w, g, detj, stream);
+}
+
+int sf_geom_affine_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
+                           const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
+                           const double *deriv2, const double *x0, const double *x1, const double *x2, double *dfe,
+                           double *ge, double *je, void *stream)
+{
+    return geom_affine<3, double>({nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2}, {x0, x1, x2},
+                                  dfe, ge, je, stream);
+}
+
+int sf_geom_affine_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                            const double *deriv0, const double *deriv1, const double *x0, const double *x1, double *dfe,
+                            double *ge, double *je, void *stream)
+{
+    return geom_affine<2, double>({nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
+                                  {x0, x1, nullptr}, dfe, ge, je, stream);
+}
+
+int sf_geom_affine_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
+                           const float *basis2, const float *deriv0, const float *deriv1, const float *deriv2,
+                           const float *x0, const float *x1, const float *x2, float *dfe, float *ge, float *je,
+                           void *stream)
+{
+    return geom_affine<3, float>({nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2}, {x0, x1, x2},
+                                 dfe, ge, je, stream);
+}
+
+int sf_geom_affine_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
+                            const float *deriv0, const float *deriv1, const float *x0, const float *x1, float *dfe,
+                            float *ge, float *je, void *stream)
+{
+    return geom_affine<2, float>({nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
+                                 {x0, x1, nullptr}, dfe, ge, je, stream);
 }
 
 // ---- gather-scatter: Q, Q^T and Q Q^T of a local-to-global map, and the setup that inverts the map --------------------

@@ -776,6 +776,110 @@ int sf_diag_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const f
                                const float *g, const float *w, double lambda, float *out, void *stream);
 
 /*
+ * GEOMETRIC FACTORS from the coordinates of every element: what sf_helmholtz_* / sf_diag_helmholtz_* (g, w),
+ * sf_physderiv_* / sf_iprodderiv_* (df, w) and their affine forms (ge, je, dfe) take, computed from the mesh in ONE
+ * kernel.  The element is isoparametric: coordinate a of element e is the field x_a[e] of nm0*nm1[*nm2] modal
+ * coefficients in the layout of `in` of every other call (p fastest, nm_d = nq_d - 1), expanded in the same bases.
+ *   X_a = B x_a,   J[a][b] = D_b X_a = d x_a / d xi_b   at every quadrature point,   a, b = 0 .. d-1
+ *   df[e][c][k][j][i],   c = a*d + b for d xi_b / d x_a: the inverse of J, d*d planes -- the df of sf_physderiv_*
+ *   detj[e][k][j][i] = det J, with its sign: a negative value marks an inverted element (w hides the sign)
+ *   w[e][k][j][i] = |det J| * q,   q = qw2[k] * (qw1[j] * qw0[i])   (2D: qw1[j] * qw0[i]) -- the w of sf_helmholtz_*
+ *   g[e][c][k][j][i],   c = 00, 01, 02, 11, 12, 22 (2D: 00, 01, 11):   G_ab = w * sum_x df[x*d + a] * df[x*d + b]
+ *                                                                       -- the g of sf_helmholtz_*
+ * Per element the call moves d nm^d + (d*d + d(d+1)/2 + 2) nq^d scalars when every output is asked for; no intermediate
+ * point image reaches HBM.
+ * Layout: basis_d and deriv_d exactly as in sf_helmholtz_*; qw_d the nq_d one-dimensional quadrature weights of
+ * direction d, as in sf_affine_helmholtz_*; x_a: d separate caller-owned arrays.  Every output plane is laid out like
+ * the output of BwdTrans (i fastest) and goes into its consumer with no copy.
+ * Any output may be NULL: it is then neither written nor validated, and its arithmetic may be left out.  All four
+ * NULL: SF_EINVAL.  qw_d may be NULL when w and g are both NULL (they are then never read, nor validated).
+ * Summation order (it defines the rounding; every sum in ascending index, the first product a multiply, then FMAs; the
+ * wave kernels and the fallback follow it alike):
+ *   1. forward sweeps p -> i, q -> j, r -> k of x_a, as BwdTrans:           X_a
+ *   2. J[a][b] = D_b X_a
+ *   3. 3D: cof[a][b] = fma(J[a+1][b+1], J[a+2][b+2], -(J[a+1][b+2] * J[a+2][b+1])), indices mod 3
+ *      2D: cof = (J11, -J10, -J01, J00) in the order of c
+ *   4. det = J[0][0] * cof[0][0], then det = fma(J[0][b], cof[0][b], det) for b = 1 [, 2]
+ *   5. r = 1 / det (a correctly rounded division),   df[a*d + b] = cof[a][b] * r
+ *   6. q as above,   w = |det| * q
+ *   7. G_ab = w * (sum_x df[x*d + a] * df[x*d + b]), x ascending
+ * A point with det == 0 gives inf / NaN at that point only: nothing is refused on the device, no neighbour is touched.
+ * Routes, as sf_physderiv_*: SF_VARIANT_AUTO runs the fused wave kernel for the isotropic orders of its table (3D nq
+ * 2..8, 2D nq 2..16) when every x_a and every output that is not NULL are 16-byte aligned, else GENERIC;
+ * SF_VARIANT_WAVE returns SF_ENOTBUILT off that table and SF_EALIGN unless they are 16-byte aligned; SF_VARIANT_GENERIC
+ * (one workgroup per element, latency-bound) takes any extents up to 12 per direction in 3D and 32 in 2D; any other
+ * variant SF_ENOTBUILT, extents beyond those bounds SF_ENOTBUILT.  The bases, the derivative matrices and qw_d need only
+ * scalar alignment on every route.
+ * Validation, before any HIP call, in this order: (1) an extent < 2 or a variant outside [0, SF_NUM_VARIANTS):
+ * SF_EINVAL; (2) nelmt == 0: SF_OK; (3) a null basis, deriv or x_a, all four outputs null, or a null qw_d while w or g
+ * is asked for: SF_EINVAL; (4) any of them (an output, qw_d: only if it is looked at) not scalar-aligned: SF_EALIGN;
+ * (5) any output overlapping any x_a or another output, compared as byte ranges of their full sizes: SF_EINVAL;
+ * (6) extents beyond the fallback's bounds: SF_ENOTBUILT; (7) an unsupported variant: SF_ENOTBUILT.
+ * NOT in-place safe: an output that overlaps a coordinate array or another output is refused, not undefined; the inputs
+ * may overlap each other (all are only read).
+ * No internal workspace and no allocation: every call is a single kernel node, capture-safe from the process's first
+ * call.
+ */
+int sf_geom_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                    const double *basis0, const double *basis1, const double *basis2,
+                    const double *deriv0, const double *deriv1, const double *deriv2,
+                    const double *qw0, const double *qw1, const double *qw2,
+                    const double *x0, const double *x1, const double *x2,
+                    double *df, double *w, double *g, double *detj, void *stream);
+int sf_geom_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                            const double *basis0, const double *basis1, const double *basis2,
+                            const double *deriv0, const double *deriv1, const double *deriv2,
+                            const double *qw0, const double *qw1, const double *qw2,
+                            const double *x0, const double *x1, const double *x2,
+                            double *df, double *w, double *g, double *detj, void *stream);
+int sf_geom_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                     const double *deriv0, const double *deriv1, const double *qw0, const double *qw1,
+                     const double *x0, const double *x1, double *df, double *w, double *g, double *detj,
+                     void *stream);
+int sf_geom_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                             const double *basis1, const double *deriv0, const double *deriv1, const double *qw0,
+                             const double *qw1, const double *x0, const double *x1, double *df, double *w,
+                             double *g, double *detj, void *stream);
+/* T = float (AUTO route; every array 4-byte aligned) */
+int sf_geom_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
+                    const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
+                    const float *deriv2, const float *qw0, const float *qw1, const float *qw2, const float *x0,
+                    const float *x1, const float *x2, float *df, float *w, float *g, float *detj, void *stream);
+int sf_geom_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
+                     const float *deriv0, const float *deriv1, const float *qw0, const float *qw1,
+                     const float *x0, const float *x1, float *df, float *w, float *g, float *detj, void *stream);
+
+/*
+ * sf_geom_* for elements the caller knows to be AFFINE (a constant Jacobian): the same formulas at the point
+ * (k, j, i) = (0, 0, 0) only, written as the per-element constants that sf_affine_helmholtz_* and sf_aff_physderiv_* /
+ * sf_aff_iprodderiv_* take:
+ *   dfe[e][c] = df of that point, c = a*d + b;   je[e] = |det J|;   ge[e][c] = je * sum_x dfe[x*d + a] * dfe[x*d + b],
+ *   c = 00, 01, 02, 11, 12, 22 (2D: 00, 01, 11)
+ * No quadrature weights enter: the affine operators multiply by q themselves.  Steps 1-5 and 7 of sf_geom_* in the same
+ * order, so dfe[e][c] and je[e] equal df[e][c][0][0][0] and |detj[e][0][0][0]| of sf_geom_* on the same coordinates BIT
+ * FOR BIT.  Whether the element is affine is not checked.
+ * Any output may be NULL (neither written nor validated); all three NULL: SF_EINVAL.  One plain small kernel without
+ * variants, for any extents the GENERIC route of sf_geom_* takes (beyond: SF_ENOTBUILT); every array needs only scalar
+ * alignment.  Validation in the order of sf_geom_* without the variant; an output overlapping any x_a or another output:
+ * SF_EINVAL.  No internal workspace and no allocation: a single kernel node, capture-safe from the first call.
+ */
+int sf_geom_affine_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                           const double *basis0, const double *basis1, const double *basis2,
+                           const double *deriv0, const double *deriv1, const double *deriv2,
+                           const double *x0, const double *x1, const double *x2,
+                           double *dfe, double *ge, double *je, void *stream);
+int sf_geom_affine_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                            const double *basis1, const double *deriv0, const double *deriv1, const double *x0,
+                            const double *x1, double *dfe, double *ge, double *je, void *stream);
+int sf_geom_affine_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
+                           const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
+                           const float *deriv2, const float *x0, const float *x1, const float *x2, float *dfe,
+                           float *ge, float *je, void *stream);
+int sf_geom_affine_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
+                            const float *deriv0, const float *deriv1, const float *x0, const float *x1,
+                            float *dfe, float *ge, float *je, void *stream);
+
+/*
  * GATHER-SCATTER between the element-local coefficients the operators above work on and the global degrees of freedom
  * of a continuous-Galerkin space: with Q the nlocal x nglobal matrix of a local-to-global map, global_to_local applies
  * Q, assemble Q^T and gs Q Q^T, so that  A = Q^T blockdiag(H_e) Q  is  global_to_local -> sf_helmholtz_* -> assemble,
