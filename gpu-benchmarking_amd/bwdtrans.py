@@ -769,6 +769,123 @@ def affine_physderiv_autograd(nq, bases, derivs, dfe, inp):
     return _AffinePhysDeriv.apply(inp, nq, dfe, *bases, *derivs)
 
 
+def _tensor_extents(what, ni, no, dim):
+    ni, no = tuple(int(x) for x in ni), tuple(int(x) for x in no)
+    if len(ni) != dim or len(no) != dim:
+        raise ValueError(f"{what}: {dim} input and {dim} output extents")
+    return ni, no
+
+
+def _tensor_call(what, shape, ni, no, mats, inp, trans, out, variant, stream):
+    dim = 3 if shape == "hex" else 2
+    ni, no = _tensor_extents(what, ni, no, dim)
+    if len(mats) != dim:
+        raise ValueError(f"{what}: {dim} extents need {dim} matrices")
+    if not isinstance(inp, torch.Tensor):
+        raise TypeError(f"{what}: in must be a tensor")
+    if inp.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"{what}: in must be float64 or float32")
+    if min(ni + no) < 1:
+        raise capi.SumfactError(capi.SF_EINVAL, what)
+    nin, nout = 1, 1
+    for a, b in zip(ni, no):
+        nin, nout = nin * a, nout * b
+    nelmt = inp.numel() // nin
+    if nelmt * nin != inp.numel():
+        raise ValueError(f"{what}: in.numel() is not a multiple of the input values per element ({nin})")
+    if out is None:
+        out = torch.empty(nelmt * nout, dtype=inp.dtype, device=inp.device)
+    operands = [(f"m{d}", m, a * b, False) for d, (m, a, b) in enumerate(zip(mats, ni, no))]
+    operands += [("in", inp, nelmt * nin, False), ("out", out, nelmt * nout, False)]
+    _check_operands(what, operands, inp)
+    sfx = "f64" if inp.dtype == torch.float64 else "f32"
+    fn = getattr(capi.lib(), f"sf_tensor_{shape}_{sfx}_variant")
+    with torch.cuda.device(inp.device):
+        rc = fn(_variant(variant), *ni, *no, int(bool(trans)), nelmt,
+                *(_dev_ptr(t, name, inp.dtype) for name, t, _, _ in operands), _stream(stream, inp.device))
+    capi.check(rc, what)
+    return out
+
+
+def tensor_hex(ni, no, m0, m1, m2, x, trans=False, out=None, variant="auto", stream=None):
+    """The tensor-product apply with independent input / output extents on x's device: out[e][k][j][i] = sum_rqp
+    x[e][r][q][p] M0(p,i) M1(q,j) M2(r,k), M_d(a,b) = m_d[a*no_d + b] (trans false: m_d row-major ni_d x no_d) or
+    m_d[b*ni_d + a] (trans true: row-major no_d x ni_d).  x holds ni0*ni1*ni2 values per element, out no0*no1*no2; out
+    may not overlap x.  float64 and float32; variant "auto", "wave" (the compiled table) or "generic"."""
+    return _tensor_call("tensor_hex", "hex", ni, no, (m0, m1, m2), x, trans, out, variant, stream)
+
+
+def tensor_quad(ni, no, m0, m1, x, trans=False, out=None, variant="auto", stream=None):
+    """tensor_hex in 2D: out[e][j][i] = sum_qp x[e][q][p] M0(p,i) M1(q,j)."""
+    return _tensor_call("tensor_quad", "quad", ni, no, (m0, m1), x, trans, out, variant, stream)
+
+
+def _tensor_spec_args(ni, no, trans, dtype):
+    dim = len(tuple(ni))
+    if dim not in (2, 3):
+        raise ValueError("ni / no must hold 2 (quad) or 3 (hex) extents")
+    ni, no = _tensor_extents("specialise_tensor", ni, no, dim)
+    if dtype not in (torch.float64, torch.float32):
+        raise TypeError("dtype must be torch.float64 or torch.float32")
+    pad = (1,) * (3 - dim)
+    return (dim,) + ni + pad + no + pad + (int(bool(trans)), 8 if dtype == torch.float64 else 4)
+
+
+def specialise_tensor(ni, no, trans=False, dtype=torch.float64, device=None):
+    """Compile (once per process) and load (once per device) the wave kernel of the tensor shape ni -> no, `trans`, on
+    `device` (default: the current device).  Returns SF_OK, or SF_ECOMPILE when the shape is refused (its slab exceeds the
+    limit, it would spill, hiprtc is missing, or the current stream is capturing: nothing is compiled then): AUTO calls
+    of tensor_hex / tensor_quad then keep the any-extent kernel.  The log is specialise_log()."""
+    args = _tensor_spec_args(ni, no, trans, dtype)
+    with torch.cuda.device(device if device is not None else torch.cuda.current_device()):
+        if torch.cuda.is_current_stream_capturing():
+            return capi.SF_ECOMPILE
+        rc = capi.lib().sf_specialise_tensor(*args)
+    if rc not in (capi.SF_OK, capi.SF_ECOMPILE):
+        capi.check(rc, "sf_specialise_tensor")
+    return rc
+
+
+def tensor_specialisation_state(ni, no, trans=False, dtype=torch.float64, device=None):
+    """(state, launches) of the tensor specialisation on `device`: state 0 none, 1 ready, SF_ECOMPILE refused."""
+    n = ctypes.c_uint64(0)
+    with torch.cuda.device(device if device is not None else torch.cuda.current_device()):
+        rc = capi.lib().sf_tensor_specialisation_state(*_tensor_spec_args(ni, no, trans, dtype), ctypes.byref(n))
+    if rc not in (0, 1, capi.SF_ECOMPILE):
+        capi.check(rc, "sf_tensor_specialisation_state")
+    return rc, n.value
+
+
+class _Tensor(torch.autograd.Function):
+    """AUTO tensor apply forward; its input gradient is the same call with trans flipped and ni / no swapped."""
+
+    @staticmethod
+    def forward(ctx, inp, ni, no, trans, *mats):
+        ctx.ni, ctx.no, ctx.trans, ctx.shape = ni, no, trans, inp.shape
+        ctx.save_for_backward(*mats)
+        fn = tensor_hex if len(ni) == 3 else tensor_quad
+        return fn(ni, no, *mats, inp.contiguous(), trans=trans)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        mats = ctx.saved_tensors
+        fn = tensor_hex if len(ctx.ni) == 3 else tensor_quad
+        gin = fn(ctx.no, ctx.ni, *mats, grad_out.contiguous(), trans=not ctx.trans)
+        return (gin.reshape(ctx.shape), None, None, None) + (None,) * len(mats)
+
+
+def tensor_autograd(ni, no, mats, inp, trans=False):
+    """tensor_hex / tensor_quad (AUTO) with a backward pass: the gradient with respect to `inp` is the transposed apply
+    of grad_out, the same matrices with `trans` flipped and ni / no swapped.  The matrices are constants: one that requires
+    grad is refused.  Returns the flat output."""
+    ni, no, mats = tuple(int(x) for x in ni), tuple(int(x) for x in no), tuple(mats)
+    if len(ni) not in (2, 3) or len(no) != len(ni) or len(mats) != len(ni):
+        raise ValueError("tensor_autograd: 2 or 3 extents in and out, one matrix per extent")
+    if any(m.requires_grad for m in mats):
+        raise ValueError("tensor_autograd: the matrices are constants; detach them (no gradient flows to a matrix)")
+    return _Tensor.apply(inp, ni, no, bool(trans), *mats)
+
+
 def _spec_args(nq, dtype):
     nq = tuple(int(x) for x in nq)
     if len(nq) not in (2, 3):

@@ -91,6 +91,21 @@ def _geom_symbols():
 
 SYMBOLS.update(_geom_symbols())
 
+
+def _tensor_symbols():
+    """sf_tensor_{hex,quad}_{f64,f64_variant,f32,f32_variant}: [variant,] the input extents, the output extents, trans,
+    nelmt, one matrix per direction, in, out, stream; sf_specialise_tensor / sf_tensor_specialisation_state: dim, three
+    input and three output extents, trans, scalar_bytes[, launches]."""
+    for shape, dim in (("hex", 3), ("quad", 2)):
+        for sfx in ("f64", "f64_variant", "f32", "f32_variant"):
+            head = [_i] if sfx.endswith("_variant") else []
+            yield f"sf_tensor_{shape}_{sfx}", (_i, head + [_u] * (2 * dim) + [_i, _sz] + [_vp] * (dim + 2) + [_vp])
+    yield "sf_specialise_tensor", (_i, [_i] + [_u] * 6 + [_i, _i])
+    yield "sf_tensor_specialisation_state", (_i, [_i] + [_u] * 6 + [_i, _i, ctypes.POINTER(_u64)])
+
+
+SYMBOLS.update(_tensor_symbols())
+
 _lib = None
 
 

@@ -9,7 +9,8 @@
 // transpose IProductWRTDerivBase in iprodderiv.hip / iprodderiv_f32.hip / iprodderiv_generic.hip, the affine-element forms
 // of those two in affine_deriv.hip / affine_deriv_f32.hip / affine_deriv_generic.hip, the diagonal of the
 // Helmholtz operator in diag.hip / diag_f32.hip / diag_generic.hip, the gather-scatter between local coefficients and
-// global degrees of freedom in gs.hip, the geometric factors from element coordinates (geom, geom_affine below; their
+// global degrees of freedom in gs.hip, the tensor-product apply with independent input / output extents (tensor below) in
+// tensor.hip / tensor_quad.hip / tensor_f32.hip / tensor_quad_f32.hip / tensor_generic.hip / rtc.hip, the geometric factors from element coordinates (geom, geom_affine below; their
 // launchers are declared in geom_args.h) in geom.hip / geom_f32.hip / geom_generic.hip.
 #include "geom_args.h"
 #include "sf_dispatch.h"
@@ -176,6 +177,46 @@ static int iprod(int variant, const unsigned (&nq)[3], size_t nelmt, const T *co
     return route<DIM>(
         variant, nq, iprod_generic_built(DIM, nq[0], nq[1], nq[2]), iprod_wave_built(DIM, nq[0]), in, out,
         [&] { return launch_iprod_wave<DIM, T>(nq[0], a, s); }, [&] { return launch_iprod_generic<DIM, T>(nq, a, s); });
+}
+
+// ---- the tensor-product apply with independent input / output extents (sf_tensor_*) -----------------------------------
+// The order of sf_mass_*: extents, trans and the variant's range, an empty batch, nulls, alignment, out over in.  AUTO on
+// 16-byte-aligned in / out: the compiled table, then a specialisation the caller made ready (sf_specialise_tensor), then
+// the any-extent kernel, which also takes buffers aligned only to the scalar.
+template <int DIM, typename T>
+static int tensor(int variant, const unsigned (&ni)[3], const unsigned (&no)[3], int trans, size_t nelmt,
+                  const T *const (&m)[3], const T *in, T *out, void *stream)
+{
+    bool range = (trans == 0 || trans == 1) && variant >= 0 && variant < SF_NUM_VARIANTS;
+    for (int d = 0; d < DIM; ++d)
+        range = range && ni[d] >= 1 && no[d] >= 1;
+    const int rc = validate(range, nelmt, {m[0], m[1], DIM == 3 ? m[2] : m[0], in, out}, sizeof(T));
+    if (rc != kProceed)
+        return rc;
+    if (!tensor_generic_built(DIM, ni, no)) // before the products below can overflow
+        return SF_ENOTBUILT;
+    // not in-place safe (the word-grid loads of a chunk read 16-byte words that straddle the neighbouring element)
+    const size_t in_bytes  = sizeof(T) * nelmt * ni[0] * ni[1] * (DIM == 3 ? ni[2] : 1);
+    const size_t out_bytes = sizeof(T) * nelmt * no[0] * no[1] * (DIM == 3 ? no[2] : 1);
+    if (overlaps(out, out_bytes, in, in_bytes))
+        return SF_EINVAL;
+    if (variant != SF_VARIANT_AUTO && variant != SF_VARIANT_WAVE && variant != SF_VARIANT_GENERIC)
+        return SF_ENOTBUILT;
+    const hipStream_t s = (hipStream_t)stream;
+    const auto a        = make_args<DIM, T>(m, in, nullptr, out, nelmt);
+    const bool vec_ok   = aligned(in, 16) && aligned(out, 16);
+    const bool table    = tensor_wave_built(DIM, ni, no);
+    if (variant == SF_VARIANT_WAVE)
+        return !table ? (int)SF_ENOTBUILT : (!vec_ok ? (int)SF_EALIGN : launch_tensor_wave<DIM, T>(ni, no, trans, a, s));
+    if (variant == SF_VARIANT_AUTO && vec_ok)
+    {
+        if (table)
+            return launch_tensor_wave<DIM, T>(ni, no, trans, a, s);
+        const int spec = launch_tensor_specialised(DIM, ni, no, trans, (int)sizeof(T), m[0], m[1], m[2], in, out, a.nelmt, s);
+        if (spec != SF_ENOTBUILT)
+            return spec;
+    }
+    return launch_tensor_generic<DIM, T>(ni, no, trans, a, s);
 }
 
 // ---- the fused mass operator B^T diag(w) B: one validation and routing for both dimensions and both scalar types ----
@@ -1410,6 +1451,71 @@ int sf_device_info(int *num_cu, int *wave_size, char *name, size_t name_len)
         std::snprintf(name, name_len, "%s (%s)", p.name, p.gcnArchName);
     }
     return SF_OK;
+}
+
+// ---- tensor-product apply ----------------------------------------------------------------------------------------
+int sf_tensor_hex_f64_variant(int variant, unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1, unsigned no2,
+                              int trans, size_t nelmt, const double *m0, const double *m1, const double *m2,
+                              const double *in, double *out, void *stream)
+{
+    return tensor<3, double>(variant, {ni0, ni1, ni2}, {no0, no1, no2}, trans, nelmt, {m0, m1, m2}, in, out, stream);
+}
+
+int sf_tensor_hex_f64(unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1, unsigned no2, int trans,
+                      size_t nelmt, const double *m0, const double *m1, const double *m2, const double *in, double *out,
+                      void *stream)
+{
+    return tensor<3, double>(SF_VARIANT_AUTO, {ni0, ni1, ni2}, {no0, no1, no2}, trans, nelmt, {m0, m1, m2}, in, out, stream);
+}
+
+int sf_tensor_quad_f64_variant(int variant, unsigned ni0, unsigned ni1, unsigned no0, unsigned no1, int trans, size_t nelmt,
+                               const double *m0, const double *m1, const double *in, double *out, void *stream)
+{
+    return tensor<2, double>(variant, {ni0, ni1, 1u}, {no0, no1, 1u}, trans, nelmt, {m0, m1, nullptr}, in, out, stream);
+}
+
+int sf_tensor_quad_f64(unsigned ni0, unsigned ni1, unsigned no0, unsigned no1, int trans, size_t nelmt, const double *m0,
+                       const double *m1, const double *in, double *out, void *stream)
+{
+    return tensor<2, double>(SF_VARIANT_AUTO, {ni0, ni1, 1u}, {no0, no1, 1u}, trans, nelmt, {m0, m1, nullptr}, in, out, stream);
+}
+
+int sf_tensor_hex_f32_variant(int variant, unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1, unsigned no2,
+                              int trans, size_t nelmt, const float *m0, const float *m1, const float *m2, const float *in,
+                              float *out, void *stream)
+{
+    return tensor<3, float>(variant, {ni0, ni1, ni2}, {no0, no1, no2}, trans, nelmt, {m0, m1, m2}, in, out, stream);
+}
+
+int sf_tensor_hex_f32(unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1, unsigned no2, int trans,
+                      size_t nelmt, const float *m0, const float *m1, const float *m2, const float *in, float *out,
+                      void *stream)
+{
+    return tensor<3, float>(SF_VARIANT_AUTO, {ni0, ni1, ni2}, {no0, no1, no2}, trans, nelmt, {m0, m1, m2}, in, out, stream);
+}
+
+int sf_tensor_quad_f32_variant(int variant, unsigned ni0, unsigned ni1, unsigned no0, unsigned no1, int trans, size_t nelmt,
+                               const float *m0, const float *m1, const float *in, float *out, void *stream)
+{
+    return tensor<2, float>(variant, {ni0, ni1, 1u}, {no0, no1, 1u}, trans, nelmt, {m0, m1, nullptr}, in, out, stream);
+}
+
+int sf_tensor_quad_f32(unsigned ni0, unsigned ni1, unsigned no0, unsigned no1, int trans, size_t nelmt, const float *m0,
+                       const float *m1, const float *in, float *out, void *stream)
+{
+    return tensor<2, float>(SF_VARIANT_AUTO, {ni0, ni1, 1u}, {no0, no1, 1u}, trans, nelmt, {m0, m1, nullptr}, in, out, stream);
+}
+
+int sf_specialise_tensor(int dim, unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1, unsigned no2,
+                         int trans, int scalar_bytes)
+{
+    return rtc_specialise_tensor(dim, {ni0, ni1, ni2}, {no0, no1, no2}, trans, scalar_bytes);
+}
+
+int sf_tensor_specialisation_state(int dim, unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1,
+                                   unsigned no2, int trans, int scalar_bytes, uint64_t *launches)
+{
+    return rtc_tensor_state(dim, {ni0, ni1, ni2}, {no0, no1, no2}, trans, scalar_bytes, launches);
 }
 
 // ---- run-time specialisation (rtc.hip) -------------------------------------------------------------------------

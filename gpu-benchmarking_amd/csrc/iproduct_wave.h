@@ -13,7 +13,8 @@
 // Sweep order i -> p (B0), then j -> q (B1), then k -> r (B2); each sum is taken in ascending index.  A sweep contracts a
 // pencil of nq values into nm values with the DOT-PRODUCT form acc[p] = sum_i u[i] * B[p][i]: the caller's basis array is
 // read as it is, row by row (row p = B[p][0 .. nq), contiguous), through the two-deep SGPR ring of contract() -- no
-// transposed copy, no workspace, so every launch is capture-safe.
+// transposed copy, no workspace, so every launch is capture-safe.  contract_dot lives next to contract in
+// bwdtrans_wave.h: the tensor kernels of bwdtrans_aniso.h use both.
 //
 // Both kernels are the front fragments of the fused operators (frag/wave_slab.inc .. frag/chunk_fetch_next.inc) and the
 // sweeps of frag/sweep.inc with contract_dot.  The last sweep of the quad kernel stays written out: as frag/sweep.inc
@@ -29,64 +30,6 @@ namespace sf
 // chunk I/O (chunk_fetch, chunk_stage, chunk_flush) reads it as it is.
 template <int NQ, int EC, int DIM, typename T = double>
 using IprodGeom = SweepGeom<DIM, EC, T, NQ, NQ - 1, NQ, NQ - 1, DIM == 3 ? NQ : 1, DIM == 3 ? NQ - 1 : 1>;
-
-// ------------------------------------------------------------------------------------------------
-// Dot-product contraction, columns [I0, I0+NB) of every basis row: acc[s][p] (+)= sum_i u[s][i] * B[p*NIN + i], ascending
-// i (I0 == 0 starts the sums).  The rows go through a two-deep SGPR ring in the order of contract(): (1) touch row p (the
-// wait for its scalar loads lands here), (2) request row p+1, (3) the FMAs of row p, (4) an order fence on row p's
-// results, so that neither the next row's loads nor its FMAs move across.  BASIS_SMEM streams whole rows (NB = NIN);
-// BASIS_SMEM_COLS{,16} take the rows in blocks of 8 / 16 columns, then the next block.
-// ------------------------------------------------------------------------------------------------
-template <int NIN, int NOUT, int NPASS, int I0, int KB, typename T>
-__device__ __forceinline__ void contract_dot_cols(const T (&u)[NPASS][NIN], T (&acc)[NPASS][NOUT],
-                                                  const T *__restrict__ bas, int &zero)
-{
-    constexpr int NB = (NIN - I0) < KB ? (NIN - I0) : KB;
-    T b[2][NB];
-#pragma unroll
-    for (int i = 0; i < NB; ++i)
-        b[0][i] = bas[zero + I0 + i];
-#pragma unroll
-    for (int p = 0; p < NOUT; ++p)
-    {
-#pragma unroll
-        for (int i = 0; i < NB; ++i)
-            asm volatile("" : "+s"(zero) : "s"(b[p % 2][i]));
-        if (p + 1 < NOUT)
-        {
-#pragma unroll
-            for (int i = 0; i < NB; ++i)
-                b[(p + 1) % 2][i] = bas[zero + (p + 1) * NIN + I0 + i];
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int s = 0; s < NPASS; ++s)
-        {
-            T a = (I0 == 0) ? u[s][0] * b[p % 2][0] : fma_t(u[s][I0], b[p % 2][0], acc[s][p]);
-#pragma unroll
-            for (int i = 1; i < NB; ++i)
-                a = fma_t(u[s][I0 + i], b[p % 2][i], a);
-            acc[s][p] = a;
-        }
-#pragma unroll
-        for (int s = 0; s < NPASS; ++s)
-            asm volatile("" : "+s"(zero) : "v"(acc[s][p]));
-    }
-    if constexpr (I0 + NB < NIN)
-        contract_dot_cols<NIN, NOUT, NPASS, I0 + NB, KB, T>(u, acc, bas, zero);
-}
-
-template <int NIN, int NOUT, int NPASS, int BMODE, typename T>
-__device__ __forceinline__ void contract_dot(const T (&u)[NPASS][NIN], T (&acc)[NPASS][NOUT], const T *__restrict__ bas)
-{
-    static_assert(BMODE == BASIS_SMEM || BMODE == BASIS_SMEM_COLS || BMODE == BASIS_SMEM_COLS16,
-                  "the transposed kernels take the basis as scalar operands");
-    // opaque zero offset: the pointer stays a provably global kernel argument (s_load), the loads stay in the loop
-    int zero = 0;
-    asm volatile("s_mov_b32 %0, 0" : "=s"(zero));
-    constexpr int KB = BMODE == BASIS_SMEM ? NIN : (BMODE == BASIS_SMEM_COLS ? 8 : 16);
-    contract_dot_cols<NIN, NOUT, NPASS, 0, KB, T>(u, acc, bas, zero);
-}
 
 // ------------------------------------------------------------------------------------------------
 // 3D hex

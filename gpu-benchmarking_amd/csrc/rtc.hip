@@ -1,7 +1,8 @@
 // rtc.hip -- load / launch half of the run-time specialisation: sf_specialise() compiles (once per process, through
 // rtc_compile.cc) and loads (once per device) the wave-per-chunk kernel of bwdtrans_aniso.h for the
-// extents a caller names; AUTO then launches it for shapes the compiled tables miss.  Nothing here compiles or loads
-// behind a launch: a launch only finds what sf_specialise() made ready.
+// extents a caller names; AUTO then launches it for shapes the compiled tables miss.  sf_specialise_tensor() does the
+// same for the tensor kernels of that header (independent input / output extents, sf_tensor_*), under keys of their own.
+// Nothing here compiles or loads behind a launch: a launch only finds what sf_specialise() made ready.
 #include "bwdtrans_aniso.h"
 #include "rtc_compile.h"
 #include "sf_dispatch.h"
@@ -39,6 +40,30 @@ static_assert(rtc_pins3<6, 6, 12, 8>() && rtc_pins3<12, 10, 8, 8>() && rtc_pins3
                   rtc_pins3<3, 5, 4, 8>() && rtc_pins3<2, 3, 2, 8>() && rtc_pins3<16, 12, 14, 8>() &&
                   rtc_pins3<3, 5, 4, 4>() && rtc_pins3<6, 6, 12, 4>(),
               "3D launch configuration");
+
+// tensor_cfg against SweepGeom for the shapes the tests name off the table (the table's own are pinned in tensor_launch.h)
+template <int DIM, int I0, int O0, int I1, int O1, int I2, int O2, int S> constexpr bool tensor_pins()
+{
+    constexpr int ni[3] = {I0, I1, I2}, no[3] = {O0, O1, O2};
+    constexpr RtcCfg c  = tensor_cfg(DIM, ni, no, S);
+    using T             = typename std::conditional<S == 8, double, float>::type;
+    using G             = SweepGeom<DIM, c.ec, T, I0, O0, I1, O1, I2, O2>;
+    return c.slab == G::SLAB && c.lds == slab_lds_bytes<G, c.wpb>();
+}
+static_assert(tensor_pins<3, 4, 7, 4, 7, 4, 7, 8>() && tensor_pins<3, 7, 4, 7, 4, 7, 4, 8>() &&
+                  tensor_pins<3, 5, 8, 3, 3, 6, 4, 8>() && tensor_pins<3, 7, 8, 7, 8, 7, 8, 8>() &&
+                  tensor_pins<3, 3, 4, 3, 4, 3, 4, 8>() && tensor_pins<3, 8, 7, 8, 7, 8, 7, 8>() &&
+                  tensor_pins<3, 4, 3, 4, 3, 4, 3, 8>() && tensor_pins<3, 3, 5, 4, 4, 6, 2, 8>() &&
+                  tensor_pins<3, 1, 4, 2, 2, 5, 1, 8>() && tensor_pins<3, 16, 16, 2, 3, 1, 1, 8>() &&
+                  tensor_pins<3, 1, 16, 16, 1, 16, 1, 8>() && tensor_pins<3, 4, 7, 4, 7, 4, 7, 4>() &&
+                  tensor_pins<3, 5, 8, 3, 3, 6, 4, 4>(),
+              "3D tensor launch configuration");
+static_assert(tensor_pins<2, 1, 4, 9, 3, 1, 1, 8>() && tensor_pins<2, 10, 15, 6, 9, 1, 1, 8>() &&
+                  tensor_pins<2, 7, 8, 7, 8, 1, 1, 8>() && tensor_pins<2, 15, 16, 15, 16, 1, 1, 8>() &&
+                  tensor_pins<2, 8, 7, 8, 7, 1, 1, 8>() && tensor_pins<2, 16, 15, 16, 15, 1, 1, 8>() &&
+                  tensor_pins<2, 24, 20, 7, 24, 1, 1, 8>() && tensor_pins<2, 9, 6, 9, 6, 1, 1, 4>() &&
+                  tensor_pins<2, 10, 15, 6, 9, 1, 1, 4>(),
+              "2D tensor launch configuration");
 
 namespace
 {
@@ -108,13 +133,9 @@ int launch(Loaded &L, int dim, const void *b0, const void *b1, const void *b2, c
     return SF_OK;
 }
 
-} // namespace
-
-int rtc_specialise(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes)
+// compile (once per process and arch) and load (once per device) the kernel of `k`
+int specialise(const RtcKey &k)
 {
-    RtcKey k;
-    if (rtc_key(dim, nq0, nq1, nq2, scalar_bytes, &k) != SF_OK)
-        return SF_EINVAL;
     int dev      = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess)
@@ -132,9 +153,9 @@ int rtc_specialise(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar
         cc->rc     = rtc_compile(k, arch, &cc->code);
         cc->serial = ++g_compiles;
     }
-    char head[256];
-    std::snprintf(head, sizeof head, "sf_specialise %s, device %d (%s): compile #%u, %.3f s\n%s\n",
-                  rtc_describe(k).c_str(), dev, arch.c_str(), cc->serial, cc->code.seconds,
+    char head[320];
+    std::snprintf(head, sizeof head, "sf_specialise%s %s, device %d (%s): compile #%u, %.3f s\n%s\n",
+                  k.kind == 1 ? "_tensor" : "", rtc_describe(k).c_str(), dev, arch.c_str(), cc->serial, cc->code.seconds,
                   rtc_name_expression(k).c_str());
     t_log = head + cc->code.log;
 
@@ -179,11 +200,8 @@ int rtc_specialise(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar
     return SF_OK;
 }
 
-int rtc_state(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes, uint64_t *launches)
+int state(const RtcKey &k, uint64_t *launches)
 {
-    RtcKey k;
-    if (rtc_key(dim, nq0, nq1, nq2, scalar_bytes, &k) != SF_OK)
-        return SF_EINVAL;
     int dev      = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess)
@@ -193,6 +211,65 @@ int rtc_state(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_byte
     if (launches)
         *launches = it == g_loaded.end() ? 0 : it->second->launches.load(std::memory_order_relaxed);
     return it == g_loaded.end() ? 0 : it->second->state;
+}
+
+} // namespace
+
+int rtc_specialise(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes)
+{
+    RtcKey k;
+    if (rtc_key(dim, nq0, nq1, nq2, scalar_bytes, &k) != SF_OK)
+        return SF_EINVAL;
+    return specialise(k);
+}
+
+int rtc_state(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes, uint64_t *launches)
+{
+    RtcKey k;
+    if (rtc_key(dim, nq0, nq1, nq2, scalar_bytes, &k) != SF_OK)
+        return SF_EINVAL;
+    return state(k, launches);
+}
+
+// The tensor kernels.  A request while a blocking stream of the device is capturing is refused before anything is
+// compiled or loaded (a module load is not a capturable call); the Python binding refuses the same for the stream it
+// knows to be capturing.
+int rtc_specialise_tensor(int dim, const unsigned (&ni)[3], const unsigned (&no)[3], int trans, int scalar_bytes)
+{
+    RtcKey k;
+    if (rtc_tensor_key(dim, ni, no, trans, scalar_bytes, &k) != SF_OK)
+        return SF_EINVAL;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const hipError_t ce        = hipStreamIsCapturing(nullptr, &cap);
+    (void)hipGetLastError(); // any other error is the device's: specialise() reports it
+    if (ce == hipErrorStreamCaptureImplicit || (ce == hipSuccess && cap != hipStreamCaptureStatusNone))
+    {
+        t_log = "sf_specialise_tensor " + rtc_describe(k) + ": refused, a stream capture is under way\n";
+        return SF_ECOMPILE;
+    }
+    return specialise(k);
+}
+
+int rtc_tensor_state(int dim, const unsigned (&ni)[3], const unsigned (&no)[3], int trans, int scalar_bytes,
+                     uint64_t *launches)
+{
+    RtcKey k;
+    if (rtc_tensor_key(dim, ni, no, trans, scalar_bytes, &k) != SF_OK)
+        return SF_EINVAL;
+    return state(k, launches);
+}
+
+int launch_tensor_specialised(int dim, const unsigned (&ni)[3], const unsigned (&no)[3], int trans, int scalar_bytes,
+                              const void *m0, const void *m1, const void *m2, const void *in, void *out, uint64_t nelmt,
+                              hipStream_t s)
+{
+    if (g_ready.load(std::memory_order_relaxed) == 0) // the common case: one relaxed load
+        return SF_ENOTBUILT;
+    RtcKey k;
+    if (rtc_tensor_key(dim, ni, no, trans, scalar_bytes, &k) != SF_OK)
+        return SF_ENOTBUILT;
+    Loaded *L = ready(k);
+    return L ? launch(*L, dim, m0, m1, m2, in, out, nelmt, s) : SF_ENOTBUILT;
 }
 
 int launch_specialised(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes, const void *b0,

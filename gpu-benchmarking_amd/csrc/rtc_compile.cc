@@ -111,17 +111,45 @@ int rtc_key(int dim, unsigned nq0, unsigned nq1, unsigned nq2, int scalar_bytes,
     return SF_OK;
 }
 
+int rtc_tensor_key(int dim, const unsigned (&ni)[3], const unsigned (&no)[3], int trans, int scalar_bytes, RtcKey *k)
+{
+    if ((dim != 2 && dim != 3) || (scalar_bytes != 4 && scalar_bytes != 8) || (trans != 0 && trans != 1))
+        return SF_EINVAL;
+    const unsigned mx = dim == 3 ? (unsigned)kTensorMaxExt3 : (unsigned)kTensorMaxExt2;
+    for (int d = 0; d < dim; ++d)
+        if (ni[d] < 1 || no[d] < 1 || ni[d] > mx || no[d] > mx)
+            return SF_EINVAL;
+    *k       = RtcKey{dim, (int)no[0], (int)no[1], dim == 3 ? (int)no[2] : 0, scalar_bytes};
+    k->kind  = 1;
+    k->ni0   = (int)ni[0];
+    k->ni1   = (int)ni[1];
+    k->ni2   = dim == 3 ? (int)ni[2] : 0;
+    k->trans = trans;
+    return SF_OK;
+}
+
 RtcCfg rtc_cfg_of(const RtcKey &k)
 {
+    if (k.kind == 1)
+    {
+        const int ni[3] = {k.ni0, k.ni1, k.dim == 3 ? k.ni2 : 1}, no[3] = {k.nq0, k.nq1, k.dim == 3 ? k.nq2 : 1};
+        return tensor_cfg(k.dim, ni, no, k.sbytes);
+    }
     return rtc_cfg(k.dim, k.nq0, k.nq1, k.nq2, k.sbytes);
 }
 
 std::string rtc_name_expression(const RtcKey &k)
 {
     const RtcCfg c = rtc_cfg_of(k);
-    char buf[160];
+    char buf[200];
     const char *t = k.sbytes == 8 ? "double" : "float";
-    if (k.dim == 3)
+    if (k.kind == 1 && k.dim == 3)
+        std::snprintf(buf, sizeof buf, "sf::hex_tensor_wave_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %s>",
+                      k.ni0, k.nq0, k.ni1, k.nq1, k.ni2, k.nq2, k.trans, c.ec, c.wpb, c.bmode, c.minw, c.xg, t);
+    else if (k.kind == 1)
+        std::snprintf(buf, sizeof buf, "sf::quad_tensor_wave_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %s>", k.ni0,
+                      k.nq0, k.ni1, k.nq1, k.trans, c.ec, c.wpb, c.bmode, c.minw, c.xg, t);
+    else if (k.dim == 3)
         std::snprintf(buf, sizeof buf, "sf::hex_wave3_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %s>", k.nq0, k.nq1, k.nq2,
                       c.ec, c.wpb, c.bmode, c.minw, c.xg, t);
     else
@@ -137,8 +165,15 @@ std::vector<std::string> rtc_options(const std::string &arch)
 
 std::string rtc_describe(const RtcKey &k)
 {
-    char buf[64];
-    if (k.dim == 3)
+    char buf[96];
+    const char *tr = k.trans ? ":t" : "";
+    if (k.kind == 1 && k.dim == 3)
+        std::snprintf(buf, sizeof buf, "%s 3D %d>%dx%d>%dx%d>%d%s", k.sbytes == 8 ? "fp64" : "fp32", k.ni0, k.nq0, k.ni1,
+                      k.nq1, k.ni2, k.nq2, tr);
+    else if (k.kind == 1)
+        std::snprintf(buf, sizeof buf, "%s 2D %d>%dx%d>%d%s", k.sbytes == 8 ? "fp64" : "fp32", k.ni0, k.nq0, k.ni1, k.nq1,
+                      tr);
+    else if (k.dim == 3)
         std::snprintf(buf, sizeof buf, "%s 3D %dx%dx%d", k.sbytes == 8 ? "fp64" : "fp32", k.nq0, k.nq1, k.nq2);
     else
         std::snprintf(buf, sizeof buf, "%s 2D %dx%d", k.sbytes == 8 ? "fp64" : "fp32", k.nq0, k.nq1);

@@ -87,4 +87,75 @@ constexpr RtcCfg rtc_cfg(int dim, int nq0, int nq1, int nq2, int sbytes)
     return c;
 }
 
+// ---- sf_tensor_*: the wave kernels with independent input / output extents (hex_tensor_wave_kernel,
+// quad_tensor_wave_kernel of bwdtrans_aniso.h).  One function serves the ahead-of-time table (tensor_launch.h) and the
+// run-time specialisation (rtc.hip).  A first choice, not a tuned one: the rules of rtc_cfg with "points" read as "the
+// larger of the two images", so that ni = nq - 1, no = nq reproduces rtc_cfg (pinned below).
+constexpr int kTensorMaxExt3 = 16, kTensorMaxExt2 = 24; // extents per direction a specialisation takes, from 1
+
+// SweepGeom<DIM, EC, T, I0, O0, I1, O1, I2, O2>::SLAB (2D: ni[2] = no[2] = 1), vw = scalars per 16-byte lane
+constexpr int tensor_slab(int dim, const int (&ni)[3], const int (&no)[3], int ec, int vw)
+{
+    const int i2 = dim == 3 ? ni[2] : 1, o2 = dim == 3 ? no[2] : 1;
+    const int p0 = ec * i2 * ni[1], p1 = ec * no[0] * i2, p2 = ec * no[1] * no[0];
+    const int w2 = dim == 3 ? p2 * (i2 | 1) : 0;
+    const int slab0 = rtc_max(rtc_max(p0 * (ni[0] | 1), p1 * (ni[1] | 1)), w2);
+    return (rtc_max(slab0, ec * no[0] * no[1] * o2) + vw - 1) / vw * vw;
+}
+
+// elements per chunk for fp64: about 512 (3D) / 256 (2D) scalars of the larger image, in 2D at least 48 pencils in the
+// wider sweep
+constexpr int tensor_ec(int dim, const int (&ni)[3], const int (&no)[3])
+{
+    if (dim == 3)
+        return rtc_clamp(512 / rtc_max(ni[0] * ni[1] * ni[2], no[0] * no[1] * no[2]), 1, 8);
+    return rtc_clamp(rtc_max(256 / rtc_max(ni[0] * ni[1], no[0] * no[1]), rtc_cdiv(48, rtc_max(ni[1], no[0]))), 1, 16);
+}
+
+// 2D ignores ni[2] / no[2]; sbytes 8 (fp64) or 4 (fp32: twice the elements, the same bytes)
+constexpr RtcCfg tensor_cfg(int dim, const int (&ni)[3], const int (&no)[3], int sbytes)
+{
+    RtcCfg c{};
+    int mx = 1;
+    for (int d = 0; d < dim; ++d)
+        mx = rtc_max(mx, rtc_max(ni[d], no[d]));
+    c.ec    = tensor_ec(dim, ni, no) * (sbytes == 4 ? 2 : 1);
+    c.bmode = (mx <= 10 || sbytes == 4) ? kRtcBasisSmem : kRtcBasisCols;
+    c.minw  = 2;
+    c.xg    = 64;
+    c.slab  = tensor_slab(dim, ni, no, c.ec, 16 / sbytes);
+    c.wpb   = 4;
+    while (c.wpb > 1 && (size_t)sbytes * c.wpb * c.slab > (size_t)kRtcMaxLds)
+        c.wpb >>= 1;
+    c.lds = (size_t)sbytes * c.wpb * c.slab;
+    c.ok  = c.lds <= (size_t)kRtcMaxLds;
+    return c;
+}
+
+// ni = nq - 1, no = nq is rtc_cfg
+constexpr bool tensor_cfg_is_rtc_cfg(int dim, int nq0, int nq1, int nq2, int sbytes)
+{
+    const int ni[3] = {nq0 - 1, nq1 - 1, dim == 3 ? nq2 - 1 : 1}, no[3] = {nq0, nq1, dim == 3 ? nq2 : 1};
+    const RtcCfg a = tensor_cfg(dim, ni, no, sbytes), b = rtc_cfg(dim, nq0, nq1, nq2, sbytes);
+    return a.ec == b.ec && a.wpb == b.wpb && a.bmode == b.bmode && a.minw == b.minw && a.xg == b.xg && a.slab == b.slab &&
+           a.lds == b.lds && a.ok == b.ok;
+}
+constexpr bool tensor_cfg_is_rtc_cfg_everywhere()
+{
+    for (int s = 4; s <= 8; s += 4)
+    {
+        for (int a = 2; a <= kRtcMaxExt3; ++a)
+            for (int b = 2; b <= kRtcMaxExt3; ++b)
+                for (int c = 2; c <= kRtcMaxExt3; ++c)
+                    if (!tensor_cfg_is_rtc_cfg(3, a, b, c, s))
+                        return false;
+        for (int a = 2; a <= kRtcMaxExt2; ++a)
+            for (int b = 2; b <= kRtcMaxExt2; ++b)
+                if (!tensor_cfg_is_rtc_cfg(2, a, b, 0, s))
+                    return false;
+    }
+    return true;
+}
+static_assert(tensor_cfg_is_rtc_cfg_everywhere(), "tensor_cfg with ni = nq - 1, no = nq is rtc_cfg");
+
 } // namespace sf

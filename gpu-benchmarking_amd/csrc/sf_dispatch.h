@@ -84,6 +84,23 @@ template <int DIM, typename T> int launch_iprod_wave(unsigned nq, const ArgsT<DI
 template <int DIM, typename T> int launch_iprod_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, hipStream_t s);
 bool iprod_wave_built(int dim, unsigned nq);
 bool iprod_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
+// The tensor-product apply with independent input / output extents, out = (M2 (x) M1 (x) M0) in (tensor.hip,
+// tensor_quad.hip and their _f32 twins: the wave kernels of the table in tensor_launch.h; tensor_generic.hip: any extents
+// from 1 up to 16 per direction in 3D and 32 in 2D; rtc.hip: a wave kernel compiled at run time for one shape).  ni[2] and
+// no[2] are 1 in 2D; a.b0 .. a.b2 are the matrices, row-major ni x no (trans 0) or no x ni (trans 1); a.wsp is not used.
+template <int DIM, typename T>
+int launch_tensor_wave(const unsigned (&ni)[3], const unsigned (&no)[3], int trans, const ArgsT<DIM, T> &a, hipStream_t s);
+template <int DIM, typename T>
+int launch_tensor_generic(const unsigned (&ni)[3], const unsigned (&no)[3], int trans, const ArgsT<DIM, T> &a,
+                          hipStream_t s);
+bool tensor_wave_built(int dim, const unsigned (&ni)[3], const unsigned (&no)[3]);
+bool tensor_generic_built(int dim, const unsigned (&ni)[3], const unsigned (&no)[3]);
+int rtc_specialise_tensor(int dim, const unsigned (&ni)[3], const unsigned (&no)[3], int trans, int scalar_bytes);
+int rtc_tensor_state(int dim, const unsigned (&ni)[3], const unsigned (&no)[3], int trans, int scalar_bytes,
+                     uint64_t *launches);
+int launch_tensor_specialised(int dim, const unsigned (&ni)[3], const unsigned (&no)[3], int trans, int scalar_bytes,
+                              const void *m0, const void *m1, const void *m2, const void *in, void *out, uint64_t nelmt,
+                              hipStream_t s);
 // The fused mass operator B^T diag(w) B (mass.hip / mass_f32.hip: the wave kernels of mass_wave.h, 3D nq 2..11, 2D 2..16;
 // mass_generic.hip: any extents up to 16 per direction in 3D and 32 in 2D).  `w`: one weight per quadrature point per
 // element; a.wsp is not used.

@@ -926,6 +926,73 @@ int sf_assemble_f32(size_t nglobal, const int32_t *rows, const int32_t *perm, co
 int sf_gs_f64(size_t nglobal, const int32_t *rows, const int32_t *perm, const double *sign, double *local, void *stream);
 int sf_gs_f32(size_t nglobal, const int32_t *rows, const int32_t *perm, const float *sign, float *local, void *stream);
 
+/*
+ * TENSOR-PRODUCT APPLY with independent input and output extents: one small matrix per direction applied to every
+ * element, the input length ni_d and the output length no_d of a direction named separately.  What interpolation between
+ * point sets (n -> n), dealiasing and over-integration (n -> ceil(3n/2) and back), p-multigrid prolongation and
+ * restriction (nc -> nf and its transpose), and BwdTrans / IProductWRTBase with a quadrature order chosen independently
+ * of the polynomial order have in common.  Every other operator of this header keeps nm = nq - 1.
+ *   3D: out[e][k][j][i] = sum_r sum_q sum_p in[e][r][q][p] * M0(p,i) * M1(q,j) * M2(r,k)
+ *   2D: out[e][j][i]    = sum_q sum_p       in[e][q][p]    * M0(p,i) * M1(q,j)
+ *   trans = 0:  M_d(a,b) = m_d[a*no_d + b]   (row-major ni_d x no_d, the layout of a BwdTrans basis)
+ *   trans = 1:  M_d(a,b) = m_d[b*ni_d + a]   (row-major no_d x ni_d: the same array an IProductWRTBase reads)
+ * `in` holds ni0*ni1[*ni2] scalars per element, fastest index first; `out` holds no0*no1[*no2].  One `trans` serves
+ * every direction.  With A the operator of (ni, no, trans = 0, m), its transpose A^T is (no, ni, trans = 1, m): the same
+ * arrays.
+ * Order of operations (it defines the rounding and is the same in every kernel of the family): direction 0, then 1, then
+ * 2; every sum in ascending summed index; the first term a multiplication, the rest FMAs.  Hence, by value: with
+ * ni = nq - 1, no = nq, trans = 0 the result equals sf_bwdtrans_*; with ni = nq, no = nq - 1, trans = 1 it equals
+ * sf_iproduct_*; and every route below gives the same bits.
+ * Routes.  SF_VARIANT_AUTO with 16-byte-aligned in / out: (1) the compiled table of wave kernels -- isotropic pairs, every
+ * direction the same, both trans: 3D n -> n for n 2..8, n -> ceil(3n/2) and ceil(3n/2) -> n for n 2..6; 2D n -> n for
+ * n 2..16, the 3/2 pairs for n 2..10; (2) a specialisation the caller made ready with sf_specialise_tensor(); (3) the
+ * any-extent kernel.  in / out aligned only to the scalar take the any-extent kernel.  SF_VARIANT_WAVE runs the table
+ * only: SF_ENOTBUILT off it, SF_EALIGN unless in / out are 16-byte aligned.  SF_VARIANT_GENERIC (one workgroup per
+ * element, latency-bound) takes extents from 1 up to 16 per direction in 3D and 32 in 2D, input and output independently;
+ * beyond, SF_ENOTBUILT on every route.  Any other variant: SF_ENOTBUILT.  The launch configurations of the table are a
+ * first choice (one rule for every shape), not tuned ones; a pair whose kernel needed scratch under that rule would get
+ * smaller chunks or leave the table -- no kernel ships with scratch.  The matrices need only scalar alignment.
+ * Validation, before any HIP call, in this order: (1) an extent of 0, trans other than 0 / 1 or a variant outside
+ * [0, SF_NUM_VARIANTS): SF_EINVAL; (2) nelmt == 0: SF_OK; (3) a null matrix, in or out: SF_EINVAL; (4) any of them not
+ * scalar-aligned: SF_EALIGN; (5) extents beyond the any-extent kernel's bounds: SF_ENOTBUILT; (6) `out` overlapping `in`,
+ * compared as byte ranges of their full sizes: SF_EINVAL; (7) an unsupported variant: SF_ENOTBUILT.
+ * NOT in-place safe (overlap is refused, not undefined).  No workspace, no allocation: every call is a single kernel
+ * node, capture-safe from the process's first call.
+ */
+int sf_tensor_hex_f64(unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1, unsigned no2, int trans,
+                      size_t nelmt, const double *m0, const double *m1, const double *m2, const double *in, double *out,
+                      void *stream);
+int sf_tensor_hex_f64_variant(int variant, unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1,
+                              unsigned no2, int trans, size_t nelmt, const double *m0, const double *m1, const double *m2,
+                              const double *in, double *out, void *stream);
+int sf_tensor_quad_f64(unsigned ni0, unsigned ni1, unsigned no0, unsigned no1, int trans, size_t nelmt, const double *m0,
+                       const double *m1, const double *in, double *out, void *stream);
+int sf_tensor_quad_f64_variant(int variant, unsigned ni0, unsigned ni1, unsigned no0, unsigned no1, int trans, size_t nelmt,
+                               const double *m0, const double *m1, const double *in, double *out, void *stream);
+/* T = float: the same routes and variants (m / in / out 4-byte aligned) */
+int sf_tensor_hex_f32(unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1, unsigned no2, int trans,
+                      size_t nelmt, const float *m0, const float *m1, const float *m2, const float *in, float *out,
+                      void *stream);
+int sf_tensor_hex_f32_variant(int variant, unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1,
+                              unsigned no2, int trans, size_t nelmt, const float *m0, const float *m1, const float *m2,
+                              const float *in, float *out, void *stream);
+int sf_tensor_quad_f32(unsigned ni0, unsigned ni1, unsigned no0, unsigned no1, int trans, size_t nelmt, const float *m0,
+                       const float *m1, const float *in, float *out, void *stream);
+int sf_tensor_quad_f32_variant(int variant, unsigned ni0, unsigned ni1, unsigned no0, unsigned no1, int trans, size_t nelmt,
+                               const float *m0, const float *m1, const float *in, float *out, void *stream);
+/* Compile (once per process) and load (once per device) the wave kernel of one tensor shape, as sf_specialise() does for
+ * BwdTrans and under keys of its own: dim 2 or 3 (dim 2 ignores ni2 / no2), every extent 1..16 in 3D and 1..24 in 2D,
+ * trans 0 / 1, scalar_bytes 8 or 4; anything else SF_EINVAL.  SF_OK: ready, AUTO calls of sf_tensor_* on that shape with
+ * 16-byte-aligned in / out launch it (and count the launch) unless the compiled table holds the shape.  SF_ECOMPILE: the
+ * shape is refused -- one wave's LDS slab would exceed 64 KiB, the kernel would need scratch, hiprtc is missing, or a
+ * stream capture is under way on the device (nothing is compiled then) -- and AUTO keeps the any-extent kernel.  Never
+ * called behind a launch.  The log is sf_last_specialise_log(); sf_shutdown() unloads the modules.
+ * sf_tensor_specialisation_state: 0 none, 1 ready, SF_ECOMPILE refused; *launches (may be NULL) the launches so far. */
+int sf_specialise_tensor(int dim, unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1, unsigned no2,
+                         int trans, int scalar_bytes);
+int sf_tensor_specialisation_state(int dim, unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1,
+                                   unsigned no2, int trans, int scalar_bytes, uint64_t *launches);
+
 #ifdef __cplusplus
 }
 #endif
