@@ -565,6 +565,83 @@ def geom_quad(nq, basis0, basis1, deriv0, deriv1, qw0, qw1, x, outputs=GEOM_OUTP
     return _geom("geom_quad", nq, (basis0, basis1), (deriv0, deriv1), (qw0, qw1), x, outputs, out, variant, stream)
 
 
+def _byte_range(t):
+    return t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
+
+
+def _advect(what, nq, bases, derivs, df, w, c, inp, out, variant, stream):
+    """The one call path of advect_*: the number of fields, sizes, dtypes, devices and overlap are checked here (before any
+    library call), pointers and alignment in the C ABI."""
+    nq = tuple(int(q) for q in nq)
+    d = len(nq)
+    nmt, nqt = 1, 1
+    for q in nq:
+        nmt, nqt = nmt * (q - 1), nqt * q
+    if nmt <= 0:
+        raise capi.SumfactError(capi.SF_EINVAL, what)
+    if isinstance(inp, torch.Tensor):
+        nf = inp.shape[0] if inp.dim() == 2 else 1
+    else:
+        inp = list(inp)
+        nf = len(inp)
+    if nf not in (1, d):
+        raise capi.SumfactError(capi.SF_EINVAL, f"{what}: {nf} fields, not 1 or {d}")
+    ins = _input_parts(what, inp, nf)
+    first = ins[0]
+    nelmt = first.numel() // nmt
+    if nelmt * nmt != first.numel():
+        raise ValueError(f"{what}: in_a.numel() is not a multiple of the modes per element ({nmt})")
+    if isinstance(c, torch.Tensor) and c.numel() != d * nelmt * nqt:
+        raise ValueError(f"{what}: c has {c.numel()} values, not {d} x {nelmt * nqt}")
+    cs = _input_parts(what, c, d)
+    ret, outs = _output_parts(what, out, nf, nelmt * nmt, first)
+    operands = [(f"basis{a}", b, (q - 1) * q, False) for a, (b, q) in enumerate(zip(bases, nq))]
+    operands += _per_direction("deriv", derivs, lambda q: q * q, nq)
+    operands += [("df", df, nelmt * d * d * nqt, False), ("w", w, nelmt * nqt, False)]
+    operands += [(f"c{j}", t, nelmt * nqt, False) for j, t in enumerate(cs)]
+    _check_operands(what, operands + [(f"out{a}", t, nelmt * nmt, False) for a, t in enumerate(outs)], first)
+    # an output may not overlap what the call reads or another output
+    reads = [(name, t) for name, t, _, _ in operands] + [(f"in{a}", t) for a, t in enumerate(ins)]
+    for a, o in enumerate(outs):
+        lo, hi = _byte_range(o)
+        for name, t in reads + [(f"out{f}", outs[f]) for f in range(a)]:
+            tl, th = _byte_range(t)
+            if lo < th and tl < hi:
+                raise capi.SumfactError(capi.SF_EINVAL, f"{what}: out{a} overlaps {name}")
+    f32 = first.dtype == torch.float32
+    dtype = torch.float32 if f32 else torch.float64
+    v = _variant(variant)
+    if f32 and v != VARIANTS["auto"]:
+        raise ValueError(f"{what}: float32 has the AUTO route only")
+    fn = getattr(capi.lib(), f"sf_{what}_{'f32' if f32 else 'f64_variant'}")
+    ptrs = [_dev_ptr(t, name, dtype) for name, t, _, _ in operands]
+    ptrs += [_dev_ptr(t, f"in{a}", dtype) for a, t in enumerate(ins)] + [None] * (d - nf)
+    ptrs += [_dev_ptr(t, f"out{a}", dtype) for a, t in enumerate(outs)] + [None] * (d - nf)
+    with torch.cuda.device(first.device):
+        rc = fn(*(() if f32 else (v,)), *nq, nelmt, nf, *ptrs, _stream(stream, first.device))
+    capi.check(rc, what)
+    return ret
+
+
+def advect_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, df, w, c, inp, out=None, variant="auto", stream=None):
+    """The weak advection term (c . grad) u tested against the basis, in one kernel on inp's device: with u_a = B in_a and
+    J[a][b] = D_b u_a, beta_b = sum_j c[j] df[3 j + b] and r_a = w (sum_b beta_b J[a][b]) per point, out[a] = B^T r_a.  The
+    bases and derivative matrices of helmholtz_hex; df the nine planes of physderiv_hex / geom_hex, w the weight plane of
+    mass_hex / geom_hex; c a (3, nelmt * nq0*nq1*nq2) tensor with contiguous rows or a sequence of three flat tensors, the
+    advecting velocity at the quadrature points in the layout of bwdtrans_hex's output; inp a (nf, nelmt * nm0*nm1*nm2)
+    tensor with contiguous rows or a sequence of nf flat tensors, nf = 1 (scalar transport; a flat tensor is one field) or
+    3 (a vector field: one read of df, w, c for all three).  Returns a (nf, nelmt * nm0*nm1*nm2) tensor, rows aligned as
+    physderiv_hex returns them; `out` may be such a tensor or a sequence of nf flat tensors (then returned as a tuple).
+    No output may overlap an input or another output.  float64 takes variant "auto", "wave" or "generic"; float32 the AUTO
+    route.  A plain function: no autograd."""
+    return _advect("advect_hex", nq, (basis0, basis1, basis2), (deriv0, deriv1, deriv2), df, w, c, inp, out, variant, stream)
+
+
+def advect_quad(nq, basis0, basis1, deriv0, deriv1, df, w, c, inp, out=None, variant="auto", stream=None):
+    """The weak advection term in 2D: four planes of df (c = 2 a + b), two planes of c, nf = 1 or 2 fields."""
+    return _advect("advect_quad", nq, (basis0, basis1), (deriv0, deriv1), df, w, c, inp, out, variant, stream)
+
+
 def _geom_affine(what, nq, bases, derivs, x, stream):
     d = len(nq)
     per = {"dfe": d * d, "ge": d * (d + 1) // 2, "je": 1}

@@ -92,6 +92,18 @@ def _geom_symbols():
 SYMBOLS.update(_geom_symbols())
 
 
+def _advect_symbols():
+    """sf_advect_{hex,quad}_{f64,f64_variant,f32}: [variant,] the extents, nelmt, nf, basis / deriv per direction, df, w,
+    c_j per direction, in_a and out_a per direction, stream."""
+    for shape, dim in (("hex", 3), ("quad", 2)):
+        for sfx in ("f64", "f64_variant", "f32"):
+            head = [_i] if sfx == "f64_variant" else []
+            yield f"sf_advect_{shape}_{sfx}", (_i, head + [_u] * dim + [_sz, _u] + [_vp] * (5 * dim + 2) + [_vp])
+
+
+SYMBOLS.update(_advect_symbols())
+
+
 def _tensor_symbols():
     """sf_tensor_{hex,quad}_{f64,f64_variant,f32,f32_variant}: [variant,] the input extents, the output extents, trans,
     nelmt, one matrix per direction, in, out, stream; sf_specialise_tensor / sf_tensor_specialisation_state: dim, three

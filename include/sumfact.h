@@ -880,6 +880,70 @@ int sf_geom_affine_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const floa
                             float *dfe, float *ge, float *je, void *stream);
 
 /*
+ * THE WEAK ADVECTION TERM (c . grad) u tested against the basis, for nf = 1 or d fields, in ONE kernel: the first-order
+ * term of an advection-diffusion or Navier-Stokes step and of an Oseen operator.  For every element e and field a:
+ *   u_a      = B in_a[e]                              forward sweeps p -> i, q -> j, r -> k, as BwdTrans
+ *   J[a][b]  = D_b u_a                                collocation derivative, b = 0 .. d-1
+ *   beta_b   = sum_j c_j[e] * df[e][j*d + b]          per point; j ascending
+ *   r_a      = w[e] * (sum_b beta_b * J[a][b])        per point; b ascending, then one multiply by w
+ *   out_a[e] = B^T r_a                                transposed sweeps k -> r', j -> q', i -> p', as IProductWRTBase
+ * df: the d*d planes of the inverse Jacobian in the layout of sf_physderiv_* / sf_geom_* (c = a*d + b for
+ * d xi_b / d x_a); w: the weight plane of sf_mass_* / sf_geom_*; c_j: d planes of the advecting velocity at the
+ * quadrature points, each laid out like the output of BwdTrans (from sf_bwdtrans_* of a modal velocity, or from anywhere
+ * else); in_a / out_a: nm0*nm1[*nm2] modes per element, nm_d = nq_d - 1, the layout of `in` of every other call.
+ * nf = 1 is scalar transport: in1.. / out1.. are ignored, may be NULL and are never written.  nf = d advects a vector
+ * field: all d fields share one read of df, w and c.  Any other nf: SF_EINVAL.  All of df, w, c_j are required.
+ * Per element the call moves (d*d + d + 1) nq^d + 2 nf nm^d scalars; no point image reaches HBM.
+ * Summation order (it defines the rounding; every sum in ascending index, the first product a multiply, then FMAs; the
+ * wave kernels and the fallback follow it alike, bit for bit): the five lines above, in that order.  beta is formed
+ * first on purpose: d*d FMAs per point shared by the fields.  out_a of a call with nf = 1 and in = in_a equals out_a of
+ * the call with nf = d bit for bit.
+ * Routes, as sf_physderiv_*: SF_VARIANT_AUTO runs the fused wave kernel for the isotropic orders of its table (3D nq
+ * 2..8, 2D nq 2..16) when every in_a and out_a (a < nf) are 16-byte aligned, else GENERIC; SF_VARIANT_WAVE returns
+ * SF_ENOTBUILT off that table and SF_EALIGN unless they are 16-byte aligned; SF_VARIANT_GENERIC (one workgroup per
+ * element, latency-bound) takes any extents up to 12 per direction in 3D and 32 in 2D; any other variant SF_ENOTBUILT,
+ * extents beyond those bounds SF_ENOTBUILT.  df, w, c_j, the bases and the derivative matrices need only scalar
+ * alignment on every route.
+ * Validation, before any HIP call, in this order: (1) an extent < 2, a variant outside [0, SF_NUM_VARIANTS) or nf other
+ * than 1 or d: SF_EINVAL; (2) nelmt == 0: SF_OK; (3) a null basis, deriv, df, w, c_j, or in_a / out_a with a < nf:
+ * SF_EINVAL; (4) any of them not scalar-aligned: SF_EALIGN; (5) any out_a overlapping anything the call reads or another
+ * out_a, compared as byte ranges of their full sizes: SF_EINVAL; (6) extents beyond the fallback's bounds: SF_ENOTBUILT;
+ * (7) an unsupported variant: SF_ENOTBUILT.
+ * NOT in-place safe: an overlapping output is refused, not undefined; the inputs may overlap each other.
+ * No internal workspace and no allocation: every call is a single kernel node, capture-safe from the process's first
+ * call.
+ */
+int sf_advect_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, unsigned nf,
+                      const double *basis0, const double *basis1, const double *basis2,
+                      const double *deriv0, const double *deriv1, const double *deriv2,
+                      const double *df, const double *w, const double *c0, const double *c1, const double *c2,
+                      const double *in0, const double *in1, const double *in2,
+                      double *out0, double *out1, double *out2, void *stream);
+int sf_advect_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, unsigned nf,
+                              const double *basis0, const double *basis1, const double *basis2,
+                              const double *deriv0, const double *deriv1, const double *deriv2,
+                              const double *df, const double *w, const double *c0, const double *c1, const double *c2,
+                              const double *in0, const double *in1, const double *in2,
+                              double *out0, double *out1, double *out2, void *stream);
+int sf_advect_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf, const double *basis0,
+                       const double *basis1, const double *deriv0, const double *deriv1, const double *df,
+                       const double *w, const double *c0, const double *c1, const double *in0, const double *in1,
+                       double *out0, double *out1, void *stream);
+int sf_advect_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf,
+                               const double *basis0, const double *basis1, const double *deriv0, const double *deriv1,
+                               const double *df, const double *w, const double *c0, const double *c1,
+                               const double *in0, const double *in1, double *out0, double *out1, void *stream);
+/* T = float (AUTO route; every array 4-byte aligned) */
+int sf_advect_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, unsigned nf, const float *basis0,
+                      const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
+                      const float *deriv2, const float *df, const float *w, const float *c0, const float *c1,
+                      const float *c2, const float *in0, const float *in1, const float *in2, float *out0,
+                      float *out1, float *out2, void *stream);
+int sf_advect_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf, const float *basis0, const float *basis1,
+                       const float *deriv0, const float *deriv1, const float *df, const float *w, const float *c0,
+                       const float *c1, const float *in0, const float *in1, float *out0, float *out1, void *stream);
+
+/*
  * GATHER-SCATTER between the element-local coefficients the operators above work on and the global degrees of freedom
  * of a continuous-Galerkin space: with Q the nlocal x nglobal matrix of a local-to-global map, global_to_local applies
  * Q, assemble Q^T and gs Q Q^T, so that  A = Q^T blockdiag(H_e) Q  is  global_to_local -> sf_helmholtz_* -> assemble,
