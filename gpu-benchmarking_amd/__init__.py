@@ -26,6 +26,6 @@ from .bwdtrans import (  # noqa: F401
     diag_tables, diag_helmholtz_hex, diag_helmholtz_quad,
     GsMap, gs_setup, global_to_local, assemble, gs,
     geom_hex, geom_quad, geom_affine_hex, geom_affine_quad, GEOM_OUTPUTS,
-    advect_hex, advect_quad,
+    advect_hex, advect_quad, affine_advect_hex, affine_advect_quad,
     tensor_hex, tensor_quad, specialise_tensor, tensor_specialisation_state, tensor_autograd,
 )

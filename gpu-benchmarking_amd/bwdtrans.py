@@ -569,9 +569,14 @@ def _byte_range(t):
     return t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
 
 
-def _advect(what, nq, bases, derivs, df, w, c, inp, out, variant, stream):
-    """The one call path of advect_*: the number of fields, sizes, dtypes, devices and overlap are checked here (before any
-    library call), pointers and alignment in the C ABI."""
+def _advect_planes(d, df, w):
+    return lambda nelmt, nqt: [("df", df, nelmt * d * d * nqt, False), ("w", w, nelmt * nqt, False)]
+
+
+def _advect(what, nq, bases, derivs, geometry, c, inp, out, variant, stream):
+    """The one call path of advect_* and affine_advect_*: the number of fields, sizes, dtypes, devices and overlap are
+    checked here (before any library call), pointers and alignment in the C ABI.  geometry(nelmt, nqt): the operands
+    between the derivative matrices and c, as _check_operands takes them; one that is None and may be goes as NULL."""
     nq = tuple(int(q) for q in nq)
     d = len(nq)
     nmt, nqt = 1, 1
@@ -597,11 +602,11 @@ def _advect(what, nq, bases, derivs, df, w, c, inp, out, variant, stream):
     ret, outs = _output_parts(what, out, nf, nelmt * nmt, first)
     operands = [(f"basis{a}", b, (q - 1) * q, False) for a, (b, q) in enumerate(zip(bases, nq))]
     operands += _per_direction("deriv", derivs, lambda q: q * q, nq)
-    operands += [("df", df, nelmt * d * d * nqt, False), ("w", w, nelmt * nqt, False)]
+    operands += geometry(nelmt, nqt)
     operands += [(f"c{j}", t, nelmt * nqt, False) for j, t in enumerate(cs)]
     _check_operands(what, operands + [(f"out{a}", t, nelmt * nmt, False) for a, t in enumerate(outs)], first)
     # an output may not overlap what the call reads or another output
-    reads = [(name, t) for name, t, _, _ in operands] + [(f"in{a}", t) for a, t in enumerate(ins)]
+    reads = [(name, t) for name, t, _, _ in operands if t is not None] + [(f"in{a}", t) for a, t in enumerate(ins)]
     for a, o in enumerate(outs):
         lo, hi = _byte_range(o)
         for name, t in reads + [(f"out{f}", outs[f]) for f in range(a)]:
@@ -613,8 +618,8 @@ def _advect(what, nq, bases, derivs, df, w, c, inp, out, variant, stream):
     v = _variant(variant)
     if f32 and v != VARIANTS["auto"]:
         raise ValueError(f"{what}: float32 has the AUTO route only")
-    fn = getattr(capi.lib(), f"sf_{what}_{'f32' if f32 else 'f64_variant'}")
-    ptrs = [_dev_ptr(t, name, dtype) for name, t, _, _ in operands]
+    fn = getattr(capi.lib(), f"sf_{what.replace('affine_', 'aff_')}_{'f32' if f32 else 'f64_variant'}")
+    ptrs = [None if t is None else _dev_ptr(t, name, dtype) for name, t, _, _ in operands]
     ptrs += [_dev_ptr(t, f"in{a}", dtype) for a, t in enumerate(ins)] + [None] * (d - nf)
     ptrs += [_dev_ptr(t, f"out{a}", dtype) for a, t in enumerate(outs)] + [None] * (d - nf)
     with torch.cuda.device(first.device):
@@ -634,12 +639,42 @@ def advect_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, df, w, c, inp
     physderiv_hex returns them; `out` may be such a tensor or a sequence of nf flat tensors (then returned as a tuple).
     No output may overlap an input or another output.  float64 takes variant "auto", "wave" or "generic"; float32 the AUTO
     route.  A plain function: no autograd."""
-    return _advect("advect_hex", nq, (basis0, basis1, basis2), (deriv0, deriv1, deriv2), df, w, c, inp, out, variant, stream)
+    return _advect("advect_hex", nq, (basis0, basis1, basis2), (deriv0, deriv1, deriv2), _advect_planes(3, df, w), c, inp,
+                   out, variant, stream)
 
 
 def advect_quad(nq, basis0, basis1, deriv0, deriv1, df, w, c, inp, out=None, variant="auto", stream=None):
     """The weak advection term in 2D: four planes of df (c = 2 a + b), two planes of c, nf = 1 or 2 fields."""
-    return _advect("advect_quad", nq, (basis0, basis1), (deriv0, deriv1), df, w, c, inp, out, variant, stream)
+    return _advect("advect_quad", nq, (basis0, basis1), (deriv0, deriv1), _advect_planes(2, df, w), c, inp, out, variant,
+                   stream)
+
+
+def _advect_constants(nq, qws, dfe, je):
+    d = len(nq)
+    unweighted = je is None             # the quadrature weights are then never read and may be None as well
+    return lambda nelmt, nqt: (
+        [(f"qw{i}", t, int(q), unweighted) for i, (t, q) in enumerate(zip(qws, nq))]
+        + [("dfe", dfe, nelmt * d * d, False), ("je", je, nelmt, True)])
+
+
+def affine_advect_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, qw0, qw1, qw2, dfe, je, c, inp, out=None,
+                      variant="auto", stream=None):
+    """advect_hex on affine elements in one kernel: beta_b = sum_j c[j] dfe[e][3 j + b] and r_a = (je[e] qw2[k] (qw1[j]
+    qw0[i])) (sum_b beta_b J[a][b]) per point, out[a] = B^T r_a.  qw_d the one-dimensional quadrature weights and je[e] =
+    |det J| as in affine_iprodderiv_hex, dfe the nine constants per element of affine_physderiv_hex / geom_affine_hex
+    (required).  je=None: no weight at all, je and qw_d are never read (qw_d may then be None too).  With je, bit for bit
+    advect_hex on df planes filled with the constants and w = je * (qw2 * (qw1 * qw0)); without, advect_hex with w a plane
+    of ones.  c, inp, out, nf and variants as advect_hex.  A plain function: no autograd."""
+    return _advect("affine_advect_hex", nq, (basis0, basis1, basis2), (deriv0, deriv1, deriv2),
+                   _advect_constants(nq, (qw0, qw1, qw2), dfe, je), c, inp, out, variant, stream)
+
+
+def affine_advect_quad(nq, basis0, basis1, deriv0, deriv1, qw0, qw1, dfe, je, c, inp, out=None, variant="auto",
+                       stream=None):
+    """advect_quad on affine elements: four constants per element (c = 2 a + b), je[e] or None (then qw_d are never read),
+    two planes of c, nf = 1 or 2 fields."""
+    return _advect("affine_advect_quad", nq, (basis0, basis1), (deriv0, deriv1), _advect_constants(nq, (qw0, qw1), dfe, je),
+                   c, inp, out, variant, stream)
 
 
 def _geom_affine(what, nq, bases, derivs, x, stream):

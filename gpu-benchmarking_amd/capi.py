@@ -104,6 +104,18 @@ def _advect_symbols():
 SYMBOLS.update(_advect_symbols())
 
 
+def _affine_advect_symbols():
+    """sf_aff_advect_{hex,quad}_{f64,f64_variant,f32}: [variant,] the extents, nelmt, nf, basis / deriv / qw per direction,
+    dfe, je, c_j per direction, in_a and out_a per direction, stream."""
+    for shape, dim in (("hex", 3), ("quad", 2)):
+        for sfx in ("f64", "f64_variant", "f32"):
+            head = [_i] if sfx == "f64_variant" else []
+            yield f"sf_aff_advect_{shape}_{sfx}", (_i, head + [_u] * dim + [_sz, _u] + [_vp] * (6 * dim + 2) + [_vp])
+
+
+SYMBOLS.update(_affine_advect_symbols())
+
+
 def _tensor_symbols():
     """sf_tensor_{hex,quad}_{f64,f64_variant,f32,f32_variant}: [variant,] the input extents, the output extents, trans,
     nelmt, one matrix per direction, in, out, stream; sf_specialise_tensor / sf_tensor_specialisation_state: dim, three

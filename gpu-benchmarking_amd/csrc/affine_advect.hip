@@ -1,0 +1,20 @@
+// affine_advect.hip -- fp64 instantiations of the affine advection kernels (affine_advect_wave.h) + nq dispatch;
+// configuration in affine_advect_launch.h.  The fp32 instantiations are in affine_advect_f32.hip (the two halves build in
+// parallel).
+#include "affine_advect_launch.h"
+
+namespace sf
+{
+
+template int launch_affine_advect_wave<3, double>(unsigned, const HexArgs &, const AffineAdvectArgsT<double> &,
+                                                  hipStream_t);
+template int launch_affine_advect_wave<2, double>(unsigned, const QuadArgs &, const AffineAdvectArgsT<double> &,
+                                                  hipStream_t);
+
+// the Helmholtz table: 3D isotropic nq 2..8, 2D isotropic nq 2..16
+bool affine_advect_wave_built(int dim, unsigned nq)
+{
+    return nq >= 2 && nq <= (dim == 3 ? 8u : 16u);
+}
+
+} // namespace sf

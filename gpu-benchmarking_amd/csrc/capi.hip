@@ -12,8 +12,10 @@
 // global degrees of freedom in gs.hip, the tensor-product apply with independent input / output extents (tensor below) in
 // tensor.hip / tensor_quad.hip / tensor_f32.hip / tensor_quad_f32.hip / tensor_generic.hip / rtc.hip, the geometric factors from element coordinates (geom, geom_affine below; their
 // launchers are declared in geom_args.h) in geom.hip / geom_f32.hip / geom_generic.hip, the weak advection term (advect
-// below; advect_args.h) in advect.hip / advect_f32.hip / advect_generic.hip.
+// below; advect_args.h) in advect.hip / advect_f32.hip / advect_generic.hip, its affine-element form (affine_advect below;
+// affine_advect_args.h) in affine_advect.hip / affine_advect_f32.hip / affine_advect_generic.hip.
 #include "advect_args.h"
+#include "affine_advect_args.h"
 #include "geom_args.h"
 #include "sf_dispatch.h"
 
@@ -613,6 +615,56 @@ static int advect(int variant, const unsigned (&nq)[3], size_t nelmt, unsigned n
         variant, nq, advect_generic_built(DIM, nq[0], nq[1], nq[2]), advect_wave_built(DIM, nq[0]), (const void *)in_bits,
         (const void *)out_bits, [&] { return launch_advect_wave<DIM, T>(nq[0], a, x, s); },
         [&] { return launch_advect_generic<DIM, T>(nq, a, x, s); });
+}
+
+// ---- the weak advection term on affine elements: one validation and routing for both dimensions and scalar types -------
+// The order of sf_advect_*, with dfe (required) in the place of df and the quadrature weights and je in the place of w:
+// `je` and every `qw` are looked at only when je is not null.  Every in_a and out_a that the call takes (a < nf) is a
+// 16-byte stream of the wave kernels; those with a >= nf are not looked at.
+template <int DIM, typename T>
+static int affine_advect(int variant, const unsigned (&nq)[3], size_t nelmt, unsigned nf, const T *const (&b)[3],
+                         const T *const (&d)[3], const T *const (&qw)[3], const T *dfe, const T *je,
+                         const T *const (&c)[3], const T *const (&in)[3], T *const (&out)[3], void *stream)
+{
+    const bool has_w = je != nullptr;
+    const bool nf_ok = nf == 1 || nf == (unsigned)DIM;
+    const T *i1 = nf_ok && nf > 1 ? in[1] : in[0], *i2 = nf_ok && nf > 2 ? in[2] : in[0];
+    T *o1 = nf_ok && nf > 1 ? out[1] : out[0], *o2 = nf_ok && nf > 2 ? out[2] : out[0];
+    const int rc = validate(range_ok<DIM>(variant, nq) && nf_ok, nelmt,
+                            {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], dfe, c[0], c[1],
+                             DIM == 3 ? c[2] : c[0], in[0], i1, i2, out[0], o1, o2, has_w ? qw[0] : dfe,
+                             has_w ? qw[1] : dfe, has_w && DIM == 3 ? qw[2] : dfe, has_w ? je : dfe},
+                            sizeof(T));
+    if (rc != kProceed)
+        return rc;
+    // an output may not overlap what the call reads or another output
+    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
+    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
+    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
+    uintptr_t in_bits = 0, out_bits = 0; // 16-byte aligned exactly when every stream is
+    for (unsigned a = 0; a < nf; ++a)
+    {
+        if (overlaps(out[a], modes_bytes, dfe, sizeof(T) * nelmt * DIM * DIM) ||
+            (has_w && overlaps(out[a], modes_bytes, je, sizeof(T) * nelmt)))
+            return SF_EINVAL;
+        for (int j = 0; j < DIM; ++j)
+            if (overlaps(out[a], modes_bytes, c[j], points_bytes))
+                return SF_EINVAL;
+        for (unsigned f = 0; f < nf; ++f)
+            if (overlaps(out[a], modes_bytes, in[f], modes_bytes) || (f < a && overlaps(out[a], modes_bytes, out[f], modes_bytes)))
+                return SF_EINVAL;
+        in_bits |= (uintptr_t)in[a];
+        out_bits |= (uintptr_t)out[a];
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    const auto a        = make_args<DIM, T>(b, nullptr, nullptr, nullptr, nelmt);
+    const AffineAdvectArgsT<T> x{d[0], d[1], d[2], has_w ? qw[0] : nullptr, has_w ? qw[1] : nullptr,
+                                 has_w ? qw[2] : nullptr, dfe, je, c[0], c[1], c[2], in[0], i1, i2, out[0], o1, o2,
+                                 (int)nf};
+    return route<DIM>(
+        variant, nq, affine_advect_generic_built(DIM, nq[0], nq[1], nq[2]), affine_advect_wave_built(DIM, nq[0]),
+        (const void *)in_bits, (const void *)out_bits, [&] { return launch_affine_advect_wave<DIM, T>(nq[0], a, x, s); },
+        [&] { return launch_affine_advect_generic<DIM, T>(nq, a, x, s); });
 }
 
 // ---- gather-scatter: the checks of the four calls, in the order include/sumfact.h documents --------------------------
@@ -1365,6 +1417,74 @@ int sf_advect_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf, co
 {
     return advect<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, nf, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
                             df, w, {c0, c1, nullptr}, {in0, in1, nullptr}, {out0, out1, nullptr}, stream);
+}
+
+// ---- the weak advection term on affine elements, out_a = B^T [(je q) (c . grad) B in_a], nf = 1 or d fields ---------
+int sf_aff_advect_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, unsigned nf,
+                                  const double *basis0, const double *basis1, const double *basis2,
+                                  const double *deriv0, const double *deriv1, const double *deriv2, const double *qw0,
+                                  const double *qw1, const double *qw2, const double *dfe, const double *je,
+                                  const double *c0, const double *c1, const double *c2, const double *in0,
+                                  const double *in1, const double *in2, double *out0, double *out1, double *out2,
+                                  void *stream)
+{
+    return affine_advect<3, double>(variant, {nq0, nq1, nq2}, nelmt, nf, {basis0, basis1, basis2},
+                                    {deriv0, deriv1, deriv2}, {qw0, qw1, qw2}, dfe, je, {c0, c1, c2}, {in0, in1, in2},
+                                    {out0, out1, out2}, stream);
+}
+
+int sf_aff_advect_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, unsigned nf, const double *basis0,
+                          const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
+                          const double *deriv2, const double *qw0, const double *qw1, const double *qw2,
+                          const double *dfe, const double *je, const double *c0, const double *c1, const double *c2,
+                          const double *in0, const double *in1, const double *in2, double *out0, double *out1,
+                          double *out2, void *stream)
+{
+    return affine_advect<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, nf, {basis0, basis1, basis2},
+                                    {deriv0, deriv1, deriv2}, {qw0, qw1, qw2}, dfe, je, {c0, c1, c2}, {in0, in1, in2},
+                                    {out0, out1, out2}, stream);
+}
+
+int sf_aff_advect_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf,
+                                   const double *basis0, const double *basis1, const double *deriv0,
+                                   const double *deriv1, const double *qw0, const double *qw1, const double *dfe,
+                                   const double *je, const double *c0, const double *c1, const double *in0,
+                                   const double *in1, double *out0, double *out1, void *stream)
+{
+    return affine_advect<2, double>(variant, {nq0, nq1, 0u}, nelmt, nf, {basis0, basis1, nullptr},
+                                    {deriv0, deriv1, nullptr}, {qw0, qw1, nullptr}, dfe, je, {c0, c1, nullptr},
+                                    {in0, in1, nullptr}, {out0, out1, nullptr}, stream);
+}
+
+int sf_aff_advect_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf, const double *basis0,
+                           const double *basis1, const double *deriv0, const double *deriv1, const double *qw0,
+                           const double *qw1, const double *dfe, const double *je, const double *c0, const double *c1,
+                           const double *in0, const double *in1, double *out0, double *out1, void *stream)
+{
+    return affine_advect<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, nf, {basis0, basis1, nullptr},
+                                    {deriv0, deriv1, nullptr}, {qw0, qw1, nullptr}, dfe, je, {c0, c1, nullptr},
+                                    {in0, in1, nullptr}, {out0, out1, nullptr}, stream);
+}
+
+int sf_aff_advect_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, unsigned nf, const float *basis0,
+                          const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
+                          const float *deriv2, const float *qw0, const float *qw1, const float *qw2, const float *dfe,
+                          const float *je, const float *c0, const float *c1, const float *c2, const float *in0,
+                          const float *in1, const float *in2, float *out0, float *out1, float *out2, void *stream)
+{
+    return affine_advect<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, nf, {basis0, basis1, basis2},
+                                   {deriv0, deriv1, deriv2}, {qw0, qw1, qw2}, dfe, je, {c0, c1, c2}, {in0, in1, in2},
+                                   {out0, out1, out2}, stream);
+}
+
+int sf_aff_advect_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf, const float *basis0,
+                           const float *basis1, const float *deriv0, const float *deriv1, const float *qw0,
+                           const float *qw1, const float *dfe, const float *je, const float *c0, const float *c1,
+                           const float *in0, const float *in1, float *out0, float *out1, void *stream)
+{
+    return affine_advect<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, nf, {basis0, basis1, nullptr},
+                                   {deriv0, deriv1, nullptr}, {qw0, qw1, nullptr}, dfe, je, {c0, c1, nullptr},
+                                   {in0, in1, nullptr}, {out0, out1, nullptr}, stream);
 }
 
 // ---- gather-scatter: Q, Q^T and Q Q^T of a local-to-global map, and the setup that inverts the map --------------------

@@ -944,6 +944,77 @@ int sf_advect_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf, co
                        const float *c1, const float *in0, const float *in1, float *out0, float *out1, void *stream);
 
 /*
+ * sf_advect_* on AFFINE elements: the weak advection term with a constant Jacobian per element.  For every element e
+ * and field a < nf, nf = 1 or d:
+ *   u_a      = B in_a[e]                                forward sweeps, as sf_advect_*
+ *   J[a][b]  = D_b u_a
+ *   beta_b   = sum_j c_j[e][pt] * dfe[e][j*d + b]       per point; j ascending; first product a multiply, then FMAs
+ *   q        = qw2[k] * (qw1[j] * qw0[i])               (2D: qw1[j] * qw0[i])
+ *   r_a      = (je[e] * q) * (sum_b beta_b * J[a][b])   b ascending, then one multiply by the weight
+ *   out_a[e] = B^T r_a                                  transposed sweeps, as sf_advect_*
+ * Per element the call moves d nq^d + 2 nf nm^d + d*d + 1 scalars where sf_advect_* moves (d*d + d + 1) nq^d + 2 nf nm^d.
+ * Layout: basis_d, deriv_d, c_j, in_a and out_a exactly as in sf_advect_*.  dfe[e][c]: the d*d constants of
+ * sf_aff_physderiv_* / sf_geom_affine_*, the same array in the same order c = a*d + b (not symmetric); required.
+ * qw_d: the nq_d one-dimensional quadrature weights of direction d and je[e]: one scalar per element (|det J_e|), both as
+ * in sf_aff_iprodderiv_*.  c_j: the d planes of the advecting velocity at the points; required.
+ * If je is NULL no weight is applied at all, r_a = sum_b beta_b J[a][b]: je and every qw_d are then never read (nor
+ * validated).  nf = 1 is scalar transport: in1.. / out1.. are ignored, may be NULL and are never written.  nf = d shares
+ * one read of c, dfe and je over the fields.  Any other nf: SF_EINVAL.
+ * Bit contract.  The order of operations is that of sf_advect_* with df_ab replaced by the element's constant and w by
+ * je * (qw2 * (qw1 * qw0)) formed in the working precision in exactly that association.  On a route the result is
+ * therefore BIT FOR BIT that of sf_advect_* on the same route with df planes filled with the constants and w expanded
+ * that way; with je NULL, that of sf_advect_* with w a plane of ones.  This holds in fp64 and fp32.  out_a of a call with
+ * nf = 1 and in = in_a equals out_a of the call with nf = d bit for bit.
+ * Routes, as sf_advect_*: SF_VARIANT_AUTO runs the fused wave kernel for the isotropic orders of its table (3D nq 2..8,
+ * 2D nq 2..16) when every in_a and out_a (a < nf) are 16-byte aligned, else GENERIC; SF_VARIANT_WAVE returns
+ * SF_ENOTBUILT off that table and SF_EALIGN unless they are 16-byte aligned; SF_VARIANT_GENERIC (one workgroup per
+ * element, latency-bound) takes any extents up to 12 per direction in 3D and 32 in 2D; any other variant SF_ENOTBUILT,
+ * extents beyond those bounds SF_ENOTBUILT.  dfe, je, qw_d, c_j, the bases and the derivative matrices need only scalar
+ * alignment on every route.
+ * Validation, before any HIP call, in this order: (1) an extent < 2, a variant outside [0, SF_NUM_VARIANTS) or nf other
+ * than 1 or d: SF_EINVAL; (2) nelmt == 0: SF_OK; (3) a null basis, deriv, dfe, c_j, or in_a / out_a with a < nf, or --
+ * only when je is not null -- a null qw_d: SF_EINVAL; (4) any of them (je, qw_d only when je is not null) not
+ * scalar-aligned: SF_EALIGN; (5) any out_a overlapping anything the call reads or another out_a, compared as byte ranges
+ * of their full sizes: SF_EINVAL; (6) extents beyond the fallback's bounds: SF_ENOTBUILT; (7) an unsupported variant:
+ * SF_ENOTBUILT.
+ * NOT in-place safe: an overlapping output is refused, not undefined; the inputs may overlap each other.
+ * No internal workspace and no allocation: every call is a single kernel node, capture-safe from the process's first
+ * call.
+ */
+int sf_aff_advect_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, unsigned nf, const double *basis0,
+                          const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
+                          const double *deriv2, const double *qw0, const double *qw1, const double *qw2,
+                          const double *dfe, const double *je, const double *c0, const double *c1, const double *c2,
+                          const double *in0, const double *in1, const double *in2, double *out0, double *out1,
+                          double *out2, void *stream);
+int sf_aff_advect_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, unsigned nf,
+                                  const double *basis0, const double *basis1, const double *basis2,
+                                  const double *deriv0, const double *deriv1, const double *deriv2, const double *qw0,
+                                  const double *qw1, const double *qw2, const double *dfe, const double *je,
+                                  const double *c0, const double *c1, const double *c2, const double *in0,
+                                  const double *in1, const double *in2, double *out0, double *out1, double *out2,
+                                  void *stream);
+int sf_aff_advect_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf, const double *basis0,
+                           const double *basis1, const double *deriv0, const double *deriv1, const double *qw0,
+                           const double *qw1, const double *dfe, const double *je, const double *c0, const double *c1,
+                           const double *in0, const double *in1, double *out0, double *out1, void *stream);
+int sf_aff_advect_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf,
+                                   const double *basis0, const double *basis1, const double *deriv0,
+                                   const double *deriv1, const double *qw0, const double *qw1, const double *dfe,
+                                   const double *je, const double *c0, const double *c1, const double *in0,
+                                   const double *in1, double *out0, double *out1, void *stream);
+/* T = float (AUTO route; every array 4-byte aligned) */
+int sf_aff_advect_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, unsigned nf, const float *basis0,
+                          const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
+                          const float *deriv2, const float *qw0, const float *qw1, const float *qw2, const float *dfe,
+                          const float *je, const float *c0, const float *c1, const float *c2, const float *in0,
+                          const float *in1, const float *in2, float *out0, float *out1, float *out2, void *stream);
+int sf_aff_advect_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf, const float *basis0,
+                           const float *basis1, const float *deriv0, const float *deriv1, const float *qw0,
+                           const float *qw1, const float *dfe, const float *je, const float *c0, const float *c1,
+                           const float *in0, const float *in1, float *out0, float *out1, void *stream);
+
+/*
  * GATHER-SCATTER between the element-local coefficients the operators above work on and the global degrees of freedom
  * of a continuous-Galerkin space: with Q the nlocal x nglobal matrix of a local-to-global map, global_to_local applies
  * Q, assemble Q^T and gs Q Q^T, so that  A = Q^T blockdiag(H_e) Q  is  global_to_local -> sf_helmholtz_* -> assemble,
