@@ -27,5 +27,6 @@ from .bwdtrans import (  # noqa: F401
     GsMap, gs_setup, global_to_local, assemble, gs,
     geom_hex, geom_quad, geom_affine_hex, geom_affine_quad, GEOM_OUTPUTS,
     advect_hex, advect_quad, affine_advect_hex, affine_advect_quad,
+    vecgrad_hex, vecgrad_quad, VECGRAD_OUTPUTS,
     tensor_hex, tensor_quad, specialise_tensor, tensor_specialisation_state, tensor_autograd,
 )

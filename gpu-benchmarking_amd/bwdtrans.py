@@ -677,6 +677,102 @@ def affine_advect_quad(nq, basis0, basis1, deriv0, deriv1, qw0, qw1, dfe, je, c,
                    c, inp, out, variant, stream)
 
 
+VECGRAD_OUTPUTS = ("grad", "div", "curl")
+
+
+def _vecgrad(what, nq, bases, derivs, df, inp, outputs, out, variant, stream):
+    """The one call path of vecgrad_*: the outputs asked for, sizes, dtypes, devices and overlap are checked here (before
+    any library call), pointers and alignment in the C ABI.  Returns the dict of the outputs asked for."""
+    nq = tuple(int(q) for q in nq)
+    d = len(nq)
+    nmt, nqt = 1, 1
+    for q in nq:
+        nmt, nqt = nmt * (q - 1), nqt * q
+    if nmt <= 0:
+        raise capi.SumfactError(capi.SF_EINVAL, what)
+    ins = _input_parts(what, inp, d)
+    first = ins[0]
+    nelmt = first.numel() // nmt
+    if nelmt * nmt != first.numel():
+        raise ValueError(f"{what}: in_a.numel() is not a multiple of the modes per element ({nmt})")
+    names = tuple(outputs)
+    for name in names:
+        if name not in VECGRAD_OUTPUTS:
+            raise ValueError(f"{what}: unknown output {name!r}; the outputs are {VECGRAD_OUTPUTS}")
+    if not names:
+        raise capi.SumfactError(capi.SF_EINVAL, what)
+    given = dict(out or {})
+    for name in given:
+        if name not in names:
+            raise ValueError(f"{what}: out holds {name!r}, which is not asked for")
+    ret, parts = {}, []                 # parts: (name, flat tensor, numel) in the order of the C signature
+    for name, per in (("grad", d * d * nqt), ("div", nqt)):
+        if name in names:
+            t = given.get(name)
+            ret[name] = torch.empty(nelmt * per, dtype=first.dtype, device=first.device) if t is None else t
+            parts.append((name, ret[name], nelmt * per))
+    ncurl = d * (d - 1) // 2
+    if "curl" in names:
+        if ncurl == 1:
+            t = given.get("curl")
+            ret["curl"] = torch.empty(nelmt * nqt, dtype=first.dtype, device=first.device) if t is None else t
+            parts.append(("curl0", ret["curl"], nelmt * nqt))
+        else:
+            ret["curl"], rows = _output_parts(f"{what}: curl", given.get("curl"), ncurl, nelmt * nqt, first)
+            parts += [(f"curl{n}", t, nelmt * nqt) for n, t in enumerate(rows)]
+    operands = [(f"basis{a}", b, (q - 1) * q, False) for a, (b, q) in enumerate(zip(bases, nq))]
+    operands += _per_direction("deriv", derivs, lambda q: q * q, nq)
+    operands += [("df", df, nelmt * d * d * nqt, False)]
+    _check_operands(what, operands + [(name, t, need, False) for name, t, need in parts], first)
+    # an output may not overlap what the call reads or another output
+    reads = [(name, t) for name, t, _, _ in operands] + [(f"in{a}", t) for a, t in enumerate(ins)]
+    for n, (oname, o, _) in enumerate(parts):
+        lo, hi = _byte_range(o)
+        for name, t in reads + [(p[0], p[1]) for p in parts[:n]]:
+            tl, th = _byte_range(t)
+            if lo < th and tl < hi:
+                raise capi.SumfactError(capi.SF_EINVAL, f"{what}: {oname} overlaps {name}")
+    f32 = first.dtype == torch.float32
+    dtype = torch.float32 if f32 else torch.float64
+    v = _variant(variant)
+    if f32 and v != VARIANTS["auto"]:
+        raise ValueError(f"{what}: float32 has the AUTO route only")
+    fn = getattr(capi.lib(), f"sf_{what}_{'f32' if f32 else 'f64_variant'}")
+    ptrs = [_dev_ptr(t, name, dtype) for name, t, _, _ in operands]
+    ptrs += [_dev_ptr(t, f"in{a}", dtype) for a, t in enumerate(ins)]
+    by_name = {name: t for name, t, _ in parts}
+    ptrs += [_dev_ptr(by_name[name], name, dtype) if name in by_name else None
+             for name in ["grad", "div"] + [f"curl{n}" for n in range(ncurl)]]
+    with torch.cuda.device(first.device):
+        rc = fn(*(() if f32 else (v,)), *nq, nelmt, *ptrs, _stream(stream, first.device))
+    capi.check(rc, what)
+    return {name: ret[name] for name in names}
+
+
+def vecgrad_hex(nq, basis0, basis1, basis2, deriv0, deriv1, deriv2, df, inp, outputs=VECGRAD_OUTPUTS, out=None,
+                variant="auto", stream=None):
+    """The gradient, divergence and curl of a vector field at the quadrature points, in one kernel on inp's device: with
+    u_a = B in_a and J[a][b] = D_b u_a, grad[a][j] = sum_b df[3 j + b] J[a][b] = d u_a / d x_j per point.  The bases and
+    derivative matrices of helmholtz_hex; df the nine planes of physderiv_hex / geom_hex (required); inp a (3, nelmt *
+    nm0*nm1*nm2) tensor with contiguous rows or a sequence of three flat tensors.  Returns a dict of tensors with the keys
+    of `outputs`: "grad" (flat, nine planes per element in the layout of df, plane 3 a + j equal to output j of
+    physderiv_hex on in_a bit for bit), "div" (flat, grad[0][0] + grad[1][1] + grad[2][2]) and "curl" (a (3, nelmt *
+    nq0*nq1*nq2) tensor, rows aligned as advect_hex returns them: grad[2][1] - grad[1][2], grad[0][2] - grad[2][0],
+    grad[1][0] - grad[0][1]); every plane in the layout of bwdtrans_hex's output.  out: a dict name -> tensor for the
+    outputs the caller owns ("curl": such a (3, n) tensor or a sequence of three flat tensors, then returned as a tuple).
+    No output may overlap an input or another output.  float64 takes variant "auto", "wave" or "generic"; float32 the
+    AUTO route.  A plain function: no autograd."""
+    return _vecgrad("vecgrad_hex", nq, (basis0, basis1, basis2), (deriv0, deriv1, deriv2), df, inp, outputs, out, variant,
+                    stream)
+
+
+def vecgrad_quad(nq, basis0, basis1, deriv0, deriv1, df, inp, outputs=VECGRAD_OUTPUTS, out=None, variant="auto",
+                 stream=None):
+    """vecgrad_hex in 2D: two fields, four planes of df and of "grad" (c = 2 a + j), "div" = grad[0][0] + grad[1][1],
+    "curl" one flat plane, grad[1][0] - grad[0][1]."""
+    return _vecgrad("vecgrad_quad", nq, (basis0, basis1), (deriv0, deriv1), df, inp, outputs, out, variant, stream)
+
+
 def _geom_affine(what, nq, bases, derivs, x, stream):
     d = len(nq)
     per = {"dfe": d * d, "ge": d * (d + 1) // 2, "je": 1}

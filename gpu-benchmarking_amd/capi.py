@@ -116,6 +116,19 @@ def _affine_advect_symbols():
 SYMBOLS.update(_affine_advect_symbols())
 
 
+def _vecgrad_symbols():
+    """sf_vecgrad_{hex,quad}_{f64,f64_variant,f32}: [variant,] the extents, nelmt, basis / deriv per direction, df, in_a per
+    direction, grad, div, the d(d-1)/2 planes of the curl, stream."""
+    for shape, dim in (("hex", 3), ("quad", 2)):
+        for sfx in ("f64", "f64_variant", "f32"):
+            head = [_i] if sfx == "f64_variant" else []
+            ptrs = 3 * dim + 1 + 2 + dim * (dim - 1) // 2
+            yield f"sf_vecgrad_{shape}_{sfx}", (_i, head + [_u] * dim + [_sz] + [_vp] * ptrs + [_vp])
+
+
+SYMBOLS.update(_vecgrad_symbols())
+
+
 def _tensor_symbols():
     """sf_tensor_{hex,quad}_{f64,f64_variant,f32,f32_variant}: [variant,] the input extents, the output extents, trans,
     nelmt, one matrix per direction, in, out, stream; sf_specialise_tensor / sf_tensor_specialisation_state: dim, three

@@ -13,11 +13,13 @@
 // tensor.hip / tensor_quad.hip / tensor_f32.hip / tensor_quad_f32.hip / tensor_generic.hip / rtc.hip, the geometric factors from element coordinates (geom, geom_affine below; their
 // launchers are declared in geom_args.h) in geom.hip / geom_f32.hip / geom_generic.hip, the weak advection term (advect
 // below; advect_args.h) in advect.hip / advect_f32.hip / advect_generic.hip, its affine-element form (affine_advect below;
-// affine_advect_args.h) in affine_advect.hip / affine_advect_f32.hip / affine_advect_generic.hip.
+// affine_advect_args.h) in affine_advect.hip / affine_advect_f32.hip / affine_advect_generic.hip, the gradient, divergence
+// and curl of a vector field (vecgrad below; vecgrad_args.h) in vecgrad.hip / vecgrad_f32.hip / vecgrad_generic.hip.
 #include "advect_args.h"
 #include "affine_advect_args.h"
 #include "geom_args.h"
 #include "sf_dispatch.h"
+#include "vecgrad_args.h"
 
 #include <cstdio>
 #include <cstring>
@@ -665,6 +667,60 @@ static int affine_advect(int variant, const unsigned (&nq)[3], size_t nelmt, uns
         variant, nq, affine_advect_generic_built(DIM, nq[0], nq[1], nq[2]), affine_advect_wave_built(DIM, nq[0]),
         (const void *)in_bits, (const void *)out_bits, [&] { return launch_affine_advect_wave<DIM, T>(nq[0], a, x, s); },
         [&] { return launch_affine_advect_generic<DIM, T>(nq, a, x, s); });
+}
+
+// ---- gradient, divergence and curl of a vector field: one validation and routing for both dimensions and scalar types ----
+// The order of sf_geom_*, with df (required) and DIM fields of modes in the place of the coordinates, and up to five
+// outputs, each looked at only when it is not null (all null: refused with the nulls; 3D: curl0..2 all null or none,
+// refused with the nulls too; 2D: curl1, curl2 are not looked at).  Every in_a and every output that is asked for is a
+// 16-byte stream of the wave kernels.
+template <int DIM, typename T>
+static int vecgrad(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *const (&d)[3],
+                   const T *df, const T *const (&in)[3], T *grad, T *div, T *const (&curl)[3], void *stream)
+{
+    constexpr int NC = DIM == 3 ? 3 : 1; // planes of the curl
+    T *c[3]          = {curl[0], DIM == 3 ? curl[1] : nullptr, DIM == 3 ? curl[2] : nullptr};
+    const int ncurl  = (c[0] != nullptr) + (c[1] != nullptr) + (c[2] != nullptr);
+    const T *some    = grad ? grad : (div ? div : (c[0] ? c[0] : (c[1] ? c[1] : c[2]))); // an output asked for, if any
+    const int rc     = validate(range_ok<DIM>(variant, nq), nelmt,
+                                {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], df, in[0], in[1],
+                                 DIM == 3 ? in[2] : in[0], some, grad ? grad : some, div ? div : some, c[0] ? c[0] : some,
+                                 c[1] ? c[1] : some, c[2] ? c[2] : some},
+                                sizeof(T), ncurl == 0 || ncurl == NC);
+    if (rc != kProceed)
+        return rc;
+    // an output may not overlap what the call reads or another output
+    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
+    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
+    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
+    const T *const out[5]     = {grad, div, c[0], c[1], c[2]};
+    const size_t out_bytes[5] = {DIM * DIM * points_bytes, points_bytes, points_bytes, points_bytes, points_bytes};
+    uintptr_t in_bits = 0, out_bits = 0; // 16-byte aligned exactly when every stream is
+    for (int a = 0; a < DIM; ++a)
+        in_bits |= (uintptr_t)in[a];
+    for (int o = 0; o < 5; ++o)
+    {
+        if (!out[o])
+            continue;
+        if (overlaps(out[o], out_bytes[o], df, DIM * DIM * points_bytes))
+            return SF_EINVAL;
+        for (int a = 0; a < DIM; ++a)
+            if (overlaps(out[o], out_bytes[o], in[a], modes_bytes) ||
+                overlaps(out[o], out_bytes[o], b[a], sizeof(T) * (nq[a] - 1) * nq[a]) ||
+                overlaps(out[o], out_bytes[o], d[a], sizeof(T) * nq[a] * nq[a]))
+                return SF_EINVAL;
+        for (int p = 0; p < o; ++p)
+            if (out[p] && overlaps(out[o], out_bytes[o], out[p], out_bytes[p]))
+                return SF_EINVAL;
+        out_bits |= (uintptr_t)out[o];
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    const auto a        = make_args<DIM, T>(b, nullptr, nullptr, nullptr, nelmt);
+    const VecgradArgsT<T> x{d[0], d[1], d[2], df, in[0], in[1], in[2], grad, div, c[0], c[1], c[2]};
+    return route<DIM>(
+        variant, nq, vecgrad_generic_built(DIM, nq[0], nq[1], nq[2]), vecgrad_wave_built(DIM, nq[0]),
+        (const void *)in_bits, (const void *)out_bits, [&] { return launch_vecgrad_wave<DIM, T>(nq[0], a, x, s); },
+        [&] { return launch_vecgrad_generic<DIM, T>(nq, a, x, s); });
 }
 
 // ---- gather-scatter: the checks of the four calls, in the order include/sumfact.h documents --------------------------
@@ -1485,6 +1541,60 @@ int sf_aff_advect_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf
     return affine_advect<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, nf, {basis0, basis1, nullptr},
                                    {deriv0, deriv1, nullptr}, {qw0, qw1, nullptr}, dfe, je, {c0, c1, nullptr},
                                    {in0, in1, nullptr}, {out0, out1, nullptr}, stream);
+}
+
+// ---- the gradient, divergence and curl of a vector field at the quadrature points ---------------------------------------
+int sf_vecgrad_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
+                               const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
+                               const double *deriv2, const double *df, const double *in0, const double *in1,
+                               const double *in2, double *grad, double *div, double *curl0, double *curl1, double *curl2,
+                               void *stream)
+{
+    return vecgrad<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2}, df,
+                              {in0, in1, in2}, grad, div, {curl0, curl1, curl2}, stream);
+}
+
+int sf_vecgrad_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0, const double *basis1,
+                       const double *basis2, const double *deriv0, const double *deriv1, const double *deriv2,
+                       const double *df, const double *in0, const double *in1, const double *in2, double *grad,
+                       double *div, double *curl0, double *curl1, double *curl2, void *stream)
+{
+    return vecgrad<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
+                              df, {in0, in1, in2}, grad, div, {curl0, curl1, curl2}, stream);
+}
+
+int sf_vecgrad_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                                const double *basis1, const double *deriv0, const double *deriv1, const double *df,
+                                const double *in0, const double *in1, double *grad, double *div, double *curl0,
+                                void *stream)
+{
+    return vecgrad<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr}, df,
+                              {in0, in1, nullptr}, grad, div, {curl0, nullptr, nullptr}, stream);
+}
+
+int sf_vecgrad_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                        const double *deriv0, const double *deriv1, const double *df, const double *in0,
+                        const double *in1, double *grad, double *div, double *curl0, void *stream)
+{
+    return vecgrad<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
+                              df, {in0, in1, nullptr}, grad, div, {curl0, nullptr, nullptr}, stream);
+}
+
+int sf_vecgrad_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
+                       const float *basis2, const float *deriv0, const float *deriv1, const float *deriv2,
+                       const float *df, const float *in0, const float *in1, const float *in2, float *grad, float *div,
+                       float *curl0, float *curl1, float *curl2, void *stream)
+{
+    return vecgrad<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
+                             df, {in0, in1, in2}, grad, div, {curl0, curl1, curl2}, stream);
+}
+
+int sf_vecgrad_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
+                        const float *deriv0, const float *deriv1, const float *df, const float *in0, const float *in1,
+                        float *grad, float *div, float *curl0, void *stream)
+{
+    return vecgrad<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
+                             df, {in0, in1, nullptr}, grad, div, {curl0, nullptr, nullptr}, stream);
 }
 
 // ---- gather-scatter: Q, Q^T and Q Q^T of a local-to-global map, and the setup that inverts the map --------------------

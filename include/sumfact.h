@@ -1015,6 +1015,72 @@ int sf_aff_advect_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf
                            const float *in0, const float *in1, float *out0, float *out1, void *stream);
 
 /*
+ * GRADIENT, DIVERGENCE AND CURL OF A VECTOR FIELD at the quadrature points, in ONE kernel: the velocity-gradient tensor
+ * behind a strain rate, an eddy viscosity or a Q-criterion, the divergence residual and the vorticity of an
+ * incompressible-flow step.  For every element e and field a = 0 .. d-1:
+ *   u_a        = B in_a[e]                              forward sweeps p -> i, q -> j, r -> k, as BwdTrans
+ *   J[a][b]    = D_b u_a                                collocation derivative, b = 0 .. d-1
+ *   grad[a][j] = sum_b df[e][j*d + b] * J[a][b]         per point; b ascending; this is d u_a / d x_j, step 3 of
+ *                                                       sf_physderiv_* applied to field a
+ *   div        = (grad[0][0] + grad[1][1]) [+ grad[2][2]]      plain additions of the rounded entries
+ *   3D: curl0 = grad[2][1] - grad[1][2],   curl1 = grad[0][2] - grad[2][0],   curl2 = grad[1][0] - grad[0][1]
+ *   2D: curl0 = grad[1][0] - grad[0][1]                        plain subtractions of the rounded entries
+ * Layout: basis_d, deriv_d, in_a (d separate caller-owned arrays of nm0*nm1[*nm2] modes per element) and df (required;
+ * the d*d planes, c = a*d + b for d xi_b / d x_a) exactly as in sf_advect_* / sf_physderiv_*.  grad[e][c][k][j][i]: d*d
+ * planes per element in the layout of df, c = a*d + j.  div, curl0 and -- in 3D -- curl1, curl2: separate caller-owned
+ * arrays of one plane per element in the layout of the output of BwdTrans, so that each goes straight into
+ * sf_iproduct_*, sf_mass_* or, as c_j, into sf_advect_*.
+ * Any of grad, div and the curl may be NULL: it is then neither written nor validated.  All NULL: SF_EINVAL.  In 3D
+ * curl0, curl1, curl2 are all NULL or all not NULL; anything else: SF_EINVAL.
+ * Per element the call moves d nm^d + d*d nq^d + n_out nq^d scalars, n_out the number of planes asked for (at most
+ * d*d + 1 + d(d-1)/2); no intermediate point image reaches HBM.  d calls of sf_physderiv_* read df d times.
+ * Summation order (it defines the rounding; every sum in ascending index, the first product a multiply, then FMAs; the
+ * wave kernels and the fallback follow it alike): the lines above, in that order.  Plane a*d + j of grad therefore
+ * equals output j of sf_physderiv_* on in_a on the same route BIT FOR BIT, div and curl equal the sums and differences
+ * of those planes formed in the order written above, and in float64 the wave kernels and the fallback agree bit for
+ * bit.  The reference-space form (no df) is not offered.
+ * Routes, as sf_geom_*: SF_VARIANT_AUTO runs the fused wave kernel for the isotropic orders of its table (3D nq 2..8,
+ * 2D nq 2..16) when every in_a and every output that is not NULL are 16-byte aligned, else GENERIC; SF_VARIANT_WAVE
+ * returns SF_ENOTBUILT off that table and SF_EALIGN unless they are 16-byte aligned; SF_VARIANT_GENERIC (one workgroup
+ * per element, latency-bound) takes any extents up to 12 per direction in 3D and 32 in 2D; any other variant
+ * SF_ENOTBUILT, extents beyond those bounds SF_ENOTBUILT.  df, the bases and the derivative matrices need only scalar
+ * alignment on every route.
+ * Validation, before any HIP call, in this order: (1) an extent < 2 or a variant outside [0, SF_NUM_VARIANTS):
+ * SF_EINVAL; (2) nelmt == 0: SF_OK; (3) a null basis, deriv, df or in_a, every output null, or -- in 3D -- only some of
+ * curl0..2 null: SF_EINVAL; (4) any of them (an output: only if it is not null) not scalar-aligned: SF_EALIGN; (5) any
+ * output overlapping anything the call reads or another output, compared as byte ranges of their full sizes: SF_EINVAL;
+ * (6) extents beyond the fallback's bounds: SF_ENOTBUILT; (7) an unsupported variant: SF_ENOTBUILT.
+ * NOT in-place safe: an overlapping output is refused, not undefined; the inputs may overlap each other.
+ * No internal workspace and no allocation: every call is a single kernel node, capture-safe from the process's first
+ * call.
+ */
+int sf_vecgrad_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                       const double *basis0, const double *basis1, const double *basis2,
+                       const double *deriv0, const double *deriv1, const double *deriv2,
+                       const double *df, const double *in0, const double *in1, const double *in2,
+                       double *grad, double *div, double *curl0, double *curl1, double *curl2, void *stream);
+int sf_vecgrad_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
+                               const double *basis0, const double *basis1, const double *basis2,
+                               const double *deriv0, const double *deriv1, const double *deriv2,
+                               const double *df, const double *in0, const double *in1, const double *in2,
+                               double *grad, double *div, double *curl0, double *curl1, double *curl2, void *stream);
+int sf_vecgrad_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
+                        const double *deriv0, const double *deriv1, const double *df, const double *in0,
+                        const double *in1, double *grad, double *div, double *curl0, void *stream);
+int sf_vecgrad_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
+                                const double *basis1, const double *deriv0, const double *deriv1, const double *df,
+                                const double *in0, const double *in1, double *grad, double *div, double *curl0,
+                                void *stream);
+/* T = float (AUTO route; every array 4-byte aligned) */
+int sf_vecgrad_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
+                       const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
+                       const float *deriv2, const float *df, const float *in0, const float *in1, const float *in2,
+                       float *grad, float *div, float *curl0, float *curl1, float *curl2, void *stream);
+int sf_vecgrad_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
+                        const float *deriv0, const float *deriv1, const float *df, const float *in0, const float *in1,
+                        float *grad, float *div, float *curl0, void *stream);
+
+/*
  * GATHER-SCATTER between the element-local coefficients the operators above work on and the global degrees of freedom
  * of a continuous-Galerkin space: with Q the nlocal x nglobal matrix of a local-to-global map, global_to_local applies
  * Q, assemble Q^T and gs Q Q^T, so that  A = Q^T blockdiag(H_e) Q  is  global_to_local -> sf_helmholtz_* -> assemble,

@@ -1,0 +1,294 @@
+"""CPU-side checks of the gradient, divergence and curl of a vector field (include/sumfact.h sf_vecgrad_*): the exports
+and their Python binding, argument validation before any HIP call, the refusals of the Python layer, the resources of
+the wave kernels, and the test reference (tests/vecgrad_ref.py) against a dense restatement, against its evaluation in
+working precision, against deliberately wrong variants and against a closed form.  No test here needs a GPU."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from geom_ref import deformed, gll_operands, ref_geom
+from physderiv_ref import dense_physderiv, physderiv_n
+from vecgrad_ref import CURL_PAIRS, U64, output_excess, ref_vecgrad, vecgrad_eval, vecgrad_excess, vecgrad_n
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "gpu-benchmarking_amd")
+NEW = ["sf_vecgrad_hex_f64", "sf_vecgrad_hex_f64_variant", "sf_vecgrad_quad_f64", "sf_vecgrad_quad_f64_variant",
+       "sf_vecgrad_hex_f32", "sf_vecgrad_quad_f32"]
+SHAPES = [(3, 3, 3), (4, 3, 5), (4, 4), (5, 3)]
+ids = lambda nq: "x".join(str(q) for q in nq)      # noqa: E731
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    import __graft_entry__ as ge
+    if not os.path.exists(os.path.join(PKG, "lib", "libsumfact.so")):
+        ge.build()
+    return ge.load_package()
+
+
+def case(nq, nelmt, seed):
+    """Bases, derivative matrices, df and d fields, uniform in [-1, 1)."""
+    rng = np.random.default_rng(seed)
+    d = len(nq)
+    nmt, nqt = int(np.prod([q - 1 for q in nq])), int(np.prod(nq))
+    B = [rng.uniform(-1, 1, (q - 1) * q) for q in nq]
+    D = [rng.uniform(-1, 1, q * q) for q in nq]
+    df = rng.uniform(-1, 1, nelmt * d * d * nqt)
+    x = [rng.uniform(-1, 1, nelmt * nmt) for _ in range(d)]
+    return B, D, df, x
+
+
+def test_the_counts_of_the_bounds():
+    assert vecgrad_n((8, 8, 8), "grad") == 24 + 8 + 3 == physderiv_n((8, 8, 8))
+    assert vecgrad_n((8, 8, 8), "div") == 35 + 2 and vecgrad_n((8, 8, 8), "curl") == 35 + 1
+    assert vecgrad_n((5, 3), "grad") == 8 + 5 + 2 and vecgrad_n((5, 3), "div") == 15 + 1 and vecgrad_n((5, 3), "curl") == 15 + 1
+    for nq in SHAPES:
+        assert vecgrad_n(nq, "div") == physderiv_n(nq) + len(nq) - 1 and vecgrad_n(nq, "curl") == physderiv_n(nq) + 1
+
+
+@pytest.mark.parametrize("nq", SHAPES, ids=ids)
+def test_reference_against_a_dense_matrix(nq):
+    """Two restatements in long double: the sweeps of ref_vecgrad and dense point x mode matrices, element by element
+    and field by field, with div and curl formed from the dense entries.  They differ by long-double rounding only:
+    held to the bounds at u = 2^-63."""
+    nelmt, d = 3, len(nq)
+    nmt, nqt = int(np.prod([q - 1 for q in nq])), int(np.prod(nq))
+    B, D, df, x = case(nq, nelmt, 5)
+    ref, absref = ref_vecgrad(nq, nelmt, B, D, df, x)
+    assert ref["grad"].shape == (nelmt * d * d * nqt,) and ref["div"].shape == (nelmt * nqt,)
+    assert ref["curl"].shape == ((3, nelmt * nqt) if d == 3 else (nelmt * nqt,))
+    g = np.stack([np.stack([dense_physderiv(nq, B, D, df.reshape(nelmt, -1)[e], x[a].reshape(nelmt, nmt)[e])
+                            for a in range(d)]) for e in range(nelmt)])                     # [e][a][j][point]
+    dense = {"grad": g.reshape(-1), "div": sum(g[:, a, a] for a in range(d)).reshape(-1)}
+    curl = [(g[:, p, q] - g[:, r, s]).reshape(-1) for (p, q), (r, s) in CURL_PAIRS[d]]
+    dense["curl"] = np.stack(curl) if d == 3 else curl[0]
+    q = vecgrad_excess(dense, ref, absref, nq, 2.0 ** -63)
+    assert set(q) == {"grad", "div", "curl"} and max(q.values()) <= 1.0, q
+    assert all(float(np.max(np.abs(v))) > 0 for v in ref.values())
+
+
+@pytest.mark.parametrize("nq", SHAPES, ids=ids)
+def test_working_precision_within_the_bounds(nq):
+    """The fp64 and the fp32 evaluation of the operator, step by step in that precision, within gamma_N absref of the
+    long-double reference on the (rounded) inputs, each output with its own N."""
+    nelmt = 4
+    B, D, df, x = case(nq, nelmt, 7)
+    ref, absref = ref_vecgrad(nq, nelmt, B, D, df, x)
+    q = vecgrad_excess(vecgrad_eval(nq, nelmt, B, D, df, x), ref, absref, nq, U64)
+    assert max(q.values()) <= 1.0, q
+    r32 = lambda vs: [np.asarray(v, dtype=np.float32).astype(np.float64) for v in vs]      # noqa: E731  inputs rounded
+    own32 = vecgrad_eval(nq, nelmt, B, D, df, x, dt=np.float32)
+    ref32, abs32 = ref_vecgrad(nq, nelmt, r32(B), r32(D), r32([df])[0], r32(x))
+    q = vecgrad_excess(own32, ref32, abs32, nq, 2.0 ** -24)
+    assert own32["grad"].dtype == np.float32 and max(q.values()) <= 1.0, q
+
+
+@pytest.mark.parametrize("mutate,output", [("df-transposed", "grad"), ("grad-transposed", "grad"), ("curl-sign", "curl"),
+                                           ("div-row", "div")])
+@pytest.mark.parametrize("nq", SHAPES, ids=ids)
+def test_wrong_variants_exceed_the_bound(nq, mutate, output):
+    nelmt = 4
+    B, D, df, x = case(nq, nelmt, 9)
+    ref, absref = ref_vecgrad(nq, nelmt, B, D, df, x)
+    bad = vecgrad_eval(nq, nelmt, B, D, df, x, mutate=mutate)
+    assert output_excess(bad[output], ref[output], absref[output], nq, U64, output) > 1e6, mutate
+
+
+CLOSED_FORM_MEASURED = {(5, 5, 5): 4.45e-18, (9, 9): 1.22e-17}
+
+
+@pytest.mark.parametrize("nq", [(5, 5, 5), (9, 9)], ids=ids)
+def test_closed_form_on_the_elements_own_coordinates(nq):
+    """The fields are linear combinations in_a = sum_c A[a][c] x_c of the element's own modal coordinates on a deformed
+    element, df geom_ref's long-double values: grad x_c = e_c, so grad = A at every point, div = tr A and curl its
+    antisymmetric part.  The deviation is the conditioning of the geometry (df is the inverse of a Jacobian known to
+    long-double rounding), not a derived quantity: it is measured in long double as max |out - exact| / max |A|, and
+    16 x the measured value is asserted.  Measured: 4.45e-18 at (5, 5, 5), 1.22e-17 at (9, 9) (long double, eps 2^-63 =
+    1.08e-19)."""
+    nelmt, d = 6, len(nq)
+    B, D, Q = gll_operands(nq)
+    xs, _ = deformed(nq, nelmt, 12)
+    df = ref_geom(nq, nelmt, B, D, Q, xs, U64).val["df"]
+    assert df.dtype == np.longdouble
+    A = np.random.default_rng(3).uniform(-1, 1, (d, d)).astype(np.longdouble)
+    fields = [sum(A[a][c] * np.asarray(xs[c], dtype=np.longdouble) for c in range(d)) for a in range(d)]
+    out, _ = ref_vecgrad(nq, nelmt, B, D, df, fields)
+    scale = float(np.max(np.abs(A)))
+    grad = out["grad"].reshape(nelmt, d * d, -1)
+    worst = max(float(np.max(np.abs(grad[:, a * d + j] - A[a][j]))) for a in range(d) for j in range(d))
+    worst = max(worst, float(np.max(np.abs(out["div"] - sum(A[a][a] for a in range(d))))))
+    curl = out["curl"] if d == 3 else out["curl"][None]
+    for n, ((p, q), (r, s)) in enumerate(CURL_PAIRS[d]):
+        worst = max(worst, float(np.max(np.abs(curl[n] - (A[p][q] - A[r][s])))))
+    worst /= scale
+    print(f"closed form {nq}: max |out - exact| / max |A| = {worst:.3g}")
+    assert worst <= 16 * CLOSED_FORM_MEASURED[tuple(nq)]
+
+
+def test_vecgrad_exports(pkg):
+    lib = pkg.capi.lib()
+    header = open(os.path.join(ROOT, "include", "sumfact.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    declared = set(re.findall(r"\b(sf_vecgrad_\w+)\s*\(", code))
+    assert declared == set(NEW) == {n for n in pkg.capi.SYMBOLS if n.startswith("sf_vecgrad_")}
+    want = {"sf_vecgrad_hex_f64": 20, "sf_vecgrad_hex_f64_variant": 21, "sf_vecgrad_hex_f32": 20,
+            "sf_vecgrad_quad_f64": 14, "sf_vecgrad_quad_f64_variant": 15, "sf_vecgrad_quad_f32": 14}
+    for name in NEW:
+        assert hasattr(lib, name), name
+        args = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", code).group(1)
+        assert len(args.split(",")) == len(pkg.capi.SYMBOLS[name][1]) == want[name], name
+    for name in ("vecgrad_hex", "vecgrad_quad"):
+        assert callable(getattr(pkg, name)), name
+    assert pkg.VECGRAD_OUTPUTS == ("grad", "div", "curl")
+    for needle in ("grad[a][j] = sum_b df[e][j*d + b] * J[a][b]", "curl0 = grad[2][1] - grad[1][2]",
+                   "curl0, curl1, curl2 are all NULL or all not NULL", "All NULL: SF_EINVAL"):
+        assert needle in header, needle
+
+
+def test_validation_without_a_gpu(pkg):
+    """Every rule of the documented order by return code; no call here reaches a launch."""
+    lib, c = pkg.capi.lib(), pkg.capi
+    A = 0x100000                                                       # 16-byte-aligned dummies, never dereferenced
+    wave, generic, thread = pkg.VARIANTS["wave"], pkg.VARIANTS["generic"], pkg.VARIANTS["thread"]
+    step = 0x1000000
+    DF, X, G, DV, CU = A + step, A + 3 * step, A + 7 * step, A + 10 * step, A + 11 * step
+    C3 = (CU, CU + step, CU + 2 * step)
+
+    def hex_(variant, nq, nelmt, b=(A,) * 3, d=(A + 0x1000,) * 3, df=DF, x=(X, X + step, X + 2 * step), grad=G, div=DV,
+             curl=C3):
+        return lib.sf_vecgrad_hex_f64_variant(variant, *nq, nelmt, *b, *d, df, *x, grad, div, *curl, None)
+
+    def quad(variant, nq, nelmt, b=(A,) * 2, d=(A + 0x1000,) * 2, df=DF, x=(X, X + step), grad=G, div=DV, curl=CU):
+        return lib.sf_vecgrad_quad_f64_variant(variant, *nq, nelmt, *b, *d, df, *x, grad, div, curl, None)
+
+    n3, n2, N3 = (8, 8, 8), (9, 9), (None,) * 3
+    # (1) an extent < 2, a variant out of range -- before everything else
+    assert hex_(0, (1, 8, 8), 4) == c.SF_EINVAL and quad(0, (9, 1), 4) == c.SF_EINVAL and hex_(99, n3, 4) == c.SF_EINVAL
+    assert hex_(-1, n3, 0) == c.SF_EINVAL and quad(0, (1, 9), 0, df=None) == c.SF_EINVAL
+    # (2) an empty batch, whatever the pointers
+    assert hex_(0, n3, 0, b=N3, df=None, grad=None, div=None, curl=N3) == c.SF_OK
+    assert quad(0, n2, 0, x=(None, None)) == c.SF_OK and hex_(0, n3, 0, curl=(CU, None, None)) == c.SF_OK
+    # (3) nulls: a basis, a derivative matrix, df, a field; every output null; in 3D only some of the curl
+    assert hex_(0, n3, 4, df=None) == c.SF_EINVAL and quad(0, n2, 4, df=None) == c.SF_EINVAL
+    assert hex_(0, n3, 4, x=(X, X + step, None)) == c.SF_EINVAL and quad(0, n2, 4, x=(None, X)) == c.SF_EINVAL
+    assert hex_(0, n3, 4, b=(A, None, A)) == c.SF_EINVAL and hex_(0, n3, 4, d=(A, A, None)) == c.SF_EINVAL
+    assert hex_(0, n3, 4, grad=None, div=None, curl=N3) == c.SF_EINVAL
+    assert quad(0, n2, 4, grad=None, div=None, curl=None) == c.SF_EINVAL
+    for some in ((CU, None, None), (None, CU, None), (None, None, CU), (CU, CU + step, None), (None, CU, CU + step)):
+        assert hex_(0, n3, 4, curl=some) == c.SF_EINVAL, some
+        assert hex_(0, n3, 4, grad=None, div=None, curl=some) == c.SF_EINVAL, some
+    # an output that is null is not looked at: every single output alone goes through to the routes
+    assert hex_(wave, (9, 9, 9), 4, div=None, curl=N3) == c.SF_ENOTBUILT
+    assert hex_(wave, (9, 9, 9), 4, grad=None, curl=N3) == c.SF_ENOTBUILT
+    assert hex_(wave, (9, 9, 9), 4, grad=None, div=None) == c.SF_ENOTBUILT
+    assert quad(wave, (17, 17), 4, grad=None, div=None) == c.SF_ENOTBUILT
+    assert quad(wave, (17, 17), 4, div=None, curl=None) == c.SF_ENOTBUILT
+    # (4) scalar alignment, after the nulls
+    assert hex_(0, n3, 4, df=DF + 4) == c.SF_EALIGN and hex_(0, n3, 4, div=DV + 2) == c.SF_EALIGN
+    assert hex_(0, n3, 4, curl=(CU, CU + step + 4, CU + 2 * step)) == c.SF_EALIGN
+    assert hex_(0, n3, 4, df=DF + 4, x=(X, None, X)) == c.SF_EINVAL
+    assert hex_(0, n3, 4, df=DF + 4, curl=(CU, None, None)) == c.SF_EINVAL
+    assert lib.sf_vecgrad_quad_f32(9, 9, 4, A, A, A, A, DF, X, X + step, G + 2, DV, CU, None) == c.SF_EALIGN
+    # (5) an output over anything the call reads or another output, as byte ranges of their full sizes
+    modes, points = 8 * 4 * 7 ** 3, 8 * 4 * 8 ** 3
+    p9 = 8 * 4 * 9 ** 3
+    assert hex_(wave, (9, 9, 9), 4, div=G + 9 * p9 - 8) == c.SF_EINVAL                     # div inside grad
+    assert hex_(wave, (9, 9, 9), 4, div=G + 9 * p9) == c.SF_ENOTBUILT
+    assert hex_(wave, (9, 9, 9), 4, curl=(CU, CU + p9 - 8, CU + 2 * step)) == c.SF_EINVAL   # curl1 inside curl0
+    outs = {"grad": 9 * points, "div": points, "curl0": points, "curl2": points}
+    for what, base, size in (("df", DF, 9 * points), ("in0", X, modes), ("in2", X + 2 * step, modes), ("basis", A, 8 * 7 * 8),
+                             ("deriv", A + 0x1000, 8 * 8 * 8)):
+        for name, nbytes in outs.items():
+            for at in (base + size - 8, base - nbytes + 8):
+                kw = {"curl": tuple(at if name == f"curl{k}" else C3[k] for k in range(3))} if name.startswith("curl") \
+                    else {name: at}
+                assert hex_(generic, n3, 4, **kw) == c.SF_EINVAL, (what, name)
+    assert quad(generic, n2, 4, curl=X + step) == c.SF_EINVAL and quad(generic, n2, 4, grad=DV - 8) == c.SF_EINVAL
+    assert hex_(thread, (13, 4, 4), 4, grad=X) == c.SF_EINVAL                              # before the routes
+    assert hex_(wave, (9, 9, 9), 4, grad=None, div=DV, curl=N3, df=DF) == c.SF_ENOTBUILT
+    # (6) extents beyond the fallback's bounds, then (7) an unsupported variant, "wave" off its table or unaligned
+    for v in (0, wave, generic, thread):
+        assert hex_(v, (13, 2, 2), 4) == c.SF_ENOTBUILT and quad(v, (33, 2), 4) == c.SF_ENOTBUILT
+    for v in ("thread", "block-lds", "block-glb", "mfma", "mfma4", "wave-rt"):
+        assert hex_(pkg.VARIANTS[v], n3, 4) == c.SF_ENOTBUILT and quad(pkg.VARIANTS[v], (8, 8), 4) == c.SF_ENOTBUILT
+    assert hex_(wave, (6, 6, 12), 4) == c.SF_ENOTBUILT and hex_(wave, (9, 9, 9), 4) == c.SF_ENOTBUILT
+    assert quad(wave, (17, 17), 4) == c.SF_ENOTBUILT
+    assert hex_(wave, n3, 4, x=(X + 8, X + step, X + 2 * step)) == c.SF_EALIGN              # a field only 8-byte aligned
+    assert hex_(wave, n3, 4, div=DV + 8) == c.SF_EALIGN and hex_(wave, n3, 4, curl=(CU, CU + step, CU + 2 * step + 8)) == c.SF_EALIGN
+    assert quad(wave, (8, 8), 4, grad=G + 8) == c.SF_EALIGN
+
+
+def test_the_python_layer_refuses_without_a_device(pkg):
+    """The number of fields, unknown or no outputs, sizes and overlapping buffers are refused before any pointer reaches
+    the library: host tensors are enough to show it."""
+    import torch
+    nq, nelmt = (4, 4, 4), 3
+    nmt, nqt = 27, 64
+    t = lambda n: torch.zeros(n, dtype=torch.float64)                  # noqa: E731
+    bs, ds = [t(12)] * 3, [t(16)] * 3
+    df = t(nelmt * 9 * nqt)
+    x = torch.zeros((3, nelmt * nmt), dtype=torch.float64)
+    einval = []
+    einval.append(lambda: pkg.vecgrad_hex(nq, *bs, *ds, df, x, outputs=()))
+    einval.append(lambda: pkg.vecgrad_hex(nq, *bs, *ds, df, x, out={"grad": df}))
+    einval.append(lambda: pkg.vecgrad_hex(nq, *bs, *ds, df, x, outputs=("div",), out={"div": df[5:5 + nelmt * nqt]}))
+    einval.append(lambda: pkg.vecgrad_hex(nq, *bs, *ds, df, x, outputs=("div",), out={"div": x.reshape(-1)[:nelmt * nqt]}))
+    o = t(nelmt * nqt)
+    einval.append(lambda: pkg.vecgrad_hex(nq, *bs, *ds, df, x, out={"div": o, "curl": [o, t(nelmt * nqt), t(nelmt * nqt)]}))
+    g = t(nelmt * 9 * nqt)
+    einval.append(lambda: pkg.vecgrad_hex(nq, *bs, *ds, df, x, out={"grad": g, "div": g[:nelmt * nqt]}))
+    einval.append(lambda: pkg.vecgrad_hex((1, 4, 4), *bs, *ds, df, x))
+    q = t(nelmt * 4 * 16)
+    einval.append(lambda: pkg.vecgrad_quad((4, 4), *bs[:2], *ds[:2], q, torch.zeros((2, nelmt * 9), dtype=torch.float64),
+                                           outputs=("curl",), out={"curl": q[7:7 + nelmt * 16]}))
+    for call in einval:
+        with pytest.raises(pkg.capi.SumfactError) as ei:
+            call()
+        assert ei.value.rc == pkg.capi.SF_EINVAL
+    for bad in (x[:2], [x[0], x[1]], torch.zeros((4, nelmt * nmt), dtype=torch.float64)):
+        with pytest.raises(ValueError):
+            pkg.vecgrad_hex(nq, *bs, *ds, df, bad)
+    with pytest.raises(ValueError):
+        pkg.vecgrad_hex(nq, *bs, *ds, df, x, outputs=("grad", "vorticity"))
+    with pytest.raises(ValueError):
+        pkg.vecgrad_hex(nq, *bs, *ds, df, x, outputs=("div",), out={"grad": g})
+    with pytest.raises(ValueError):
+        pkg.vecgrad_hex(nq, *bs, *ds, df[:-1], x)
+    with pytest.raises(ValueError):
+        pkg.vecgrad_hex(nq, *bs, *ds, df, x, out={"div": t(nelmt * nqt - 1)})
+    with pytest.raises(ValueError):
+        pkg.vecgrad_hex(nq, *bs, *ds, df, x.float())
+    with pytest.raises(ValueError):
+        pkg.vecgrad_hex(nq, *bs, *ds, df.float(), x.float(), variant="wave")
+
+
+ROW = re.compile(r"^((?:hex|quad)_vecgrad_wave_kernel<(\d+), .*, (\d+), (double|float)>)\s+vgpr\s+(\d+) agpr\s+\d+ sgpr\s+(\d+) "
+                 r"scratch\s+(-?\d+) spill v(-?\d+)/s(-?\d+) occ (\d+)")
+
+
+def test_wave_instantiations_use_no_scratch():
+    """Every wave instantiation: no scratch, no spills, at most 256 VGPRs; the set is exactly 3D nq 2..8 and 2D nq 2..16
+    for double and float with the full output mask (7): 44 kernels.  Prints VGPRs / occupancy per kernel (the table of
+    DESIGN.md s4.22)."""
+    got = {}
+    for src in ("vecgrad.hip", "vecgrad_f32.hip"):
+        out = subprocess.run(["python3", os.path.join(PKG, "tools", "kernel_resources.py"),
+                              os.path.join(PKG, "csrc", src), "vecgrad_wave_kernel"],
+                             capture_output=True, text=True, cwd=PKG, timeout=1800).stdout
+        rows = [ROW.match(ln) for ln in out.splitlines() if ln.strip()]
+        assert rows and all(rows), out
+        for m in rows:
+            name, nq, mask, t = m.group(1), int(m.group(2)), int(m.group(3)), m.group(4)
+            dim = 3 if name.startswith("hex") else 2
+            assert (t == "float") == (src == "vecgrad_f32.hip"), (src, name)
+            got[(dim, nq, t, mask)] = m
+            print(f"{dim}D nq {nq:2d} {t:6s} mask {mask}: {int(m.group(5)):3d} VGPRs, {int(m.group(6)):3d} SGPRs, "
+                  f"occupancy {m.group(10)}")
+            assert int(m.group(7)) == 0 and int(m.group(8)) == 0 and int(m.group(9)) == 0, m.string
+            assert 0 < int(m.group(5)) <= 256, m.string
+    orders = [(3, n) for n in range(2, 9)] + [(2, n) for n in range(2, 17)]
+    want = {(d, n, t, 7) for d, n in orders for t in ("double", "float")}
+    assert len(want) == 44 and set(got) == want, sorted(map(str, want ^ set(got)))
