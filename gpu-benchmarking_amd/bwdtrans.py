@@ -7,6 +7,7 @@ in[e][r][q][p], out[e][k][j][i].
 """
 import collections
 import ctypes
+import itertools
 
 import torch
 
@@ -51,6 +52,59 @@ def _dev_ptr(t, name, dtype=torch.float64):
 
 def _variant(v):
     return VARIANTS[v] if isinstance(v, str) else int(v)
+
+
+# ---- the steps every call path below shares ----------------------------------------------------------------------------
+def _extents(what, nq):
+    """(nq as ints, modes per element, points per element): nm = nq - 1 modes per direction."""
+    nq = tuple(int(q) for q in nq)
+    nmt, nqt = 1, 1
+    for q in nq:
+        nmt, nqt = nmt * (q - 1), nqt * q
+    if nmt <= 0:
+        raise capi.SumfactError(capi.SF_EINVAL, what)
+    return nq, nmt, nqt
+
+
+def _batch(what, t, per, name, unit):
+    """The number of elements, from the operand that sizes the batch: t holds `per` `unit` per element."""
+    nelmt = t.numel() // per
+    if nelmt * per != t.numel():
+        raise ValueError(f"{what}: {name}.numel() is not a multiple of the {unit} per element ({per})")
+    return nelmt
+
+
+def _entry(what, stem, f32, variant, f32_takes="auto"):
+    """(the entry point, its leading arguments) of sf_<stem>_*.  variant None: the call has none.  float64 goes to
+    _f64_variant; float32 to _f32, which is the AUTO route: f32_takes "auto" refuses any other variant, "any" quietly
+    drops it (BwdTrans), "all" says there is an _f32_variant (sf_tensor_*)."""
+    sfx = "f32" if f32 else "f64"
+    if variant is None:
+        return getattr(capi.lib(), f"sf_{stem}_{sfx}"), ()
+    v = _variant(variant)
+    if f32 and f32_takes == "auto" and v != VARIANTS["auto"]:
+        raise ValueError(f"{what}: float32 has the AUTO route only")
+    if f32 and f32_takes != "all":
+        return getattr(capi.lib(), f"sf_{stem}_f32"), ()
+    return getattr(capi.lib(), f"sf_{stem}_{sfx}_variant"), (v,)
+
+
+def _refuse_overlap(what, outs, reads):
+    """An output may not overlap what the call reads or an earlier output, as byte ranges.  outs, reads: (name, tensor)."""
+    span = lambda t: (t.data_ptr(), t.data_ptr() + t.numel() * t.element_size())       # noqa: E731
+    for n, (oname, o) in enumerate(outs):
+        lo, hi = span(o)
+        for name, t in reads + outs[:n]:
+            tl, th = span(t)
+            if lo < th and tl < hi:
+                raise capi.SumfactError(capi.SF_EINVAL, f"{what}: {oname} overlaps {name}")
+
+
+def _launch(what, fn, like, stream, args):
+    """fn(*args, stream) on like's device and its current stream; `args` may be lazy, it is read on that device."""
+    with torch.cuda.device(like.device):
+        rc = fn(*args, _stream(stream, like.device))
+    capi.check(rc, what)
 
 
 def hex_wsp_doubles(nq, nelmt):
@@ -129,26 +183,18 @@ def _operator_call(what, fam, nq, bases, inp, out, variant, stream, wsp=None):
     """The one call path of bwdtrans_* / iproduct_* / mass_* / helmholtz_* / affine_helmholtz_* / physderiv_* /
     iprodderiv_* / affine_physderiv_* / affine_iprodderiv_* / diag_helmholtz_*: sizes, dtypes and devices are checked here (before any library call), pointers, alignment and overlap in
     the C ABI."""
-    nq = tuple(int(x) for x in nq)
     ins = None
     if fam.inp_parts > 1:               # every part like the first, which stands for them below
         ins = _input_parts(what, inp, fam.inp_parts)
         inp = ins[0]
-    nmt, nqt = 1, 1
-    for q in nq:
-        nmt, nqt = nmt * (q - 1), nqt * q
-    if nmt <= 0:
-        raise capi.SumfactError(capi.SF_EINVAL, what)
+    nq, nmt, nqt = _extents(what, nq)
     n_in, n_out = nqt if fam.inp_points else nmt, nqt if fam.out_points else nmt
     if fam.inp_parts == 0:
         if not isinstance(inp, torch.Tensor):
             raise TypeError(f"{what}: the operand that sizes the batch must be a tensor")
         n_in = fam.anchor(nqt)
-    nelmt = inp.numel() // n_in
-    if nelmt * n_in != inp.numel():
-        raise ValueError(f"{what}: {'in' if fam.inp_parts else 'the operand that sizes the batch'}.numel() is not a "
-                         f"multiple of the {'values' if not fam.inp_parts else 'points' if fam.inp_points else 'modes'} "
-                         f"per element ({n_in})")
+    nelmt = _batch(what, inp, n_in, "in" if fam.inp_parts else "the operand that sizes the batch",
+                   "values" if not fam.inp_parts else "points" if fam.inp_points else "modes")
     if fam.out_parts > 1:
         out, outs = _output_parts(what, out, fam.out_parts, nelmt * n_out, inp)
     else:
@@ -167,10 +213,9 @@ def _operator_call(what, fam, nq, bases, inp, out, variant, stream, wsp=None):
             raise ValueError(f"{what}: wsp has {wsp.numel()} values, the variant needs {need[v]}")
         if wsp is None and not f32 and v in need and nelmt:
             wsp = torch.empty(max(need.values()), dtype=torch.float64, device=inp.device)
-    if f32 and v != VARIANTS["auto"] and not fam.f32_ignores_variant:
-        raise ValueError(f"{what}: float32 has the AUTO route only")
+    fn, head = _entry(what, f"{fam.stem}_{'hex' if len(nq) == 3 else 'quad'}", f32, v,
+                      "any" if fam.f32_ignores_variant else "auto")
     dtype = torch.float32 if f32 else torch.float64
-    fn = getattr(capi.lib(), f"sf_{fam.stem}_{'hex' if len(nq) == 3 else 'quad'}_{'f32' if f32 else 'f64_variant'}")
     ptrs = [None if t is None else _dev_ptr(t, name, dtype) for name, t, _, _ in operands]
     if lam is not None:
         ptrs.append(ctypes.c_double(lam))
@@ -180,10 +225,8 @@ def _operator_call(what, fam, nq, bases, inp, out, variant, stream, wsp=None):
         ptrs.append(_dev_ptr(inp, "in", dtype))
     if fam.wsp_need is not None and not f32:
         ptrs.append(None if wsp is None else _dev_ptr(wsp, "wsp", dtype))
-    with torch.cuda.device(inp.device):
-        rc = fn(*(() if f32 else (v,)), *nq, nelmt, *ptrs, *(_dev_ptr(t, name, dtype) for name, t in zip(out_names, outs)),
-                _stream(stream, inp.device))
-    capi.check(rc, what)
+    ptrs += [_dev_ptr(t, name, dtype) for name, t in zip(out_names, outs)]
+    _launch(what, fn, inp, stream, (*head, *nq, nelmt, *ptrs))
     return out
 
 
@@ -205,18 +248,14 @@ def bwdtrans_hex_mfma4(nq, basis0, basis1, basis2, inp, direct, out=None, stream
     if not isinstance(inp, torch.Tensor):
         raise TypeError(f"{what}: in must be a tensor")
     nmt, nqt = (nq - 1) ** 3, nq ** 3
-    nelmt = inp.numel() // nmt
-    if nelmt * nmt != inp.numel():
-        raise ValueError(f"{what}: in.numel() is not a multiple of the modes per element ({nmt})")
+    nelmt = _batch(what, inp, nmt, "in", "modes")
     if out is None:
         out = torch.empty(nelmt * nqt, dtype=inp.dtype, device=inp.device)
     operands = [(f"basis{d}", b, (nq - 1) * nq, False) for d, b in enumerate((basis0, basis1, basis2))]
     operands += [("in", inp, nelmt * nmt, False), ("out", out, nelmt * nqt, False)]
     _check_operands(what, operands, inp)
-    with torch.cuda.device(inp.device):
-        rc = capi.lib().sf_bwdtrans_hex_f64_mfma4(int(bool(direct)), nq, nelmt, *(_dev_ptr(t, name) for name, t, _, _ in operands),
-                                                  _stream(stream, inp.device))
-    capi.check(rc, what)
+    _launch(what, capi.lib().sf_bwdtrans_hex_f64_mfma4, inp, stream,
+            itertools.chain((int(bool(direct)), nq, nelmt), (_dev_ptr(t, name) for name, t, _, _ in operands)))
     return out
 
 
@@ -484,18 +523,10 @@ def _geom_call(what, nq, bases, derivs, qws, x, names, per, out, variant, stream
     (name -> scalars per element, in the order of the C signature); out: None or a dict name -> flat tensor (a name that
     is asked for and missing is allocated); variant None: the call has none (the affine form).  Returns the dict of the
     outputs asked for."""
-    nq = tuple(int(q) for q in nq)
-    d = len(nq)
-    xs = _input_parts(what, x, d)
+    xs = _input_parts(what, x, len(nq))
     inp = xs[0]
-    nmt = 1
-    for q in nq:
-        nmt *= q - 1
-    if nmt <= 0:
-        raise capi.SumfactError(capi.SF_EINVAL, what)
-    nelmt = inp.numel() // nmt
-    if nelmt * nmt != inp.numel():
-        raise ValueError(f"{what}: x_a.numel() is not a multiple of the modes per element ({nmt})")
+    nq, nmt, _ = _extents(what, nq)
+    nelmt = _batch(what, inp, nmt, "x_a", "modes")
     names = tuple(names)
     for name in names:
         if name not in per:
@@ -517,21 +548,11 @@ def _geom_call(what, nq, bases, derivs, qws, x, names, per, out, variant, stream
     _check_operands(what, operands + [(name, outs[name], nelmt * per[name], False) for name in names], inp)
     f32 = inp.dtype == torch.float32
     dtype = torch.float32 if f32 else torch.float64
-    head = ()
-    if variant is None:
-        fn = getattr(capi.lib(), f"sf_{what}_{'f32' if f32 else 'f64'}")
-    else:
-        v = _variant(variant)
-        if f32 and v != VARIANTS["auto"]:
-            raise ValueError(f"{what}: float32 has the AUTO route only")
-        fn = getattr(capi.lib(), f"sf_{what}_{'f32' if f32 else 'f64_variant'}")
-        head = () if f32 else (v,)
+    fn, head = _entry(what, what, f32, variant)
     ptrs = [None if t is None else _dev_ptr(t, name, dtype) for name, t, _, _ in operands]
     ptrs += [_dev_ptr(t, f"x{a}", dtype) for a, t in enumerate(xs)]
     ptrs += [_dev_ptr(outs[name], name, dtype) if name in names else None for name in per]
-    with torch.cuda.device(inp.device):
-        rc = fn(*head, *nq, nelmt, *ptrs, _stream(stream, inp.device))
-    capi.check(rc, what)
+    _launch(what, fn, inp, stream, (*head, *nq, nelmt, *ptrs))
     return {name: outs[name] for name in names}
 
 
@@ -565,10 +586,6 @@ def geom_quad(nq, basis0, basis1, deriv0, deriv1, qw0, qw1, x, outputs=GEOM_OUTP
     return _geom("geom_quad", nq, (basis0, basis1), (deriv0, deriv1), (qw0, qw1), x, outputs, out, variant, stream)
 
 
-def _byte_range(t):
-    return t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
-
-
 def _advect_planes(d, df, w):
     return lambda nelmt, nqt: [("df", df, nelmt * d * d * nqt, False), ("w", w, nelmt * nqt, False)]
 
@@ -577,13 +594,8 @@ def _advect(what, nq, bases, derivs, geometry, c, inp, out, variant, stream):
     """The one call path of advect_* and affine_advect_*: the number of fields, sizes, dtypes, devices and overlap are
     checked here (before any library call), pointers and alignment in the C ABI.  geometry(nelmt, nqt): the operands
     between the derivative matrices and c, as _check_operands takes them; one that is None and may be goes as NULL."""
-    nq = tuple(int(q) for q in nq)
+    nq, nmt, nqt = _extents(what, nq)
     d = len(nq)
-    nmt, nqt = 1, 1
-    for q in nq:
-        nmt, nqt = nmt * (q - 1), nqt * q
-    if nmt <= 0:
-        raise capi.SumfactError(capi.SF_EINVAL, what)
     if isinstance(inp, torch.Tensor):
         nf = inp.shape[0] if inp.dim() == 2 else 1
     else:
@@ -593,9 +605,7 @@ def _advect(what, nq, bases, derivs, geometry, c, inp, out, variant, stream):
         raise capi.SumfactError(capi.SF_EINVAL, f"{what}: {nf} fields, not 1 or {d}")
     ins = _input_parts(what, inp, nf)
     first = ins[0]
-    nelmt = first.numel() // nmt
-    if nelmt * nmt != first.numel():
-        raise ValueError(f"{what}: in_a.numel() is not a multiple of the modes per element ({nmt})")
+    nelmt = _batch(what, first, nmt, "in_a", "modes")
     if isinstance(c, torch.Tensor) and c.numel() != d * nelmt * nqt:
         raise ValueError(f"{what}: c has {c.numel()} values, not {d} x {nelmt * nqt}")
     cs = _input_parts(what, c, d)
@@ -605,26 +615,15 @@ def _advect(what, nq, bases, derivs, geometry, c, inp, out, variant, stream):
     operands += geometry(nelmt, nqt)
     operands += [(f"c{j}", t, nelmt * nqt, False) for j, t in enumerate(cs)]
     _check_operands(what, operands + [(f"out{a}", t, nelmt * nmt, False) for a, t in enumerate(outs)], first)
-    # an output may not overlap what the call reads or another output
     reads = [(name, t) for name, t, _, _ in operands if t is not None] + [(f"in{a}", t) for a, t in enumerate(ins)]
-    for a, o in enumerate(outs):
-        lo, hi = _byte_range(o)
-        for name, t in reads + [(f"out{f}", outs[f]) for f in range(a)]:
-            tl, th = _byte_range(t)
-            if lo < th and tl < hi:
-                raise capi.SumfactError(capi.SF_EINVAL, f"{what}: out{a} overlaps {name}")
+    _refuse_overlap(what, [(f"out{a}", t) for a, t in enumerate(outs)], reads)
     f32 = first.dtype == torch.float32
     dtype = torch.float32 if f32 else torch.float64
-    v = _variant(variant)
-    if f32 and v != VARIANTS["auto"]:
-        raise ValueError(f"{what}: float32 has the AUTO route only")
-    fn = getattr(capi.lib(), f"sf_{what.replace('affine_', 'aff_')}_{'f32' if f32 else 'f64_variant'}")
+    fn, head = _entry(what, what.replace("affine_", "aff_"), f32, variant)
     ptrs = [None if t is None else _dev_ptr(t, name, dtype) for name, t, _, _ in operands]
     ptrs += [_dev_ptr(t, f"in{a}", dtype) for a, t in enumerate(ins)] + [None] * (d - nf)
     ptrs += [_dev_ptr(t, f"out{a}", dtype) for a, t in enumerate(outs)] + [None] * (d - nf)
-    with torch.cuda.device(first.device):
-        rc = fn(*(() if f32 else (v,)), *nq, nelmt, nf, *ptrs, _stream(stream, first.device))
-    capi.check(rc, what)
+    _launch(what, fn, first, stream, (*head, *nq, nelmt, nf, *ptrs))
     return ret
 
 
@@ -683,18 +682,11 @@ VECGRAD_OUTPUTS = ("grad", "div", "curl")
 def _vecgrad(what, nq, bases, derivs, df, inp, outputs, out, variant, stream):
     """The one call path of vecgrad_*: the outputs asked for, sizes, dtypes, devices and overlap are checked here (before
     any library call), pointers and alignment in the C ABI.  Returns the dict of the outputs asked for."""
-    nq = tuple(int(q) for q in nq)
+    nq, nmt, nqt = _extents(what, nq)
     d = len(nq)
-    nmt, nqt = 1, 1
-    for q in nq:
-        nmt, nqt = nmt * (q - 1), nqt * q
-    if nmt <= 0:
-        raise capi.SumfactError(capi.SF_EINVAL, what)
     ins = _input_parts(what, inp, d)
     first = ins[0]
-    nelmt = first.numel() // nmt
-    if nelmt * nmt != first.numel():
-        raise ValueError(f"{what}: in_a.numel() is not a multiple of the modes per element ({nmt})")
+    nelmt = _batch(what, first, nmt, "in_a", "modes")
     names = tuple(outputs)
     for name in names:
         if name not in VECGRAD_OUTPUTS:
@@ -724,28 +716,17 @@ def _vecgrad(what, nq, bases, derivs, df, inp, outputs, out, variant, stream):
     operands += _per_direction("deriv", derivs, lambda q: q * q, nq)
     operands += [("df", df, nelmt * d * d * nqt, False)]
     _check_operands(what, operands + [(name, t, need, False) for name, t, need in parts], first)
-    # an output may not overlap what the call reads or another output
     reads = [(name, t) for name, t, _, _ in operands] + [(f"in{a}", t) for a, t in enumerate(ins)]
-    for n, (oname, o, _) in enumerate(parts):
-        lo, hi = _byte_range(o)
-        for name, t in reads + [(p[0], p[1]) for p in parts[:n]]:
-            tl, th = _byte_range(t)
-            if lo < th and tl < hi:
-                raise capi.SumfactError(capi.SF_EINVAL, f"{what}: {oname} overlaps {name}")
+    _refuse_overlap(what, [(name, t) for name, t, _ in parts], reads)
     f32 = first.dtype == torch.float32
     dtype = torch.float32 if f32 else torch.float64
-    v = _variant(variant)
-    if f32 and v != VARIANTS["auto"]:
-        raise ValueError(f"{what}: float32 has the AUTO route only")
-    fn = getattr(capi.lib(), f"sf_{what}_{'f32' if f32 else 'f64_variant'}")
+    fn, head = _entry(what, what, f32, variant)
     ptrs = [_dev_ptr(t, name, dtype) for name, t, _, _ in operands]
     ptrs += [_dev_ptr(t, f"in{a}", dtype) for a, t in enumerate(ins)]
     by_name = {name: t for name, t, _ in parts}
     ptrs += [_dev_ptr(by_name[name], name, dtype) if name in by_name else None
              for name in ["grad", "div"] + [f"curl{n}" for n in range(ncurl)]]
-    with torch.cuda.device(first.device):
-        rc = fn(*(() if f32 else (v,)), *nq, nelmt, *ptrs, _stream(stream, first.device))
-    capi.check(rc, what)
+    _launch(what, fn, first, stream, (*head, *nq, nelmt, *ptrs))
     return {name: ret[name] for name in names}
 
 
@@ -998,20 +979,15 @@ def _tensor_call(what, shape, ni, no, mats, inp, trans, out, variant, stream):
     nin, nout = 1, 1
     for a, b in zip(ni, no):
         nin, nout = nin * a, nout * b
-    nelmt = inp.numel() // nin
-    if nelmt * nin != inp.numel():
-        raise ValueError(f"{what}: in.numel() is not a multiple of the input values per element ({nin})")
+    nelmt = _batch(what, inp, nin, "in", "input values")
     if out is None:
         out = torch.empty(nelmt * nout, dtype=inp.dtype, device=inp.device)
     operands = [(f"m{d}", m, a * b, False) for d, (m, a, b) in enumerate(zip(mats, ni, no))]
     operands += [("in", inp, nelmt * nin, False), ("out", out, nelmt * nout, False)]
     _check_operands(what, operands, inp)
-    sfx = "f64" if inp.dtype == torch.float64 else "f32"
-    fn = getattr(capi.lib(), f"sf_tensor_{shape}_{sfx}_variant")
-    with torch.cuda.device(inp.device):
-        rc = fn(_variant(variant), *ni, *no, int(bool(trans)), nelmt,
-                *(_dev_ptr(t, name, inp.dtype) for name, t, _, _ in operands), _stream(stream, inp.device))
-    capi.check(rc, what)
+    fn, head = _entry(what, f"tensor_{shape}", inp.dtype == torch.float32, variant, "all")
+    _launch(what, fn, inp, stream, itertools.chain(head, ni, no, (int(bool(trans)), nelmt),
+                                                   (_dev_ptr(t, name, inp.dtype) for name, t, _, _ in operands)))
     return out
 
 

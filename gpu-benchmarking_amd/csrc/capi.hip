@@ -1,26 +1,15 @@
 // capi.hip -- the extern "C" boundary of libsumfact.so (declared in include/sumfact.h).
-// Validation + dispatch only: every operator entry point forwards to one template <int DIM, typename T> function below
-// (bwdtrans, iprod, mass, helmholtz, affine, physderiv, iprodderiv, affine_physderiv, affine_iprodderiv, diag), which validates, builds ArgsT<DIM, T> and routes to the launchers that
-// sf_dispatch.h declares.  Kernels live in bwdtrans_hex.hip / bwdtrans_quad.hip / bwdtrans_rt.hip /
-// bwdtrans_generic.hip / aux_kernels.hip, IProductWRTBase in iproduct.hip / iproduct_generic.hip, the fused mass
-// operator in mass.hip / mass_f32.hip / mass_generic.hip, the fused Helmholtz operator in helmholtz.hip /
-// helmholtz_f32.hip / helmholtz_generic.hip, its affine-element form in affine.hip / affine_f32.hip / affine_generic.hip,
-// BwdTrans fused with the physical-space gradient in physderiv.hip / physderiv_f32.hip / physderiv_generic.hip, its
-// transpose IProductWRTDerivBase in iprodderiv.hip / iprodderiv_f32.hip / iprodderiv_generic.hip, the affine-element forms
-// of those two in affine_deriv.hip / affine_deriv_f32.hip / affine_deriv_generic.hip, the diagonal of the
-// Helmholtz operator in diag.hip / diag_f32.hip / diag_generic.hip, the gather-scatter between local coefficients and
-// global degrees of freedom in gs.hip, the tensor-product apply with independent input / output extents (tensor below) in
-// tensor.hip / tensor_quad.hip / tensor_f32.hip / tensor_quad_f32.hip / tensor_generic.hip / rtc.hip, the geometric factors from element coordinates (geom, geom_affine below; their
-// launchers are declared in geom_args.h) in geom.hip / geom_f32.hip / geom_generic.hip, the weak advection term (advect
-// below; advect_args.h) in advect.hip / advect_f32.hip / advect_generic.hip, its affine-element form (affine_advect below;
-// affine_advect_args.h) in affine_advect.hip / affine_advect_f32.hip / affine_advect_generic.hip, the gradient, divergence
-// and curl of a vector field (vecgrad below; vecgrad_args.h) in vecgrad.hip / vecgrad_f32.hip / vecgrad_generic.hip.
+// Validation + dispatch only, no kernels: every operator entry point forwards to one template <int DIM, typename T>
+// function below, which declares its operands (Operands), has them checked in the documented order (check()), builds the
+// args structs and routes to the launchers that sf_dispatch.h and the *_args.h headers declare.  DESIGN.md lists which
+// translation unit holds which kernels.
 #include "advect_args.h"
 #include "affine_advect_args.h"
 #include "geom_args.h"
 #include "sf_dispatch.h"
 #include "vecgrad_args.h"
 
+#include <cassert>
 #include <cstdio>
 #include <cstring>
 #include <initializer_list>
@@ -40,28 +29,150 @@ static inline bool overlaps(const void *p, size_t np, const void *q, size_t nq)
     return a < b + nq && b < a + np;
 }
 
+// ---- the operands of a call and the one check of them ----------------------------------------------------------------
+// What an operand is to the check, OR-ed together.
+enum : unsigned
+{
+    kIn  = 1u << 0, // the call reads it
+    kOut = 1u << 1, // the call writes it: it may lie over no kGuard operand and over no other output
+    // Outputs may not lie over this one.  The families with an overlap rule guard what they read per element (in, x, c, w,
+    // g, df and the per-element constants) and sf_diag_helmholtz_* its tables.  Bases, derivative matrices and
+    // quadrature weights are guarded by sf_vecgrad_* alone (bases and derivative matrices): elsewhere an output over
+    // one of them goes through to the launch.  That difference came with the family, nobody decided it; it is kept as
+    // it is here, because unifying it changes what a caller sees.  sf_bwdtrans_* and sf_iproduct_* guard nothing.
+    kGuard  = 1u << 2,
+    kStream = 1u << 3, // a 16-byte stream of the wave kernels: its address enters the bits that route() tests
+    kAbsent = 1u << 4, // a null that the call documents as "not looked at": no step of the check sees it
+};
+
+struct Operand
+{
+    const void *p;
+    size_t bytes; // what the call touches from p on
+    unsigned role;
+};
+constexpr int kMaxOperands = 20; // sf_aff_advect_hex_*: three each of basis, deriv, qw, c, in, out, and dfe, je
+
 // Steps (1)-(4) of the validation order documented in include/sumfact.h, before any HIP call: the extents / variant range
-// (SF_EINVAL), an empty batch (SF_OK), a null among `ptrs` or a refused value (SF_EINVAL), a pointer of `ptrs` that is
-// not `align`-aligned (SF_EALIGN).  kProceed: none of these, the caller goes on.  A pointer the call does not take (the
-// third basis in 2D, a weight that is never read) is passed as one that it does.
+// (SF_EINVAL), an empty batch (SF_OK), a null among the operands that are present or a refused value (SF_EINVAL), an
+// operand that is not aligned to the scalar (SF_EALIGN).  kProceed: none of these, the caller goes on.
 constexpr int kProceed = 1 << 30; // neither an SF_* code nor a hipError_t
-static int validate(bool range_ok, size_t nelmt, std::initializer_list<const void *> ptrs, size_t align,
-                    bool values_ok = true)
+static int check_present(bool range_ok, size_t nelmt, const Operand *ops, int n, size_t scalar, bool values_ok)
 {
     if (!range_ok)
         return SF_EINVAL;
     if (nelmt == 0)
         return SF_OK;
-    for (const void *p : ptrs)
-        if (!p)
+    for (int i = 0; i < n; ++i)
+        if (!(ops[i].role & kAbsent) && !ops[i].p)
             return SF_EINVAL;
     if (!values_ok)
         return SF_EINVAL;
-    for (const void *p : ptrs)
-        if (!aligned(p, align))
+    for (int i = 0; i < n; ++i)
+        if (!(ops[i].role & kAbsent) && !aligned(ops[i].p, scalar))
             return SF_EALIGN;
     return kProceed;
 }
+
+// Step (5): every output against every guarded operand and every earlier output, as byte ranges (SF_EINVAL).
+static int check_disjoint(const Operand *ops, int n)
+{
+    for (int i = 0; i < n; ++i)
+    {
+        if ((ops[i].role & (kOut | kAbsent)) != kOut)
+            continue;
+        for (int j = 0; j < n; ++j)
+        {
+            const unsigned r = ops[j].role;
+            if (!(r & kAbsent) && ((r & kGuard) || ((r & kOut) && j < i)) &&
+                overlaps(ops[i].p, ops[i].bytes, ops[j].p, ops[j].bytes))
+                return SF_EINVAL;
+        }
+    }
+    return kProceed;
+}
+
+// Steps (1)-(5).  On kProceed `streams` is the OR of the addresses of the kStream operands that are present: 16-byte
+// aligned exactly when every one of them is, which is what route() asks of its `in` and `out`.
+static int check(bool range_ok, size_t nelmt, const Operand *ops, int n, size_t scalar, bool values_ok, const void *&streams)
+{
+    int rc = check_present(range_ok, nelmt, ops, n, scalar, values_ok);
+    if (rc == kProceed)
+        rc = check_disjoint(ops, n);
+    if (rc != kProceed)
+        return rc;
+    uintptr_t bits = 0;
+    for (int i = 0; i < n; ++i)
+        if ((ops[i].role & (kStream | kAbsent)) == kStream)
+            bits |= (uintptr_t)ops[i].p;
+    streams = (const void *)bits;
+    return kProceed;
+}
+
+// Steps (1)-(4) for the calls that pass bare pointers, all of them required (sf_bwdtrans_hex_f64_mfma4,
+// sf_bwdtrans_specialised).  A pointer the call does not take (the third basis in 2D) is passed as one that it does.
+static int validate(bool range_ok, size_t nelmt, std::initializer_list<const void *> ptrs, size_t align)
+{
+    Operand ops[kMaxOperands];
+    int n = 0;
+    for (const void *p : ptrs)
+        ops[n++] = {p, 0, kIn};
+    return check_present(range_ok, nelmt, ops, n, align, true);
+}
+
+// The operand list of one call, on the stack, with the byte lengths its entries are written in: over the batch, one
+// scalar per element (`elmt`), one field of modes (`modes`), one field of quadrature points (`points`).
+template <int DIM, typename T> struct Operands
+{
+    const unsigned (&nq)[3];
+    const size_t nelmt, elmt, modes, points;
+    Operand v[kMaxOperands];
+    int n               = 0;
+    const void *streams = nullptr; // set by check(): what route() takes as `in` and as `out`
+
+    Operands(const unsigned (&nq_)[3], size_t nelmt_)
+        : nq(nq_), nelmt(nelmt_), elmt(sizeof(T) * nelmt_),
+          modes(sizeof(T) * nelmt_ * (nq_[0] - 1) * (nq_[1] - 1) * (DIM == 3 ? nq_[2] - 1 : 1)),
+          points(sizeof(T) * nelmt_ * nq_[0] * nq_[1] * (DIM == 3 ? nq_[2] : 1))
+    {
+    }
+    void add(const void *p, size_t bytes, unsigned role)
+    {
+        assert(n < kMaxOperands);
+        v[n++] = {p, bytes, role};
+    }
+    // an operand the call looks at only on a condition it documents
+    void add_if(bool looked_at, const void *p, size_t bytes, unsigned role)
+    {
+        add(p, bytes, looked_at ? role : role | kAbsent);
+    }
+    // one operand per direction, the first `count` of them looked at
+    template <typename P> void each(P *const (&p)[3], size_t bytes, unsigned role, unsigned count = DIM)
+    {
+        for (unsigned a = 0; a < (unsigned)DIM; ++a)
+            add_if(a < count, p[a], bytes, role);
+    }
+    void bases(const T *const (&b)[3], unsigned role = kIn) // nm x nq per direction
+    {
+        for (int a = 0; a < DIM; ++a)
+            add(b[a], sizeof(T) * (nq[a] - 1) * nq[a], role);
+    }
+    void matrices(const T *const (&b)[3], const T *const (&d)[3], unsigned role = kIn) // the bases, then nq x nq per direction
+    {
+        bases(b, role);
+        for (int a = 0; a < DIM; ++a)
+            add(d[a], sizeof(T) * nq[a] * nq[a], role);
+    }
+    void weights(const T *const (&qw)[3], bool looked_at = true) // the nq one-dimensional quadrature weights per direction
+    {
+        for (int a = 0; a < DIM; ++a)
+            add_if(looked_at, qw[a], sizeof(T) * nq[a], kIn);
+    }
+    int check(bool range_ok, bool values_ok = true)
+    {
+        return ::check(range_ok, nelmt, v, n, sizeof(T), values_ok, streams);
+    }
+};
 
 template <int DIM> static bool range_ok(int variant, const unsigned (&nq)[3])
 {
@@ -107,7 +218,11 @@ template <int DIM, typename T>
 static int bwdtrans(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *in, T *wsp, T *out,
                     void *stream)
 {
-    const int pre = validate(range_ok<DIM>(variant, nq), nelmt, {b[0], b[1], DIM == 3 ? b[2] : b[0], in, out}, sizeof(T));
+    Operands<DIM, T> o(nq, nelmt); // no overlap rule: nothing is guarded
+    o.bases(b);
+    o.add(in, o.modes, kIn | kStream);
+    o.add(out, o.points, kOut | kStream);
+    const int pre = o.check(range_ok<DIM>(variant, nq));
     if (pre != kProceed)
         return pre;
     constexpr bool f64 = std::is_same<T, double>::value, hex64 = DIM == 3 && f64;
@@ -170,25 +285,34 @@ static int bwdtrans(int variant, const unsigned (&nq)[3], size_t nelmt, const T 
     return SF_ENOTBUILT;
 }
 
-// ---- IProductWRTBase: one validation and routing for both dimensions and both scalar types ---------------------------
+// ---- the operator families: each declares its operands, has them checked, builds its args and routes ------------------
+// Where a family reads "not in-place safe": the word-grid loads of a chunk read 16-byte words that straddle the
+// neighbouring element, so an output may not lie over what the call reads per element.
+
+// ---- IProductWRTBase --------------------------------------------------------------------------------------------------
 template <int DIM, typename T>
 static int iprod(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *in, T *out,
                  void *stream)
 {
-    const int rc = validate(range_ok<DIM>(variant, nq), nelmt, {b[0], b[1], DIM == 3 ? b[2] : b[0], in, out}, sizeof(T));
+    Operands<DIM, T> o(nq, nelmt); // no overlap rule: nothing is guarded
+    o.bases(b);
+    o.add(in, o.points, kIn | kStream);
+    o.add(out, o.modes, kOut | kStream);
+    const int rc = o.check(range_ok<DIM>(variant, nq));
     if (rc != kProceed)
         return rc;
     const hipStream_t s = (hipStream_t)stream;
     const auto a        = make_args<DIM, T>(b, in, nullptr, out, nelmt);
     return route<DIM>(
-        variant, nq, iprod_generic_built(DIM, nq[0], nq[1], nq[2]), iprod_wave_built(DIM, nq[0]), in, out,
+        variant, nq, iprod_generic_built(DIM, nq[0], nq[1], nq[2]), iprod_wave_built(DIM, nq[0]), o.streams, o.streams,
         [&] { return launch_iprod_wave<DIM, T>(nq[0], a, s); }, [&] { return launch_iprod_generic<DIM, T>(nq, a, s); });
 }
 
 // ---- the tensor-product apply with independent input / output extents (sf_tensor_*) -----------------------------------
-// The order of sf_mass_*: extents, trans and the variant's range, an empty batch, nulls, alignment, out over in.  AUTO on
-// 16-byte-aligned in / out: the compiled table, then a specialisation the caller made ready (sf_specialise_tensor), then
-// the any-extent kernel, which also takes buffers aligned only to the scalar.
+// Its own order: steps (1)-(4), then tensor_generic_built, and only then the overlap of out and in, because the byte
+// lengths below can overflow for extents that the fallback does not take.  AUTO on 16-byte-aligned in / out: the compiled
+// table, then a specialisation the caller made ready (sf_specialise_tensor), then the any-extent kernel, which also
+// takes buffers aligned only to the scalar.
 template <int DIM, typename T>
 static int tensor(int variant, const unsigned (&ni)[3], const unsigned (&no)[3], int trans, size_t nelmt,
                   const T *const (&m)[3], const T *in, T *out, void *stream)
@@ -196,15 +320,19 @@ static int tensor(int variant, const unsigned (&ni)[3], const unsigned (&no)[3],
     bool range = (trans == 0 || trans == 1) && variant >= 0 && variant < SF_NUM_VARIANTS;
     for (int d = 0; d < DIM; ++d)
         range = range && ni[d] >= 1 && no[d] >= 1;
-    const int rc = validate(range, nelmt, {m[0], m[1], DIM == 3 ? m[2] : m[0], in, out}, sizeof(T));
+    const Operand ops[5] = {
+        {m[0], sizeof(T) * ni[0] * no[0], kIn},
+        {m[1], sizeof(T) * ni[1] * no[1], kIn},
+        {m[2], sizeof(T) * ni[2] * no[2], DIM == 3 ? kIn : kIn | kAbsent},
+        {in, sizeof(T) * nelmt * ni[0] * ni[1] * (DIM == 3 ? ni[2] : 1), kIn | kGuard}, // not in-place safe
+        {out, sizeof(T) * nelmt * no[0] * no[1] * (DIM == 3 ? no[2] : 1), kOut},
+    };
+    const int rc = check_present(range, nelmt, ops, 5, sizeof(T), true);
     if (rc != kProceed)
         return rc;
-    if (!tensor_generic_built(DIM, ni, no)) // before the products below can overflow
+    if (!tensor_generic_built(DIM, ni, no)) // bounds the extents: the byte lengths above mean something from here on
         return SF_ENOTBUILT;
-    // not in-place safe (the word-grid loads of a chunk read 16-byte words that straddle the neighbouring element)
-    const size_t in_bytes  = sizeof(T) * nelmt * ni[0] * ni[1] * (DIM == 3 ? ni[2] : 1);
-    const size_t out_bytes = sizeof(T) * nelmt * no[0] * no[1] * (DIM == 3 ? no[2] : 1);
-    if (overlaps(out, out_bytes, in, in_bytes))
+    if (check_disjoint(ops, 5) != kProceed)
         return SF_EINVAL;
     if (variant != SF_VARIANT_AUTO && variant != SF_VARIANT_WAVE && variant != SF_VARIANT_GENERIC)
         return SF_ENOTBUILT;
@@ -225,253 +353,202 @@ static int tensor(int variant, const unsigned (&ni)[3], const unsigned (&no)[3],
     return launch_tensor_generic<DIM, T>(ni, no, trans, a, s);
 }
 
-// ---- the fused mass operator B^T diag(w) B: one validation and routing for both dimensions and both scalar types ----
+// ---- the fused mass operator B^T diag(w) B ------------------------------------------------------------------------------
 template <int DIM, typename T>
 static int mass(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *w, const T *in,
                 T *out, void *stream)
 {
-    const int rc =
-        validate(range_ok<DIM>(variant, nq), nelmt, {b[0], b[1], DIM == 3 ? b[2] : b[0], w, in, out}, sizeof(T));
+    Operands<DIM, T> o(nq, nelmt); // not in-place safe
+    o.bases(b);
+    o.add(w, o.points, kIn | kGuard);
+    o.add(in, o.modes, kIn | kGuard | kStream);
+    o.add(out, o.modes, kOut | kStream);
+    const int rc = o.check(range_ok<DIM>(variant, nq));
     if (rc != kProceed)
         return rc;
-    // not in-place safe (the word-grid loads of a chunk read 16-byte words that straddle the neighbouring element)
-    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
-    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
-    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
-    if (overlaps(out, modes_bytes, in, modes_bytes) || overlaps(out, modes_bytes, w, points_bytes))
-        return SF_EINVAL;
     const hipStream_t s = (hipStream_t)stream;
     const auto a        = make_args<DIM, T>(b, in, nullptr, out, nelmt);
     return route<DIM>(
-        variant, nq, mass_generic_built(DIM, nq[0], nq[1], nq[2]), mass_wave_built(DIM, nq[0]), in, out,
+        variant, nq, mass_generic_built(DIM, nq[0], nq[1], nq[2]), mass_wave_built(DIM, nq[0]), o.streams, o.streams,
         [&] { return launch_mass_wave<DIM, T>(nq[0], a, w, s); },
         [&] { return launch_mass_generic<DIM, T>(nq, a, w, s); });
 }
 
-// ---- the fused Helmholtz operator: one validation and routing for both dimensions and both scalar types ---------------
-// The order of sf_mass_*, extended to the derivative matrices, g and lambda; `w` is looked at only when lambda != 0.
+// ---- the fused Helmholtz operator ----------------------------------------------------------------------------------------
+// `w` is looked at only when lambda != 0; a lambda that is not finite is the refused value.
 template <int DIM, typename T>
 static int helmholtz(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *const (&d)[3],
                      const T *g, const T *w, double lambda, const T *in, T *out, void *stream)
 {
     const bool has_w = lambda != 0.0; // false for NaN too, which is refused with the nulls
-    const int rc     = validate(range_ok<DIM>(variant, nq), nelmt,
-                                {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], g, in, out,
-                                 has_w ? w : g},
-                                sizeof(T), lambda - lambda == 0.0);
+    Operands<DIM, T> o(nq, nelmt);    // not in-place safe
+    o.matrices(b, d);
+    o.add(g, DIM * (DIM + 1) / 2 * o.points, kIn | kGuard);
+    o.add_if(has_w, w, o.points, kIn | kGuard);
+    o.add(in, o.modes, kIn | kGuard | kStream);
+    o.add(out, o.modes, kOut | kStream);
+    const int rc = o.check(range_ok<DIM>(variant, nq), lambda - lambda == 0.0);
     if (rc != kProceed)
         return rc;
-    // not in-place safe, as sf_mass_*
-    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
-    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
-    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
-    if (overlaps(out, modes_bytes, in, modes_bytes) || overlaps(out, modes_bytes, g, (DIM == 3 ? 6 : 3) * points_bytes) ||
-        (has_w && overlaps(out, modes_bytes, w, points_bytes)))
-        return SF_EINVAL;
     const hipStream_t s = (hipStream_t)stream;
     const auto a        = make_args<DIM, T>(b, in, nullptr, out, nelmt);
     const HelmArgsT<T> x{d[0], d[1], d[2], g, has_w ? w : nullptr, (T)lambda}; // lambda is rounded to T here, once
     return route<DIM>(
-        variant, nq, helmholtz_generic_built(DIM, nq[0], nq[1], nq[2]), helmholtz_wave_built(DIM, nq[0]), in, out,
-        [&] { return launch_helmholtz_wave<DIM, T>(nq[0], a, x, s); },
+        variant, nq, helmholtz_generic_built(DIM, nq[0], nq[1], nq[2]), helmholtz_wave_built(DIM, nq[0]), o.streams,
+        o.streams, [&] { return launch_helmholtz_wave<DIM, T>(nq[0], a, x, s); },
         [&] { return launch_helmholtz_generic<DIM, T>(nq, a, x, s); });
 }
 
-// ---- the fused Helmholtz operator on affine elements: one validation and routing for both dimensions and scalar types --
-// The order of sf_helmholtz_*, with the quadrature weights and ge in the place of g and je in the place of w: `je` is
-// looked at only when lambda != 0.
+// ---- the fused Helmholtz operator on affine elements ----------------------------------------------------------------------
+// sf_helmholtz_* with the quadrature weights and ge in the place of g and je in the place of w: `je` is looked at only
+// when lambda != 0.
 template <int DIM, typename T>
 static int affine(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *const (&d)[3],
                   const T *const (&qw)[3], const T *ge, const T *je, double lambda, const T *in, T *out, void *stream)
 {
     const bool has_j = lambda != 0.0; // false for NaN too, which is refused with the nulls
-    const int rc     = validate(range_ok<DIM>(variant, nq), nelmt,
-                                {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], qw[0], qw[1],
-                                 DIM == 3 ? qw[2] : qw[0], ge, in, out, has_j ? je : ge},
-                                sizeof(T), lambda - lambda == 0.0);
+    Operands<DIM, T> o(nq, nelmt);    // not in-place safe
+    o.matrices(b, d);
+    o.weights(qw);
+    o.add(ge, DIM * (DIM + 1) / 2 * o.elmt, kIn | kGuard);
+    o.add_if(has_j, je, o.elmt, kIn | kGuard);
+    o.add(in, o.modes, kIn | kGuard | kStream);
+    o.add(out, o.modes, kOut | kStream);
+    const int rc = o.check(range_ok<DIM>(variant, nq), lambda - lambda == 0.0);
     if (rc != kProceed)
         return rc;
-    // not in-place safe, as sf_mass_*
-    const size_t mz          = DIM == 3 ? nq[2] - 1 : 1;
-    const size_t modes_bytes = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
-    if (overlaps(out, modes_bytes, in, modes_bytes) || overlaps(out, modes_bytes, ge, sizeof(T) * nelmt * (DIM == 3 ? 6 : 3)) ||
-        (has_j && overlaps(out, modes_bytes, je, sizeof(T) * nelmt)))
-        return SF_EINVAL;
     const hipStream_t s = (hipStream_t)stream;
     const auto a        = make_args<DIM, T>(b, in, nullptr, out, nelmt);
     // lambda is rounded to T here, once
     const AffineArgsT<T> x{d[0], d[1], d[2], qw[0], qw[1], qw[2], ge, has_j ? je : nullptr, (T)lambda};
     return route<DIM>(
-        variant, nq, affine_generic_built(DIM, nq[0], nq[1], nq[2]), affine_wave_built(DIM, nq[0]), in, out,
+        variant, nq, affine_generic_built(DIM, nq[0], nq[1], nq[2]), affine_wave_built(DIM, nq[0]), o.streams, o.streams,
         [&] { return launch_affine_wave<DIM, T>(nq[0], a, x, s); },
         [&] { return launch_affine_generic<DIM, T>(nq, a, x, s); });
 }
 
-// ---- BwdTrans fused with the physical-space gradient: one validation and routing for both dimensions and scalar types --
-// The order of sf_helmholtz_*, with df in the place of g (looked at only when it is not null) and DIM outputs of nq^d
-// points per element each.
+// ---- BwdTrans fused with the physical-space gradient ------------------------------------------------------------------------
+// df is looked at only when it is not null; DIM outputs of nq^d points per element each.
 template <int DIM, typename T>
 static int physderiv(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *const (&d)[3],
                      const T *df, const T *in, T *const (&out)[3], void *stream)
 {
-    const int rc = validate(range_ok<DIM>(variant, nq), nelmt,
-                            {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], in, out[0], out[1],
-                             DIM == 3 ? out[2] : out[0], df ? df : in},
-                            sizeof(T));
+    Operands<DIM, T> o(nq, nelmt);
+    o.matrices(b, d);
+    o.add_if(df != nullptr, df, DIM * DIM * o.points, kIn | kGuard);
+    o.add(in, o.modes, kIn | kGuard | kStream);
+    o.each(out, o.points, kOut | kStream);
+    const int rc = o.check(range_ok<DIM>(variant, nq));
     if (rc != kProceed)
         return rc;
-    // an output may not overlap what the call reads or another output
-    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
-    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
-    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
-    uintptr_t out_bits        = 0; // 16-byte aligned exactly when every output is
-    for (int a = 0; a < DIM; ++a)
-    {
-        if (overlaps(out[a], points_bytes, in, modes_bytes) ||
-            (df && overlaps(out[a], points_bytes, df, DIM * DIM * points_bytes)))
-            return SF_EINVAL;
-        for (int c = 0; c < a; ++c)
-            if (overlaps(out[a], points_bytes, out[c], points_bytes))
-                return SF_EINVAL;
-        out_bits |= (uintptr_t)out[a];
-    }
     const hipStream_t s = (hipStream_t)stream;
     const auto a        = make_args<DIM, T>(b, in, nullptr, nullptr, nelmt);
     const PhysDerivArgsT<T> x{d[0], d[1], d[2], df, out[0], out[1], out[2]};
     return route<DIM>(
-        variant, nq, physderiv_generic_built(DIM, nq[0], nq[1], nq[2]), physderiv_wave_built(DIM, nq[0]), in,
-        (const void *)out_bits, [&] { return launch_physderiv_wave<DIM, T>(nq[0], a, x, s); },
+        variant, nq, physderiv_generic_built(DIM, nq[0], nq[1], nq[2]), physderiv_wave_built(DIM, nq[0]), o.streams,
+        o.streams, [&] { return launch_physderiv_wave<DIM, T>(nq[0], a, x, s); },
         [&] { return launch_physderiv_generic<DIM, T>(nq, a, x, s); });
 }
 
-// ---- IProductWRTDerivBase, the transpose of the gradient: one validation and routing for both dimensions and scalar types --
-// The order of sf_physderiv_*, with DIM inputs of nq^d points per element each, df and w in front of them (each looked at
-// only when it is not null) and one output of modes.  Only `out` is a 16-byte stream of the wave kernels.
+// ---- IProductWRTDerivBase, the transpose of the gradient ----------------------------------------------------------------
+// DIM inputs of nq^d points per element each; df and w are each looked at only when not null.  Only `out` is a 16-byte
+// stream of the wave kernels.
 template <int DIM, typename T>
 static int iprodderiv(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *const (&d)[3],
                       const T *df, const T *w, const T *const (&in)[3], T *out, void *stream)
 {
-    const int rc = validate(range_ok<DIM>(variant, nq), nelmt,
-                            {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], in[0], in[1],
-                             DIM == 3 ? in[2] : in[0], out, df ? df : in[0], w ? w : in[0]},
-                            sizeof(T));
+    Operands<DIM, T> o(nq, nelmt);
+    o.matrices(b, d);
+    o.add_if(df != nullptr, df, DIM * DIM * o.points, kIn | kGuard);
+    o.add_if(w != nullptr, w, o.points, kIn | kGuard);
+    o.each(in, o.points, kIn | kGuard);
+    o.add(out, o.modes, kOut | kStream);
+    const int rc = o.check(range_ok<DIM>(variant, nq));
     if (rc != kProceed)
         return rc;
-    // the output may not overlap what the call reads
-    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
-    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
-    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
-    for (int a = 0; a < DIM; ++a)
-        if (overlaps(out, modes_bytes, in[a], points_bytes))
-            return SF_EINVAL;
-    if ((df && overlaps(out, modes_bytes, df, DIM * DIM * points_bytes)) || (w && overlaps(out, modes_bytes, w, points_bytes)))
-        return SF_EINVAL;
     const hipStream_t s = (hipStream_t)stream;
     const auto a        = make_args<DIM, T>(b, nullptr, nullptr, out, nelmt);
     const IprodDerivArgsT<T> x{d[0], d[1], d[2], df, w, in[0], in[1], in[2]};
     return route<DIM>(
-        variant, nq, iprodderiv_generic_built(DIM, nq[0], nq[1], nq[2]), iprodderiv_wave_built(DIM, nq[0]), out, out,
-        [&] { return launch_iprodderiv_wave<DIM, T>(nq[0], a, x, s); },
+        variant, nq, iprodderiv_generic_built(DIM, nq[0], nq[1], nq[2]), iprodderiv_wave_built(DIM, nq[0]), o.streams,
+        o.streams, [&] { return launch_iprodderiv_wave<DIM, T>(nq[0], a, x, s); },
         [&] { return launch_iprodderiv_generic<DIM, T>(nq, a, x, s); });
 }
 
-// ---- the gradient on affine elements: one validation and routing for both dimensions and scalar types ------------------
-// The order of sf_physderiv_*, with the d*d constants per element dfe in the place of df; dfe is required.
+// ---- the gradient on affine elements -------------------------------------------------------------------------------------
+// sf_physderiv_* with the d*d constants per element dfe in the place of df; dfe is required.
 template <int DIM, typename T>
 static int affine_physderiv(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3],
                             const T *const (&d)[3], const T *dfe, const T *in, T *const (&out)[3], void *stream)
 {
-    const int rc = validate(range_ok<DIM>(variant, nq), nelmt,
-                            {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], in, out[0], out[1],
-                             DIM == 3 ? out[2] : out[0], dfe},
-                            sizeof(T));
+    Operands<DIM, T> o(nq, nelmt);
+    o.matrices(b, d);
+    o.add(dfe, DIM * DIM * o.elmt, kIn | kGuard);
+    o.add(in, o.modes, kIn | kGuard | kStream);
+    o.each(out, o.points, kOut | kStream);
+    const int rc = o.check(range_ok<DIM>(variant, nq));
     if (rc != kProceed)
         return rc;
-    // an output may not overlap what the call reads per element or another output
-    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
-    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
-    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
-    uintptr_t out_bits        = 0; // 16-byte aligned exactly when every output is
-    for (int a = 0; a < DIM; ++a)
-    {
-        if (overlaps(out[a], points_bytes, in, modes_bytes) || overlaps(out[a], points_bytes, dfe, sizeof(T) * nelmt * DIM * DIM))
-            return SF_EINVAL;
-        for (int c = 0; c < a; ++c)
-            if (overlaps(out[a], points_bytes, out[c], points_bytes))
-                return SF_EINVAL;
-        out_bits |= (uintptr_t)out[a];
-    }
     const hipStream_t s = (hipStream_t)stream;
     const auto a        = make_args<DIM, T>(b, in, nullptr, nullptr, nelmt);
     const AffinePhysDerivArgsT<T> x{d[0], d[1], d[2], dfe, out[0], out[1], out[2]};
     return route<DIM>(
-        variant, nq, affine_deriv_generic_built(DIM, nq[0], nq[1], nq[2]), affine_deriv_wave_built(DIM, nq[0]), in,
-        (const void *)out_bits, [&] { return launch_affine_physderiv_wave<DIM, T>(nq[0], a, x, s); },
+        variant, nq, affine_deriv_generic_built(DIM, nq[0], nq[1], nq[2]), affine_deriv_wave_built(DIM, nq[0]), o.streams,
+        o.streams, [&] { return launch_affine_physderiv_wave<DIM, T>(nq[0], a, x, s); },
         [&] { return launch_affine_physderiv_generic<DIM, T>(nq, a, x, s); });
 }
 
-// ---- the weak divergence on affine elements: one validation and routing for both dimensions and scalar types -----------
-// The order of sf_iprodderiv_*, with dfe (required) in the place of df and the quadrature weights and je in the place of
-// w: `je` and every `qw` are looked at only when je is not null.  Only `out` is a 16-byte stream of the wave kernels.
+// ---- the weak divergence on affine elements --------------------------------------------------------------------------------
+// sf_iprodderiv_* with dfe (required) in the place of df and the quadrature weights and je in the place of w: `je` and
+// every `qw` are looked at only when je is not null.  Only `out` is a 16-byte stream of the wave kernels.
 template <int DIM, typename T>
 static int affine_iprodderiv(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3],
                              const T *const (&d)[3], const T *const (&qw)[3], const T *dfe, const T *je,
                              const T *const (&in)[3], T *out, void *stream)
 {
     const bool has_w = je != nullptr;
-    const int rc     = validate(range_ok<DIM>(variant, nq), nelmt,
-                                {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], in[0], in[1],
-                                 DIM == 3 ? in[2] : in[0], out, dfe, has_w ? qw[0] : dfe, has_w ? qw[1] : dfe,
-                                 has_w && DIM == 3 ? qw[2] : dfe, has_w ? je : dfe},
-                                sizeof(T));
+    Operands<DIM, T> o(nq, nelmt);
+    o.matrices(b, d);
+    o.weights(qw, has_w);
+    o.add(dfe, DIM * DIM * o.elmt, kIn | kGuard);
+    o.add_if(has_w, je, o.elmt, kIn | kGuard);
+    o.each(in, o.points, kIn | kGuard);
+    o.add(out, o.modes, kOut | kStream);
+    const int rc = o.check(range_ok<DIM>(variant, nq));
     if (rc != kProceed)
         return rc;
-    // the output may not overlap what the call reads per element
-    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
-    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
-    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
-    for (int a = 0; a < DIM; ++a)
-        if (overlaps(out, modes_bytes, in[a], points_bytes))
-            return SF_EINVAL;
-    if (overlaps(out, modes_bytes, dfe, sizeof(T) * nelmt * DIM * DIM) || (has_w && overlaps(out, modes_bytes, je, sizeof(T) * nelmt)))
-        return SF_EINVAL;
     const hipStream_t s = (hipStream_t)stream;
     const auto a        = make_args<DIM, T>(b, nullptr, nullptr, out, nelmt);
     const AffineIprodDerivArgsT<T> x{d[0],  d[1], d[2], has_w ? qw[0] : nullptr, has_w ? qw[1] : nullptr,
                                      has_w ? qw[2] : nullptr, dfe, je, in[0], in[1], in[2]};
     return route<DIM>(
-        variant, nq, affine_deriv_generic_built(DIM, nq[0], nq[1], nq[2]), affine_deriv_wave_built(DIM, nq[0]), out, out,
-        [&] { return launch_affine_iprodderiv_wave<DIM, T>(nq[0], a, x, s); },
+        variant, nq, affine_deriv_generic_built(DIM, nq[0], nq[1], nq[2]), affine_deriv_wave_built(DIM, nq[0]), o.streams,
+        o.streams, [&] { return launch_affine_iprodderiv_wave<DIM, T>(nq[0], a, x, s); },
         [&] { return launch_affine_iprodderiv_generic<DIM, T>(nq, a, x, s); });
 }
 
-// ---- the diagonal of the fused Helmholtz operator: one validation and routing for both dimensions and scalar types ------
-// The order of sf_helmholtz_* without `in`: the table triples of sf_diag_tables_* stand where the bases do, `w` is looked
-// at only when lambda != 0, `out` is the only 16-byte stream of the wave kernels.
+// ---- the diagonal of the fused Helmholtz operator ------------------------------------------------------------------------
+// sf_helmholtz_* without `in`: the table triples of sf_diag_tables_* stand where the bases do (and are guarded), `w` is
+// looked at only when lambda != 0, `out` is the only 16-byte stream of the wave kernels.
 template <int DIM, typename T>
 static int diag(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&tab)[3], const T *g, const T *w,
                 double lambda, T *out, void *stream)
 {
     const bool has_w = lambda != 0.0; // false for NaN too, which is refused with the nulls
-    const int rc     = validate(range_ok<DIM>(variant, nq), nelmt,
-                                {tab[0], tab[1], DIM == 3 ? tab[2] : tab[0], g, out, has_w ? w : g}, sizeof(T),
-                                lambda - lambda == 0.0);
+    Operands<DIM, T> o(nq, nelmt);
+    for (int d = 0; d < DIM; ++d)
+        o.add(tab[d], sizeof(T) * 3 * (nq[d] - 1) * nq[d], kIn | kGuard);
+    o.add(g, DIM * (DIM + 1) / 2 * o.points, kIn | kGuard);
+    o.add_if(has_w, w, o.points, kIn | kGuard);
+    o.add(out, o.modes, kOut | kStream);
+    const int rc = o.check(range_ok<DIM>(variant, nq), lambda - lambda == 0.0);
     if (rc != kProceed)
         return rc;
-    // the output may not overlap what the call reads
-    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
-    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
-    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
-    if (overlaps(out, modes_bytes, g, (DIM == 3 ? 6 : 3) * points_bytes) || (has_w && overlaps(out, modes_bytes, w, points_bytes)))
-        return SF_EINVAL;
-    for (int d = 0; d < DIM; ++d)
-        if (overlaps(out, modes_bytes, tab[d], sizeof(T) * 3 * (nq[d] - 1) * nq[d]))
-            return SF_EINVAL;
     const hipStream_t s = (hipStream_t)stream;
     const auto a        = make_args<DIM, T>(tab, nullptr, nullptr, out, nelmt); // the tables in the place of the bases
     const DiagArgsT<T> x{g, has_w ? w : nullptr, (T)lambda};                    // lambda is rounded to T here, once
     return route<DIM>(
-        variant, nq, diag_generic_built(DIM, nq[0], nq[1], nq[2]), diag_wave_built(DIM, nq[0]), out, out,
+        variant, nq, diag_generic_built(DIM, nq[0], nq[1], nq[2]), diag_wave_built(DIM, nq[0]), o.streams, o.streams,
         [&] { return launch_diag_wave<DIM, T>(nq[0], a, x, s); }, [&] { return launch_diag_generic<DIM, T>(nq, a, x, s); });
 }
 
@@ -490,83 +567,51 @@ template <typename T> static int diag_tables(unsigned nq, const T *basis, const 
     return launch_diag_tables<T>(nq, basis, deriv, tab, (hipStream_t)stream);
 }
 
-// ---- the geometric factors from element coordinates: one validation and routing for both dimensions and scalar types ----
-// The order of sf_physderiv_*, with DIM coordinate streams of modes in the place of `in` and four outputs, each looked at
-// only when it is not null (all four null: refused with the nulls); the quadrature weights are looked at only when w or
-// g is asked for.  Every x_a and every output that is asked for is a 16-byte stream of the wave kernels.
+// ---- the geometric factors from element coordinates ----------------------------------------------------------------------
+// DIM coordinate streams of modes and four outputs, each looked at only when it is not null (all four null: refused with
+// the nulls); the quadrature weights are looked at only when w or g is asked for.  Every x_a and every output that is
+// asked for is a 16-byte stream of the wave kernels.
 template <int DIM, typename T>
 static int geom(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *const (&d)[3],
                 const T *const (&qw)[3], const T *const (&x)[3], T *df, T *w, T *g, T *detj, void *stream)
 {
     const bool has_q = w || g;
-    const T *some    = df ? df : (w ? w : (g ? g : detj)); // an output that is asked for, null if none is
-    const int rc     = validate(range_ok<DIM>(variant, nq), nelmt,
-                                {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], x[0], x[1],
-                                 DIM == 3 ? x[2] : x[0], some, has_q ? qw[0] : x[0], has_q ? qw[1] : x[0],
-                                 has_q && DIM == 3 ? qw[2] : x[0], df ? df : some, w ? w : some, g ? g : some,
-                                 detj ? detj : some},
-                                sizeof(T));
+    Operands<DIM, T> o(nq, nelmt);
+    o.matrices(b, d);
+    o.weights(qw, has_q);
+    o.each(x, o.modes, kIn | kGuard | kStream);
+    o.add_if(df != nullptr, df, DIM * DIM * o.points, kOut | kStream);
+    o.add_if(w != nullptr, w, o.points, kOut | kStream);
+    o.add_if(g != nullptr, g, DIM * (DIM + 1) / 2 * o.points, kOut | kStream);
+    o.add_if(detj != nullptr, detj, o.points, kOut | kStream);
+    const int rc = o.check(range_ok<DIM>(variant, nq), df || w || g || detj);
     if (rc != kProceed)
         return rc;
-    // an output may not overlap a coordinate stream or another output
-    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
-    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
-    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
-    const T *const out[4]     = {df, w, g, detj};
-    const size_t out_bytes[4] = {DIM * DIM * points_bytes, points_bytes, DIM * (DIM + 1) / 2 * points_bytes, points_bytes};
-    uintptr_t in_bits = 0, out_bits = 0; // 16-byte aligned exactly when every stream is
-    for (int a = 0; a < DIM; ++a)
-        in_bits |= (uintptr_t)x[a];
-    for (int o = 0; o < 4; ++o)
-    {
-        if (!out[o])
-            continue;
-        for (int a = 0; a < DIM; ++a)
-            if (overlaps(out[o], out_bytes[o], x[a], modes_bytes))
-                return SF_EINVAL;
-        for (int p = 0; p < o; ++p)
-            if (out[p] && overlaps(out[o], out_bytes[o], out[p], out_bytes[p]))
-                return SF_EINVAL;
-        out_bits |= (uintptr_t)out[o];
-    }
     const hipStream_t s = (hipStream_t)stream;
     const auto a        = make_args<DIM, T>(b, nullptr, nullptr, nullptr, nelmt);
     const GeomArgsT<T> ga{d[0], d[1], d[2], has_q ? qw[0] : nullptr, has_q ? qw[1] : nullptr, has_q ? qw[2] : nullptr,
                           x[0], x[1], x[2], df, w, g, detj};
     return route<DIM>(
-        variant, nq, geom_generic_built(DIM, nq[0], nq[1], nq[2]), geom_wave_built(DIM, nq[0]), (const void *)in_bits,
-        (const void *)out_bits, [&] { return launch_geom_wave<DIM, T>(nq[0], a, ga, s); },
+        variant, nq, geom_generic_built(DIM, nq[0], nq[1], nq[2]), geom_wave_built(DIM, nq[0]), o.streams, o.streams,
+        [&] { return launch_geom_wave<DIM, T>(nq[0], a, ga, s); },
         [&] { return launch_geom_generic<DIM, T>(nq, a, ga, s); });
 }
 
-// The affine form: the order of sf_geom_* without a variant and without quadrature weights; one small kernel for any
-// extents the fallback takes.
+// The affine form: sf_geom_* without a variant and without quadrature weights; one small kernel for any extents the
+// fallback takes.
 template <int DIM, typename T>
 static int geom_affine(const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *const (&d)[3],
                        const T *const (&x)[3], T *dfe, T *ge, T *je, void *stream)
 {
-    const T *some = dfe ? dfe : (ge ? ge : je);
-    const int rc  = validate(range_ok<DIM>(SF_VARIANT_AUTO, nq), nelmt,
-                             {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], x[0], x[1],
-                              DIM == 3 ? x[2] : x[0], some, dfe ? dfe : some, ge ? ge : some, je ? je : some},
-                             sizeof(T));
+    Operands<DIM, T> o(nq, nelmt);
+    o.matrices(b, d);
+    o.each(x, o.modes, kIn | kGuard);
+    o.add_if(dfe != nullptr, dfe, DIM * DIM * o.elmt, kOut);
+    o.add_if(ge != nullptr, ge, DIM * (DIM + 1) / 2 * o.elmt, kOut);
+    o.add_if(je != nullptr, je, o.elmt, kOut);
+    const int rc = o.check(range_ok<DIM>(SF_VARIANT_AUTO, nq), dfe || ge || je);
     if (rc != kProceed)
         return rc;
-    const size_t mz           = DIM == 3 ? nq[2] - 1 : 1;
-    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
-    const T *const out[3]     = {dfe, ge, je};
-    const size_t out_bytes[3] = {sizeof(T) * nelmt * DIM * DIM, sizeof(T) * nelmt * (DIM * (DIM + 1) / 2), sizeof(T) * nelmt};
-    for (int o = 0; o < 3; ++o)
-    {
-        if (!out[o])
-            continue;
-        for (int a = 0; a < DIM; ++a)
-            if (overlaps(out[o], out_bytes[o], x[a], modes_bytes))
-                return SF_EINVAL;
-        for (int p = 0; p < o; ++p)
-            if (out[p] && overlaps(out[o], out_bytes[o], out[p], out_bytes[p]))
-                return SF_EINVAL;
-    }
     if (!geom_generic_built(DIM, nq[0], nq[1], nq[2]))
         return SF_ENOTBUILT;
     const auto a = make_args<DIM, T>(b, nullptr, nullptr, nullptr, nelmt);
@@ -574,106 +619,73 @@ static int geom_affine(const unsigned (&nq)[3], size_t nelmt, const T *const (&b
     return launch_geom_affine<DIM, T>(nq, a, ga, (hipStream_t)stream);
 }
 
-// ---- the weak advection term: one validation and routing for both dimensions and scalar types --------------------------
-// The order of sf_physderiv_*, with df, w and the DIM planes of the advecting velocity in front of nf = 1 or DIM fields of
-// modes in and out; all of df, w, c_j are required.  Every in_a and out_a that the call takes (a < nf) is a 16-byte
-// stream of the wave kernels; those with a >= nf are not looked at.
+// ---- the weak advection term ------------------------------------------------------------------------------------------------
+// df, w and the DIM planes of the advecting velocity in front of nf = 1 or DIM fields of modes in and out (another nf is
+// out of range); all of df, w, c_j are required.  Every in_a and out_a that the call takes (a < nf) is a 16-byte stream of
+// the wave kernels; those with a >= nf are not looked at, and the args carry field 0 in their place.
 template <int DIM, typename T>
 static int advect(int variant, const unsigned (&nq)[3], size_t nelmt, unsigned nf, const T *const (&b)[3],
                   const T *const (&d)[3], const T *df, const T *w, const T *const (&c)[3], const T *const (&in)[3],
                   T *const (&out)[3], void *stream)
 {
-    const bool nf_ok = nf == 1 || nf == (unsigned)DIM;
-    const T *i1 = nf_ok && nf > 1 ? in[1] : in[0], *i2 = nf_ok && nf > 2 ? in[2] : in[0];
-    T *o1 = nf_ok && nf > 1 ? out[1] : out[0], *o2 = nf_ok && nf > 2 ? out[2] : out[0];
-    const int rc = validate(range_ok<DIM>(variant, nq) && nf_ok, nelmt,
-                            {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], df, w, c[0], c[1],
-                             DIM == 3 ? c[2] : c[0], in[0], i1, i2, out[0], o1, o2},
-                            sizeof(T));
+    Operands<DIM, T> o(nq, nelmt);
+    o.matrices(b, d);
+    o.add(df, DIM * DIM * o.points, kIn | kGuard);
+    o.add(w, o.points, kIn | kGuard);
+    o.each(c, o.points, kIn | kGuard);
+    o.each(in, o.modes, kIn | kGuard | kStream, nf);
+    o.each(out, o.modes, kOut | kStream, nf);
+    const int rc = o.check(range_ok<DIM>(variant, nq) && (nf == 1 || nf == (unsigned)DIM));
     if (rc != kProceed)
         return rc;
-    // an output may not overlap what the call reads or another output
-    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
-    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
-    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
-    uintptr_t in_bits = 0, out_bits = 0; // 16-byte aligned exactly when every stream is
-    for (unsigned a = 0; a < nf; ++a)
-    {
-        if (overlaps(out[a], modes_bytes, df, DIM * DIM * points_bytes) || overlaps(out[a], modes_bytes, w, points_bytes))
-            return SF_EINVAL;
-        for (int j = 0; j < DIM; ++j)
-            if (overlaps(out[a], modes_bytes, c[j], points_bytes))
-                return SF_EINVAL;
-        for (unsigned f = 0; f < nf; ++f)
-            if (overlaps(out[a], modes_bytes, in[f], modes_bytes) || (f < a && overlaps(out[a], modes_bytes, out[f], modes_bytes)))
-                return SF_EINVAL;
-        in_bits |= (uintptr_t)in[a];
-        out_bits |= (uintptr_t)out[a];
-    }
     const hipStream_t s = (hipStream_t)stream;
     const auto a        = make_args<DIM, T>(b, nullptr, nullptr, nullptr, nelmt);
-    const AdvectArgsT<T> x{d[0], d[1], d[2], df, w, c[0], c[1], c[2], in[0], i1, i2, out[0], o1, o2, (int)nf};
+    const int f1 = nf > 1 ? 1 : 0, f2 = nf > 2 ? 2 : 0;
+    const AdvectArgsT<T> x{d[0], d[1], d[2], df, w, c[0], c[1], c[2], in[0], in[f1], in[f2], out[0], out[f1], out[f2],
+                           (int)nf};
     return route<DIM>(
-        variant, nq, advect_generic_built(DIM, nq[0], nq[1], nq[2]), advect_wave_built(DIM, nq[0]), (const void *)in_bits,
-        (const void *)out_bits, [&] { return launch_advect_wave<DIM, T>(nq[0], a, x, s); },
+        variant, nq, advect_generic_built(DIM, nq[0], nq[1], nq[2]), advect_wave_built(DIM, nq[0]), o.streams, o.streams,
+        [&] { return launch_advect_wave<DIM, T>(nq[0], a, x, s); },
         [&] { return launch_advect_generic<DIM, T>(nq, a, x, s); });
 }
 
-// ---- the weak advection term on affine elements: one validation and routing for both dimensions and scalar types -------
-// The order of sf_advect_*, with dfe (required) in the place of df and the quadrature weights and je in the place of w:
-// `je` and every `qw` are looked at only when je is not null.  Every in_a and out_a that the call takes (a < nf) is a
-// 16-byte stream of the wave kernels; those with a >= nf are not looked at.
+// ---- the weak advection term on affine elements -----------------------------------------------------------------------------
+// sf_advect_* with dfe (required) in the place of df and the quadrature weights and je in the place of w: `je` and every
+// `qw` are looked at only when je is not null.
 template <int DIM, typename T>
 static int affine_advect(int variant, const unsigned (&nq)[3], size_t nelmt, unsigned nf, const T *const (&b)[3],
                          const T *const (&d)[3], const T *const (&qw)[3], const T *dfe, const T *je,
                          const T *const (&c)[3], const T *const (&in)[3], T *const (&out)[3], void *stream)
 {
     const bool has_w = je != nullptr;
-    const bool nf_ok = nf == 1 || nf == (unsigned)DIM;
-    const T *i1 = nf_ok && nf > 1 ? in[1] : in[0], *i2 = nf_ok && nf > 2 ? in[2] : in[0];
-    T *o1 = nf_ok && nf > 1 ? out[1] : out[0], *o2 = nf_ok && nf > 2 ? out[2] : out[0];
-    const int rc = validate(range_ok<DIM>(variant, nq) && nf_ok, nelmt,
-                            {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], dfe, c[0], c[1],
-                             DIM == 3 ? c[2] : c[0], in[0], i1, i2, out[0], o1, o2, has_w ? qw[0] : dfe,
-                             has_w ? qw[1] : dfe, has_w && DIM == 3 ? qw[2] : dfe, has_w ? je : dfe},
-                            sizeof(T));
+    Operands<DIM, T> o(nq, nelmt);
+    o.matrices(b, d);
+    o.weights(qw, has_w);
+    o.add(dfe, DIM * DIM * o.elmt, kIn | kGuard);
+    o.add_if(has_w, je, o.elmt, kIn | kGuard);
+    o.each(c, o.points, kIn | kGuard);
+    o.each(in, o.modes, kIn | kGuard | kStream, nf);
+    o.each(out, o.modes, kOut | kStream, nf);
+    const int rc = o.check(range_ok<DIM>(variant, nq) && (nf == 1 || nf == (unsigned)DIM));
     if (rc != kProceed)
         return rc;
-    // an output may not overlap what the call reads or another output
-    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
-    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
-    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
-    uintptr_t in_bits = 0, out_bits = 0; // 16-byte aligned exactly when every stream is
-    for (unsigned a = 0; a < nf; ++a)
-    {
-        if (overlaps(out[a], modes_bytes, dfe, sizeof(T) * nelmt * DIM * DIM) ||
-            (has_w && overlaps(out[a], modes_bytes, je, sizeof(T) * nelmt)))
-            return SF_EINVAL;
-        for (int j = 0; j < DIM; ++j)
-            if (overlaps(out[a], modes_bytes, c[j], points_bytes))
-                return SF_EINVAL;
-        for (unsigned f = 0; f < nf; ++f)
-            if (overlaps(out[a], modes_bytes, in[f], modes_bytes) || (f < a && overlaps(out[a], modes_bytes, out[f], modes_bytes)))
-                return SF_EINVAL;
-        in_bits |= (uintptr_t)in[a];
-        out_bits |= (uintptr_t)out[a];
-    }
     const hipStream_t s = (hipStream_t)stream;
     const auto a        = make_args<DIM, T>(b, nullptr, nullptr, nullptr, nelmt);
+    const int f1 = nf > 1 ? 1 : 0, f2 = nf > 2 ? 2 : 0;
     const AffineAdvectArgsT<T> x{d[0], d[1], d[2], has_w ? qw[0] : nullptr, has_w ? qw[1] : nullptr,
-                                 has_w ? qw[2] : nullptr, dfe, je, c[0], c[1], c[2], in[0], i1, i2, out[0], o1, o2,
-                                 (int)nf};
+                                 has_w ? qw[2] : nullptr, dfe, je, c[0], c[1], c[2], in[0], in[f1], in[f2], out[0],
+                                 out[f1], out[f2], (int)nf};
     return route<DIM>(
         variant, nq, affine_advect_generic_built(DIM, nq[0], nq[1], nq[2]), affine_advect_wave_built(DIM, nq[0]),
-        (const void *)in_bits, (const void *)out_bits, [&] { return launch_affine_advect_wave<DIM, T>(nq[0], a, x, s); },
+        o.streams, o.streams, [&] { return launch_affine_advect_wave<DIM, T>(nq[0], a, x, s); },
         [&] { return launch_affine_advect_generic<DIM, T>(nq, a, x, s); });
 }
 
-// ---- gradient, divergence and curl of a vector field: one validation and routing for both dimensions and scalar types ----
-// The order of sf_geom_*, with df (required) and DIM fields of modes in the place of the coordinates, and up to five
-// outputs, each looked at only when it is not null (all null: refused with the nulls; 3D: curl0..2 all null or none,
-// refused with the nulls too; 2D: curl1, curl2 are not looked at).  Every in_a and every output that is asked for is a
-// 16-byte stream of the wave kernels.
+// ---- gradient, divergence and curl of a vector field ------------------------------------------------------------------------
+// df (required) and DIM fields of modes, and up to five outputs, each looked at only when it is not null (all null:
+// refused with the nulls; 3D: curl0..2 all null or none, refused with the nulls too; 2D: curl1, curl2 are not looked at).
+// Every in_a and every output that is asked for is a 16-byte stream of the wave kernels.  The one family whose outputs
+// may not lie over a basis or a derivative matrix (see kGuard).
 template <int DIM, typename T>
 static int vecgrad(int variant, const unsigned (&nq)[3], size_t nelmt, const T *const (&b)[3], const T *const (&d)[3],
                    const T *df, const T *const (&in)[3], T *grad, T *div, T *const (&curl)[3], void *stream)
@@ -681,45 +693,23 @@ static int vecgrad(int variant, const unsigned (&nq)[3], size_t nelmt, const T *
     constexpr int NC = DIM == 3 ? 3 : 1; // planes of the curl
     T *c[3]          = {curl[0], DIM == 3 ? curl[1] : nullptr, DIM == 3 ? curl[2] : nullptr};
     const int ncurl  = (c[0] != nullptr) + (c[1] != nullptr) + (c[2] != nullptr);
-    const T *some    = grad ? grad : (div ? div : (c[0] ? c[0] : (c[1] ? c[1] : c[2]))); // an output asked for, if any
-    const int rc     = validate(range_ok<DIM>(variant, nq), nelmt,
-                                {b[0], b[1], DIM == 3 ? b[2] : b[0], d[0], d[1], DIM == 3 ? d[2] : d[0], df, in[0], in[1],
-                                 DIM == 3 ? in[2] : in[0], some, grad ? grad : some, div ? div : some, c[0] ? c[0] : some,
-                                 c[1] ? c[1] : some, c[2] ? c[2] : some},
-                                sizeof(T), ncurl == 0 || ncurl == NC);
+    Operands<DIM, T> o(nq, nelmt);
+    o.matrices(b, d, kIn | kGuard);
+    o.add(df, DIM * DIM * o.points, kIn | kGuard);
+    o.each(in, o.modes, kIn | kGuard | kStream);
+    o.add_if(grad != nullptr, grad, DIM * DIM * o.points, kOut | kStream);
+    o.add_if(div != nullptr, div, o.points, kOut | kStream);
+    for (int k = 0; k < 3; ++k)
+        o.add_if(c[k] != nullptr, c[k], o.points, kOut | kStream);
+    const int rc = o.check(range_ok<DIM>(variant, nq), (grad || div || ncurl) && (ncurl == 0 || ncurl == NC));
     if (rc != kProceed)
         return rc;
-    // an output may not overlap what the call reads or another output
-    const size_t nz = DIM == 3 ? nq[2] : 1, mz = DIM == 3 ? nq[2] - 1 : 1;
-    const size_t modes_bytes  = sizeof(T) * nelmt * (nq[0] - 1) * (nq[1] - 1) * mz;
-    const size_t points_bytes = sizeof(T) * nelmt * nq[0] * nq[1] * nz;
-    const T *const out[5]     = {grad, div, c[0], c[1], c[2]};
-    const size_t out_bytes[5] = {DIM * DIM * points_bytes, points_bytes, points_bytes, points_bytes, points_bytes};
-    uintptr_t in_bits = 0, out_bits = 0; // 16-byte aligned exactly when every stream is
-    for (int a = 0; a < DIM; ++a)
-        in_bits |= (uintptr_t)in[a];
-    for (int o = 0; o < 5; ++o)
-    {
-        if (!out[o])
-            continue;
-        if (overlaps(out[o], out_bytes[o], df, DIM * DIM * points_bytes))
-            return SF_EINVAL;
-        for (int a = 0; a < DIM; ++a)
-            if (overlaps(out[o], out_bytes[o], in[a], modes_bytes) ||
-                overlaps(out[o], out_bytes[o], b[a], sizeof(T) * (nq[a] - 1) * nq[a]) ||
-                overlaps(out[o], out_bytes[o], d[a], sizeof(T) * nq[a] * nq[a]))
-                return SF_EINVAL;
-        for (int p = 0; p < o; ++p)
-            if (out[p] && overlaps(out[o], out_bytes[o], out[p], out_bytes[p]))
-                return SF_EINVAL;
-        out_bits |= (uintptr_t)out[o];
-    }
     const hipStream_t s = (hipStream_t)stream;
     const auto a        = make_args<DIM, T>(b, nullptr, nullptr, nullptr, nelmt);
     const VecgradArgsT<T> x{d[0], d[1], d[2], df, in[0], in[1], in[2], grad, div, c[0], c[1], c[2]};
     return route<DIM>(
-        variant, nq, vecgrad_generic_built(DIM, nq[0], nq[1], nq[2]), vecgrad_wave_built(DIM, nq[0]),
-        (const void *)in_bits, (const void *)out_bits, [&] { return launch_vecgrad_wave<DIM, T>(nq[0], a, x, s); },
+        variant, nq, vecgrad_generic_built(DIM, nq[0], nq[1], nq[2]), vecgrad_wave_built(DIM, nq[0]), o.streams,
+        o.streams, [&] { return launch_vecgrad_wave<DIM, T>(nq[0], a, x, s); },
         [&] { return launch_vecgrad_generic<DIM, T>(nq, a, x, s); });
 }
 

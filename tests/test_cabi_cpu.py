@@ -76,6 +76,39 @@ def test_hex_mfma4_export_validates_as_the_variant_without_gpu(pkg):
             assert lib.sf_bwdtrans_hex_f64_mfma4(direct, nq, nelmt, b0, b1, b2, x, out, None) == want, (direct, nq, nelmt)
 
 
+def _no_gpu():
+    import torch
+    return not torch.cuda.is_available()
+
+
+@pytest.mark.skipif(not _no_gpu(), reason="replays calls on dummy pointers, which must never meet a real device")
+def test_recorded_return_codes(pkg):
+    """Every operator entry point answers the cases of tests/golden/make_capi_codes.py -- nulls, misalignment, every
+    ordered pair of pointers on one address, an empty batch, a bad extent or variant, two defects at once -- as the build
+    that tests/golden/capi_return_codes.json was recorded from did: the validation order and the guarded pairs of every
+    family, none of the calls reaching the HIP runtime.  No case is left out: the count per symbol is asserted."""
+    import importlib.util
+    import json
+    golden = os.path.join(ROOT, "tests", "golden")
+    spec = importlib.util.spec_from_file_location("make_capi_codes", os.path.join(golden, "make_capi_codes.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(golden, "capi_return_codes.json")) as fh:
+        recorded = json.load(fh)["symbols"]
+    symbols = pkg.capi.SYMBOLS
+    names = gen.operator_symbols(symbols)
+    assert sorted(recorded) == names and len(names) == 96
+    got = gen.replay(pkg.capi.lib(), symbols)
+    wrong, total = [], 0
+    for name in names:
+        want = recorded[name]
+        assert len(got[name]) == len(want) == gen.case_count(name, symbols[name][1]), name
+        total += len(want)
+        wrong += [f"{name}, {label}: rc {rc}, recorded {-int(w)}" for (label, rc), w in zip(got[name], want) if rc != -int(w)]
+    assert total == 22610
+    assert not wrong, f"{len(wrong)} of {total} cases differ:\n" + "\n".join(wrong[:40])
+
+
 def test_library_reads_no_environment_variable():
     """The kernels' configuration is what the source says: no file under csrc/ reads the environment."""
     csrc = os.path.join(ROOT, "gpu-benchmarking_amd", "csrc")
