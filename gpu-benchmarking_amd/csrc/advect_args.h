@@ -28,4 +28,13 @@ int launch_advect_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a, const
 bool advect_wave_built(int dim, unsigned nq);
 bool advect_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2);
 
+// The LDS classes of the any-extent advection kernels (advect_generic.hip, affine_advect_generic.hip) in scalars: two
+// point images.  3D 12^3: 3456; 2D 32^2: 2048, the small class.
+constexpr int kAdvSmallCap = 2048, kAdvLargeCap = 2 * 12 * 12 * 12;
+// LDS the extents need: two point images
+inline unsigned advect_need(int dim, unsigned nq0, unsigned nq1, unsigned nq2)
+{
+    return 2 * nq0 * nq1 * (dim == 3 ? nq2 : 1);
+}
+
 } // namespace sf

@@ -9,8 +9,10 @@
 //   3D: in_a (B) -> w1 (A) -> w2 (B) -> u_a (A) -> r_a (B) -> t1 (A) -> t2 (B) -> out_a (HBM)
 //   2D: in_a (A) -> w1 (B) -> u_a (A) -> r_a (B) -> t1 (A) -> out_a (HBM)
 // so beta of a point is formed once per field here (the same arithmetic on the same values: the same bits), where the
-// wave kernels form it once.  The sweeps and the derivatives of a point are the fragments frag/ae_forward_*.inc,
-// frag/ae_deriv_*.inc and frag/ae_transposed_*.inc (any_extent.h).
+// wave kernels form it once.  The body of the loop over the fields is frag/ae_advect_field.inc (any_extent.h), shared with
+// affine_advect_generic.hip: it strings frag/ae_forward_*.inc, frag/ae_deriv_*.inc and frag/ae_transposed_*.inc together
+// around the point step.  This unit's own: where df comes from (AE_ADV_DF, the planes) and the value a point stores
+// (AE_ADV_VALUE, the weight plane times the sum).  The LDS classes are in advect_args.h.
 // Every buffer is read and written with scalar accesses: scalar alignment is enough.  No workspace and static LDS only:
 // every launch is a single kernel node that needs no function attribute, capture-safe from the first call.
 // Latency-bound (a barrier per sweep, one element per workgroup), not a roofline target.  Extents up to 12 per direction
@@ -20,9 +22,6 @@
 
 namespace sf
 {
-
-// LDS classes in scalars: two point images.  3D 12^3: 3456; 2D 32^2: 2048, the small class.
-constexpr int kAdvSmallCap = 2048, kAdvLargeCap = 2 * 12 * 12 * 12;
 
 template <typename T, int DIM, int CAP, int NT>
 __global__ __launch_bounds__(NT) void advect_generic_kernel(
@@ -44,68 +43,11 @@ __global__ __launch_bounds__(NT) void advect_generic_kernel(
         const T *ce2 = DIM == 3 ? c2 + e * (uint64_t)nqt : nullptr;
         for (int a = 0; a < nf; ++a)
         {
-            const T *src = (a == 0 ? x0 : (a == 1 ? x1 : x2)) + e * (uint64_t)nmt;
-            T *dst       = (a == 0 ? out0 : (a == 1 ? out1 : out2)) + e * (uint64_t)nmt;
-            const T *P0  = A; // the point image of u_a
-            if constexpr (DIM == 2)
-            {
-#define AE_MODES A
-#define AE_W1 B
-#define AE_POINTS A
-#define AE_POINT_VALUE(s) s
-#include "frag/ae_forward_2d.inc"
-                for (int x = tid; x < nqt; x += NT)
-                {
-                    T J0, J1;
-#define AE_DU0 J0
-#define AE_DU1 J1
-#include "frag/ae_deriv_2d.inc"
-                    const T v0 = ce0[x], v1 = ce1[x];
-                    const T be0 = sfma(v1, dfe[2 * nqt + x], v0 * dfe[x]);
-                    const T be1 = sfma(v1, dfe[3 * nqt + x], v0 * dfe[nqt + x]);
-                    B[x]        = we[x] * sfma(be1, J1, be0 * J0);
-                }
-                __syncthreads();
-#define AE_POINTS B
-#define AE_T1 A
-#include "frag/ae_transposed_2d.inc"
-            }
-            else
-            {
-#define AE_MODES B
-#define AE_W1 A
-#define AE_W2 B
-#define AE_POINTS A
-#define AE_POINT_VALUE(s) s
-#include "frag/ae_forward_3d.inc"
-                for (int x = tid; x < nqt; x += NT)
-                {
-                    T J0, J1, J2;
-#define AE_DU0 J0
-#define AE_DU1 J1
-#define AE_DU2 J2
-#include "frag/ae_deriv_3d.inc"
-                    const T v0 = ce0[x], v1 = ce1[x], v2 = ce2[x];
-                    const T be0 = sfma(v2, dfe[6 * nqt + x], sfma(v1, dfe[3 * nqt + x], v0 * dfe[x]));
-                    const T be1 = sfma(v2, dfe[7 * nqt + x], sfma(v1, dfe[4 * nqt + x], v0 * dfe[nqt + x]));
-                    const T be2 = sfma(v2, dfe[8 * nqt + x], sfma(v1, dfe[5 * nqt + x], v0 * dfe[2 * nqt + x]));
-                    B[x]        = we[x] * sfma(be2, J2, sfma(be1, J1, be0 * J0));
-                }
-                __syncthreads();
-#define AE_POINTS B
-#define AE_T1 A
-#define AE_T2 B
-#include "frag/ae_transposed_3d.inc"
-            }
-            __syncthreads(); // the next field, or the next element, overwrites the images
+#define AE_ADV_DF(c) dfe[(c) * nqt + x]
+#define AE_ADV_VALUE(r, i, j, k) B[x] = we[x] * (r);
+#include "frag/ae_advect_field.inc"
         }
     }
-}
-
-// LDS the extents need: two point images
-static inline unsigned advect_need(int dim, unsigned nq0, unsigned nq1, unsigned nq2)
-{
-    return 2 * nq0 * nq1 * (dim == 3 ? nq2 : 1);
 }
 
 template <int DIM, typename T>

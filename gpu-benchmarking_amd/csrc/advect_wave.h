@@ -13,7 +13,12 @@
 // frag/geom_coordinate_{2d,3d}.inc, once per field with GEOM_X = in_a, over the slab of GeomGeom (the images of the fields
 // 0 .. d-2 kept behind the front's slab).  Either way dk[a] is the register pencil d u_a / d xi_(d-1) of the column's lane.
 // The back is that of the mass kernel, once per field out of dk[a]: frag/advect_field_back.inc strings
-// transposed_last, transposed1 (3D) and transposed0 together.  This header's own: the ring of df, w, c and the walk.
+// transposed_last, transposed1 (3D) and transposed0 together.
+// Shared text (csrc/frag/*.inc, the form mass_wave.h describes; affine_advect_wave.h includes the same files): wave_open;
+// per chunk chunk_head, ring_offsets (the ring's clamped column offsets), then field_front_{2d,3d} (NF = 1) or
+// fields_front_{2d,3d} (NF = d), either with the ring primed by ADV_PRIME where the front has its place for it; behind the
+// walk advect_back (advect_field_back for every field).  This header's own: the ring of df, w, c and the arithmetic of
+// the walk.
 //
 // Order of operations (it defines the rounding; every sum in ascending index, the first product a multiply, then FMAs):
 //   1. forward sweeps p -> i, q -> j, r -> k of in_a                              (u_a, the point values)
@@ -82,24 +87,13 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_advect_wave_kernel(
     uint64_t nelmt)
 {
     static_assert(NF == 1 || NF == 3, "one field or d");
-    using G          = AdvectGeom<NQ, EC, 3, NF, T>;
-    using M          = typename G::M;
-    using F          = typename G::F;
-    using IO         = MassIo<M>;
-    constexpr int NM = G::NM, NMP = F::NMP, NQP = G::NQP, NQ2 = NQ * NQ, NQT = NQ2 * NQ;
-    constexpr int NPASS = G::NPASS, NP = G::NP, RING = G::RING, NV = 13;
-    constexpr int PL = NQ * NQP, ES = NQ * PL; // plane and element stride of a point image
-    static_assert(KMAP > 0, "short-lived waves only");
-
-#include "frag/wave_slab.inc"
-    // NF = 3: d u_0 / d xi_1, d u_0 / d xi_0, d u_1 / d xi_1, d u_1 / d xi_0 behind the front's slab; NF = 1: not used
-    T *kept = slab;
-    if constexpr (NF == 3)
-        kept = slab + GeomGeom<NQ, EC, 3, T>::KEPT_BASE;
-#include "frag/wave_chunks.inc"
-#include "frag/lane_roles_3d.inc"
-    const T *in = x0; // the stream the fragments fetch and stage: the field at hand
-#include "frag/chunk_fetch_first.inc"
+    using G            = AdvectGeom<NQ, EC, 3, NF, T>;
+    constexpr int RING = G::RING, NV = 13;
+    // NF = d: the images of the fields 0 .. d-2 behind the front's slab; NF = 1: not used
+#define OPEN_DIM 3
+#define OPEN_KEPT_BASE (NF == 3 ? GeomGeom<NQ, EC, 3, T>::KEPT_BASE : 0)
+#define OPEN_LANE_SETUP
+#include "frag/wave_open.inc"
 
     uint64_t c = it.first;
     for (uint64_t n = 0; n < it.count; ++n, c += it.step)
@@ -111,50 +105,25 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_advect_wave_kernel(
         const T *wc  = w + c * (uint64_t)(EC * NQT);
         const T *cc0 = c0 + c * (uint64_t)(EC * NQT), *cc1 = c1 + c * (uint64_t)(EC * NQT),
                 *cc2 = c2 + c * (uint64_t)(EC * NQT);
-        int doff[NPASS], woff[NPASS];
-#pragma unroll
-        for (int s = 0; s < NPASS; ++s)
-        {
-            const int e = ecol[s] < evalid ? ecol[s] : evalid - 1;
-            doff[s]     = e * (9 * NQT) + colp[s];
-            woff[s]     = e * NQT + colp[s];
-        }
+#define RING_OFF doff[NPASS], woff[NPASS]
+#define RING_SET doff[s] = e * (9 * NQT) + colp[s], woff[s] = e * NQT + colp[s];
+#include "frag/ring_offsets.inc"
         T av[RING][NPASS][NV];
+        // the first slices of the ring, requested by the front
+#define ADV_PRIME                                                                                                      \
+    _Pragma("unroll") for (int r = 0; r < RING; ++r)                                                                   \
+        load_advect_slice<NPASS, 3, NQ2, NQT>(av[r], dc, wc, cc0, cc1, cc2, doff, woff, r);
         if constexpr (NF == 1)
         {
-            T *imgU = slab;          // u, then du / d xi_1
-            T *imgD = slab + G::IMG; // du / d xi_0
-#include "frag/chunk_stage.inc"
-#pragma unroll
-            for (int r = 0; r < RING; ++r)
-                load_advect_slice<NPASS, 3, NQ2, NQT>(av[r], dc, wc, cc0, cc1, cc2, doff, woff, r);
-#include "frag/chunk_fetch_next.inc"
-#include "frag/forward0.inc"
-#include "frag/forward1_3d.inc"
-            {
-                T u[NPASS][NQ];
-                T(&dreg)[NPASS][NQ] = dk[0];
-#include "frag/point_values_3d.inc"
-            }
+#define FRONT_PRIME ADV_PRIME
+#include "frag/field_front_3d.inc"
         }
         else
         {
-#define GEOM_A 0
-#define GEOM_X x0
-#define GEOM_NEXT x1
-#include "frag/geom_coordinate_3d.inc"
-#define GEOM_A 1
-#define GEOM_X x1
-#define GEOM_NEXT x2
-#include "frag/geom_coordinate_3d.inc"
-#pragma unroll
-            for (int r = 0; r < RING; ++r)
-                load_advect_slice<NPASS, 3, NQ2, NQT>(av[r], dc, wc, cc0, cc1, cc2, doff, woff, r);
-#define GEOM_A 2
-#define GEOM_X x2
-#define GEOM_NEXT x0
-#include "frag/geom_coordinate_3d.inc"
+#define FRONT_PRIME ADV_PRIME
+#include "frag/fields_front_3d.inc"
         }
+#undef ADV_PRIME
         // ---- the walk over k: beta of the point, r_a over dk[a] ------------------------------------------
 #pragma unroll
         for (int k = 0; k < NQ; ++k)
@@ -187,21 +156,8 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_advect_wave_kernel(
         }
         wave_lds_fence(); // the images are read: the back takes the slab
         // ---- the back, once per field: out_a = B^T r_a out of dk[a] --------------------------------------
-#define ADV_DIM 3
-#define ADV_A 0
-#define ADV_OUT out0
-#include "frag/advect_field_back.inc"
-        if constexpr (NF == 3)
-        {
-#define ADV_DIM 3
-#define ADV_A 1
-#define ADV_OUT out1
-#include "frag/advect_field_back.inc"
-#define ADV_DIM 3
-#define ADV_A 2
-#define ADV_OUT out2
-#include "frag/advect_field_back.inc"
-        }
+#define ADV_BACK_DIM 3
+#include "frag/advect_back.inc"
     }
 }
 
@@ -215,23 +171,13 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_advect_wave_kernel(
     const T *__restrict__ x0, const T *__restrict__ x1, T *__restrict__ out0, T *__restrict__ out1, uint64_t nelmt)
 {
     static_assert(NF == 1 || NF == 2, "one field or d");
-    using G          = AdvectGeom<NQ, EC, 2, NF, T>;
-    using M          = typename G::M;
-    using F          = typename G::F;
-    using IO         = MassIo<M>;
-    constexpr int NM = G::NM, NMP = F::NMP, NQP = G::NQP, NQT = NQ * NQ;
-    constexpr int NPASS = G::NPASS, NP = G::NP, RING = G::RING, NV = 7;
-    constexpr int ES = NQ * NQP; // element stride of the point image
-    static_assert(KMAP > 0, "short-lived waves only");
-
-#include "frag/wave_slab.inc"
-    T *kept = slab; // NF = 2: d u_0 / d xi_0 behind the front's slab; NF = 1: not used
-    if constexpr (NF == 2)
-        kept = slab + GeomGeom<NQ, EC, 2, T>::KEPT_BASE;
-#include "frag/wave_chunks.inc"
-#include "frag/lane_roles_2d.inc"
-    const T *in = x0; // the stream the fragments fetch and stage: the field at hand
-#include "frag/chunk_fetch_first.inc"
+    using G            = AdvectGeom<NQ, EC, 2, NF, T>;
+    constexpr int RING = G::RING, NV = 7;
+    // NF = d: the images of the fields 0 .. d-2 behind the front's slab; NF = 1: not used
+#define OPEN_DIM 2
+#define OPEN_KEPT_BASE (NF == 2 ? GeomGeom<NQ, EC, 2, T>::KEPT_BASE : 0)
+#define OPEN_LANE_SETUP
+#include "frag/wave_open.inc"
 
     uint64_t c = it.first;
     for (uint64_t n = 0; n < it.count; ++n, c += it.step)
@@ -242,42 +188,24 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_advect_wave_kernel(
         const T *dc  = df + c * (uint64_t)(EC * 4 * NQT);
         const T *wc  = w + c * (uint64_t)(EC * NQT);
         const T *cc0 = c0 + c * (uint64_t)(EC * NQT), *cc1 = c1 + c * (uint64_t)(EC * NQT);
-        int doff[NPASS], woff[NPASS];
-#pragma unroll
-        for (int s = 0; s < NPASS; ++s)
-        {
-            const int e = ecol[s] < evalid ? ecol[s] : evalid - 1;
-            doff[s]     = e * (4 * NQT) + colp[s];
-            woff[s]     = e * NQT + colp[s];
-        }
+#define RING_OFF doff[NPASS], woff[NPASS]
+#define RING_SET doff[s] = e * (4 * NQT) + colp[s], woff[s] = e * NQT + colp[s];
+#include "frag/ring_offsets.inc"
         T av[RING][NPASS][NV];
+#define ADV_PRIME                                                                                                      \
+    _Pragma("unroll") for (int r = 0; r < RING; ++r)                                                                   \
+        load_advect_slice<NPASS, 2, NQ, NQT>(av[r], dc, wc, cc0, cc1, (const T *)nullptr, doff, woff, r);
         if constexpr (NF == 1)
         {
-            T *imgU = slab; // u, then du / d xi_0
-#include "frag/chunk_stage.inc"
-#pragma unroll
-            for (int r = 0; r < RING; ++r)
-                load_advect_slice<NPASS, 2, NQ, NQT>(av[r], dc, wc, cc0, cc1, (const T *)nullptr, doff, woff, r);
-#include "frag/chunk_fetch_next.inc"
-#include "frag/forward0.inc"
-            {
-                T u[NPASS][NQ];
-                T(&dreg)[NPASS][NQ] = dk[0];
-#include "frag/point_values_2d.inc"
-            }
+#define FRONT_PRIME ADV_PRIME
+#include "frag/field_front_2d.inc"
         }
         else
         {
-#define GEOM_A 0
-#define GEOM_X x0
-#include "frag/geom_coordinate_2d.inc"
-#pragma unroll
-            for (int r = 0; r < RING; ++r)
-                load_advect_slice<NPASS, 2, NQ, NQT>(av[r], dc, wc, cc0, cc1, (const T *)nullptr, doff, woff, r);
-#define GEOM_A 1
-#define GEOM_X x1
-#include "frag/geom_coordinate_2d.inc"
+#define FRONT_PRIME ADV_PRIME
+#include "frag/fields_front_2d.inc"
         }
+#undef ADV_PRIME
         // ---- the walk over j ---------------------------------------------------------------------------
 #pragma unroll
         for (int j = 0; j < NQ; ++j)
@@ -308,17 +236,8 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_advect_wave_kernel(
         }
         wave_lds_fence(); // the images are read: the back takes the slab
         // ---- the back, once per field --------------------------------------------------------------------
-#define ADV_DIM 2
-#define ADV_A 0
-#define ADV_OUT out0
-#include "frag/advect_field_back.inc"
-        if constexpr (NF == 2)
-        {
-#define ADV_DIM 2
-#define ADV_A 1
-#define ADV_OUT out1
-#include "frag/advect_field_back.inc"
-        }
+#define ADV_BACK_DIM 2
+#include "frag/advect_back.inc"
     }
 }
 

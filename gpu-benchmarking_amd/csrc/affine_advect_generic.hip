@@ -10,20 +10,20 @@
 //   3D: in_a (B) -> w1 (A) -> w2 (B) -> u_a (A) -> r_a (B) -> t1 (A) -> t2 (B) -> out_a (HBM)
 //   2D: in_a (A) -> w1 (B) -> u_a (A) -> r_a (B) -> t1 (A) -> out_a (HBM)
 // so beta and the weight of a point are formed once per field here (the same arithmetic on the same values: the same
-// bits), where the wave kernels form them once.  The sweeps and the derivatives of a point are the fragments
-// frag/ae_forward_*.inc, frag/ae_deriv_*.inc and frag/ae_transposed_*.inc (any_extent.h).
+// bits), where the wave kernels form them once.  The body of the loop over the fields is frag/ae_advect_field.inc
+// (any_extent.h), the text advect_generic.hip includes.  This unit's own: the element set-up, where df comes from
+// (AE_ADV_DF, the constants) and the value a point stores (AE_ADV_VALUE, with the weight formed from je and qw_d).  The
+// LDS classes are those of advect_generic.hip, in advect_args.h.
 // Every buffer is read and written with scalar accesses: scalar alignment is enough.  No workspace and static LDS only:
 // every launch is a single kernel node that needs no function attribute, capture-safe from the first call.  `je` and
 // `qw_d` are not dereferenced when has_w is false.  Latency-bound, not a roofline target.  Extents up to 12 per direction
 // in 3D and 32 in 2D, the bounds of the Helmholtz fallback; beyond, SF_ENOTBUILT.
+#include "advect_args.h"
 #include "affine_advect_args.h"
 #include "helmholtz_generic.h"
 
 namespace sf
 {
-
-// LDS classes in scalars: two point images, as advect_generic.hip.  3D 12^3: 3456; 2D 32^2: 2048, the small class.
-constexpr int kAffAdvSmallCap = 2048, kAffAdvLargeCap = 2 * 12 * 12 * 12;
 
 template <typename T, int DIM, int CAP, int NT>
 __global__ __launch_bounds__(NT) void affine_advect_generic_kernel(
@@ -49,77 +49,15 @@ __global__ __launch_bounds__(NT) void affine_advect_generic_kernel(
         const T *ce2 = DIM == 3 ? c2 + e * (uint64_t)nqt : nullptr;
         for (int a = 0; a < nf; ++a)
         {
-            const T *src = (a == 0 ? x0 : (a == 1 ? x1 : x2)) + e * (uint64_t)nmt;
-            T *dst       = (a == 0 ? out0 : (a == 1 ? out1 : out2)) + e * (uint64_t)nmt;
-            const T *P0  = A; // the point image of u_a
-            if constexpr (DIM == 2)
-            {
-#define AE_MODES A
-#define AE_W1 B
-#define AE_POINTS A
-#define AE_POINT_VALUE(s) s
-#include "frag/ae_forward_2d.inc"
-                for (int x = tid; x < nqt; x += NT)
-                {
-                    T J0, J1;
-#define AE_DU0 J0
-#define AE_DU1 J1
-#include "frag/ae_deriv_2d.inc"
-                    const T v0 = ce0[x], v1 = ce1[x];
-                    const T be0 = sfma(v1, dd[2], v0 * dd[0]);
-                    const T be1 = sfma(v1, dd[3], v0 * dd[1]);
-                    T r         = sfma(be1, J1, be0 * J0);
-                    if (has_w)
-                        r = (jee * (qw1[x / nq0] * qw0[x % nq0])) * r;
-                    B[x] = r;
-                }
-                __syncthreads();
-#define AE_POINTS B
-#define AE_T1 A
-#include "frag/ae_transposed_2d.inc"
-            }
-            else
-            {
-#define AE_MODES B
-#define AE_W1 A
-#define AE_W2 B
-#define AE_POINTS A
-#define AE_POINT_VALUE(s) s
-#include "frag/ae_forward_3d.inc"
-                for (int x = tid; x < nqt; x += NT)
-                {
-                    T J0, J1, J2;
-#define AE_DU0 J0
-#define AE_DU1 J1
-#define AE_DU2 J2
-#include "frag/ae_deriv_3d.inc"
-                    const T v0 = ce0[x], v1 = ce1[x], v2 = ce2[x];
-                    const T be0 = sfma(v2, dd[6], sfma(v1, dd[3], v0 * dd[0]));
-                    const T be1 = sfma(v2, dd[7], sfma(v1, dd[4], v0 * dd[1]));
-                    const T be2 = sfma(v2, dd[8], sfma(v1, dd[5], v0 * dd[2]));
-                    T r         = sfma(be2, J2, sfma(be1, J1, be0 * J0));
-                    if (has_w)
-                    {
-                        const int kj = x / nq0;
-                        r            = (jee * (qw2[kj / nq1] * (qw1[kj % nq1] * qw0[x % nq0]))) * r;
-                    }
-                    B[x] = r;
-                }
-                __syncthreads();
-#define AE_POINTS B
-#define AE_T1 A
-#define AE_T2 B
-#include "frag/ae_transposed_3d.inc"
-            }
-            __syncthreads(); // the next field, or the next element, overwrites the images
+#define AE_ADV_DF(c) dd[c]
+#define AE_ADV_VALUE(r, i, j, k)                                                                                       \
+    T v = (r);                                                                                                         \
+    if (has_w)                                                                                                         \
+        v = (jee * (DIM == 3 ? qw2[k] * (qw1[j] * qw0[i]) : qw1[j] * qw0[i])) * v;                                     \
+    B[x] = v;
+#include "frag/ae_advect_field.inc"
         }
     }
-}
-
-// LDS the extents need: two point images
-static inline unsigned affine_advect_need(int dim, unsigned nq0, unsigned nq1, unsigned nq2)
-{
-    return 2 * nq0 * nq1 * (dim == 3 ? nq2 : 1);
 }
 
 template <int DIM, typename T>
@@ -127,9 +65,9 @@ int launch_affine_advect_generic(const unsigned (&nq)[3], const ArgsT<DIM, T> &a
                                  hipStream_t s)
 {
     return launch_any_extent(affine_advect_generic_built(DIM, nq[0], nq[1], nq[2]),
-                             affine_advect_need(DIM, nq[0], nq[1], nq[2]) <= (unsigned)kAffAdvSmallCap,
-                             affine_advect_generic_kernel<T, DIM, kAffAdvSmallCap, 64>,
-                             affine_advect_generic_kernel<T, DIM, kAffAdvLargeCap, 256>, a.nelmt, s, a.b0, a.b1,
+                             advect_need(DIM, nq[0], nq[1], nq[2]) <= (unsigned)kAdvSmallCap,
+                             affine_advect_generic_kernel<T, DIM, kAdvSmallCap, 64>,
+                             affine_advect_generic_kernel<T, DIM, kAdvLargeCap, 256>, a.nelmt, s, a.b0, a.b1,
                              basis2(a), x.d0, x.d1, x.d2, x.qw0, x.qw1, x.qw2, x.dfe, x.je, x.je != nullptr, x.c0, x.c1,
                              x.c2, x.in0, x.in1, x.in2, x.out0, x.out1, x.out2, a.nelmt, x.nf, (int)nq[0], (int)nq[1],
                              (int)nq[2]);
@@ -148,7 +86,7 @@ template int launch_affine_advect_generic<2, float>(const unsigned (&)[3], const
 bool affine_advect_generic_built(int dim, unsigned nq0, unsigned nq1, unsigned nq2)
 {
     return helm_extents_built(dim, nq0, nq1, nq2) &&
-           affine_advect_need(dim, nq0, nq1, dim == 3 ? nq2 : 0) <= (unsigned)kAffAdvLargeCap;
+           advect_need(dim, nq0, nq1, dim == 3 ? nq2 : 0) <= (unsigned)kAdvLargeCap;
 }
 
 } // namespace sf

@@ -55,19 +55,7 @@ static int go_affine_advect(const ArgsT<DIM, T> &a, const AffineAdvectArgsT<T> &
 template <int DIM, typename T>
 int launch_affine_advect_wave(unsigned nq, const ArgsT<DIM, T> &a, const AffineAdvectArgsT<T> &x, hipStream_t s)
 {
-#define SF_CASE(N) case N: return go_affine_advect<DIM, N, T>(a, x, s);
-    if constexpr (DIM == 3)
-        switch (nq)
-        {
-            SF_HELM_HEX_CASES(SF_CASE)
-        }
-    else
-        switch (nq)
-        {
-            SF_HELM_QUAD_CASES(SF_CASE)
-        }
-#undef SF_CASE
-    return SF_ENOTBUILT;
+    return with_helm_order<DIM>(nq, [&](auto n) { return go_affine_advect<DIM, decltype(n)::value, T>(a, x, s); });
 }
 
 } // namespace sf

@@ -10,7 +10,12 @@
 // 1: the gradient front over HelmGeom; NF = d: frag/geom_coordinate_{2d,3d}.inc once per field over GeomGeom with the
 // kept images), the same back (frag/advect_field_back.inc once per field), the fragments unchanged in text -- with the
 // df and w part of the ring taken out: per element the call moves d nq^d + 2 NF nm^d + d*d + 1 scalars where the
-// deformed one moves (d*d + d + 1) nq^d + 2 NF nm^d.  This header's own: the ring of c, the constants and the walk.
+// deformed one moves (d*d + d + 1) nq^d + 2 NF nm^d.
+// Shared text (csrc/frag/*.inc, the sequence advect_wave.h lists): wave_open, ring_offsets, field_front_{2d,3d} or
+// fields_front_{2d,3d} with AFF_PRIME (the ring primed, the constants loaded), advect_back.  This header's own: the ring of
+// c, the constants, the weight products and the arithmetic of the walk.  The weight product of the column goes into
+// wave_open as its OPEN_LANE_SETUP: formed behind the opening, after the first request, it changed 44 of the 89 kernels
+// of affine_advect_f32.hip.
 //
 // Order of operations.  That of advect_wave.h with df_ab replaced by the element's constant and w by (je_e q), q formed
 // as qw2 * (qw1 * qw0): every sum in ascending index, the first product a multiply, then FMAs.  On a route the results
@@ -73,32 +78,20 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_affine_advect_wave_kerne
     const T *__restrict__ x2, T *__restrict__ out0, T *__restrict__ out1, T *__restrict__ out2, uint64_t nelmt)
 {
     static_assert(NF == 1 || NF == 3, "one field or d");
-    using G          = AdvectGeom<NQ, EC, 3, NF, T>;
-    using M          = typename G::M;
-    using F          = typename G::F;
-    using IO         = MassIo<M>;
-    constexpr int NM = G::NM, NMP = F::NMP, NQP = G::NQP, NQ2 = NQ * NQ, NQT = NQ2 * NQ;
-    constexpr int NPASS = G::NPASS, NP = G::NP, RING = G::RING, NCOMP = 9;
-    constexpr int PL = NQ * NQP, ES = NQ * PL; // plane and element stride of a point image
-    static_assert(KMAP > 0, "short-lived waves only");
-
-#include "frag/wave_slab.inc"
-    // NF = 3: d u_0 / d xi_1, d u_0 / d xi_0, d u_1 / d xi_1, d u_1 / d xi_0 behind the front's slab; NF = 1: not used
-    T *kept = slab;
-    if constexpr (NF == 3)
-        kept = slab + GeomGeom<NQ, EC, 3, T>::KEPT_BASE;
-#include "frag/wave_chunks.inc"
-#include "frag/lane_roles_3d.inc"
-    T qji[NPASS]; // qw1[j] qw0[i] of the column
-    (void)qji;    // unused without the weight
-    if constexpr (HASW)
-    {
-#pragma unroll
-        for (int s = 0; s < NPASS; ++s)
-            qji[s] = qw1[colp[s] / NQ] * qw0[colp[s] % NQ];
+    using G            = AdvectGeom<NQ, EC, 3, NF, T>;
+    constexpr int RING = G::RING, NCOMP = 9;
+    // NF = d: the images of the fields 0 .. d-2 behind the front's slab; NF = 1: not used
+#define OPEN_DIM 3
+#define OPEN_KEPT_BASE (NF == 3 ? GeomGeom<NQ, EC, 3, T>::KEPT_BASE : 0)
+    // qji = qw1[j] qw0[i] of the column; unused without the weight
+#define OPEN_LANE_SETUP                                                                                                \
+    T qji[NPASS];                                                                                                      \
+    (void)qji;                                                                                                         \
+    if constexpr (HASW)                                                                                                \
+    {                                                                                                                  \
+        _Pragma("unroll") for (int s = 0; s < NPASS; ++s) qji[s] = qw1[colp[s] / NQ] * qw0[colp[s] % NQ];              \
     }
-    const T *in = x0; // the stream the fragments fetch and stage: the field at hand
-#include "frag/chunk_fetch_first.inc"
+#include "frag/wave_open.inc"
 
     uint64_t c = it.first;
     for (uint64_t n = 0; n < it.count; ++n, c += it.step)
@@ -108,52 +101,26 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_affine_advect_wave_kerne
         // the ring of c: every lane's offsets are in bounds
         const T *cc0 = c0 + c * (uint64_t)(EC * NQT), *cc1 = c1 + c * (uint64_t)(EC * NQT),
                 *cc2 = c2 + c * (uint64_t)(EC * NQT);
-        int coff[NPASS];
-#pragma unroll
-        for (int s = 0; s < NPASS; ++s)
-        {
-            const int e = ecol[s] < evalid ? ecol[s] : evalid - 1;
-            coff[s]     = e * NQT + colp[s];
-        }
+#define RING_OFF coff[NPASS]
+#define RING_SET coff[s] = e * NQT + colp[s];
+#include "frag/ring_offsets.inc"
         T cv[RING][NPASS][3];
         T dv[NPASS][NCOMP], lj[NPASS]; // the constants of this chunk's elements (lj = je_e)
+        // the first slices of the ring and the constants, requested by the front
+#define AFF_PRIME                                                                                                      \
+    _Pragma("unroll") for (int r = 0; r < RING; ++r) load_c_slice<NPASS, 3, NQ2>(cv[r], cc0, cc1, cc2, coff, r);       \
+    load_element_constants<NPASS, NCOMP, EC, HASW>(dv, lj, dfe, je, T(1), c * (uint64_t)EC, ecol, evalid);
         if constexpr (NF == 1)
         {
-            T *imgU = slab;          // u, then du / d xi_1
-            T *imgD = slab + G::IMG; // du / d xi_0
-#include "frag/chunk_stage.inc"
-#pragma unroll
-            for (int r = 0; r < RING; ++r)
-                load_c_slice<NPASS, 3, NQ2>(cv[r], cc0, cc1, cc2, coff, r);
-            load_element_constants<NPASS, NCOMP, EC, HASW>(dv, lj, dfe, je, T(1), c * (uint64_t)EC, ecol, evalid);
-#include "frag/chunk_fetch_next.inc"
-#include "frag/forward0.inc"
-#include "frag/forward1_3d.inc"
-            {
-                T u[NPASS][NQ];
-                T(&dreg)[NPASS][NQ] = dk[0];
-#include "frag/point_values_3d.inc"
-            }
+#define FRONT_PRIME AFF_PRIME
+#include "frag/field_front_3d.inc"
         }
         else
         {
-#define GEOM_A 0
-#define GEOM_X x0
-#define GEOM_NEXT x1
-#include "frag/geom_coordinate_3d.inc"
-#define GEOM_A 1
-#define GEOM_X x1
-#define GEOM_NEXT x2
-#include "frag/geom_coordinate_3d.inc"
-#pragma unroll
-            for (int r = 0; r < RING; ++r)
-                load_c_slice<NPASS, 3, NQ2>(cv[r], cc0, cc1, cc2, coff, r);
-            load_element_constants<NPASS, NCOMP, EC, HASW>(dv, lj, dfe, je, T(1), c * (uint64_t)EC, ecol, evalid);
-#define GEOM_A 2
-#define GEOM_X x2
-#define GEOM_NEXT x0
-#include "frag/geom_coordinate_3d.inc"
+#define FRONT_PRIME AFF_PRIME
+#include "frag/fields_front_3d.inc"
         }
+#undef AFF_PRIME
         // ---- the walk over k: beta of the point, r_a over dk[a] ------------------------------------------
 #pragma unroll
         for (int k = 0; k < NQ; ++k)
@@ -201,21 +168,8 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_affine_advect_wave_kerne
         }
         wave_lds_fence(); // the images are read: the back takes the slab
         // ---- the back, once per field: out_a = B^T r_a out of dk[a] --------------------------------------
-#define ADV_DIM 3
-#define ADV_A 0
-#define ADV_OUT out0
-#include "frag/advect_field_back.inc"
-        if constexpr (NF == 3)
-        {
-#define ADV_DIM 3
-#define ADV_A 1
-#define ADV_OUT out1
-#include "frag/advect_field_back.inc"
-#define ADV_DIM 3
-#define ADV_A 2
-#define ADV_OUT out2
-#include "frag/advect_field_back.inc"
-        }
+#define ADV_BACK_DIM 3
+#include "frag/advect_back.inc"
     }
 }
 
@@ -230,31 +184,20 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_affine_advect_wave_kern
     T *__restrict__ out0, T *__restrict__ out1, uint64_t nelmt)
 {
     static_assert(NF == 1 || NF == 2, "one field or d");
-    using G          = AdvectGeom<NQ, EC, 2, NF, T>;
-    using M          = typename G::M;
-    using F          = typename G::F;
-    using IO         = MassIo<M>;
-    constexpr int NM = G::NM, NMP = F::NMP, NQP = G::NQP, NQT = NQ * NQ;
-    constexpr int NPASS = G::NPASS, NP = G::NP, RING = G::RING, NCOMP = 4;
-    constexpr int ES = NQ * NQP; // element stride of the point image
-    static_assert(KMAP > 0, "short-lived waves only");
-
-#include "frag/wave_slab.inc"
-    T *kept = slab; // NF = 2: d u_0 / d xi_0 behind the front's slab; NF = 1: not used
-    if constexpr (NF == 2)
-        kept = slab + GeomGeom<NQ, EC, 2, T>::KEPT_BASE;
-#include "frag/wave_chunks.inc"
-#include "frag/lane_roles_2d.inc"
-    T qi[NPASS]; // qw0[i] of the column
-    (void)qi;    // unused without the weight
-    if constexpr (HASW)
-    {
-#pragma unroll
-        for (int s = 0; s < NPASS; ++s)
-            qi[s] = qw0[colp[s]];
+    using G            = AdvectGeom<NQ, EC, 2, NF, T>;
+    constexpr int RING = G::RING, NCOMP = 4;
+    // NF = d: the images of the fields 0 .. d-2 behind the front's slab; NF = 1: not used
+#define OPEN_DIM 2
+#define OPEN_KEPT_BASE (NF == 2 ? GeomGeom<NQ, EC, 2, T>::KEPT_BASE : 0)
+    // qi = qw0[i] of the column; unused without the weight
+#define OPEN_LANE_SETUP                                                                                                \
+    T qi[NPASS];                                                                                                       \
+    (void)qi;                                                                                                          \
+    if constexpr (HASW)                                                                                                \
+    {                                                                                                                  \
+        _Pragma("unroll") for (int s = 0; s < NPASS; ++s) qi[s] = qw0[colp[s]];                                        \
     }
-    const T *in = x0; // the stream the fragments fetch and stage: the field at hand
-#include "frag/chunk_fetch_first.inc"
+#include "frag/wave_open.inc"
 
     uint64_t c = it.first;
     for (uint64_t n = 0; n < it.count; ++n, c += it.step)
@@ -263,44 +206,26 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_affine_advect_wave_kern
         T dk[2][NPASS][NQ]; // d u_a / d xi_1 over j, then r_a
         // the ring of c and the constants, as in the 3D kernel
         const T *cc0 = c0 + c * (uint64_t)(EC * NQT), *cc1 = c1 + c * (uint64_t)(EC * NQT);
-        int coff[NPASS];
-#pragma unroll
-        for (int s = 0; s < NPASS; ++s)
-        {
-            const int e = ecol[s] < evalid ? ecol[s] : evalid - 1;
-            coff[s]     = e * NQT + colp[s];
-        }
+#define RING_OFF coff[NPASS]
+#define RING_SET coff[s] = e * NQT + colp[s];
+#include "frag/ring_offsets.inc"
         T cv[RING][NPASS][2];
         T dv[NPASS][NCOMP], lj[NPASS];
+#define AFF_PRIME                                                                                                      \
+    _Pragma("unroll") for (int r = 0; r < RING; ++r)                                                                   \
+        load_c_slice<NPASS, 2, NQ>(cv[r], cc0, cc1, (const T *)nullptr, coff, r);                                      \
+    load_element_constants<NPASS, NCOMP, EC, HASW>(dv, lj, dfe, je, T(1), c * (uint64_t)EC, ecol, evalid);
         if constexpr (NF == 1)
         {
-            T *imgU = slab; // u, then du / d xi_0
-#include "frag/chunk_stage.inc"
-#pragma unroll
-            for (int r = 0; r < RING; ++r)
-                load_c_slice<NPASS, 2, NQ>(cv[r], cc0, cc1, (const T *)nullptr, coff, r);
-            load_element_constants<NPASS, NCOMP, EC, HASW>(dv, lj, dfe, je, T(1), c * (uint64_t)EC, ecol, evalid);
-#include "frag/chunk_fetch_next.inc"
-#include "frag/forward0.inc"
-            {
-                T u[NPASS][NQ];
-                T(&dreg)[NPASS][NQ] = dk[0];
-#include "frag/point_values_2d.inc"
-            }
+#define FRONT_PRIME AFF_PRIME
+#include "frag/field_front_2d.inc"
         }
         else
         {
-#define GEOM_A 0
-#define GEOM_X x0
-#include "frag/geom_coordinate_2d.inc"
-#pragma unroll
-            for (int r = 0; r < RING; ++r)
-                load_c_slice<NPASS, 2, NQ>(cv[r], cc0, cc1, (const T *)nullptr, coff, r);
-            load_element_constants<NPASS, NCOMP, EC, HASW>(dv, lj, dfe, je, T(1), c * (uint64_t)EC, ecol, evalid);
-#define GEOM_A 1
-#define GEOM_X x1
-#include "frag/geom_coordinate_2d.inc"
+#define FRONT_PRIME AFF_PRIME
+#include "frag/fields_front_2d.inc"
         }
+#undef AFF_PRIME
         // ---- the walk over j ---------------------------------------------------------------------------
 #pragma unroll
         for (int j = 0; j < NQ; ++j)
@@ -344,17 +269,8 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_affine_advect_wave_kern
         }
         wave_lds_fence(); // the images are read: the back takes the slab
         // ---- the back, once per field --------------------------------------------------------------------
-#define ADV_DIM 2
-#define ADV_A 0
-#define ADV_OUT out0
-#include "frag/advect_field_back.inc"
-        if constexpr (NF == 2)
-        {
-#define ADV_DIM 2
-#define ADV_A 1
-#define ADV_OUT out1
-#include "frag/advect_field_back.inc"
-        }
+#define ADV_BACK_DIM 2
+#include "frag/advect_back.inc"
     }
 }
 

@@ -18,7 +18,7 @@ template int launch_affine_iprodderiv_wave<2, double>(unsigned, const QuadArgs &
 // the Helmholtz table: 3D isotropic nq 2..8, 2D isotropic nq 2..16
 bool affine_deriv_wave_built(int dim, unsigned nq)
 {
-    return nq >= 2 && nq <= (dim == 3 ? 8u : 16u);
+    return helm_order_built(dim, nq);
 }
 
 } // namespace sf

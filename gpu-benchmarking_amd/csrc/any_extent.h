@@ -1,16 +1,24 @@
 // any_extent.h -- what the any-extent kernels of iproduct_generic.hip, mass_generic.hip, helmholtz_generic.h (with
-// helmholtz_generic.hip and affine_generic.hip), physderiv_generic.hip and iprodderiv_generic.hip share: the scalar FMA,
-// the ascending strided dot product of their sweeps, and the guarded launch of one of their two LDS classes.
+// helmholtz_generic.hip and affine_generic.hip), physderiv_generic.hip, iprodderiv_generic.hip and the units built on
+// them (geom_, advect_, affine_advect_ and vecgrad_generic.hip) share: the scalar FMA, the ascending strided dot product
+// of their sweeps, and the guarded launch of one of their two LDS classes.
 // The kernel text they share is in frag/ae_*.inc, #included in place (each fragment opens with its contract):
 //   ae_prologue.inc                      the element constants
 //   ae_forward_{2d,3d}.inc               modes staged, forward sweeps p -> i, q -> j, r -> k   (mass, Helmholtz, physderiv)
 //   ae_deriv_{2d,3d}.inc                 du_a of a point                                       (Helmholtz, physderiv)
 //   ae_deriv_transposed_{2d,3d}.inc      D_a^T of a point's terms                              (Helmholtz, iprodderiv)
 //   ae_transposed_{2d,3d}.inc            transposed sweeps k -> r', j -> q', i -> p'           (mass, Helmholtz, iprodderiv)
+// and, stringing those together for the kernels over several fields:
+//   ae_fields_forward.inc                d fields forward into the images R0 .. R(d-1)         (geom, vecgrad)
+//   ae_jacobian.inc                      J[a][b] = D_b u_a of a point                          (geom, vecgrad)
+//   ae_advect_field.inc                  one field of the advection term, modes in to modes out (advect, affine advect)
 // The names the kernels agree on, which the fragments take from the scope: T, DIM, NT; nq0 nq1 nq2; nm0 nm1 nm2, nz, n01,
 // nqt, nmt, tid (ae_prologue.inc); b0 b1 b2, d0 d1 d2; src, dst of the element; x, the index of a loop over points; P0 ..
-// P3, the point images of the derivative kernels.  The images of a sweep are parameters: AE_* macros that the kernel
-// defines just before the #include and the fragment undefines, so that a definition left out does not compile.
+// P3, the point images of the derivative kernels.  The kernels over several fields add: e, the element; x0 x1 x2, the
+// modes of the fields; R0 .. R3, the four regions of geom and vecgrad, and J[DIM][DIM]; A, B, the two regions of the
+// advection kernels, with a (the field), out0 out1 out2 and ce0 ce1 ce2 (the planes of c of the element).  The images of
+// a sweep are parameters: AE_* macros that the kernel defines just before the #include and the fragment undefines, so
+// that a definition left out does not compile.
 // iproduct_generic.hip sweeps in the other order and keeps its own text; only its launch is shared.
 #pragma once
 

@@ -45,19 +45,7 @@ template <int DIM, int NQ, typename T> static int go_diag(const ArgsT<DIM, T> &a
 template <int DIM, typename T>
 int launch_diag_wave(unsigned nq, const ArgsT<DIM, T> &a, const DiagArgsT<T> &x, hipStream_t s)
 {
-#define SF_CASE(N) case N: return go_diag<DIM, N, T>(a, x, s);
-    if constexpr (DIM == 3)
-        switch (nq)
-        {
-            SF_HELM_HEX_CASES(SF_CASE)
-        }
-    else
-        switch (nq)
-        {
-            SF_HELM_QUAD_CASES(SF_CASE)
-        }
-#undef SF_CASE
-    return SF_ENOTBUILT;
+    return with_helm_order<DIM>(nq, [&](auto n) { return go_diag<DIM, decltype(n)::value, T>(a, x, s); });
 }
 
 } // namespace sf

@@ -8,9 +8,11 @@
 // stay in R0 .. R(d-1), the forward sweeps of coordinate a work in the regions behind its image:
 //   3D, coordinate a: modes (R(a+1)) -> w1 (Ra) -> w2 (R(a+1)) -> X_a (Ra)
 //   2D, coordinate a: modes (R(a+1)) -> w1 (behind the modes, fewer than 2 nqt scalars in all) -> X_a (Ra)
-// so 4 nqt scalars in both dimensions, the classes of the Helmholtz fallback.  The forward sweeps and the derivatives of
-// a point are the fragments frag/ae_forward_*.inc and frag/ae_deriv_*.inc, the text of physderiv_generic.hip: a
-// coordinate field goes through the arithmetic `in` goes through there.
+// so 4 nqt scalars in both dimensions, the classes of the Helmholtz fallback.  The d coordinates forward are
+// frag/ae_fields_forward.inc and J of a point is frag/ae_jacobian.inc (any_extent.h), the text vecgrad_generic.hip
+// includes too; they string frag/ae_forward_*.inc and frag/ae_deriv_*.inc together, the text of physderiv_generic.hip:
+// a coordinate field goes through the arithmetic `in` goes through there.  This unit's own: the weight of the point
+// (handed to ae_jacobian as AE_POINT_WITH), geom_point and the stores.
 // Every buffer is read and written with scalar accesses: scalar alignment is enough.  An output that is null is not
 // written (a run-time check per plane; the arithmetic is not compiled out here).  No workspace and static LDS only: every
 // launch is a single kernel node that needs no function attribute, capture-safe from the first call.
@@ -41,106 +43,16 @@ __global__ __launch_bounds__(NT) void geom_generic_kernel(
     const int npts   = AFFINE ? 1 : nqt;
     for (uint64_t e = blockIdx.x; e < nelmt; e += gridDim.x)
     {
-        if constexpr (DIM == 2)
-        {
-            (void)R3;
-            {
-                const T *src = x0 + e * (uint64_t)nmt;
-                T *W1        = R1 + nmt;
-#define AE_MODES R1
-#define AE_W1 W1
-#define AE_POINTS R0
-#define AE_POINT_VALUE(s) s
-#include "frag/ae_forward_2d.inc"
-            }
-            {
-                const T *src = x1 + e * (uint64_t)nmt;
-                T *W1        = R2 + nmt;
-#define AE_MODES R2
-#define AE_W1 W1
-#define AE_POINTS R1
-#define AE_POINT_VALUE(s) s
-#include "frag/ae_forward_2d.inc"
-            }
-        }
-        else
-        {
-            {
-                const T *src = x0 + e * (uint64_t)nmt;
-#define AE_MODES R1
-#define AE_W1 R0
-#define AE_W2 R1
-#define AE_POINTS R0
-#define AE_POINT_VALUE(s) s
-#include "frag/ae_forward_3d.inc"
-            }
-            {
-                const T *src = x1 + e * (uint64_t)nmt;
-#define AE_MODES R2
-#define AE_W1 R1
-#define AE_W2 R2
-#define AE_POINTS R1
-#define AE_POINT_VALUE(s) s
-#include "frag/ae_forward_3d.inc"
-            }
-            {
-                const T *src = x2 + e * (uint64_t)nmt;
-#define AE_MODES R3
-#define AE_W1 R2
-#define AE_W2 R3
-#define AE_POINTS R2
-#define AE_POINT_VALUE(s) s
-#include "frag/ae_forward_3d.inc"
-            }
-        }
+#include "frag/ae_fields_forward.inc"
         // J[a][b] = D_b X_a of the point, then the factors of the point
         for (int x = tid; x < npts; x += NT)
         {
             T J[DIM][DIM];
             T q = T(0);
-            if constexpr (DIM == 2)
-            {
-                {
-                    const T *P0 = R0;
-#define AE_DU0 J[0][0]
-#define AE_DU1 J[0][1]
-#include "frag/ae_deriv_2d.inc"
-                    if (has_q)
-                        q = qw1[j] * qw0[i];
-                }
-                {
-                    const T *P0 = R1;
-#define AE_DU0 J[1][0]
-#define AE_DU1 J[1][1]
-#include "frag/ae_deriv_2d.inc"
-                }
-            }
-            else
-            {
-                {
-                    const T *P0 = R0;
-#define AE_DU0 J[0][0]
-#define AE_DU1 J[0][1]
-#define AE_DU2 J[0][2]
-#include "frag/ae_deriv_3d.inc"
-                    if (has_q)
-                        q = qw2[k] * (qw1[j] * qw0[i]);
-                }
-                {
-                    const T *P0 = R1;
-#define AE_DU0 J[1][0]
-#define AE_DU1 J[1][1]
-#define AE_DU2 J[1][2]
-#include "frag/ae_deriv_3d.inc"
-                }
-                {
-                    const T *P0 = R2;
-#define AE_DU0 J[2][0]
-#define AE_DU1 J[2][1]
-#define AE_DU2 J[2][2]
-#include "frag/ae_deriv_3d.inc"
-                }
-            }
+#define AE_POINT_WITH(i, j, k)                                                                                         \
+    if (has_q)                                                                                                         \
+        q = DIM == 3 ? qw2[k] * (qw1[j] * qw0[i]) : qw1[j] * qw0[i];
+#include "frag/ae_jacobian.inc"
             GeomPoint<DIM, T> p;
             geom_point<DIM, kGeomAll, !AFFINE>(J, q, p);
             // AFFINE: one value per element and component; else one plane of nqt points per element and component

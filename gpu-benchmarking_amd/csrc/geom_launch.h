@@ -75,19 +75,7 @@ template <int DIM, int NQ, typename T> static int go_geom(const ArgsT<DIM, T> &a
 template <int DIM, typename T>
 int launch_geom_wave(unsigned nq, const ArgsT<DIM, T> &a, const GeomArgsT<T> &x, hipStream_t s)
 {
-#define SF_CASE(N) case N: return go_geom<DIM, N, T>(a, x, s);
-    if constexpr (DIM == 3)
-        switch (nq)
-        {
-            SF_HELM_HEX_CASES(SF_CASE)
-        }
-    else
-        switch (nq)
-        {
-            SF_HELM_QUAD_CASES(SF_CASE)
-        }
-#undef SF_CASE
-    return SF_ENOTBUILT;
+    return with_helm_order<DIM>(nq, [&](auto n) { return go_geom<DIM, decltype(n)::value, T>(a, x, s); });
 }
 
 } // namespace sf

@@ -9,8 +9,14 @@
 // The front half of the gradient kernels (physderiv_wave.h: chunk_fetch / chunk_stage, the forward sweeps, the
 // derivative steps -- the same text, csrc/frag/*.inc, up to point_values) runs d times per chunk, once per coordinate;
 // the walk over the point columns then gathers the d x d entries of J, inverts (geom_point.h) and stores up to
-// d*d + d(d+1)/2 + 2 planes.  No point image reaches HBM but the outputs.  This header's own: the kept images, the walk
-// and its stores; the unit of one coordinate with its prefetch is frag/geom_coordinate_{2d,3d}.inc, included d times.
+// d*d + d(d+1)/2 + 2 planes.  No point image reaches HBM but the outputs.
+// Shared text (csrc/frag/*.inc, the form mass_wave.h describes; vecgrad_wave.h, advect_wave.h and affine_advect_wave.h
+// include the same files).  Each kernel is, in order: wave_open (the names of the geometry, the slab and its kept
+// images, the chunks, the lane roles, the first request); per chunk chunk_head, fields_front_{2d,3d} (the unit of one
+// coordinate with its prefetch, geom_coordinate_{2d,3d}, once per coordinate); in the walk walk_stores (the store mask and
+// the output offsets), point_jacobian_{2d,3d} (J of the point out of the images and dk) and planes_store (df, g).  This
+// header's own: the slab with the kept images (GeomGeom), the weight products, the arithmetic of the point and which
+// planes it stores.
 //
 // Order of operations (it defines the rounding; every sum in ascending index, the first product a multiply, then FMAs):
 //   1. forward sweeps p -> i, q -> j, r -> k of x_a                              (X_a, the point values)
@@ -67,21 +73,11 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_geom_wave_kernel(
     T *__restrict__ df, T *__restrict__ w, T *__restrict__ g, T *__restrict__ detj, uint64_t nelmt)
 {
     using G          = GeomGeom<NQ, EC, 3, T>;
-    using M          = typename G::M;
-    using F          = typename G::F;
-    using IO         = MassIo<M>;
-    constexpr int NM = G::NM, NMP = F::NMP, NQP = G::NQP, NQ2 = NQ * NQ, NQT = NQ2 * NQ;
-    constexpr int NPASS = G::NPASS, NP = G::NP;
-    constexpr int PL = NQ * NQP, ES = NQ * PL; // plane and element stride of a point image
     constexpr bool Q = (MASK & (kGeomW | kGeomG)) != 0;
-    static_assert(KMAP > 0, "short-lived waves only");
-
-#include "frag/wave_slab.inc"
-    T *kept = slab + G::KEPT_BASE; // d X_0 / d xi_1, d X_0 / d xi_0, d X_1 / d xi_1, d X_1 / d xi_0
-#include "frag/wave_chunks.inc"
-#include "frag/lane_roles_3d.inc"
-    const T *in = x0; // the stream the fragments fetch and stage: the coordinate at hand
-#include "frag/chunk_fetch_first.inc"
+#define OPEN_DIM 3
+#define OPEN_KEPT_BASE G::KEPT_BASE // d X_0 / d xi_1, d X_0 / d xi_0, d X_1 / d xi_1, d X_1 / d xi_0
+#define OPEN_LANE_SETUP
+#include "frag/wave_open.inc"
 
     // q01 = qw1[j] qw0[i] of this lane's columns
     T q01[NPASS];
@@ -98,29 +94,11 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_geom_wave_kernel(
     {
 #include "frag/chunk_head.inc"
         T dk[3][NPASS][NQ]; // d X_a / d xi_2 over k
-#define GEOM_A 0
-#define GEOM_X x0
-#define GEOM_NEXT x1
-#include "frag/geom_coordinate_3d.inc"
-#define GEOM_A 1
-#define GEOM_X x1
-#define GEOM_NEXT x2
-#include "frag/geom_coordinate_3d.inc"
-#define GEOM_A 2
-#define GEOM_X x2
-#define GEOM_NEXT x0
-#include "frag/geom_coordinate_3d.inc"
+#define FRONT_PRIME
+#include "frag/fields_front_3d.inc"
         // ---- the walk over k: J of the point, its factors, its stores -------------------------------
         {
-            const uint64_t e0 = c * (uint64_t)EC;
-            bool put[NPASS]; // this lane stores: it has a point column and the column's element is in the batch
-            int ooff[NPASS];
-#pragma unroll
-            for (int s = 0; s < NPASS; ++s)
-            {
-                put[s]  = own[s] && ecol[s] < evalid;
-                ooff[s] = ecol[s] * NQT + colp[s];
-            }
+#include "frag/walk_stores.inc"
 #pragma unroll
             for (int k = 0; k < NQ; ++k)
             {
@@ -130,10 +108,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_geom_wave_kernel(
 #pragma unroll
                 for (int s = 0; s < NPASS; ++s)
                 {
-                    const int o = colo[s] + k * PL;
-                    const T J[3][3] = {{kept[G::IMG + o], kept[o], dk[0][s][k]},
-                                       {kept[3 * G::IMG + o], kept[2 * G::IMG + o], dk[1][s][k]},
-                                       {slab[G::IMG + o], slab[o], dk[2][s][k]}};
+#include "frag/point_jacobian_3d.inc"
                     GeomPoint<3, T> p;
                     geom_point<3, MASK, true>(J, qk * q01[s], p);
                     if (put[s])
@@ -141,23 +116,19 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_geom_wave_kernel(
                         const int oo = ooff[s] + k * NQ2;
                         if constexpr ((MASK & kGeomDf) != 0)
                             if (df)
-                            {
-                                T *dst = df + e0 * (9 * NQT) + ecol[s] * (8 * NQT) + oo;
-#pragma unroll
-                                for (int cc = 0; cc < 9; ++cc)
-                                    dst[cc * NQT] = p.df[cc];
-                            }
+#define PLANES_DST df
+#define PLANES_N 9
+#define PLANES_VAL(cc) p.df[cc]
+#include "frag/planes_store.inc"
                         if constexpr ((MASK & kGeomW) != 0)
                             if (w)
                                 w[e0 * NQT + oo] = p.w;
                         if constexpr ((MASK & kGeomG) != 0)
                             if (g)
-                            {
-                                T *dst = g + e0 * (6 * NQT) + ecol[s] * (5 * NQT) + oo;
-#pragma unroll
-                                for (int cc = 0; cc < 6; ++cc)
-                                    dst[cc * NQT] = p.g[cc];
-                            }
+#define PLANES_DST g
+#define PLANES_N 6
+#define PLANES_VAL(cc) p.g[cc]
+#include "frag/planes_store.inc"
                         if constexpr ((MASK & kGeomDet) != 0)
                             if (detj)
                                 detj[e0 * NQT + oo] = p.det;
@@ -179,21 +150,11 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_geom_wave_kernel(
     T *__restrict__ df, T *__restrict__ w, T *__restrict__ g, T *__restrict__ detj, uint64_t nelmt)
 {
     using G          = GeomGeom<NQ, EC, 2, T>;
-    using M          = typename G::M;
-    using F          = typename G::F;
-    using IO         = MassIo<M>;
-    constexpr int NM = G::NM, NMP = F::NMP, NQP = G::NQP, NQT = NQ * NQ;
-    constexpr int NPASS = G::NPASS, NP = G::NP;
-    constexpr int ES = NQ * NQP; // element stride of the point image
     constexpr bool Q = (MASK & (kGeomW | kGeomG)) != 0;
-    static_assert(KMAP > 0, "short-lived waves only");
-
-#include "frag/wave_slab.inc"
-    T *kept = slab + G::KEPT_BASE; // d X_0 / d xi_0
-#include "frag/wave_chunks.inc"
-#include "frag/lane_roles_2d.inc"
-    const T *in = x0; // the stream the fragments fetch and stage: the coordinate at hand
-#include "frag/chunk_fetch_first.inc"
+#define OPEN_DIM 2
+#define OPEN_KEPT_BASE G::KEPT_BASE // d X_0 / d xi_0
+#define OPEN_LANE_SETUP
+#include "frag/wave_open.inc"
 
     T q0[NPASS]; // qw0[i] of this lane's columns
     const bool has_q = Q && (w != nullptr || g != nullptr);
@@ -206,23 +167,11 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_geom_wave_kernel(
     {
 #include "frag/chunk_head.inc"
         T dk[2][NPASS][NQ]; // d X_a / d xi_1 over j
-#define GEOM_A 0
-#define GEOM_X x0
-#include "frag/geom_coordinate_2d.inc"
-#define GEOM_A 1
-#define GEOM_X x1
-#include "frag/geom_coordinate_2d.inc"
+#define FRONT_PRIME
+#include "frag/fields_front_2d.inc"
         // ---- the walk over j ----------------------------------------------------------------------
         {
-            const uint64_t e0 = c * (uint64_t)EC;
-            bool put[NPASS];
-            int ooff[NPASS];
-#pragma unroll
-            for (int s = 0; s < NPASS; ++s)
-            {
-                put[s]  = own[s] && ecol[s] < evalid;
-                ooff[s] = ecol[s] * NQT + colp[s];
-            }
+#include "frag/walk_stores.inc"
 #pragma unroll
             for (int j = 0; j < NQ; ++j)
             {
@@ -232,8 +181,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_geom_wave_kernel(
 #pragma unroll
                 for (int s = 0; s < NPASS; ++s)
                 {
-                    const int o     = colo[s] + j * NQP;
-                    const T J[2][2] = {{kept[o], dk[0][s][j]}, {slab[o], dk[1][s][j]}};
+#include "frag/point_jacobian_2d.inc"
                     GeomPoint<2, T> p;
                     geom_point<2, MASK, true>(J, qj * q0[s], p);
                     if (put[s])
@@ -241,23 +189,19 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_geom_wave_kernel(
                         const int oo = ooff[s] + j * NQ;
                         if constexpr ((MASK & kGeomDf) != 0)
                             if (df)
-                            {
-                                T *dst = df + e0 * (4 * NQT) + ecol[s] * (3 * NQT) + oo;
-#pragma unroll
-                                for (int cc = 0; cc < 4; ++cc)
-                                    dst[cc * NQT] = p.df[cc];
-                            }
+#define PLANES_DST df
+#define PLANES_N 4
+#define PLANES_VAL(cc) p.df[cc]
+#include "frag/planes_store.inc"
                         if constexpr ((MASK & kGeomW) != 0)
                             if (w)
                                 w[e0 * NQT + oo] = p.w;
                         if constexpr ((MASK & kGeomG) != 0)
                             if (g)
-                            {
-                                T *dst = g + e0 * (3 * NQT) + ecol[s] * (2 * NQT) + oo;
-#pragma unroll
-                                for (int cc = 0; cc < 3; ++cc)
-                                    dst[cc * NQT] = p.g[cc];
-                            }
+#define PLANES_DST g
+#define PLANES_N 3
+#define PLANES_VAL(cc) p.g[cc]
+#include "frag/planes_store.inc"
                         if constexpr ((MASK & kGeomDet) != 0)
                             if (detj)
                                 detj[e0 * NQT + oo] = p.det;

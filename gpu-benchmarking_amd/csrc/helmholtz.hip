@@ -11,7 +11,7 @@ template int launch_helmholtz_wave<2, double>(unsigned, const QuadArgs &, const 
 // 3D isotropic nq 2..8, 2D isotropic nq 2..16
 bool helmholtz_wave_built(int dim, unsigned nq)
 {
-    return nq >= 2 && nq <= (dim == 3 ? 8u : 16u);
+    return helm_order_built(dim, nq);
 }
 
 } // namespace sf

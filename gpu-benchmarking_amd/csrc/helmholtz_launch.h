@@ -94,11 +94,11 @@ template <int DIM, int NQ, typename T, class X> static int go_helm(const ArgsT<D
 #define SF_HELM_HEX_CASES(F) F(2) F(3) F(4) F(5) F(6) F(7) F(8)
 #define SF_HELM_QUAD_CASES(F) F(2) F(3) F(4) F(5) F(6) F(7) F(8) F(9) F(10) F(11) F(12) F(13) F(14) F(15) F(16)
 
-// SF_ENOTBUILT when the order has no instantiation (helmholtz_wave_built() / affine_wave_built())
-template <int DIM, typename T, class X>
-static int launch_helm_wave(unsigned nq, const ArgsT<DIM, T> &a, const X &x, hipStream_t s)
+// The order switch of every family on this table, written once: f(std::integral_constant<int, NQ>()) for the order's
+// case, SF_ENOTBUILT for an order without one.
+template <int DIM, class Fn> static int with_helm_order(unsigned nq, Fn &&f)
 {
-#define SF_CASE(N) case N: return go_helm<DIM, N, T>(a, x, s);
+#define SF_CASE(N) case N: return f(std::integral_constant<int, N>());
     if constexpr (DIM == 3)
         switch (nq)
         {
@@ -111,6 +111,20 @@ static int launch_helm_wave(unsigned nq, const ArgsT<DIM, T> &a, const X &x, hip
         }
 #undef SF_CASE
     return SF_ENOTBUILT;
+}
+
+// whether the order has a case: what the *_wave_built() predicates of the families on this table answer
+static inline bool helm_order_built(int dim, unsigned nq)
+{
+    const auto has_case = [](auto) { return (int)SF_OK; };
+    return (dim == 3 ? with_helm_order<3>(nq, has_case) : with_helm_order<2>(nq, has_case)) == SF_OK;
+}
+
+// SF_ENOTBUILT when the order has no instantiation (helmholtz_wave_built() / affine_wave_built())
+template <int DIM, typename T, class X>
+static int launch_helm_wave(unsigned nq, const ArgsT<DIM, T> &a, const X &x, hipStream_t s)
+{
+    return with_helm_order<DIM>(nq, [&](auto n) { return go_helm<DIM, decltype(n)::value, T>(a, x, s); });
 }
 
 // instantiated for double in helmholtz.hip and for float in helmholtz_f32.hip

@@ -11,7 +11,7 @@ template int launch_vecgrad_wave<2, double>(unsigned, const QuadArgs &, const Ve
 // the Helmholtz table: 3D isotropic nq 2..8, 2D isotropic nq 2..16
 bool vecgrad_wave_built(int dim, unsigned nq)
 {
-    return nq >= 2 && nq <= (dim == 3 ? 8u : 16u);
+    return helm_order_built(dim, nq);
 }
 
 } // namespace sf

@@ -10,9 +10,10 @@
 // field a work in the regions behind its image:
 //   3D, field a: modes (R(a+1)) -> w1 (Ra) -> w2 (R(a+1)) -> u_a (Ra)
 //   2D, field a: modes (R(a+1)) -> w1 (behind the modes, fewer than 2 nqt scalars in all) -> u_a (Ra)
-// The forward sweeps and the derivatives of a point are the fragments frag/ae_forward_*.inc and frag/ae_deriv_*.inc, the
-// text of physderiv_generic.hip: field a goes through the arithmetic `in` goes through there, so plane a*d + j of grad
-// equals output j of that kernel on in_a bit for bit.
+// The d fields forward are frag/ae_fields_forward.inc and J of a point is frag/ae_jacobian.inc (any_extent.h), shared with
+// geom_generic.hip; they string frag/ae_forward_*.inc and frag/ae_deriv_*.inc together, the text of
+// physderiv_generic.hip: field a goes through the arithmetic `in` goes through there, so plane a*d + j of grad equals
+// output j of that kernel on in_a bit for bit.  This unit's own: grad of the point and the stores.
 // Every buffer is read and written with scalar accesses: scalar alignment is enough.  An output that is null is not
 // written (a run-time check per output).  No workspace and static LDS only: every launch is a single kernel node that
 // needs no function attribute, capture-safe from the first call.
@@ -37,104 +38,22 @@ __global__ __launch_bounds__(NT) void vecgrad_generic_kernel(
     T *R0 = lds, *R1 = lds + nqt, *R2 = lds + 2 * nqt, *R3 = lds + 3 * nqt;
     for (uint64_t e = blockIdx.x; e < nelmt; e += gridDim.x)
     {
-        if constexpr (DIM == 2)
-        {
-            (void)R3;
-            {
-                const T *src = x0 + e * (uint64_t)nmt;
-                T *W1        = R1 + nmt;
-#define AE_MODES R1
-#define AE_W1 W1
-#define AE_POINTS R0
-#define AE_POINT_VALUE(s) s
-#include "frag/ae_forward_2d.inc"
-            }
-            {
-                const T *src = x1 + e * (uint64_t)nmt;
-                T *W1        = R2 + nmt;
-#define AE_MODES R2
-#define AE_W1 W1
-#define AE_POINTS R1
-#define AE_POINT_VALUE(s) s
-#include "frag/ae_forward_2d.inc"
-            }
-        }
-        else
-        {
-            {
-                const T *src = x0 + e * (uint64_t)nmt;
-#define AE_MODES R1
-#define AE_W1 R0
-#define AE_W2 R1
-#define AE_POINTS R0
-#define AE_POINT_VALUE(s) s
-#include "frag/ae_forward_3d.inc"
-            }
-            {
-                const T *src = x1 + e * (uint64_t)nmt;
-#define AE_MODES R2
-#define AE_W1 R1
-#define AE_W2 R2
-#define AE_POINTS R1
-#define AE_POINT_VALUE(s) s
-#include "frag/ae_forward_3d.inc"
-            }
-            {
-                const T *src = x2 + e * (uint64_t)nmt;
-#define AE_MODES R3
-#define AE_W1 R2
-#define AE_W2 R3
-#define AE_POINTS R2
-#define AE_POINT_VALUE(s) s
-#include "frag/ae_forward_3d.inc"
-            }
-        }
+#include "frag/ae_fields_forward.inc"
         // J[a][b] = D_b u_a of the point, then grad of the point and what is asked for of it
         const T *dfe = df + e * (uint64_t)(DD * nqt);
         for (int x = tid; x < nqt; x += NT)
         {
             T J[DIM][DIM], g[DIM][DIM];
+#define AE_POINT_WITH(i, j, k)
+#include "frag/ae_jacobian.inc"
             if constexpr (DIM == 2)
             {
-                {
-                    const T *P0 = R0;
-#define AE_DU0 J[0][0]
-#define AE_DU1 J[0][1]
-#include "frag/ae_deriv_2d.inc"
-                }
-                {
-                    const T *P0 = R1;
-#define AE_DU0 J[1][0]
-#define AE_DU1 J[1][1]
-#include "frag/ae_deriv_2d.inc"
-                }
                 for (int a = 0; a < 2; ++a)
                     for (int j = 0; j < 2; ++j)
                         g[a][j] = sfma(dfe[(2 * j + 1) * nqt + x], J[a][1], dfe[(2 * j) * nqt + x] * J[a][0]);
             }
             else
             {
-                {
-                    const T *P0 = R0;
-#define AE_DU0 J[0][0]
-#define AE_DU1 J[0][1]
-#define AE_DU2 J[0][2]
-#include "frag/ae_deriv_3d.inc"
-                }
-                {
-                    const T *P0 = R1;
-#define AE_DU0 J[1][0]
-#define AE_DU1 J[1][1]
-#define AE_DU2 J[1][2]
-#include "frag/ae_deriv_3d.inc"
-                }
-                {
-                    const T *P0 = R2;
-#define AE_DU0 J[2][0]
-#define AE_DU1 J[2][1]
-#define AE_DU2 J[2][2]
-#include "frag/ae_deriv_3d.inc"
-                }
                 for (int a = 0; a < 3; ++a)
                     for (int j = 0; j < 3; ++j)
                         g[a][j] = sfma(dfe[(3 * j + 2) * nqt + x], J[a][2],

@@ -13,7 +13,10 @@
 // The front is the unit of one coordinate of geom_wave.h, frag/geom_coordinate_{2d,3d}.inc, once per field with GEOM_X =
 // in_a over the slab of GeomGeom (the images of the fields 0 .. d-2 kept behind the front's slab), as advect_wave.h with
 // NF = d: dk[a] is the register pencil d u_a / d xi_(d-1) of the column's lane and holds the bits it holds there.  The
-// ring of df is that of physderiv_wave.h (load_df_slice), the stores are those of geom_wave.h.  This header's own: the
+// ring of df is that of physderiv_wave.h (load_df_slice), the stores are those of geom_wave.h.
+// Shared text (csrc/frag/*.inc, the sequence geom_wave.h lists): wave_open; per chunk chunk_head, ring_offsets (the ring's
+// clamped column offsets), fields_front_{2d,3d} with the ring primed in front of the last field's unit; in the walk
+// walk_stores, point_jacobian_{2d,3d} and planes_store (grad).  This header's own: the ring and the arithmetic of the
 // walk.
 //
 // Order of operations (it defines the rounding; every sum in ascending index, the first product a multiply, then FMAs):
@@ -55,21 +58,12 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_vecgrad_wave_kernel(
     const T *__restrict__ x1, const T *__restrict__ x2, T *__restrict__ grad, T *__restrict__ div, T *__restrict__ curl0,
     T *__restrict__ curl1, T *__restrict__ curl2, uint64_t nelmt)
 {
-    using G          = GeomGeom<NQ, EC, 3, T>;
-    using M          = typename G::M;
-    using F          = typename G::F;
-    using IO         = MassIo<M>;
-    constexpr int NM = G::NM, NMP = F::NMP, NQP = G::NQP, NQ2 = NQ * NQ, NQT = NQ2 * NQ;
-    constexpr int NPASS = G::NPASS, NP = G::NP, RING = G::RING, NCOMP = 9;
-    constexpr int PL = NQ * NQP, ES = NQ * PL; // plane and element stride of a point image
-    static_assert(KMAP > 0, "short-lived waves only");
-
-#include "frag/wave_slab.inc"
-    T *kept = slab + G::KEPT_BASE; // d u_0 / d xi_1, d u_0 / d xi_0, d u_1 / d xi_1, d u_1 / d xi_0
-#include "frag/wave_chunks.inc"
-#include "frag/lane_roles_3d.inc"
-    const T *in = x0; // the stream the fragments fetch and stage: the field at hand
-#include "frag/chunk_fetch_first.inc"
+    using G            = GeomGeom<NQ, EC, 3, T>;
+    constexpr int RING = G::RING, NCOMP = 9;
+#define OPEN_DIM 3
+#define OPEN_KEPT_BASE G::KEPT_BASE // d u_0 / d xi_1, d u_0 / d xi_0, d u_1 / d xi_1, d u_1 / d xi_0
+#define OPEN_LANE_SETUP
+#include "frag/wave_open.inc"
 
     uint64_t c = it.first;
     for (uint64_t n = 0; n < it.count; ++n, c += it.step)
@@ -78,40 +72,16 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_vecgrad_wave_kernel(
         T dk[3][NPASS][NQ]; // d u_a / d xi_2 over k
         // the ring of df: every lane's offsets are in bounds
         const T *dc = df + c * (uint64_t)(EC * NCOMP * NQT);
-        int doff[NPASS];
-#pragma unroll
-        for (int s = 0; s < NPASS; ++s)
-        {
-            const int e = ecol[s] < evalid ? ecol[s] : evalid - 1;
-            doff[s]     = e * (NCOMP * NQT) + colp[s];
-        }
+#define RING_OFF doff[NPASS]
+#define RING_SET doff[s] = e * (NCOMP * NQT) + colp[s];
+#include "frag/ring_offsets.inc"
         T dv[RING][NPASS][NCOMP];
-#define GEOM_A 0
-#define GEOM_X x0
-#define GEOM_NEXT x1
-#include "frag/geom_coordinate_3d.inc"
-#define GEOM_A 1
-#define GEOM_X x1
-#define GEOM_NEXT x2
-#include "frag/geom_coordinate_3d.inc"
-#pragma unroll
-        for (int r = 0; r < RING; ++r)
-            load_df_slice<NPASS, NCOMP, NQ2, NQT>(dv[r], dc, doff, r);
-#define GEOM_A 2
-#define GEOM_X x2
-#define GEOM_NEXT x0
-#include "frag/geom_coordinate_3d.inc"
+#define FRONT_PRIME                                                                                                    \
+    _Pragma("unroll") for (int r = 0; r < RING; ++r) load_df_slice<NPASS, NCOMP, NQ2, NQT>(dv[r], dc, doff, r);
+#include "frag/fields_front_3d.inc"
         // ---- the walk over k: grad of the point, its stores ---------------------------------------------
         {
-            const uint64_t e0 = c * (uint64_t)EC;
-            bool put[NPASS]; // this lane stores: it has a point column and the column's element is in the batch
-            int ooff[NPASS];
-#pragma unroll
-            for (int s = 0; s < NPASS; ++s)
-            {
-                put[s]  = own[s] && ecol[s] < evalid;
-                ooff[s] = ecol[s] * NQT + colp[s];
-            }
+#include "frag/walk_stores.inc"
 #pragma unroll
             for (int k = 0; k < NQ; ++k)
             {
@@ -119,10 +89,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_vecgrad_wave_kernel(
                 for (int s = 0; s < NPASS; ++s)
                 {
                     const T(&dd)[NCOMP] = dv[k % RING][s];
-                    const int o         = colo[s] + k * PL;
-                    const T J[3][3]     = {{kept[G::IMG + o], kept[o], dk[0][s][k]},
-                                           {kept[3 * G::IMG + o], kept[2 * G::IMG + o], dk[1][s][k]},
-                                           {slab[G::IMG + o], slab[o], dk[2][s][k]}};
+#include "frag/point_jacobian_3d.inc"
                     T g[3][3];
 #pragma unroll
                     for (int a = 0; a < 3; ++a)
@@ -134,12 +101,10 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void hex_vecgrad_wave_kernel(
                         const int oo = ooff[s] + k * NQ2;
                         if constexpr ((MASK & kVecGrad) != 0)
                             if (grad)
-                            {
-                                T *dst = grad + e0 * (9 * NQT) + ecol[s] * (8 * NQT) + oo;
-#pragma unroll
-                                for (int cc = 0; cc < 9; ++cc)
-                                    dst[cc * NQT] = g[cc / 3][cc % 3];
-                            }
+#define PLANES_DST grad
+#define PLANES_N 9
+#define PLANES_VAL(cc) g[(cc) / 3][(cc) % 3]
+#include "frag/planes_store.inc"
                         if constexpr ((MASK & kVecDiv) != 0)
                             if (div)
                                 div[e0 * NQT + oo] = (g[0][0] + g[1][1]) + g[2][2];
@@ -170,21 +135,12 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_vecgrad_wave_kernel(
     const T *__restrict__ df, const T *__restrict__ x0, const T *__restrict__ x1, T *__restrict__ grad,
     T *__restrict__ div, T *__restrict__ curl0, uint64_t nelmt)
 {
-    using G          = GeomGeom<NQ, EC, 2, T>;
-    using M          = typename G::M;
-    using F          = typename G::F;
-    using IO         = MassIo<M>;
-    constexpr int NM = G::NM, NMP = F::NMP, NQP = G::NQP, NQT = NQ * NQ;
-    constexpr int NPASS = G::NPASS, NP = G::NP, RING = G::RING, NCOMP = 4;
-    constexpr int ES = NQ * NQP; // element stride of the point image
-    static_assert(KMAP > 0, "short-lived waves only");
-
-#include "frag/wave_slab.inc"
-    T *kept = slab + G::KEPT_BASE; // d u_0 / d xi_0
-#include "frag/wave_chunks.inc"
-#include "frag/lane_roles_2d.inc"
-    const T *in = x0; // the stream the fragments fetch and stage: the field at hand
-#include "frag/chunk_fetch_first.inc"
+    using G            = GeomGeom<NQ, EC, 2, T>;
+    constexpr int RING = G::RING, NCOMP = 4;
+#define OPEN_DIM 2
+#define OPEN_KEPT_BASE G::KEPT_BASE // d u_0 / d xi_0
+#define OPEN_LANE_SETUP
+#include "frag/wave_open.inc"
 
     uint64_t c = it.first;
     for (uint64_t n = 0; n < it.count; ++n, c += it.step)
@@ -193,34 +149,16 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_vecgrad_wave_kernel(
         T dk[2][NPASS][NQ]; // d u_a / d xi_1 over j
         // the ring of df, as in the 3D kernel
         const T *dc = df + c * (uint64_t)(EC * NCOMP * NQT);
-        int doff[NPASS];
-#pragma unroll
-        for (int s = 0; s < NPASS; ++s)
-        {
-            const int e = ecol[s] < evalid ? ecol[s] : evalid - 1;
-            doff[s]     = e * (NCOMP * NQT) + colp[s];
-        }
+#define RING_OFF doff[NPASS]
+#define RING_SET doff[s] = e * (NCOMP * NQT) + colp[s];
+#include "frag/ring_offsets.inc"
         T dv[RING][NPASS][NCOMP];
-#define GEOM_A 0
-#define GEOM_X x0
-#include "frag/geom_coordinate_2d.inc"
-#pragma unroll
-        for (int r = 0; r < RING; ++r)
-            load_df_slice<NPASS, NCOMP, NQ, NQT>(dv[r], dc, doff, r);
-#define GEOM_A 1
-#define GEOM_X x1
-#include "frag/geom_coordinate_2d.inc"
+#define FRONT_PRIME                                                                                                    \
+    _Pragma("unroll") for (int r = 0; r < RING; ++r) load_df_slice<NPASS, NCOMP, NQ, NQT>(dv[r], dc, doff, r);
+#include "frag/fields_front_2d.inc"
         // ---- the walk over j ---------------------------------------------------------------------------
         {
-            const uint64_t e0 = c * (uint64_t)EC;
-            bool put[NPASS];
-            int ooff[NPASS];
-#pragma unroll
-            for (int s = 0; s < NPASS; ++s)
-            {
-                put[s]  = own[s] && ecol[s] < evalid;
-                ooff[s] = ecol[s] * NQT + colp[s];
-            }
+#include "frag/walk_stores.inc"
 #pragma unroll
             for (int j = 0; j < NQ; ++j)
             {
@@ -228,8 +166,7 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_vecgrad_wave_kernel(
                 for (int s = 0; s < NPASS; ++s)
                 {
                     const T(&dd)[NCOMP] = dv[j % RING][s];
-                    const int o         = colo[s] + j * NQP;
-                    const T J[2][2]     = {{kept[o], dk[0][s][j]}, {slab[o], dk[1][s][j]}};
+#include "frag/point_jacobian_2d.inc"
                     T g[2][2];
 #pragma unroll
                     for (int a = 0; a < 2; ++a)
@@ -241,12 +178,10 @@ __global__ __launch_bounds__(kWave *WPB, MINW) void quad_vecgrad_wave_kernel(
                         const int oo = ooff[s] + j * NQ;
                         if constexpr ((MASK & kVecGrad) != 0)
                             if (grad)
-                            {
-                                T *dst = grad + e0 * (4 * NQT) + ecol[s] * (3 * NQT) + oo;
-#pragma unroll
-                                for (int cc = 0; cc < 4; ++cc)
-                                    dst[cc * NQT] = g[cc / 2][cc % 2];
-                            }
+#define PLANES_DST grad
+#define PLANES_N 4
+#define PLANES_VAL(cc) g[(cc) / 2][(cc) % 2]
+#include "frag/planes_store.inc"
                         if constexpr ((MASK & kVecDiv) != 0)
                             if (div)
                                 div[e0 * NQT + oo] = g[0][0] + g[1][1];
