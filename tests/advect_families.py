@@ -1,6 +1,8 @@
 """The advection family (sf_advect_*) for tests/test_gpu_advect.py, in the pattern of tests/fused_families.py and
-tests/geom_families.py: the literals of the cases and AdvectProblem (the data of one case on the device, its runs, its
-reference and its checks).
+tests/geom_families.py: the literals of the cases, AdvectProblem (the data of one case on the device, its runs, its
+reference and its checks) and FAMILY, the family's adapter for the tests written once in
+tests/test_gpu_multifield_common.py (stream capture, the first call inside a capture, two streams in flight, the
+SF_ENOTBUILT refusals).  The helpers it shares with the other multi-field families are tests/multifield_common.py.
 
 The Family adapter of tests/fused_families.py does not fit: this family has nf = 1 or d inputs AND outputs and d + 2
 point operands.  What fits is kept: the seeded per-value-distinct data of sf.fill_random (U[-1, 1): every coefficient
@@ -11,6 +13,7 @@ import numpy as np
 
 from advect_ref import advect_excess, ref_advect, unit_roundoff
 from fused_families import F32, F64, RAGGED, Banded, case_id, sf, sizes, to_host, torch_mod  # noqa: F401
+from multifield_common import NOT_BUILT, MultiField, ids, rows, same_bits  # noqa: F401
 
 WAVE_ORDERS = [(q,) * 3 for q in range(2, 9)] + [(q,) * 2 for q in range(2, 17)]
 WAVE_COUNT = 403
@@ -27,28 +30,6 @@ END_TO_END = (((5, 5, 5), 101), ((9, 9), 101))
 MISALIGNED = (((4, 4, 4), 130), ((8, 8, 8), 65), ((9, 9), 259))
 
 
-def ids(cases):
-    return [case_id(s) + "-" + str(n) for s, n in cases]
-
-
-def bits(torch_mod, t):
-    """The tensor as integers: equal bits, NaN included."""
-    return t.view(torch_mod.int64 if t.dtype == torch_mod.float64 else torch_mod.int32)
-
-
-def same_bits(torch_mod, a, b):
-    return a.shape == b.shape and bool(torch_mod.equal(bits(torch_mod, a), bits(torch_mod, b)))
-
-
-def rows(torch_mod, parts, n, dtype, fill=None):
-    """A (parts, n) tensor whose rows each start 256-byte aligned, as advect_* returns it."""
-    per = 256 // torch_mod.empty(0, dtype=dtype).element_size()
-    buf = torch_mod.empty((parts, (n + per - 1) // per * per), dtype=dtype, device="cuda")
-    if fill is not None:
-        buf.fill_(fill)
-    return buf[:, :n]
-
-
 class AdvectProblem:
     """One case on the device: bases, derivative matrices, df, w, c and d fields of modes, every array seeded and
     element-major."""
@@ -60,14 +41,18 @@ class AdvectProblem:
         d, fill = self.d, lambda n, s: sf.fill_random(n, s + 13 * seed, dtype=self.dtype)
         self.bs = [fill((q - 1) * q, 500 + a) for a, q in enumerate(self.nq)]
         self.ds = [fill(q * q, 600 + a) for a, q in enumerate(self.nq)]
-        self.df = fill(nelmt * d * d * self.nqt, 11)
-        self.w = fill(nelmt * self.nqt, 12)
+        self.fill_geometry(fill)
         self.c = rows(torch_mod, d, nelmt * self.nqt, self.dtype)
         self.x = rows(torch_mod, d, nelmt * self.nmt, self.dtype)
         for a in range(d):
             self.c[a].copy_(fill(nelmt * self.nqt, 20 + a))
             self.x[a].copy_(fill(nelmt * self.nmt, 30 + a))
         self._ref = None
+
+    def fill_geometry(self, fill):
+        """df and w, between the matrices and the fields in the order of the fills."""
+        self.df = fill(self.nelmt * self.d * self.d * self.nqt, 11)
+        self.w = fill(self.nelmt * self.nqt, 12)
 
     def fn(self):
         return self.sf.advect_hex if self.d == 3 else self.sf.advect_quad
@@ -102,19 +87,36 @@ class AdvectProblem:
             self._ref = ref
         return ref
 
-    def check(self, got, what, n=None, elements=None, fields=None, ref=None):
+    def check(self, got, what, n=None, elements=None, fields=None, ref=None, excess=advect_excess, label="advect", **how):
         """Every out_a of `got` (a (nf, n nm^d) tensor or a tuple of rows) within gamma_N absref of the long-double
-        reference, elementwise; prints the figure first."""
+        reference (reference(elements, fields, **how)), elementwise; prints the figure first."""
         n = self.nelmt if n is None else n
-        ref, absref = self.reference(elements, fields) if ref is None else ref
+        ref, absref = self.reference(elements, fields, **how) if ref is None else ref
         host = np.stack([to_host(t).reshape(-1) for t in got])
         if elements is not None:
             host = np.stack([h.reshape(-1, self.nmt)[np.asarray(elements)].reshape(-1) for h in host])
         else:
             ref, absref = ref[:, :n * self.nmt], absref[:, :n * self.nmt]
         assert host.shape == ref.shape, (host.shape, ref.shape)
-        q = advect_excess(host, ref, absref, self.nq, unit_roundoff(self.dtype_name))
-        print(f"{what}: advect {self.nq} {self.dtype_name} nelmt={n}: max |err| / (gamma_N absref) = {q:.3g}")
+        q = excess(host, ref, absref, self.nq, unit_roundoff(self.dtype_name))
+        print(f"{what}: {label} {self.nq} {self.dtype_name} nelmt={n}: max |err| / (gamma_N absref) = {q:.3g}")
         assert q <= 1.0, (what, self.nq, self.dtype_name, q)
         assert float(np.max(np.abs(ref))) > 0, (what, self.nq)
         return q
+
+
+def zeros(p, field=None, **_):
+    """A zeroed `out` of p.run(field=field): d rows, or one."""
+    return rows(p.torch, p.d if field is None else 1, p.nelmt * p.nmt, p.dtype, fill=0.0)
+
+
+def refused_calls(p, variant):
+    """With d fields and with one in float64; the float32 case with d."""
+    return [lambda f=f: p.run(field=f, variant=variant) for f in ((None, 0) if p.dtype_name == F64 else (None,))]
+
+
+FAMILY = MultiField(
+    name="advect", problem=AdvectProblem, graph=GRAPH, graph_modes=({"field": None}, {"field": 1}),
+    graph_check={"fields": [1]}, zeros=zeros, first_call=FIRST_CALL, first_modes=({"field": None}, {"field": 0}),
+    first_also=None, first_tail=None, first_eager=False, streams=STREAMS, stream_sample=STREAM_SAMPLE,
+    stream_seed=lambda k, nelmt: 40 + k, streams_differ=True, refused=NOT_BUILT, refused_calls=refused_calls)

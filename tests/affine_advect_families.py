@@ -1,17 +1,20 @@
 """The affine advection family (sf_aff_advect_*) for tests/test_gpu_affine_advect.py, in the pattern of
-tests/advect_families.py, whose literals, helpers and AdvectProblem it takes over unchanged: AffineAdvectProblem is an
-AdvectProblem whose df and w are the planes EXPANDED on the device from dfe, je and the quadrature weights (df[e][c][pt] =
-dfe[e][c]; w = je * (qw2 * (qw1 * qw0)) in the working precision, each product rounded once, in exactly that
-association), so that the inherited run() is the deformed call that the affine one must equal bit for bit.
+tests/advect_families.py, whose literals, helpers and AdvectProblem it takes over: AffineAdvectProblem is an AdvectProblem
+(the same seeded operands, the same check) whose df and w are the planes EXPANDED on the device from dfe, je and the
+quadrature weights (df[e][c][pt] = dfe[e][c]; w = je * (qw2 * (qw1 * qw0)) in the working precision, each product rounded
+once, in exactly that association), so that the inherited run() is the deformed call that the affine one must equal bit
+for bit.  FAMILY is the family's adapter for the tests written once in tests/test_gpu_multifield_common.py.
 """
 import ctypes
+import functools
 
 import numpy as np
 
 from advect_families import (FALLBACK, GRAPH, GUARD, MISALIGNED, POISON, RAGGED_BOUND, SCALAR, STREAM_SAMPLE,  # noqa: F401
-                             STREAMS, WAVE_COUNT, WAVE_ORDERS, AdvectProblem, ids, rows, same_bits)
-from affine_advect_ref import affine_advect_excess, ref_affine_advect, unit_roundoff
+                             STREAMS, WAVE_COUNT, WAVE_ORDERS, AdvectProblem, refused_calls, zeros)
+from affine_advect_ref import affine_advect_excess, ref_affine_advect
 from fused_families import to_host
+from multifield_common import NOT_BUILT, MultiField, ids, rows, same_bits  # noqa: F401
 
 NO_JE = (((3, 3, 3), 257), ((7, 7, 7), 257), ((8, 8, 8), 257), ((5, 5), 257), ((16, 16), 257))
 FIRST_CALL = (((8, 8, 8), 1001), ((6, 6, 12), 101), ((9, 9), 1002), ((23, 5), 101))
@@ -24,22 +27,13 @@ class AffineAdvectProblem(AdvectProblem):
     fields), the quadrature weights, dfe and je, and df, w expanded from them."""
 
     def __init__(self, sf, torch_mod, nq, nelmt, dtype_name, seed):
-        self.sf, self.torch, self.nq, self.nelmt, self.dtype_name = sf, torch_mod, tuple(nq), nelmt, dtype_name
-        self.dtype, self.seed, self.d = getattr(torch_mod, dtype_name), seed, len(nq)
-        d = self.d
-        self.nmt, self.nqt = int(np.prod([q - 1 for q in self.nq])), int(np.prod(self.nq))
-        fill = lambda n, s: sf.fill_random(n, s + 13 * seed, dtype=self.dtype)      # noqa: E731
-        self.bs = [fill((q - 1) * q, 500 + a) for a, q in enumerate(self.nq)]
-        self.ds = [fill(q * q, 600 + a) for a, q in enumerate(self.nq)]
+        super().__init__(sf, torch_mod, nq, nelmt, dtype_name, seed)
+        self._aref = {}
+
+    def fill_geometry(self, fill):
         self.qs = [fill(q, 700 + a) for a, q in enumerate(self.nq)]
-        self.dfe, self.je = fill(nelmt * d * d, 11), fill(nelmt, 12)
-        self.c = rows(torch_mod, d, nelmt * self.nqt, self.dtype)
-        self.x = rows(torch_mod, d, nelmt * self.nmt, self.dtype)
-        for a in range(d):
-            self.c[a].copy_(fill(nelmt * self.nqt, 20 + a))
-            self.x[a].copy_(fill(nelmt * self.nmt, 30 + a))
+        self.dfe, self.je = fill(self.nelmt * self.d * self.d, 11), fill(self.nelmt, 12)
         self.df, self.w = self.expand(self.dfe, self.je)
-        self._ref, self._aref = None, {}
 
     def expand(self, dfe, je):
         """(df, w) of sf_advect_* on the device; w a plane of ones when je is None."""
@@ -107,17 +101,19 @@ class AffineAdvectProblem(AdvectProblem):
         return ref
 
     def check(self, got, what, n=None, elements=None, fields=None, je=OWN):
-        """Every out_a of `got` within gamma_N absref of the long-double reference, elementwise; prints the figure first."""
-        n = self.nelmt if n is None else n
-        ref, absref = self.reference(elements, fields, je)
-        host = np.stack([to_host(t).reshape(-1) for t in got])
-        if elements is not None:
-            host = np.stack([h.reshape(-1, self.nmt)[np.asarray(elements)].reshape(-1) for h in host])
-        else:
-            ref, absref = ref[:, :n * self.nmt], absref[:, :n * self.nmt]
-        assert host.shape == ref.shape, (host.shape, ref.shape)
-        q = affine_advect_excess(host, ref, absref, self.nq, unit_roundoff(self.dtype_name), with_je=je is not None)
-        print(f"{what}: affine advect {self.nq} {self.dtype_name} nelmt={n}: max |err| / (gamma_N absref) = {q:.3g}")
-        assert q <= 1.0, (what, self.nq, self.dtype_name, q)
-        assert float(np.max(np.abs(ref))) > 0, (what, self.nq)
-        return q
+        """AdvectProblem.check against the affine reference and its bound (with or without je)."""
+        return super().check(got, what, n, elements, fields, label="affine advect", je=je,
+                             excess=functools.partial(affine_advect_excess, with_je=je is not None))
+
+
+def first_also(p, out, field=None):
+    """The first call's result equals the deformed call on the expanded planes, which runs after it."""
+    return same_bits(p.torch, out, p.deformed(field=field))
+
+
+FAMILY = MultiField(
+    name="affine_advect", problem=AffineAdvectProblem, graph=GRAPH,
+    graph_modes=({"field": None, "je": OWN}, {"field": None, "je": None}, {"field": 1, "je": OWN}), graph_check={"fields": [1]},
+    zeros=zeros, first_call=FIRST_CALL, first_modes=({"field": None}, {"field": 0}), first_also=first_also, first_tail=None,
+    first_eager=True, streams=STREAMS, stream_sample=STREAM_SAMPLE, stream_seed=lambda k, nelmt: 40 + k, streams_differ=True,
+    refused=NOT_BUILT, refused_calls=refused_calls)

@@ -19,9 +19,9 @@ import pytest
 
 from affine_deriv_ref import (affine_iprodderiv_excess, affine_iprodderiv_n, affine_physderiv_excess, affine_physderiv_n,
                               ref_affine_iprodderiv, ref_affine_physderiv)
-from fused_common import same_bits
 from fused_families import (F32, F64, NO_KERNEL, RAGGED, SCALAR, VEC, Affine, Family, Operand, _refused, case_id, own_problem,
                             sizes)
+from multifield_common import capture_replay, same_bits
 
 _GUARD = {(2, 2, 2): 33, (3, 3, 3): 1001, (5, 5, 5): 67, (6, 6, 6): 129, (8, 8, 8): 65, (5, 5): 4099, (16, 16): 127,
           (6, 6, 12): 13, (9, 9, 9): 15, (23, 5): 14}
@@ -116,16 +116,7 @@ def install_single(ns, fam):
         for present in fam.modes:
             eager = p.run(sf, present=present)
             outs = [torch_mod.zeros_like(t) for t in eager]
-            torch_mod.cuda.synchronize()
-            side = torch_mod.cuda.Stream()
-            side.wait_stream(torch_mod.cuda.current_stream())
-            g = torch_mod.cuda.CUDAGraph()
-            with torch_mod.cuda.stream(side):
-                with torch_mod.cuda.graph(g, stream=side):
-                    p.run(sf, present=present, out=outs, stream=side)
-            torch_mod.cuda.current_stream().wait_stream(side)
-            g.replay()
-            torch_mod.cuda.synchronize()
+            capture_replay(torch_mod, lambda side: p.run(sf, present=present, out=outs, stream=side))
             assert same_bits(torch_mod, outs, eager)
             assert all(float(o.abs().max()) > 0 for o in outs)
             p.check(outs, "graph", present=present)

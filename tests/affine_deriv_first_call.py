@@ -12,22 +12,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as ge  # noqa: E402
 from affine_deriv_families import BY_NAME  # noqa: E402
 from fused_families import own_problem  # noqa: E402
+from multifield_common import capture_replay  # noqa: E402
 
 fam = BY_NAME[sys.argv[1]]
 sf = ge.load_package()
 for nq, nelmt in fam.first_call:
     p = own_problem(fam, sf, torch, nq, nelmt, "float64", 40)              # nothing but sf.fill_random has run
     outs = [torch.zeros(nelmt * fam.out_per(nq), dtype=torch.float64, device="cuda") for _ in range(fam.out_parts(nq))]
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.stream(side):
-        with torch.cuda.graph(graph, stream=side):
-            p.run(sf, out=outs, stream=side)                  # the process's first call of this route
-    torch.cuda.current_stream().wait_stream(side)
-    graph.replay()
-    torch.cuda.synchronize()
+    capture_replay(torch, lambda side: p.run(sf, out=outs, stream=side))      # the process's first call of this route
     eager = p.run(sf)
     torch.cuda.synchronize()
     assert all(torch.equal(o, e) for o, e in zip(outs, eager)), nq

@@ -14,6 +14,7 @@ of iprodderiv as rows of one array, the tables of diag built once.
 import pytest
 
 from fused_families import F32, F64, Banded, case_id, own_problem
+from multifield_common import same_bits  # noqa: F401
 
 DTYPES = [F64, F32]
 
@@ -22,10 +23,6 @@ def run(torch_mod, p, sf, **kw):
     got = p.run(sf, **kw)
     torch_mod.cuda.synchronize()
     return got
-
-
-def same_bits(torch_mod, a, b):
-    return len(a) == len(b) and all(torch_mod.equal(x, y) for x, y in zip(a, b))
 
 
 def _counts_and_modes(fam, sf, torch_mod, nq, dtype_name, counts, seed):

@@ -1,26 +1,23 @@
 """The geometric-factor family (sf_geom_*, sf_geom_affine_*) for tests/test_gpu_geom.py, in the pattern of
 tests/fused_families.py and tests/affine_deriv_families.py: the literals of the cases, GeomProblem (the data of one case on
-the device, its runs, its reference and its checks) and install_single() with the bodies of the tests every fused
-family carries (refusals, stream capture, the first call of a process inside a capture, two streams in flight).
+the device, its runs, its reference and its checks) and FAMILY, the family's adapter for the tests written once in
+tests/test_gpu_multifield_common.py (refusals, stream capture, the first call of a process inside a capture, two streams
+in flight).  The helpers it shares with the other multi-field families are tests/multifield_common.py.
 
 The Family adapter itself does not fit: this family has d inputs and up to four outputs of different lengths, each with
 a bound of its own that is a running error bound (tests/geom_ref.py GeomRef), not gamma_N absref.  What fits is kept:
 prepare() gives the coordinates -- deformed elements of geom_ref.deformed(), never raw random fills, whose Jacobians
-would be singular somewhere -- the seeds, the guard bands (fused_families.Banded) and the bodies of install_single.
+would be singular somewhere -- the seeds and the guard bands (fused_families.Banded).
 
 Operands.  bases / derivs / qws: the Legendre modal basis at the Gauss-Lobatto points, its differentiation matrix and
 weights (geom_ref.gll_operands), rounded to the working precision; the reference is computed on the rounded values the
 device holds.
 """
-import os
-import subprocess
-import sys
-
 import numpy as np
-import pytest
 
-from fused_families import F32, F64, NO_KERNEL, _refused, case_id, to_host
+from fused_families import F32, NO_KERNEL, _refused, to_host
 from geom_ref import AFFINE_OUTPUTS, OUTPUTS, deformed, gll_operands, ref_geom, sizes, unit_roundoff
+from multifield_common import MultiField, bits, same_bits  # noqa: F401
 
 WAVE_3D = (((2, 2, 2), 33), ((3, 3, 3), 1001), ((5, 5, 5), 67), ((6, 6, 6), 129), ((8, 8, 8), 65))
 WAVE_2D = (((5, 5), 4099), ((16, 16), 127))
@@ -124,76 +121,36 @@ class GeomProblem:
             assert float(np.max(np.abs(ref.val[name]))) > 0, (what, name)
 
 
-def bits(torch_mod, t):
-    """The tensor as integers: equal bits, NaN included."""
-    return t.view(torch_mod.int64 if t.dtype == torch_mod.float64 else torch_mod.int32)
+def zeros(p, outputs=OUTPUTS):
+    """A zeroed `out` of p.run(outputs)."""
+    return {k: p.torch.zeros(p.nelmt * p.per[k], dtype=p.dtype, device="cuda") for k in outputs}
 
 
-def same_bits(torch_mod, a, b):
-    return a.keys() == b.keys() and all(torch_mod.equal(bits(torch_mod, a[k]), bits(torch_mod, b[k])) for k in a)
+def refused_calls(p, variant):
+    """The deformed call; under AUTO the affine form too, which has the fallback's bounds."""
+    return [lambda: p.run(variant=variant)] + ([p.run_affine] if variant == "auto" else [])
 
 
-def install_single(ns):
-    """The family's cases of the tests of tests/test_gpu_fused_common.py, with the bodies they have there."""
+def first_affine(torch_mod, problems):
+    """The affine kernel allocates its own outputs: its first call is captured through the C call's wrapper on a private
+    memory pool."""
+    p = problems[0]
+    side = torch_mod.cuda.Stream()
+    side.wait_stream(torch_mod.cuda.current_stream())
+    graph = torch_mod.cuda.CUDAGraph()
+    with torch_mod.cuda.stream(side):
+        with torch_mod.cuda.graph(graph, stream=side):
+            got = p.run_affine(stream=side)
+    torch_mod.cuda.current_stream().wait_stream(side)
+    graph.replay()
+    torch_mod.cuda.synchronize()
+    eager = p.run_affine()
+    torch_mod.cuda.synchronize()
+    assert same_bits(torch_mod, got, eager) and float(got["je"].min()) > 0
 
-    def test_refusals(sf, torch_mod):
-        """Extents outside the fallback's bounds, "wave" off the table, variants without a fused kernel: SF_ENOTBUILT."""
-        for nq, nelmt, dtype_name, variant in REFUSED:
-            p = GeomProblem(sf, torch_mod, nq, nelmt, dtype_name, 2)
-            with pytest.raises(sf.capi.SumfactError) as ei:
-                p.run(variant=variant)
-            assert ei.value.rc == sf.capi.SF_ENOTBUILT, (nq, dtype_name, variant)
-            if variant == "auto":                                   # the affine form has the fallback's bounds
-                with pytest.raises(sf.capi.SumfactError) as ei:
-                    p.run_affine()
-                assert ei.value.rc == sf.capi.SF_ENOTBUILT, (nq, dtype_name)
 
-    @pytest.mark.parametrize("nq,nelmt", GRAPH, ids=[case_id(s) + "-" + str(n) for s, n in GRAPH])
-    def test_captured_graph_replay_matches_eager(sf, torch_mod, nq, nelmt):
-        p = GeomProblem(sf, torch_mod, nq, nelmt, F64, 11)
-        for outputs in (OUTPUTS, ("df",), ("g", "w")):
-            eager = p.run(outputs)
-            outs = {k: torch_mod.zeros_like(t) for k, t in eager.items()}
-            torch_mod.cuda.synchronize()
-            side = torch_mod.cuda.Stream()
-            side.wait_stream(torch_mod.cuda.current_stream())
-            g = torch_mod.cuda.CUDAGraph()
-            with torch_mod.cuda.stream(side):
-                with torch_mod.cuda.graph(g, stream=side):
-                    p.run(outputs, out=outs, stream=side)
-            torch_mod.cuda.current_stream().wait_stream(side)
-            g.replay()
-            torch_mod.cuda.synchronize()
-            assert same_bits(torch_mod, outs, eager)
-            assert all(float(o.abs().max()) > 0 for o in outs.values())
-        sample = [0, 1, nelmt // 2, nelmt - 1]
-        p.check(outs, "graph", elements=sample)
-
-    def test_first_call_inside_a_capture():
-        """Capture-safe from the first call: a fresh child process whose first call of each route of the family (3D wave,
-        3D fallback, 2D wave, 2D fallback, then the affine kernel) is inside a stream capture; the replay equals an eager
-        call made afterwards."""
-        script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "geom_first_call.py")
-        r = subprocess.run([sys.executable, script], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0 and "first calls captured" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-
-    def test_two_streams_in_flight(sf, torch_mod):
-        """Two problems enqueued on two streams before either is waited for; a seeded sample of elements and the ends
-        against long double."""
-        streams = [torch_mod.cuda.Stream(), torch_mod.cuda.Stream()]
-        probs = [GeomProblem(sf, torch_mod, nq, nelmt, F64, nelmt % 97) for nq, nelmt in STREAMS]
-        torch_mod.cuda.synchronize()
-        outs = []
-        for p, st in zip(probs, streams):
-            with torch_mod.cuda.stream(st):
-                outs.append(p.run(stream=st))
-        torch_mod.cuda.synchronize()
-        rng = np.random.default_rng(7)
-        for p, o in zip(probs, outs):
-            ends = [0, 1, p.nelmt - 2, p.nelmt - 1]
-            sample = np.unique(np.concatenate((ends, rng.integers(0, p.nelmt, STREAM_SAMPLE))))
-            p.check(o, "stream job", elements=sample)
-
-    ns.update(test_refusals=test_refusals, test_captured_graph_replay_matches_eager=test_captured_graph_replay_matches_eager,
-              test_first_call_inside_a_capture=test_first_call_inside_a_capture,
-              test_two_streams_in_flight=test_two_streams_in_flight)
+FAMILY = MultiField(
+    name="geom", problem=GeomProblem, graph=GRAPH, graph_modes=tuple({"outputs": o} for o in (OUTPUTS, ("df",), ("g", "w"))),
+    graph_check={}, zeros=zeros, first_call=FIRST_CALL, first_modes=({"outputs": OUTPUTS},), first_also=None,
+    first_tail=first_affine, first_eager=False, streams=STREAMS, stream_sample=STREAM_SAMPLE,
+    stream_seed=lambda k, nelmt: nelmt % 97, streams_differ=False, refused=REFUSED, refused_calls=refused_calls)

@@ -10,6 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as ge  # noqa: E402
+from multifield_common import capture_replay  # noqa: E402
 
 sf = ge.load_package()
 
@@ -19,16 +20,8 @@ for ni, no, trans, nelmt in (((4, 4, 4), (6, 6, 6), 0, 1001), ((9, 5), (3, 7), 1
     x = torch.from_numpy(rng.uniform(-1, 1, nelmt * int(np.prod(ni)))).cuda()
     out = torch.zeros(nelmt * int(np.prod(no)), dtype=torch.float64, device="cuda")
     fn = sf.tensor_hex if len(ni) == 3 else sf.tensor_quad
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.stream(side):
-        with torch.cuda.graph(graph, stream=side):
-            fn(ni, no, *mats, x, trans=trans, out=out, stream=side)   # the process's first call of this route
-    torch.cuda.current_stream().wait_stream(side)
-    graph.replay()
-    torch.cuda.synchronize()
+    # the process's first call of this route
+    capture_replay(torch, lambda side: fn(ni, no, *mats, x, trans=trans, out=out, stream=side))
     eager = fn(ni, no, *mats, x, trans=trans)
     torch.cuda.synchronize()
     assert torch.equal(out, eager) and float(out.abs().max()) > 0, (ni, no)

@@ -6,7 +6,6 @@ layer, and the registers of every wave instantiation.  No test here needs a GPU.
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ from affine_advect_ref import (U32, U64, affine_advect_eval, affine_advect_exces
                                ref_affine_advect)
 from affine_deriv_ref import affine_iprodderiv_n
 from iprodderiv_ref import iprodderiv_n
+from resources_ref import kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "gpu-benchmarking_amd")
@@ -287,36 +287,23 @@ def test_the_python_layer_refuses_without_a_device(pkg):
         pkg.affine_advect_hex(nq, *bs, *ds, None, qs[1], qs[2], dfe, je, c, x)                          # qw_d with je
 
 
-ROW = re.compile(r"^((?:hex|quad)_affine_advect_wave_kernel<\d+, .*>)\s+vgpr\s+(\d+) agpr\s+\d+ sgpr\s+(\d+) "
-                 r"scratch\s+(-?\d+) spill v(-?\d+)/s(-?\d+) occ (\d+)")
+NAME = re.compile(r"(hex|quad)_affine_advect_wave_kernel<(\d+), .*, (\d+), (true|false), (float|double)>")
 
 
 def test_wave_instantiations_use_no_scratch():
     """Every wave instantiation of the family, from the compiler's resource report of the two translation units: no
     scratch, no spills, at most 256 VGPRs; the set is exactly 3D nq 2..8 and 2D nq 2..16 for double and float, one field
     and d, with and without je (176).  Prints VGPRs / occupancy per kernel (the table of DESIGN.md s4.21)."""
-    srcs = ("affine_advect.hip", "affine_advect_f32.hip")
-    procs = [subprocess.Popen(["python3", os.path.join(PKG, "tools", "kernel_resources.py"), os.path.join(PKG, "csrc", src),
-                               "advect_wave_kernel"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=PKG)
-             for src in srcs]
-    got = {}
-    for src, proc in zip(srcs, procs):
-        out = proc.communicate(timeout=1800)[0]
-        rows = [ROW.match(ln) for ln in out.splitlines() if ln.strip()]
-        assert rows and all(rows), out
-        for m in rows:
-            name = m.group(1)
-            dim = 3 if name.startswith("hex") else 2
-            nq = int(re.search(r"<(\d+),", name).group(1))
-            tail = re.search(r", (\d+), (true|false), (float|double)>$", name)
-            nf, hasw, t = int(tail.group(1)), tail.group(2) == "true", tail.group(3)
-            assert (t == "float") == (src == "affine_advect_f32.hip"), (src, name)
-            assert (dim, nq, t, nf, hasw) not in got, name
-            got[(dim, nq, t, nf, hasw)] = m
-            print(f"{dim}D nq {nq:2d} {t:6s} nf {nf} {'je' if hasw else '--'}: {int(m.group(2)):3d} VGPRs, "
-                  f"{int(m.group(3)):3d} SGPRs, occupancy {m.group(7)}")
-            assert int(m.group(4)) == 0 and int(m.group(5)) == 0 and int(m.group(6)) == 0, m.string
-            assert 0 < int(m.group(2)) <= 256, m.string
+    got = set()
+    for src, r in kernel_resources(("affine_advect.hip", "affine_advect_f32.hip"), "advect_wave_kernel"):
+        m = NAME.fullmatch(r.name)
+        assert m, r.name
+        dim, nq, nf, hasw, t = 3 if m.group(1) == "hex" else 2, int(m.group(2)), int(m.group(3)), m.group(4) == "true", m.group(5)
+        assert (t == "float") == (src == "affine_advect_f32.hip"), (src, r.name)
+        assert (dim, nq, t, nf, hasw) not in got, r.name
+        got.add((dim, nq, t, nf, hasw))
+        print(f"{dim}D nq {nq:2d} {t:6s} nf {nf} {'je' if hasw else '--'}: {r.vgpr:3d} VGPRs, {r.sgpr:3d} SGPRs, "
+              f"occupancy {r.occ}")
     orders = [(3, n) for n in range(2, 9)] + [(2, n) for n in range(2, 17)]
     want = {(d, n, t, nf, h) for d, n in orders for t in ("double", "float") for nf in (1, d) for h in (True, False)}
-    assert len(want) == 176 and set(got) == want, sorted(map(str, want ^ set(got)))
+    assert len(want) == 176 and got == want, sorted(map(str, want ^ got))

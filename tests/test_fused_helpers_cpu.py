@@ -1,6 +1,7 @@
-"""CPU checks of the two helpers the common GPU tests of the fused families lean on (tests/fused_families.py):
-check_bound(), the assertion every result is held to, and Banded, the guard bands.  No device is needed: check_bound()
-takes host arrays, Banded a device argument.
+"""CPU checks of the helpers the common tests lean on: check_bound(), the assertion every result of the fused families
+is held to, and Banded, the guard bands (tests/fused_families.py); parse(), which every kernel-resource test reads the
+compiler's report through (tests/resources_ref.py).  No device and no compiler is needed: check_bound() takes host arrays,
+Banded a device argument, parse() a line.
 """
 import numpy as np
 import pytest
@@ -8,6 +9,7 @@ import torch
 
 import fused_families as ff
 from fused_families import COMMON, F64, U64, Banded, check_bound, gamma
+from resources_ref import parse
 
 CASES = [(f, nq) for f in COMMON for nq in ((3, 4), (3, 4, 2))]
 
@@ -51,3 +53,20 @@ def test_banded_detects_one_changed_scalar_in_either_band(dtype, fill):
     src = torch.arange(11, dtype=dtype)
     c = Banded.of(torch, src, fill)
     assert torch.equal(c.view, src) and c.bands_intact(torch) and c.view.data_ptr() % 16 == c.buf.data_ptr() % 16
+
+
+def test_parse_reads_a_resource_line_and_refuses_scratch_spills_and_too_many_vgprs():
+    line = "{:70s} vgpr {:3d} agpr {:3d} sgpr {:3d} scratch {:5d} spill v{}/s{} occ {}".format
+    name = "hex_mass_wave_kernel<8, 8, 8, 1, 4, double>"
+    r = parse(line(name, 124, 0, 58, 0, 0, 0, 4))
+    assert r == (name, 124, 0, 58, 0, 0, 0, 4) and (r.vgpr, r.sgpr, r.occ) == (124, 58, 4)
+    assert parse(line(name, 256, 0, 102, 0, 0, 0, 2)).vgpr == 256
+    for bad in (line(name, 124, 0, 58, 8, 0, 0, 4),                # scratch
+                line(name, 124, 0, 58, 0, 3, 0, 4),                # a VGPR spill
+                line(name, 124, 0, 58, 0, 0, 1, 4),                # an SGPR spill
+                line(name, 257, 0, 58, 0, 0, 0, 4),                # one VGPR too many
+                line(name, -1, -1, -1, -1, -1, -1, -1),            # a report without figures
+                name + " vgpr 124 sgpr 58",                        # not the tool's line
+                "error: no such kernel"):
+        with pytest.raises(AssertionError):
+            parse(bad)

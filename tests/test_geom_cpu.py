@@ -6,7 +6,6 @@ registers of every wave instantiation.  No GPU.
 """
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,6 +14,7 @@ from numpy.polynomial import legendre as _leg
 from geom_ref import (LD, OUTPUTS, U32, U64, GeomRef, deformed, gamma, geom_eval, gll_operands, ref_geom, sizes)
 from helm_ref import COMPONENTS
 from physderiv_ref import _inv_ld, physderiv_n, ref_physderiv
+from resources_ref import kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "gpu-benchmarking_amd")
@@ -303,30 +303,21 @@ def test_validation_without_a_gpu(pkg):
     assert lib.sf_geom_affine_quad_f64(9, 9, 4, *(A,) * 4, x[0], None, *o3, None) == c.SF_EINVAL
 
 
-ROW = re.compile(r"^((?:hex|quad)_geom_wave_kernel<(\d+), .*, (\d+), (double|float)>)\s+vgpr\s+(\d+) agpr\s+\d+ sgpr\s+(\d+) "
-                 r"scratch\s+(-?\d+) spill v(-?\d+)/s(-?\d+) occ (\d+)")
+NAME = re.compile(r"(hex|quad)_geom_wave_kernel<(\d+), .*, (\d+), (double|float)>")
 
 
 def test_wave_instantiations_use_no_scratch():
     """Every wave instantiation: no scratch, no spills, at most 256 VGPRs; the set is exactly 3D nq 2..8 and 2D nq 2..16
     for double and float, each with the four output masks all (15), df (1), w (2), g and w (6): 176 kernels.  Prints
     VGPRs / occupancy per kernel (the table of DESIGN.md s4.18)."""
-    got = {}
-    for src in ("geom.hip", "geom_f32.hip"):
-        out = subprocess.run(["python3", os.path.join(PKG, "tools", "kernel_resources.py"),
-                              os.path.join(PKG, "csrc", src), "geom_wave_kernel"],
-                             capture_output=True, text=True, cwd=PKG, timeout=1800).stdout
-        rows = [ROW.match(ln) for ln in out.splitlines() if ln.strip()]
-        assert rows and all(rows), out
-        for m in rows:
-            name, nq, mask, t = m.group(1), int(m.group(2)), int(m.group(3)), m.group(4)
-            dim = 3 if name.startswith("hex") else 2
-            assert (t == "float") == (src == "geom_f32.hip"), (src, name)
-            got[(dim, nq, t, mask)] = m
-            print(f"{dim}D nq {nq:2d} {t:6s} mask {mask:2d}: {int(m.group(5)):3d} VGPRs, {int(m.group(6)):3d} SGPRs, "
-                  f"occupancy {m.group(10)}")
-            assert int(m.group(7)) == 0 and int(m.group(8)) == 0 and int(m.group(9)) == 0, m.string
-            assert 0 < int(m.group(5)) <= 256, m.string
+    got = set()
+    for src, r in kernel_resources(("geom.hip", "geom_f32.hip"), "geom_wave_kernel"):
+        m = NAME.fullmatch(r.name)
+        assert m, r.name
+        dim, nq, mask, t = 3 if m.group(1) == "hex" else 2, int(m.group(2)), int(m.group(3)), m.group(4)
+        assert (t == "float") == (src == "geom_f32.hip"), (src, r.name)
+        got.add((dim, nq, t, mask))
+        print(f"{dim}D nq {nq:2d} {t:6s} mask {mask:2d}: {r.vgpr:3d} VGPRs, {r.sgpr:3d} SGPRs, occupancy {r.occ}")
     orders = [(3, n) for n in range(2, 9)] + [(2, n) for n in range(2, 17)]
     want = {(d, n, t, mask) for d, n in orders for t in ("double", "float") for mask in (15, 1, 2, 6)}
-    assert len(want) == 176 and set(got) == want, sorted(map(str, want ^ set(got)))
+    assert len(want) == 176 and got == want, sorted(map(str, want ^ got))

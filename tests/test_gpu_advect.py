@@ -2,20 +2,20 @@
 bound (tests/advect_ref.py: elementwise |got - ref| <= gamma_N absref, N = 2 sum nq_d + max nq_d + 2 d + 1), on the seeded
 per-value-distinct data of tests/advect_families.py.  No tolerance is introduced anywhere else: routes are compared bit
 for bit, and the comparison with the chain sf_physderiv_* -> torch -> sf_iproduct_* uses the sum of the two bounds.
+The SF_ENOTBUILT refusals, stream capture, the first call inside a capture and two streams in flight are the family's
+cases of tests/test_gpu_multifield_common.py.
 """
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from advect_families import (CHAIN, END_TO_END, FALLBACK, GRAPH, GUARD, MISALIGNED, POISON, RAGGED_BOUND, SCALAR, STREAM_SAMPLE,
-                             STREAMS, WAVE_COUNT, WAVE_ORDERS, AdvectProblem, ids, rows, same_bits)
+from advect_families import (CHAIN, END_TO_END, FALLBACK, GUARD, MISALIGNED, POISON, RAGGED_BOUND, SCALAR, WAVE_COUNT, WAVE_ORDERS,
+                             AdvectProblem)
 from advect_ref import advect_excess, advect_n, ref_advect, unit_roundoff
 from fused_families import F32, F64, RAGGED, Banded, case_id, sf, to_host, torch_mod  # noqa: F401
 from geom_families import GeomProblem
+from multifield_common import ids, odd, rows, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -158,8 +158,7 @@ def test_poison_stays_in_its_element(sf, torch_mod, nq, nelmt):
 
 
 def test_refusals(sf, torch_mod):
-    """nf = 2 in 3D and a NULL df: SF_EINVAL; "wave" off the table and extents beyond the fallback's bounds:
-    SF_ENOTBUILT."""
+    """nf = 2 in 3D, nf = 0, a NULL df and too few fields: SF_EINVAL."""
     c = sf.capi
     p = AdvectProblem(sf, torch_mod, (4, 4, 4), 5, F64, 2)
     outs = [torch_mod.zeros(5 * p.nmt, dtype=p.dtype, device="cuda") for _ in range(3)]
@@ -171,64 +170,6 @@ def test_refusals(sf, torch_mod):
     with pytest.raises(c.SumfactError) as ei:
         p.run(x=p.x[:2])
     assert ei.value.rc == c.SF_EINVAL
-    for nq, variant in (((9, 9, 9), "wave"), ((6, 6, 12), "wave"), ((13, 2, 2), "auto"), ((33, 2), "auto"),
-                        ((13, 2, 2), "generic"), ((8, 8, 8), "mfma"), ((8, 8), "thread")):
-        q = AdvectProblem(sf, torch_mod, nq, 3, F64, 2)
-        for field in (None, 0):
-            with pytest.raises(c.SumfactError) as ei:
-                q.run(field=field, variant=variant)
-            assert ei.value.rc == c.SF_ENOTBUILT, (nq, variant)
-    q = AdvectProblem(sf, torch_mod, (13, 2, 2), 3, F32, 2)
-    with pytest.raises(c.SumfactError) as ei:
-        q.run()
-    assert ei.value.rc == c.SF_ENOTBUILT
-
-
-@pytest.mark.parametrize("nq,nelmt", GRAPH, ids=ids(GRAPH))
-def test_captured_graph_replay_matches_eager(sf, torch_mod, nq, nelmt):
-    p = AdvectProblem(sf, torch_mod, nq, nelmt, F64, 11)
-    for field in (None, 1):
-        eager = p.run(field=field)
-        out = rows(torch_mod, eager.shape[0], eager.shape[1], p.dtype, fill=0.0)
-        torch_mod.cuda.synchronize()
-        side = torch_mod.cuda.Stream()
-        side.wait_stream(torch_mod.cuda.current_stream())
-        g = torch_mod.cuda.CUDAGraph()
-        with torch_mod.cuda.stream(side):
-            with torch_mod.cuda.graph(g, stream=side):
-                p.run(field=field, out=out, stream=side)
-        torch_mod.cuda.current_stream().wait_stream(side)
-        g.replay()
-        torch_mod.cuda.synchronize()
-        assert same_bits(torch_mod, out, eager) and float(out.abs().max()) > 0
-    p.check(out, "graph", elements=[0, 1, nelmt // 2, nelmt - 1], fields=[1])
-
-
-def test_first_call_inside_a_capture():
-    """Capture-safe from the first call: a fresh child process whose first call of each route of the family (3D wave, 3D
-    fallback, 2D wave, 2D fallback) is inside a stream capture; the replay equals an eager call made afterwards."""
-    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "advect_first_call.py")
-    r = subprocess.run([sys.executable, script], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "first calls captured" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-
-
-def test_two_streams_in_flight(sf, torch_mod):
-    """Two problems enqueued on two streams before either is waited for; a seeded sample of elements and the ends against
-    long double."""
-    streams = [torch_mod.cuda.Stream(), torch_mod.cuda.Stream()]
-    probs = [AdvectProblem(sf, torch_mod, nq, nelmt, F64, 40 + k) for k, (nq, nelmt) in enumerate(STREAMS)]
-    torch_mod.cuda.synchronize()
-    outs = []
-    for p, st in zip(probs, streams):
-        with torch_mod.cuda.stream(st):
-            outs.append(p.run(stream=st))
-    torch_mod.cuda.synchronize()
-    rng = np.random.default_rng(7)
-    for p, o in zip(probs, outs):
-        ends = [0, 1, p.nelmt - 2, p.nelmt - 1]
-        sample = np.unique(np.concatenate((ends, rng.integers(0, p.nelmt, STREAM_SAMPLE))))
-        p.check(o, "stream job", elements=sample)
-    assert not same_bits(torch_mod, outs[0], outs[1])
 
 
 @pytest.mark.parametrize("nq,nelmt", MISALIGNED, ids=ids(MISALIGNED))
@@ -236,16 +177,9 @@ def test_misaligned_point_operands_take_the_wave_route(sf, torch_mod, nq, nelmt)
     """df, w and c_j at an odd scalar offset (8-byte aligned only) still take the wave route and give the same bits."""
     p = AdvectProblem(sf, torch_mod, nq, nelmt, F64, 29)
     clean = p.run(variant="wave")
-
-    def odd(t):
-        buf = torch_mod.empty(t.numel() + 3, dtype=t.dtype, device="cuda")
-        v = buf[1:1 + t.numel()]
-        v.copy_(t.reshape(-1))
-        assert v.data_ptr() % 16 == 8
-        return v
-
+    odd_ = lambda t: odd(torch_mod, t)                                         # noqa: E731
     for field in (None, 0):
-        got = p.run(field=field, variant="wave", df=odd(p.df), w=odd(p.w), c=[odd(p.c[j]) for j in range(p.d)])
+        got = p.run(field=field, variant="wave", df=odd_(p.df), w=odd_(p.w), c=[odd_(p.c[j]) for j in range(p.d)])
         want = clean if field is None else clean[:1]
         assert same_bits(torch_mod, got, want), (nq, field)
     assert float(clean.abs().max()) > 0

@@ -2,22 +2,20 @@
 reference and its derived bound (tests/affine_advect_ref.py: elementwise |got - ref| <= gamma_N absref, N = advect_n + d),
 and bit for bit against sf_advect_* on planes expanded on the device, on the seeded per-value-distinct data of
 tests/affine_advect_families.py.  No tolerance is introduced anywhere: comparisons are bit for bit, against the derived
-bound, or against the sum of two such bounds.
+bound, or against the sum of two such bounds.  The SF_ENOTBUILT refusals, stream capture, the first call inside a capture
+(and eagerly) and two streams in flight are the family's cases of tests/test_gpu_multifield_common.py.
 """
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from advect_ref import advect_n, gamma, ref_advect
-from affine_advect_families import (END_TO_END, FALLBACK, GRAPH, GUARD, MISALIGNED, NO_JE, OWN, POISON, RAGGED_BOUND, SCALAR,
-                                    STREAM_SAMPLE, STREAMS, WAVE_COUNT, WAVE_ORDERS, AffineAdvectProblem, ids, rows, same_bits)
+from affine_advect_families import (END_TO_END, FALLBACK, GUARD, MISALIGNED, NO_JE, POISON, RAGGED_BOUND, SCALAR, WAVE_COUNT,
+                                    WAVE_ORDERS, AffineAdvectProblem)
 from affine_advect_ref import affine_advect_n, ref_affine_advect, unit_roundoff
 from fused_families import F32, F64, RAGGED, Banded, case_id, sf, to_host, torch_mod  # noqa: F401
 from geom_families import GeomProblem
 from iprod_ref import ref_iprod
+from multifield_common import ids, odd, rows, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -156,8 +154,7 @@ def test_poison_in_the_constants_stays_in_its_element(sf, torch_mod, nq, nelmt):
 
 
 def test_refusals(sf, torch_mod):
-    """nf = 2 in 3D and a NULL dfe: SF_EINVAL; a NULL qw_d with je: SF_EINVAL, without: fine; "wave" off the table and
-    extents beyond the fallback's bounds: SF_ENOTBUILT."""
+    """nf = 2 in 3D, nf = 0, a NULL dfe and too few fields: SF_EINVAL; a NULL qw_d with je: SF_EINVAL, without: fine."""
     c = sf.capi
     p = AffineAdvectProblem(sf, torch_mod, (4, 4, 4), 5, F64, 2)
     outs = [torch_mod.zeros(5 * p.nmt, dtype=p.dtype, device="cuda") for _ in range(3)]
@@ -171,17 +168,6 @@ def test_refusals(sf, torch_mod):
     with pytest.raises(c.SumfactError) as ei:
         p.run(x=p.x[:2])
     assert ei.value.rc == c.SF_EINVAL
-    for nq, variant in (((9, 9, 9), "wave"), ((6, 6, 12), "wave"), ((13, 2, 2), "auto"), ((33, 2), "auto"),
-                        ((13, 2, 2), "generic"), ((8, 8, 8), "mfma"), ((8, 8), "thread")):
-        q = AffineAdvectProblem(sf, torch_mod, nq, 3, F64, 2)
-        for field in (None, 0):
-            with pytest.raises(c.SumfactError) as ei:
-                q.run(field=field, variant=variant)
-            assert ei.value.rc == c.SF_ENOTBUILT, (nq, variant)
-    q = AffineAdvectProblem(sf, torch_mod, (13, 2, 2), 3, F32, 2)
-    with pytest.raises(c.SumfactError) as ei:
-        q.run()
-    assert ei.value.rc == c.SF_ENOTBUILT
 
 
 @pytest.mark.parametrize("nq,nelmt", MISALIGNED, ids=ids(MISALIGNED))
@@ -190,78 +176,22 @@ def test_misaligned_operands(sf, torch_mod, nq, nelmt):
     bits.  With in / out only 8-byte aligned AUTO takes "generic" and "wave" answers SF_EALIGN."""
     p = AffineAdvectProblem(sf, torch_mod, nq, nelmt, F64, 29)
     clean = p.run(variant="wave")
-
-    def odd(t):
-        buf = torch_mod.empty(t.numel() + 3, dtype=t.dtype, device="cuda")
-        v = buf[1:1 + t.numel()]
-        v.copy_(t.reshape(-1))
-        assert v.data_ptr() % 16 == 8
-        return v
-
+    odd_ = lambda t: odd(torch_mod, t)                                         # noqa: E731
     for field in (None, 0):
-        got = p.run(field=field, variant="wave", dfe=odd(p.dfe), je=odd(p.je), qs=[odd(t) for t in p.qs],
-                    c=[odd(p.c[j]) for j in range(p.d)])
+        got = p.run(field=field, variant="wave", dfe=odd_(p.dfe), je=odd_(p.je), qs=[odd_(t) for t in p.qs],
+                    c=[odd_(p.c[j]) for j in range(p.d)])
         want = clean if field is None else clean[:1]
         assert same_bits(torch_mod, got, want), (nq, field)
     assert float(clean.abs().max()) > 0
     generic = p.run(variant="generic")
-    xs = [odd(p.x[a]) for a in range(p.d)]
-    for kw in (dict(x=xs), dict(out=[odd(clean[a]).zero_() for a in range(p.d)]),
+    xs = [odd_(p.x[a]) for a in range(p.d)]
+    for kw in (dict(x=xs), dict(out=[odd_(clean[a]).zero_() for a in range(p.d)]),
                dict(x=[p.x[0], xs[1]] + [p.x[a] for a in range(2, p.d)])):
         got = p.run(**kw)
         assert same_bits(torch_mod, torch_mod.stack(list(got)), generic), (nq, list(kw))
         with pytest.raises(sf.capi.SumfactError) as ei:
             p.run(variant="wave", **kw)
         assert ei.value.rc == sf.capi.SF_EALIGN, (nq, list(kw))
-
-
-@pytest.mark.parametrize("nq,nelmt", GRAPH, ids=ids(GRAPH))
-def test_captured_graph_replay_matches_eager(sf, torch_mod, nq, nelmt):
-    p = AffineAdvectProblem(sf, torch_mod, nq, nelmt, F64, 11)
-    for field, je in ((None, OWN), (None, None), (1, OWN)):
-        eager = p.run(field=field, je=je)
-        out = rows(torch_mod, eager.shape[0], eager.shape[1], p.dtype, fill=0.0)
-        torch_mod.cuda.synchronize()
-        side = torch_mod.cuda.Stream()
-        side.wait_stream(torch_mod.cuda.current_stream())
-        g = torch_mod.cuda.CUDAGraph()
-        with torch_mod.cuda.stream(side):
-            with torch_mod.cuda.graph(g, stream=side):
-                p.run(field=field, je=je, out=out, stream=side)
-        torch_mod.cuda.current_stream().wait_stream(side)
-        g.replay()
-        torch_mod.cuda.synchronize()
-        assert same_bits(torch_mod, out, eager) and float(out.abs().max()) > 0
-    p.check(out, "graph", elements=[0, 1, nelmt // 2, nelmt - 1], fields=[1])
-
-
-def test_first_call_inside_a_capture_and_eager():
-    """Capture-safe as a process's first call: fresh child processes whose first call of the library is the affine
-    advection call -- inside a stream capture on each route of the family (3D wave, 3D fallback, 2D wave, 2D fallback),
-    and eagerly -- with results equal to later eager calls and to the deformed call on expanded planes."""
-    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "affine_advect_first_call.py")
-    for mode in ("captured", "eager"):
-        r = subprocess.run([sys.executable, script, mode], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0 and f"first calls {mode}" in r.stdout, (mode, r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-
-
-def test_two_streams_in_flight(sf, torch_mod):
-    """Two problems enqueued on two streams before either is waited for; a seeded sample of elements and the ends against
-    long double."""
-    streams = [torch_mod.cuda.Stream(), torch_mod.cuda.Stream()]
-    probs = [AffineAdvectProblem(sf, torch_mod, nq, nelmt, F64, 40 + k) for k, (nq, nelmt) in enumerate(STREAMS)]
-    torch_mod.cuda.synchronize()
-    outs = []
-    for p, st in zip(probs, streams):
-        with torch_mod.cuda.stream(st):
-            outs.append(p.run(stream=st))
-    torch_mod.cuda.synchronize()
-    rng = np.random.default_rng(7)
-    for p, o in zip(probs, outs):
-        ends = [0, 1, p.nelmt - 2, p.nelmt - 1]
-        sample = np.unique(np.concatenate((ends, rng.integers(0, p.nelmt, STREAM_SAMPLE))))
-        p.check(o, "stream job", elements=sample)
-    assert not same_bits(torch_mod, outs[0], outs[1])
 
 
 def _affine_geometry(sf, torch_mod, nq, nelmt, dtype_name):

@@ -12,17 +12,10 @@ import sys
 import numpy as np
 import pytest
 
-from fused_common import same_bits
-from fused_families import COMMON, F64, case_id, own_problem, sf, torch_mod  # noqa: F401
+from fused_families import COMMON, F64, own_problem, sf, torch_mod  # noqa: F401
+from multifield_common import _params, capture_replay, same_bits
 
 pytestmark = pytest.mark.gpu
-
-
-def _params(names, cases, tail=lambda c: "-".join(case_id(v) for v in c[1:])):
-    """parametrize over (family, values ...) tuples; the ID: the family, then the ID the values had in its own file."""
-    cases = list(cases)
-    ids = ["-".join(filter(None, (c[0].name, tail(c)))) for c in cases]
-    return pytest.mark.parametrize(names, cases if "," in names else [c[0] for c in cases], ids=ids)
 
 
 @_params("fam", ((f,) for f in COMMON if f.refused))
@@ -41,16 +34,7 @@ def test_captured_graph_replay_matches_eager(sf, torch_mod, fam, nq, nelmt):
     for present in fam.modes:
         eager = p.run(sf, present=present)
         outs = [torch_mod.zeros_like(t) for t in eager]
-        torch_mod.cuda.synchronize()
-        side = torch_mod.cuda.Stream()
-        side.wait_stream(torch_mod.cuda.current_stream())
-        g = torch_mod.cuda.CUDAGraph()
-        with torch_mod.cuda.stream(side):
-            with torch_mod.cuda.graph(g, stream=side):
-                p.run(sf, present=present, out=outs, stream=side)
-        torch_mod.cuda.current_stream().wait_stream(side)
-        g.replay()
-        torch_mod.cuda.synchronize()
+        capture_replay(torch_mod, lambda side: p.run(sf, present=present, out=outs, stream=side))
         assert same_bits(torch_mod, outs, eager)
         assert all(float(o.abs().max()) > 0 for o in outs)
         if fam.graph_bound:

@@ -9,6 +9,9 @@ with many elements per wave: on the prescribed inputs detj = 0, w = 0, df = g = 
 random operands (test_nq2_lane_maps_on_random_operands) the wave kernel is compared bit for bit, NaN included, with the
 fallback, which the other shapes hold to the bound -- the values are rounding residuals that differ from element to
 element, so a wrong map shows.
+
+The SF_ENOTBUILT refusals, stream capture, the first call inside a capture and two streams in flight are the family's cases
+of tests/test_gpu_multifield_common.py.
 """
 import itertools
 
@@ -17,9 +20,10 @@ import pytest
 
 from affine_ref import affine_n, ref_affine
 from fused_families import F32, F64, RAGGED, Banded, case_id, sf, to_host, torch_mod  # noqa: F401
-from geom_families import (FALLBACK, SUBSETS, WAVE_2D, WAVE_3D, GeomProblem, bits, install_single, per_element, same_bits)
+from geom_families import FALLBACK, SUBSETS, WAVE_2D, WAVE_3D, GeomProblem, per_element
 from geom_ref import OUTPUTS, U64, gamma, sizes
 from helm_ref import helm_n, ref_helmholtz
+from multifield_common import bits, same_bits
 from physderiv_ref import physderiv_n, ref_physderiv
 
 pytestmark = pytest.mark.gpu
@@ -214,5 +218,3 @@ def test_end_to_end_helmholtz_on_affine_coordinates(sf, torch_mod, nq, nelmt):
     print(f"helmholtz vs affine {nq}: max err {float(np.max(err)):.3g}, max err / tol {float(np.max(err / tol)):.3g}")
     assert np.all(err <= tol) and float(a.abs().max()) > 0
 
-
-install_single(globals())

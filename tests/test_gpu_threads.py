@@ -345,7 +345,9 @@ def test_every_operator_family_interleaved(sf, torch_mod, jobs, streams):
         sts = [torch.cuda.Stream() for _ in range(nthreads)]
     torch.cuda.synchronize()
     for st in {id(s): s for s in sts}.values():     # the same calls made serially on the stream of the threads
-        again = [j.call(j.new_out(), st) for j in js]
+        fresh = [j.new_out() for j in js]
+        torch.cuda.synchronize()                    # the NaN fills run on the null stream, which `st` does not wait for
+        again = [j.call(o, st) for j, o in zip(js, fresh)]
         st.synchronize()
         for j, r, s in zip(js, again, serial):
             assert _same(torch, r, s), (j.name, "serial call on another stream")

@@ -2,21 +2,19 @@
 long-double reference and its derived bounds (tests/vecgrad_ref.py: elementwise |got - ref| <= gamma_N absref with
 N_grad = sum nq_d + max nq_d + d, N_div = N_grad + d - 1, N_curl = N_grad + 1), on the seeded per-value-distinct data of
 tests/vecgrad_families.py.  No tolerance is introduced anywhere else: routes, sf_physderiv_* and the sums and differences
-of the returned planes are compared bit for bit.
+of the returned planes are compared bit for bit.  The SF_ENOTBUILT refusals, stream capture, the first call inside a
+capture and two streams in flight are the family's cases of tests/test_gpu_multifield_common.py.
 """
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from fused_families import F32, F64, RAGGED, Banded, case_id, sf, to_host, torch_mod  # noqa: F401
 from geom_families import GeomProblem
-from vecgrad_families import (END_TO_END, FALLBACK, GRAPH, GUARD, MISALIGNED, PHYSDERIV, POISON, RAGGED_BOUND, STREAM_SAMPLE,
-                              STREAMS, SUBSET_SHAPES, SUBSETS, WAVE_COUNT, WAVE_ORDERS, VecgradProblem, banded_outputs,
-                              host_outputs, ids, per_element, planes, rows, same_bits, same_outputs)
+from multifield_common import ids, odd, planes, rows, same_bits
+from vecgrad_families import (END_TO_END, FALLBACK, GUARD, MISALIGNED, PHYSDERIV, POISON, RAGGED_BOUND, SUBSET_SHAPES, SUBSETS,
+                              WAVE_COUNT, WAVE_ORDERS, VecgradProblem, banded_outputs, host_outputs, per_element)
 from vecgrad_ref import CURL_PAIRS, OUTPUTS, output_excess, ref_vecgrad, unit_roundoff, vecgrad_n
 
 pytestmark = pytest.mark.gpu
@@ -31,8 +29,8 @@ def test_every_wave_order_within_the_bounds(sf, torch_mod, nq, dtype_name):
     auto = p.run()
     assert tuple(auto) == OUTPUTS
     if dtype_name == F64:
-        assert same_outputs(torch_mod, auto, p.run(variant="wave")), nq
-        assert same_outputs(torch_mod, auto, p.run(variant="generic")), nq
+        assert same_bits(torch_mod, auto, p.run(variant="wave")), nq
+        assert same_bits(torch_mod, auto, p.run(variant="generic")), nq
     p.check(auto, "auto")
 
 
@@ -45,7 +43,7 @@ def test_every_wave_order_through_auto_on_ragged_counts(sf, torch_mod, nq):
     for n in RAGGED:
         auto, generic = p.run(n), p.run(n, variant="generic")
         assert auto["grad"].shape == (n * per["grad"],) and auto["div"].shape == (n * per["div"],)
-        assert same_outputs(torch_mod, auto, generic), (nq, n)
+        assert same_bits(torch_mod, auto, generic), (nq, n)
         if n == RAGGED_BOUND:
             p.check(auto, f"ragged (first {n})", n=n, elements=np.arange(n))
 
@@ -88,7 +86,7 @@ def test_output_subsets(sf, torch_mod, nq, nelmt, names):
     torch_mod.cuda.synchronize()
     assert tuple(got) == names
     assert all(b.bands_intact(torch_mod) for b in bands)
-    assert same_outputs(torch_mod, got, {k: full[k] for k in names}), (nq, names)
+    assert same_bits(torch_mod, got, {k: full[k] for k in names}), (nq, names)
     assert all(float(t.abs().max()) > 0 for k in names for t in planes(got[k]))
 
 
@@ -96,7 +94,7 @@ def test_output_subsets(sf, torch_mod, nq, nelmt, names):
 def test_fallback_shapes_within_the_bounds(sf, torch_mod, nq, nelmt):
     p = VecgradProblem(sf, torch_mod, nq, nelmt, F64, nelmt % 101)
     auto, generic = p.run(), p.run(variant="generic")
-    assert same_outputs(torch_mod, auto, generic)
+    assert same_bits(torch_mod, auto, generic)
     p.check(generic, "generic")
 
 
@@ -123,7 +121,7 @@ def test_guard_bands_and_nan_bands(sf, torch_mod, nq, nelmt):
     torch_mod.cuda.synchronize()
     assert all(b.bands_intact(torch_mod) for b in bands)
     assert all(b.bands_intact(torch_mod) for b in bs + ds + [df] + xs)
-    assert same_outputs(torch_mod, got, clean), nq
+    assert same_bits(torch_mod, got, clean), nq
     for t in (t for v in clean.values() for t in planes(v)):
         assert not bool(torch_mod.isnan(t).any()) and float(t.abs().max()) > 0
 
@@ -189,72 +187,13 @@ def test_refusals(sf, torch_mod):
     with pytest.raises(c.SumfactError) as ei:
         p.run(outputs=())
     assert ei.value.rc == c.SF_EINVAL
-    for nq, variant in (((9, 9, 9), "wave"), ((6, 6, 12), "wave"), ((13, 2, 2), "auto"), ((33, 2), "auto"),
-                        ((13, 2, 2), "generic"), ((8, 8, 8), "mfma"), ((8, 8), "thread")):
-        q = VecgradProblem(sf, torch_mod, nq, 3, F64, 2)
-        for outputs in (OUTPUTS, ("div",)):
-            with pytest.raises(c.SumfactError) as ei:
-                q.run(outputs=outputs, variant=variant)
-            assert ei.value.rc == c.SF_ENOTBUILT, (nq, variant)
-    q = VecgradProblem(sf, torch_mod, (13, 2, 2), 3, F32, 2)
-    with pytest.raises(c.SumfactError) as ei:
-        q.run()
-    assert ei.value.rc == c.SF_ENOTBUILT
     q = VecgradProblem(sf, torch_mod, (8, 8, 8), 3, F64, 2)                          # "wave" on a stream 8-byte aligned only
-    odd = torch_mod.empty(3 * per_element(q.nq)[0]["div"] + 3, dtype=q.dtype, device="cuda")[1:-2]
-    assert odd.data_ptr() % 16 == 8
+    off = torch_mod.empty(3 * per_element(q.nq)[0]["div"] + 3, dtype=q.dtype, device="cuda")[1:-2]
+    assert off.data_ptr() % 16 == 8
     with pytest.raises(c.SumfactError) as ei:
-        q.run(outputs=("div",), out={"div": odd}, variant="wave")
+        q.run(outputs=("div",), out={"div": off}, variant="wave")
     assert ei.value.rc == c.SF_EALIGN
-    assert same_bits(torch_mod, q.run(outputs=("div",), out={"div": odd})["div"], q.run(outputs=("div",), variant="generic")["div"])
-
-
-@pytest.mark.parametrize("nq,nelmt", GRAPH, ids=ids(GRAPH))
-def test_captured_graph_replay_matches_eager(sf, torch_mod, nq, nelmt):
-    p = VecgradProblem(sf, torch_mod, nq, nelmt, F64, 11)
-    for names in (OUTPUTS, ("div", "curl")):
-        eager = p.run(outputs=names)
-        out, _ = banded_outputs(torch_mod, p, names, nelmt, 0.0)
-        torch_mod.cuda.synchronize()
-        side = torch_mod.cuda.Stream()
-        side.wait_stream(torch_mod.cuda.current_stream())
-        g = torch_mod.cuda.CUDAGraph()
-        with torch_mod.cuda.stream(side):
-            with torch_mod.cuda.graph(g, stream=side):
-                p.run(outputs=names, out=out, stream=side)
-        torch_mod.cuda.current_stream().wait_stream(side)
-        g.replay()
-        torch_mod.cuda.synchronize()
-        assert same_outputs(torch_mod, out, eager)
-        assert all(float(t.abs().max()) > 0 for v in out.values() for t in planes(v))
-    p.check(out, "graph", elements=[0, 1, nelmt // 2, nelmt - 1])
-
-
-def test_first_call_inside_a_capture():
-    """Capture-safe from the first call: a fresh child process whose first call of each route of the family (3D wave, 3D
-    fallback, 2D wave, 2D fallback) is inside a stream capture; the replay equals an eager call made afterwards."""
-    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "vecgrad_first_call.py")
-    r = subprocess.run([sys.executable, script], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "first calls captured" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-
-
-def test_two_streams_in_flight(sf, torch_mod):
-    """Two problems enqueued on two streams before either is waited for; a seeded sample of elements and the ends against
-    long double."""
-    streams = [torch_mod.cuda.Stream(), torch_mod.cuda.Stream()]
-    probs = [VecgradProblem(sf, torch_mod, nq, nelmt, F64, 40 + k) for k, (nq, nelmt) in enumerate(STREAMS)]
-    torch_mod.cuda.synchronize()
-    outs = []
-    for p, st in zip(probs, streams):
-        with torch_mod.cuda.stream(st):
-            outs.append(p.run(stream=st))
-    torch_mod.cuda.synchronize()
-    rng = np.random.default_rng(7)
-    for p, o in zip(probs, outs):
-        ends = [0, 1, p.nelmt - 2, p.nelmt - 1]
-        sample = np.unique(np.concatenate((ends, rng.integers(0, p.nelmt, STREAM_SAMPLE))))
-        p.check(o, "stream job", elements=sample)
-    assert not same_outputs(torch_mod, outs[0], outs[1])
+    assert same_bits(torch_mod, q.run(outputs=("div",), out={"div": off})["div"], q.run(outputs=("div",), variant="generic")["div"])
 
 
 @pytest.mark.parametrize("nq,nelmt", MISALIGNED, ids=ids(MISALIGNED))
@@ -262,11 +201,7 @@ def test_misaligned_df_takes_the_wave_route(sf, torch_mod, nq, nelmt):
     """df at an odd scalar offset (8-byte aligned only) still takes the wave route and gives the same bits."""
     p = VecgradProblem(sf, torch_mod, nq, nelmt, F64, 29)
     clean = p.run(variant="wave")
-    buf = torch_mod.empty(p.df.numel() + 3, dtype=p.dtype, device="cuda")
-    odd = buf[1:1 + p.df.numel()]
-    odd.copy_(p.df)
-    assert odd.data_ptr() % 16 == 8
-    assert same_outputs(torch_mod, p.run(variant="wave", df=odd), clean), nq
+    assert same_bits(torch_mod, p.run(variant="wave", df=odd(torch_mod, p.df)), clean), nq
     assert float(clean["grad"].abs().max()) > 0
 
 

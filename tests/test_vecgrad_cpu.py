@@ -4,13 +4,13 @@ the wave kernels, and the test reference (tests/vecgrad_ref.py) against a dense 
 working precision, against deliberately wrong variants and against a closed form.  No test here needs a GPU."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from geom_ref import deformed, gll_operands, ref_geom
 from physderiv_ref import dense_physderiv, physderiv_n
+from resources_ref import kernel_resources
 from vecgrad_ref import CURL_PAIRS, U64, output_excess, ref_vecgrad, vecgrad_eval, vecgrad_excess, vecgrad_n
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -265,30 +265,21 @@ def test_the_python_layer_refuses_without_a_device(pkg):
         pkg.vecgrad_hex(nq, *bs, *ds, df.float(), x.float(), variant="wave")
 
 
-ROW = re.compile(r"^((?:hex|quad)_vecgrad_wave_kernel<(\d+), .*, (\d+), (double|float)>)\s+vgpr\s+(\d+) agpr\s+\d+ sgpr\s+(\d+) "
-                 r"scratch\s+(-?\d+) spill v(-?\d+)/s(-?\d+) occ (\d+)")
+NAME = re.compile(r"(hex|quad)_vecgrad_wave_kernel<(\d+), .*, (\d+), (double|float)>")
 
 
 def test_wave_instantiations_use_no_scratch():
     """Every wave instantiation: no scratch, no spills, at most 256 VGPRs; the set is exactly 3D nq 2..8 and 2D nq 2..16
     for double and float with the full output mask (7): 44 kernels.  Prints VGPRs / occupancy per kernel (the table of
     DESIGN.md s4.22)."""
-    got = {}
-    for src in ("vecgrad.hip", "vecgrad_f32.hip"):
-        out = subprocess.run(["python3", os.path.join(PKG, "tools", "kernel_resources.py"),
-                              os.path.join(PKG, "csrc", src), "vecgrad_wave_kernel"],
-                             capture_output=True, text=True, cwd=PKG, timeout=1800).stdout
-        rows = [ROW.match(ln) for ln in out.splitlines() if ln.strip()]
-        assert rows and all(rows), out
-        for m in rows:
-            name, nq, mask, t = m.group(1), int(m.group(2)), int(m.group(3)), m.group(4)
-            dim = 3 if name.startswith("hex") else 2
-            assert (t == "float") == (src == "vecgrad_f32.hip"), (src, name)
-            got[(dim, nq, t, mask)] = m
-            print(f"{dim}D nq {nq:2d} {t:6s} mask {mask}: {int(m.group(5)):3d} VGPRs, {int(m.group(6)):3d} SGPRs, "
-                  f"occupancy {m.group(10)}")
-            assert int(m.group(7)) == 0 and int(m.group(8)) == 0 and int(m.group(9)) == 0, m.string
-            assert 0 < int(m.group(5)) <= 256, m.string
+    got = set()
+    for src, r in kernel_resources(("vecgrad.hip", "vecgrad_f32.hip"), "vecgrad_wave_kernel"):
+        m = NAME.fullmatch(r.name)
+        assert m, r.name
+        dim, nq, mask, t = 3 if m.group(1) == "hex" else 2, int(m.group(2)), int(m.group(3)), m.group(4)
+        assert (t == "float") == (src == "vecgrad_f32.hip"), (src, r.name)
+        got.add((dim, nq, t, mask))
+        print(f"{dim}D nq {nq:2d} {t:6s} mask {mask}: {r.vgpr:3d} VGPRs, {r.sgpr:3d} SGPRs, occupancy {r.occ}")
     orders = [(3, n) for n in range(2, 9)] + [(2, n) for n in range(2, 17)]
     want = {(d, n, t, 7) for d, n in orders for t in ("double", "float")}
-    assert len(want) == 44 and set(got) == want, sorted(map(str, want ^ set(got)))
+    assert len(want) == 44 and got == want, sorted(map(str, want ^ got))

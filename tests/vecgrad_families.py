@@ -1,5 +1,7 @@
 """The vector-gradient family (sf_vecgrad_*) for tests/test_gpu_vecgrad.py, in the pattern of tests/advect_families.py: the
-literals of the cases and VecgradProblem (the data of one case on the device, its runs, its reference and its checks).
+literals of the cases, VecgradProblem (the data of one case on the device, its runs, its reference and its checks) and
+FAMILY, the family's adapter for the tests written once in tests/test_gpu_multifield_common.py.  Outputs are compared
+with multifield_common.same_bits: dicts with the same keys and the same bits, a curl as a (3, n) tensor or as three rows.
 
 The Family adapter of tests/fused_families.py does not fit: this family has d inputs and up to three outputs of
 different lengths, each with a count of its own in its bound.  What fits is kept: the seeded per-value-distinct data of
@@ -11,8 +13,8 @@ import itertools
 
 import numpy as np
 
-from advect_families import ids, rows, same_bits  # noqa: F401
 from fused_families import F32, F64, RAGGED, Banded, case_id, sf, sizes, to_host, torch_mod  # noqa: F401
+from multifield_common import NOT_BUILT, MultiField, ids, planes, rows, same_bits  # noqa: F401
 from vecgrad_ref import OUTPUTS, output_excess, ref_vecgrad, unit_roundoff
 
 WAVE_ORDERS = [(q,) * 3 for q in range(2, 9)] + [(q,) * 2 for q in range(2, 17)]
@@ -29,20 +31,6 @@ FIRST_CALL = (((8, 8, 8), 1001), ((6, 6, 12), 101), ((9, 9), 1002), ((23, 5), 10
 STREAMS, STREAM_SAMPLE = (((7, 7, 7), 3001), ((7, 7, 7), 3001)), 64
 END_TO_END = (((5, 5, 5), 101), ((9, 9), 101))
 MISALIGNED = (((4, 4, 4), 130), ((8, 8, 8), 65), ((9, 9), 259))
-
-
-def planes(v):
-    """An output as a list of flat tensors: the rows of a (3, n) curl or of a tuple of three, else the tensor itself."""
-    if isinstance(v, (tuple, list)):
-        return list(v)
-    return [v[r] for r in range(v.shape[0])] if v.dim() == 2 else [v]
-
-
-def same_outputs(torch_mod, a, b):
-    """Two dicts of outputs with the same keys and the same bits."""
-    return a.keys() == b.keys() and all(
-        len(planes(a[k])) == len(planes(b[k])) and all(same_bits(torch_mod, s, t) for s, t in zip(planes(a[k]), planes(b[k])))
-        for k in a)
 
 
 def banded_outputs(torch_mod, p, names, n, guard):
@@ -144,3 +132,20 @@ class VecgradProblem:
             assert float(np.max(np.abs(r))) > 0, (what, self.nq, name)
             worst = max(worst, q)
         return worst
+
+
+def zeros(p, outputs=OUTPUTS, **_):
+    """A zeroed `out` of p.run(outputs=outputs)."""
+    return banded_outputs(p.torch, p, outputs, p.nelmt, 0.0)[0]
+
+
+def refused_calls(p, variant):
+    """With every output and with one in float64; the float32 case with every output."""
+    return [lambda o=o: p.run(outputs=o, variant=variant) for o in ((OUTPUTS, ("div",)) if p.dtype_name == F64 else (OUTPUTS,))]
+
+
+FAMILY = MultiField(
+    name="vecgrad", problem=VecgradProblem, graph=GRAPH, graph_modes=({"outputs": OUTPUTS}, {"outputs": ("div", "curl")}),
+    graph_check={}, zeros=zeros, first_call=FIRST_CALL, first_modes=({"outputs": OUTPUTS},), first_also=None, first_tail=None,
+    first_eager=False, streams=STREAMS, stream_sample=STREAM_SAMPLE, stream_seed=lambda k, nelmt: 40 + k, streams_differ=True,
+    refused=NOT_BUILT, refused_calls=refused_calls)
