@@ -12,20 +12,10 @@ physderiv_* (which re-reads the d^2 planes of df), mul / addcmul with the planes
     python3 gpu-benchmarking_amd/tools/advect_bench.py [--chain] [--check] [--json FILE] [--hex 4,6,8] [--quad 8,12,16]
                                                        [--f32] [--repeats 2]
 """
-import argparse
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from bench import HBM_PEAK_GBS, grouped_ms  # noqa: E402  (the protocol of bench.py extras())
-
-
-def _orders(s):
-    return [int(x) for x in s.split(",") if x]
+import opbench
+from opbench import chain_row, gdof_s, ms, roofline
 
 
 def make_chain(torch, sf, dim, nq, nelmt, bs, ds, df, w, c, x, out):
@@ -48,81 +38,51 @@ def make_chain(torch, sf, dim, nq, nelmt, bs, ds, df, w, c, x, out):
     return chain
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--nelmt3", type=int, default=1 << 18)
-    ap.add_argument("--nelmt2", type=int, default=1 << 20)
-    ap.add_argument("--reps", type=int, default=40)
-    ap.add_argument("--repeats", type=int, default=2)
-    ap.add_argument("--hex", type=_orders, default=[4, 6, 8])
-    ap.add_argument("--quad", type=_orders, default=[8, 12, 16])
-    ap.add_argument("--f32", action="store_true", help="fp32 as well")
-    ap.add_argument("--chain", action="store_true", help="also time physderiv + torch ops + iproduct on the same buffers")
-    ap.add_argument("--check", action="store_true", help="print max |fused - chain| / max |fused| (needs --chain)")
-    ap.add_argument("--variant", default="auto", help="fp64 route: auto, wave or generic")
-    ap.add_argument("--json", default=None, help="write the result here as well")
-    args = ap.parse_args()
+def case(s, c):
+    torch, args, dim, nelmt = s.torch, s.args, c.dim, c.nelmt
+    df = c.fill(nelmt * dim * dim * c.npt, 5)
+    w = c.fill(nelmt * c.npt, 2)
+    cv = c.fill(dim * nelmt * c.npt, 1).view(dim, nelmt * c.npt)
+    x = c.fill(dim * nelmt * c.nmt, 6).view(dim, nelmt * c.nmt)
+    adv = c.op("advect")
+    o = adv(c.ext, *c.bs, *c.ds, df, w, cv, x, **c.kw)
+    nbytes = c.nbytes("advect", nf=dim)
+    chain = o2 = None
+    if args.chain:
+        o2 = torch.empty_like(o)
+        chain = make_chain(torch, s.sf, dim, c.nq, nelmt, c.bs, c.ds, df, w, cv, x, o2)
+    rows = []
+    for rep in range(args.repeats):
+        mean_ms, min_ms = s.timed(lambda: adv(c.ext, *c.bs, *c.ds, df, w, cv, x, out=o, **c.kw))
+        row = {"repeat": rep, "t_advect": ms(mean_ms), "t_advect_min": ms(min_ms),
+               "gdof_s": gdof_s(dim * nelmt * c.nmt, mean_ms), **roofline(nbytes, mean_ms, min_ms)}
+        if chain is not None:
+            row.update(chain_row(mean_ms, *s.timed(chain)))
+        rows.append(row)
+        print(f"advect {c.label}: {row}", flush=True)
+    if chain is not None and args.check:
+        rel = float((o - o2).abs().max() / o.abs().max())
+        rows.append({"chain_rel_diff": rel})
+        print(f"advect {c.label}: max |fused - chain| / max |fused| = {rel:.3g}", flush=True)
+    return rows
 
-    import torch
-    import __graft_entry__ as ge
-    sf = ge.load_package()
-    dev = torch.device("cuda:0")
+
+def options(argv=None):
+    ap = opbench.parser(__doc__, repeats=(2, None), chain="also time physderiv + torch ops + iproduct on the same buffers",
+                        check="print max |fused - chain| / max |fused| (needs --chain)")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = options(argv)
+    s = opbench.Session(args)
     res = {"protocol": f"{args.nelmt3} (3D) / {args.nelmt2} (2D) elements, nf = d, {args.repeats} repeats of {args.reps} "
                        "groups of 8 back-to-back launches (bench.py grouped_ms); frac = algorithmic bytes / time / 8 TB/s",
-           "device": sf.device_info()["name"], "advect": {}}
-    replayed = True
-    dtypes = [("f64", torch.float64)] + ([("f32", torch.float32)] if args.f32 else [])
-    for tname, dtype in dtypes:
-        size = torch.finfo(dtype).bits // 8
-        kw = {"variant": args.variant} if dtype == torch.float64 else {}
-        for dim, orders, nelmt in ((3, args.hex, args.nelmt3), (2, args.quad, args.nelmt2)):
-            for nq in orders:
-                nm, ext = nq - 1, (nq,) * dim
-                nmt, npt = nm ** dim, nq ** dim
-                b = sf.fill_random(nm * nq, 3, dtype=dtype, device=dev)
-                d = sf.fill_random(nq * nq, 4, dtype=dtype, device=dev)
-                bs, ds = (b,) * dim, (d,) * dim
-                df = sf.fill_random(nelmt * dim * dim * npt, 5, dtype=dtype, device=dev)
-                w = sf.fill_random(nelmt * npt, 2, dtype=dtype, device=dev)
-                c = sf.fill_random(dim * nelmt * npt, 1, dtype=dtype, device=dev).view(dim, nelmt * npt)
-                x = sf.fill_random(dim * nelmt * nmt, 6, dtype=dtype, device=dev).view(dim, nelmt * nmt)
-                adv = sf.advect_hex if dim == 3 else sf.advect_quad
-                o = adv(ext, *bs, *ds, df, w, c, x, **kw)
-                nbytes = size * nelmt * ((dim * dim + dim + 1) * npt + 2 * dim * nmt)
-                chain = o2 = None
-                if args.chain:
-                    o2 = torch.empty_like(o)
-                    chain = make_chain(torch, sf, dim, nq, nelmt, bs, ds, df, w, c, x, o2)
-                rows = []
-                for rep in range(args.repeats):
-                    mean_ms, min_ms, g0 = grouped_ms(torch, lambda: adv(ext, *bs, *ds, df, w, c, x, out=o, **kw), args.reps)
-                    replayed = replayed and g0
-                    row = {"repeat": rep, "t_advect": round(mean_ms, 5), "t_advect_min": round(min_ms, 5),
-                           "gdof_s": round(dim * nelmt * nmt / mean_ms * 1e-6, 2), "gb_s": round(nbytes / mean_ms * 1e-6, 1),
-                           "frac_mean": round(nbytes / mean_ms * 1e-6 / HBM_PEAK_GBS, 4),
-                           "frac_min": round(nbytes / min_ms * 1e-6 / HBM_PEAK_GBS, 4)}
-                    if chain is not None:
-                        c_mean, c_min, g1 = grouped_ms(torch, chain, args.reps)
-                        replayed = replayed and g1
-                        row.update({"t_chain": round(c_mean, 5), "t_chain_min": round(c_min, 5),
-                                    "speedup_vs_chain": round(c_mean / mean_ms, 3), "not_slower_than_chain": mean_ms <= c_mean})
-                    rows.append(row)
-                    print(f"advect {dim}D {tname} nq {nq:2d}: {row}", flush=True)
-                if chain is not None and args.check:
-                    rel = float((o - o2).abs().max() / o.abs().max())
-                    rows.append({"chain_rel_diff": rel})
-                    print(f"advect {dim}D {tname} nq {nq:2d}: max |fused - chain| / max |fused| = {rel:.3g}", flush=True)
-                key = f"{'hex' if dim == 3 else 'quad'}_{tname}"
-                res["advect"].setdefault(key, {})[str(nq)] = rows
-                del df, w, c, x, o, o2, chain
-                torch.cuda.empty_cache()
-    res["hip_graph_replay"] = replayed
-    line = json.dumps(res)
-    print(line)
-    if args.json:
-        with open(args.json, "w") as fh:
-            fh.write(line + "\n")
+           "device": s.device_name, "advect": {}}
+    s.collect(res["advect"], lambda c: case(s, c))
+    s.emit(res)
+    return 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

@@ -13,119 +13,65 @@ two calls (the affine forms are bit for bit the deformed ones on expanded planes
     python3 gpu-benchmarking_amd/tools/affine_deriv_bench.py [--check] [--repeats 2] [--json FILE] [--hex 4,6,8]
                                                              [--quad 8,12,16] [--f32] [--no-je] [--variant auto]
 """
-import argparse
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from bench import HBM_PEAK_GBS, grouped_ms  # noqa: E402  (the protocol of bench.py extras())
+import opbench
+from opbench import scalars
 
 
-def _orders(s):
-    return [int(x) for x in s.split(",") if x]
+def case(s, c, rep, table):
+    """Both operators at one (dtype, dim, nq); returns whether every pair of outputs compared equal."""
+    torch, args, dim, nelmt, npt, nq = s.torch, s.args, c.dim, c.nelmt, c.npt, c.nq
+    qw = c.fill(nq, 6)
+    bs, ds, qs, kw = c.bs, c.ds, (qw,) * dim, c.kw
+    x = c.fill(nelmt * c.nmt, 1)
+    f = c.fill(dim * nelmt * npt, 7).view(dim, -1)
+    dfe = c.fill(nelmt * dim * dim, 5)
+    je = None if args.no_je else c.fill(nelmt, 2)
+    has_je = je is not None
+    df, w = opbench.expand_affine(torch, dim, nelmt, npt, qw, dfe, je)        # the planes of the deformed calls
+    apd, pd, aipd, ipd = c.op("affine_physderiv"), c.op("physderiv"), c.op("affine_iprodderiv"), c.op("iprodderiv")
+    og, og2 = (torch.empty((dim, nelmt * npt), dtype=c.dtype, device=s.dev) for _ in range(2))
+    om, om2 = (torch.empty(nelmt * c.nmt, dtype=c.dtype, device=s.dev) for _ in range(2))
+    calls = {
+        "gradient": (lambda: apd(c.ext, *bs, *ds, dfe, x, out=og, **kw),
+                     lambda: pd(c.ext, *bs, *ds, df, x, out=og2, **kw),
+                     scalars("affine_physderiv", dim, nq), scalars("physderiv", dim, nq), og, og2),
+        "weak_divergence": (lambda: aipd(c.ext, *bs, *ds, *qs, dfe, je, f, out=om, **kw),
+                            lambda: ipd(c.ext, *bs, *ds, df, w, f, out=om2, **kw),
+                            scalars("affine_iprodderiv", dim, nq, je=has_je), scalars("iprodderiv", dim, nq, w=has_je),
+                            om, om2)}
+    bits_ok = True
+    for op, call in calls.items():
+        row = s.versus_deformed(c, *call)
+        bits_ok = bits_ok and row.get("bits_equal", True)
+        table.setdefault(f"{op}_{c.key}", {})[str(nq)] = row
+        print(f"repeat {rep} {op} {c.label}: {row}", flush=True)
+    return bits_ok
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--nelmt3", type=int, default=1 << 18)
-    ap.add_argument("--nelmt2", type=int, default=1 << 20)
-    ap.add_argument("--reps", type=int, default=40)
-    ap.add_argument("--repeats", type=int, default=1, help="measure everything this often")
-    ap.add_argument("--hex", type=_orders, default=[4, 6, 8])
-    ap.add_argument("--quad", type=_orders, default=[8, 12, 16])
-    ap.add_argument("--f32", action="store_true", help="fp32 as well")
+def options(argv=None):
+    ap = opbench.parser(__doc__, repeats=(1, "measure everything this often"),
+                        check="compare the bits of each affine call with its deformed call",
+                        variant="fp64 route of every call: auto, wave or generic")
     ap.add_argument("--no-je", action="store_true", help="the weak divergence without weight (je = None, w = None)")
-    ap.add_argument("--check", action="store_true", help="compare the bits of each affine call with its deformed call")
-    ap.add_argument("--variant", default="auto", help="fp64 route of every call: auto, wave or generic")
-    ap.add_argument("--json", default=None, help="write the result here as well")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
 
-    import torch
-    import __graft_entry__ as ge_
-    sf = ge_.load_package()
-    dev = torch.device("cuda:0")
+
+def main(argv=None):
+    args = options(argv)
+    s = opbench.Session(args)
     res = {"protocol": f"{args.nelmt3} (3D) / {args.nelmt2} (2D) elements, {args.reps} groups of 8 back-to-back launches "
                        "(bench.py grouped_ms); frac = affine algorithmic bytes / time / 8 TB/s; ratio = deformed / affine",
-           "device": sf.device_info()["name"], "je": not args.no_je, "repeats": []}
-    replayed, bits_ok = True, True
-    dtypes = [("f64", torch.float64)] + ([("f32", torch.float32)] if args.f32 else [])
+           "device": s.device_name, "je": not args.no_je, "repeats": []}
+    bits_ok = True
     for rep in range(args.repeats):
         table = {}
-        for tname, dtype in dtypes:
-            size = torch.finfo(dtype).bits // 8
-            kw = {"variant": args.variant} if dtype == torch.float64 else {}
-            for dim, orders, nelmt in ((3, args.hex, args.nelmt3), (2, args.quad, args.nelmt2)):
-                dd = dim * dim
-                for nq in orders:
-                    nm, ext, npt = nq - 1, (nq,) * dim, nq ** dim
-                    nmt = nm ** dim
-                    b = sf.fill_random(nm * nq, 3, dtype=dtype, device=dev)
-                    d = sf.fill_random(nq * nq, 4, dtype=dtype, device=dev)
-                    qw = sf.fill_random(nq, 6, dtype=dtype, device=dev)
-                    bs, ds, qs = (b,) * dim, (d,) * dim, (qw,) * dim
-                    x = sf.fill_random(nelmt * nmt, 1, dtype=dtype, device=dev)
-                    f = sf.fill_random(dim * nelmt * npt, 7, dtype=dtype, device=dev).view(dim, -1)
-                    dfe = sf.fill_random(nelmt * dd, 5, dtype=dtype, device=dev)
-                    je = None if args.no_je else sf.fill_random(nelmt, 2, dtype=dtype, device=dev)
-                    # the planes of the deformed calls, expanded on the device in the working precision
-                    df = dfe.view(nelmt, dd, 1).expand(nelmt, dd, npt).contiguous().reshape(-1)
-                    w = None
-                    if je is not None:
-                        q = qw
-                        for _ in range(dim - 1):
-                            q = torch.outer(qw, q.reshape(-1)).reshape(-1)          # qw_d * (the product so far)
-                        w = (je.view(nelmt, 1) * q.view(1, -1)).reshape(-1).contiguous()
-                    apd, pd, aipd, ipd = ((sf.affine_physderiv_hex, sf.physderiv_hex, sf.affine_iprodderiv_hex,
-                                           sf.iprodderiv_hex) if dim == 3 else
-                                          (sf.affine_physderiv_quad, sf.physderiv_quad, sf.affine_iprodderiv_quad,
-                                           sf.iprodderiv_quad))
-                    og, og2 = (torch.empty((dim, nelmt * npt), dtype=dtype, device=dev) for _ in range(2))
-                    om, om2 = (torch.empty(nelmt * nmt, dtype=dtype, device=dev) for _ in range(2))
-                    calls = {
-                        "gradient": (lambda: apd(ext, *bs, *ds, dfe, x, out=og, **kw),
-                                     lambda: pd(ext, *bs, *ds, df, x, out=og2, **kw),
-                                     nmt + dim * npt + dd, nmt + (dim + dd) * npt, og, og2),
-                        "weak_divergence": (lambda: aipd(ext, *bs, *ds, *qs, dfe, je, f, out=om, **kw),
-                                            lambda: ipd(ext, *bs, *ds, df, w, f, out=om2, **kw),
-                                            dim * npt + nmt + dd + (je is not None),
-                                            (dim + dd + (je is not None)) * npt + nmt, om, om2)}
-                    for op, (affine, deformed, a_sc, d_sc, oa, od) in calls.items():
-                        a_mean, a_min, g0 = grouped_ms(torch, affine, args.reps)
-                        d_mean, d_min, g1 = grouped_ms(torch, deformed, args.reps)
-                        replayed = replayed and g0 and g1
-                        abytes, dbytes = size * nelmt * a_sc, size * nelmt * d_sc
-                        row = {"ms": round(a_mean, 5), "ms_min": round(a_min, 5), "scalars_per_element": a_sc,
-                               "gb_s": round(abytes / a_mean * 1e-6, 1),
-                               "frac_mean": round(abytes / a_mean * 1e-6 / HBM_PEAK_GBS, 4),
-                               "frac_min": round(abytes / a_min * 1e-6 / HBM_PEAK_GBS, 4),
-                               "ms_deformed": round(d_mean, 5), "ms_deformed_min": round(d_min, 5),
-                               "deformed_scalars_per_element": d_sc,
-                               "deformed_frac_mean": round(dbytes / d_mean * 1e-6 / HBM_PEAK_GBS, 4),
-                               "ratio": round(d_mean / a_mean, 3), "ratio_min": round(d_min / a_min, 3),
-                               "ok": bool(a_mean <= d_mean)}
-                        if args.check:
-                            torch.cuda.synchronize()
-                            row["bits_equal"] = bool(torch.equal(oa, od)) and float(oa.abs().max()) > 0
-                            bits_ok = bits_ok and row["bits_equal"]
-                        key = f"{op}_{'hex' if dim == 3 else 'quad'}_{tname}"
-                        table.setdefault(key, {})[str(nq)] = row
-                        print(f"repeat {rep} {op} {dim}D {tname} nq {nq:2d}: {row}", flush=True)
-                    del x, f, dfe, je, df, w, og, og2, om, om2, calls
-                    torch.cuda.empty_cache()
+        for c in s.sweep():
+            bits_ok = case(s, c, rep, table) and bits_ok
         res["repeats"].append(table)
-    res["hip_graph_replay"] = replayed
-    res["all_ok"] = all(r["ok"] for t in res["repeats"] for k in t.values() for r in k.values())
-    if args.check:
-        res["bits_equal"] = bits_ok
-    line = json.dumps(res)
-    print(line)
-    if args.json:
-        with open(args.json, "w") as fh:
-            fh.write(line + "\n")
+    s.emit(res, all_ok=all(r["ok"] for t in res["repeats"] for k in t.values() for r in k.values()),
+           **({"bits_equal": bits_ok} if args.check else {}))
     return 0 if bits_ok else 1
 
 

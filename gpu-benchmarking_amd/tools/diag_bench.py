@@ -15,20 +15,10 @@ more).
     python3 gpu-benchmarking_amd/tools/diag_bench.py [--chain] [--check] [--helmholtz] [--laplacian] [--json FILE]
                                                      [--hex 4,6,8] [--quad 8,12,16] [--f32]
 """
-import argparse
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from bench import HBM_PEAK_GBS, grouped_ms  # noqa: E402  (the protocol of bench.py extras())
-
-
-def _orders(s):
-    return [int(x) for x in s.split(",") if x]
+import opbench
+from opbench import chain_row, fracs, gdof_s, ms, roofline
 
 
 def make_chain(torch, dim, nq, nelmt, b, d, g, w, lam, o):
@@ -67,95 +57,57 @@ def make_chain(torch, dim, nq, nelmt, b, d, g, w, lam, o):
     return chain
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--nelmt3", type=int, default=1 << 18)
-    ap.add_argument("--nelmt2", type=int, default=1 << 20)
-    ap.add_argument("--reps", type=int, default=40)
-    ap.add_argument("--hex", type=_orders, default=[4, 6, 8])
-    ap.add_argument("--quad", type=_orders, default=[8, 12, 16])
-    ap.add_argument("--f32", action="store_true", help="fp32 as well")
-    ap.add_argument("--laplacian", action="store_true", help="lambda = 0, w = None")
-    ap.add_argument("--chain", action="store_true", help="also time the torch formulation on the same buffers")
-    ap.add_argument("--check", action="store_true", help="print max |fused - chain| / max |fused| (needs --chain)")
-    ap.add_argument("--helmholtz", action="store_true", help="also time sf_helmholtz_* at the same orders")
-    ap.add_argument("--variant", default="auto", help="fp64 route: auto, wave or generic")
-    ap.add_argument("--json", default=None, help="write the result here as well")
-    args = ap.parse_args()
+def case(s, c, lam):
+    torch, args, dim, nelmt = s.torch, s.args, c.dim, c.nelmt
+    b, d = c.bs[0], c.ds[0]
+    g = c.fill(nelmt * (dim * (dim + 1) // 2) * c.npt, 5)
+    w = None if args.laplacian else c.fill(nelmt * c.npt, 2)
+    o = torch.empty(nelmt * c.nmt, dtype=c.dtype, device=s.dev)
+    tabs = (s.sf.diag_tables(c.nq, b, d),) * dim
+    diag, helm = c.op("diag_helmholtz"), c.op("helmholtz")
+    nbytes = c.nbytes("diag_helmholtz", w=not args.laplacian)
+    mean_ms, min_ms = s.timed(lambda: diag(c.ext, *c.bs, *c.ds, g, w, lam, out=o, tabs=tabs, **c.kw))
+    row = {"ms": ms(mean_ms), "ms_min": ms(min_ms), "gdof_s": gdof_s(nelmt * c.nmt, mean_ms),
+           **roofline(nbytes, mean_ms, min_ms)}
+    if args.chain:
+        o2 = torch.empty_like(o)
+        chain = make_chain(torch, dim, c.nq, nelmt, b, d, g, w, lam, o2)
+        row.update(chain_row(mean_ms, *s.timed(chain), prefix="ms", bar=False))
+        if args.check:
+            diag(c.ext, *c.bs, *c.ds, g, w, lam, out=o, tabs=tabs, **c.kw)
+            chain()
+            torch.cuda.synchronize()
+            row["chain_rel_diff"] = float((o - o2).abs().max() / o.abs().max())
+        del chain, o2
+    if args.helmholtz:
+        x = c.fill(nelmt * c.nmt, 1)
+        h_mean, h_min = s.timed(lambda: helm(c.ext, *c.bs, *c.ds, g, w, lam, x, out=o, **c.kw))
+        row.update({"ms_helmholtz": ms(h_mean), "ms_helmholtz_min": ms(h_min),
+                    **fracs("helmholtz", c.nbytes("helmholtz", w=not args.laplacian), h_mean, h_min),
+                    "diag_over_helmholtz": round(mean_ms / h_mean, 3)})
+    print(f"diag {c.label}: {row}", flush=True)
+    return row
 
-    import torch
-    import __graft_entry__ as ge
-    sf = ge.load_package()
-    dev = torch.device("cuda:0")
+
+def options(argv=None):
+    ap = opbench.parser(__doc__, chain="also time the torch formulation on the same buffers",
+                        check="print max |fused - chain| / max |fused| (needs --chain)")
+    ap.add_argument("--laplacian", action="store_true", help="lambda = 0, w = None")
+    ap.add_argument("--helmholtz", action="store_true", help="also time sf_helmholtz_* at the same orders")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = options(argv)
+    s = opbench.Session(args)
     lam = 0.0 if args.laplacian else 0.75
     res = {"protocol": f"{args.nelmt3} (3D) / {args.nelmt2} (2D) elements, {args.reps} groups of 8 back-to-back launches "
                        "(bench.py grouped_ms); frac = algorithmic bytes / time / 8 TB/s",
-           "device": sf.device_info()["name"], "lambda": lam, "diag": {}}
-    replayed = True
-    dtypes = [("f64", torch.float64)] + ([("f32", torch.float32)] if args.f32 else [])
-    for tname, dtype in dtypes:
-        size = torch.finfo(dtype).bits // 8
-        kw = {"variant": args.variant} if dtype == torch.float64 else {}
-        for dim, orders, nelmt in ((3, args.hex, args.nelmt3), (2, args.quad, args.nelmt2)):
-            ncomp = dim * (dim + 1) // 2
-            for nq in orders:
-                nm, ext = nq - 1, (nq,) * dim
-                b = sf.fill_random(nm * nq, 3, dtype=dtype, device=dev)
-                d = sf.fill_random(nq * nq, 4, dtype=dtype, device=dev)
-                bs, ds = (b,) * dim, (d,) * dim
-                g = sf.fill_random(nelmt * ncomp * nq ** dim, 5, dtype=dtype, device=dev)
-                w = None if args.laplacian else sf.fill_random(nelmt * nq ** dim, 2, dtype=dtype, device=dev)
-                o = torch.empty(nelmt * nm ** dim, dtype=dtype, device=dev)
-                tabs = (sf.diag_tables(nq, b, d),) * dim
-                diag, helm = ((sf.diag_helmholtz_hex, sf.helmholtz_hex) if dim == 3 else
-                              (sf.diag_helmholtz_quad, sf.helmholtz_quad))
-                planes = ncomp + (0 if args.laplacian else 1)
-                nbytes = size * nelmt * (planes * nq ** dim + nm ** dim)
-
-                def frac(nb, ms):
-                    return round(nb / ms * 1e-6 / HBM_PEAK_GBS, 4)
-
-                mean_ms, min_ms, graphed = grouped_ms(torch, lambda: diag(ext, *bs, *ds, g, w, lam, out=o, tabs=tabs, **kw),
-                                                      args.reps)
-                replayed = replayed and graphed
-                row = {"ms": round(mean_ms, 5), "ms_min": round(min_ms, 5),
-                       "gdof_s": round(nelmt * nm ** dim / mean_ms * 1e-6, 2),
-                       "gb_s": round(nbytes / mean_ms * 1e-6, 1),
-                       "frac_mean": frac(nbytes, mean_ms), "frac_min": frac(nbytes, min_ms)}
-                if args.chain:
-                    o2 = torch.empty_like(o)
-                    chain = make_chain(torch, dim, nq, nelmt, b, d, g, w, lam, o2)
-                    c_mean, c_min, g1 = grouped_ms(torch, chain, args.reps)
-                    replayed = replayed and g1
-                    row.update({"ms_chain": round(c_mean, 5), "ms_chain_min": round(c_min, 5),
-                                "speedup_vs_chain": round(c_mean / mean_ms, 3)})
-                    if args.check:
-                        diag(ext, *bs, *ds, g, w, lam, out=o, tabs=tabs, **kw)
-                        chain()
-                        torch.cuda.synchronize()
-                        row["chain_rel_diff"] = float((o - o2).abs().max() / o.abs().max())
-                    del chain, o2
-                if args.helmholtz:
-                    x = sf.fill_random(nelmt * nm ** dim, 1, dtype=dtype, device=dev)
-                    h_mean, h_min, g2 = grouped_ms(torch, lambda: helm(ext, *bs, *ds, g, w, lam, x, out=o, **kw), args.reps)
-                    replayed = replayed and g2
-                    hb = nbytes + size * nelmt * nm ** dim
-                    row.update({"ms_helmholtz": round(h_mean, 5), "ms_helmholtz_min": round(h_min, 5),
-                                "helmholtz_frac_mean": frac(hb, h_mean), "helmholtz_frac_min": frac(hb, h_min),
-                                "diag_over_helmholtz": round(mean_ms / h_mean, 3)})
-                    del x
-                key = f"{'hex' if dim == 3 else 'quad'}_{tname}"
-                res["diag"].setdefault(key, {})[str(nq)] = row
-                print(f"diag {dim}D {tname} nq {nq:2d}: {row}", flush=True)
-                del g, w, o
-                torch.cuda.empty_cache()
-    res["hip_graph_replay"] = replayed
-    line = json.dumps(res)
-    print(line)
-    if args.json:
-        with open(args.json, "w") as fh:
-            fh.write(line + "\n")
+           "device": s.device_name, "lambda": lam, "diag": {}}
+    s.collect(res["diag"], lambda c: case(s, c, lam))
+    s.emit(res)
+    return 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

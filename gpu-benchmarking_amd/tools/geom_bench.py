@@ -14,23 +14,13 @@ repeat.  --check prints max |fused - chain| / max |fused| per output.
     python3 gpu-benchmarking_amd/tools/geom_bench.py [--chain] [--check] [--f32] [--json FILE] [--hex 4,6,8]
                                                      [--quad 8,12,16] [--repeats 2]
 """
-import argparse
-import json
-import os
 import sys
 
 import numpy as np
 from numpy.polynomial import legendre as _leg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from bench import HBM_PEAK_GBS, grouped_ms  # noqa: E402  (the protocol of bench.py extras())
-
-
-def _orders(s):
-    return [int(x) for x in s.split(",") if x]
+import opbench
+from opbench import chain_row, ms, roofline
 
 
 def gll(nq):
@@ -117,77 +107,50 @@ def make_chain(torch, sf, dim, nq, nelmt, bs, ds, qs, x, out):
     return chain
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--nelmt3", type=int, default=1 << 18)
-    ap.add_argument("--nelmt2", type=int, default=1 << 20)
-    ap.add_argument("--reps", type=int, default=40)
-    ap.add_argument("--repeats", type=int, default=2)
-    ap.add_argument("--hex", type=_orders, default=[4, 6, 8])
-    ap.add_argument("--quad", type=_orders, default=[8, 12, 16])
-    ap.add_argument("--f32", action="store_true", help="fp32 as well")
-    ap.add_argument("--chain", action="store_true", help="also time d x physderiv + torch pointwise ops on the same buffers")
-    ap.add_argument("--check", action="store_true", help="print max |fused - chain| / max |fused| (needs --chain)")
-    ap.add_argument("--variant", default="auto", help="fp64 route: auto, wave or generic")
-    ap.add_argument("--json", default=None, help="write the result here as well")
-    args = ap.parse_args()
+def case(s, c):
+    torch, args, dim, nelmt = s.torch, s.args, c.dim, c.nelmt
+    b, d, q = (torch.tensor(v, dtype=c.dtype, device=s.dev) for v in gll(c.nq))
+    bs, ds, qs = (b,) * dim, (d,) * dim, (q,) * dim
+    x = coordinates(torch, dim, c.nq, nelmt, c.dtype, s.dev)
+    fn = c.op("geom")
+    out = fn(c.ext, *bs, *ds, *qs, x, **c.kw)
+    nbytes = c.nbytes("geom")
+    row = {"repeats": []}
+    chain = out2 = None
+    if args.chain:
+        out2 = {k: torch.empty_like(t) for k, t in out.items()}
+        chain = make_chain(torch, s.sf, dim, c.nq, nelmt, bs, ds, qs, x, out2)
+    for _ in range(args.repeats):
+        mean_ms, min_ms = s.timed(lambda: fn(c.ext, *bs, *ds, *qs, x, out=out, **c.kw))
+        rep = {"t_geom": ms(mean_ms), "t_geom_min": ms(min_ms), **roofline(nbytes, mean_ms, min_ms)}
+        if chain is not None:
+            rep.update(chain_row(mean_ms, *s.timed(chain)))
+        row["repeats"].append(rep)
+    if chain is not None:
+        row["not_slower_than_chain"] = all(r["not_slower_than_chain"] for r in row["repeats"])
+        if args.check:
+            row["chain_rel_diff"] = {k: float((out[k] - out2[k]).abs().max() / out[k].abs().max()) for k in out}
+    print(f"geom {c.label}: {row}", flush=True)
+    return row
 
-    import torch
-    import __graft_entry__ as ge
-    sf = ge.load_package()
-    dev = torch.device("cuda:0")
+
+def options(argv=None):
+    ap = opbench.parser(__doc__, repeats=(2, None),
+                        chain="also time d x physderiv + torch pointwise ops on the same buffers",
+                        check="print max |fused - chain| / max |fused| (needs --chain)")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = options(argv)
+    s = opbench.Session(args)
     res = {"protocol": f"{args.nelmt3} (3D) / {args.nelmt2} (2D) elements, {args.repeats} repeats of {args.reps} groups of 8 "
                        "back-to-back launches (bench.py grouped_ms); frac = algorithmic bytes / time / 8 TB/s",
-           "device": sf.device_info()["name"], "geom": {}}
-    replayed = True
-    dtypes = [("f64", torch.float64)] + ([("f32", torch.float32)] if args.f32 else [])
-    for tname, dtype in dtypes:
-        size = torch.finfo(dtype).bits // 8
-        kw = {"variant": args.variant} if dtype == torch.float64 else {}
-        for dim, orders, nelmt in ((3, args.hex, args.nelmt3), (2, args.quad, args.nelmt2)):
-            for nq in orders:
-                nm, ext = nq - 1, (nq,) * dim
-                nmt, npt, ncomp = nm ** dim, nq ** dim, dim * (dim + 1) // 2
-                b, d, q = (torch.tensor(v, dtype=dtype, device=dev) for v in gll(nq))
-                bs, ds, qs = (b,) * dim, (d,) * dim, (q,) * dim
-                x = coordinates(torch, dim, nq, nelmt, dtype, dev)
-                fn = sf.geom_hex if dim == 3 else sf.geom_quad
-                out = fn(ext, *bs, *ds, *qs, x, **kw)
-                nbytes = size * nelmt * (dim * nmt + (dim * dim + ncomp + 2) * npt)
-                row = {"repeats": []}
-                chain = out2 = None
-                if args.chain:
-                    out2 = {k: torch.empty_like(t) for k, t in out.items()}
-                    chain = make_chain(torch, sf, dim, nq, nelmt, bs, ds, qs, x, out2)
-                for _ in range(args.repeats):
-                    mean_ms, min_ms, g0 = grouped_ms(torch, lambda: fn(ext, *bs, *ds, *qs, x, out=out, **kw), args.reps)
-                    replayed = replayed and g0
-                    rep = {"t_geom": round(mean_ms, 5), "t_geom_min": round(min_ms, 5),
-                           "gb_s": round(nbytes / mean_ms * 1e-6, 1),
-                           "frac_mean": round(nbytes / mean_ms * 1e-6 / HBM_PEAK_GBS, 4),
-                           "frac_min": round(nbytes / min_ms * 1e-6 / HBM_PEAK_GBS, 4)}
-                    if chain is not None:
-                        c_mean, c_min, g1 = grouped_ms(torch, chain, args.reps)
-                        replayed = replayed and g1
-                        rep.update({"t_chain": round(c_mean, 5), "t_chain_min": round(c_min, 5),
-                                    "speedup_vs_chain": round(c_mean / mean_ms, 3), "not_slower_than_chain": mean_ms <= c_mean})
-                    row["repeats"].append(rep)
-                if chain is not None:
-                    row["not_slower_than_chain"] = all(r["not_slower_than_chain"] for r in row["repeats"])
-                    if args.check:
-                        row["chain_rel_diff"] = {k: float((out[k] - out2[k]).abs().max() / out[k].abs().max()) for k in out}
-                key = f"{'hex' if dim == 3 else 'quad'}_{tname}"
-                res["geom"].setdefault(key, {})[str(nq)] = row
-                print(f"geom {dim}D {tname} nq {nq:2d}: {row}", flush=True)
-                del x, out, out2, chain
-                torch.cuda.empty_cache()
-    res["hip_graph_replay"] = replayed
-    line = json.dumps(res)
-    print(line)
-    if args.json:
-        with open(args.json, "w") as fh:
-            fh.write(line + "\n")
+           "device": s.device_name, "geom": {}}
+    s.collect(res["geom"], lambda c: case(s, c))
+    s.emit(res)
+    return 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

@@ -17,47 +17,36 @@ costs a solver iteration.  --check compares every call with torch's result (asse
     python3 gpu-benchmarking_amd/tools/gs_bench.py [--sign] [--f32] [--helmholtz] [--check] [--hex 64] [--quad 1024]
                                                    [--json FILE]
 """
-import argparse
-import json
-import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-for p in (ROOT, os.path.join(ROOT, "tests")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import opbench
+from opbench import ms, roofline
 
-from bench import HBM_PEAK_GBS, grouped_ms  # noqa: E402  (the protocol of bench.py extras())
+opbench.importable("tests")
 from gs_ref import multiplicity, structured_map  # noqa: E402  (the map builder the tests use)
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--hex", type=int, default=64, help="elements per direction of the hex mesh (0: skip)")
-    ap.add_argument("--quad", type=int, default=1024, help="elements per direction of the quad mesh (0: skip)")
+def options(argv=None):
+    ap = opbench.parser(__doc__, nelmt=None, reps=20, hex=(int, 64, "elements per direction of the hex mesh (0: skip)"),
+                        quad=(int, 1024, "elements per direction of the quad mesh (0: skip)"),
+                        check="compare with torch's results", variant=None)
     ap.add_argument("--nq", type=int, default=8)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--f32", action="store_true", help="fp32 as well")
     ap.add_argument("--sign", action="store_true", help="with a sign array (torch: a multiply more)")
     ap.add_argument("--helmholtz", action="store_true", help="hex fp64: the operator alone and between Q and Q^T")
-    ap.add_argument("--check", action="store_true", help="compare with torch's results")
-    ap.add_argument("--json", default=None, help="write the result here as well")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = options(argv)
 
     import numpy as np
-    import torch
-    import __graft_entry__ as ge
-    sf = ge.load_package()
-    dev = torch.device("cuda:0")
+    s = opbench.Session(args)
+    torch, sf, dev, timed = s.torch, s.sf, s.dev, s.timed
     nq, nm = args.nq, args.nq - 1
     res = {"protocol": f"{args.reps} groups of 8 back-to-back launches (bench.py grouped_ms); frac = algorithmic bytes / "
                        "time / 8 TB/s; *_torch = torch's formulation on the same buffers",
-           "device": sf.device_info()["name"], "nq": nq, "sign": args.sign, "gs": {}}
-    replayed = True
-
-    def frac(nb, ms):
-        return round(nb / ms * 1e-6 / HBM_PEAK_GBS, 4)
+           "device": s.device_name, "nq": nq, "sign": args.sign, "gs": {}}
 
     meshes = [("hex", (args.hex,) * 3)] * bool(args.hex) + [("quad", (args.quad,) * 2)] * bool(args.quad)
     for shape, nel in meshes:
@@ -76,8 +65,7 @@ def main():
             best = dt if best is None else min(best, dt)
         mesh = {"nel": list(nel), "nlocal": nlocal, "nglobal": nglobal, "shared": nshared, "setup_ms": round(best, 3)}
         print(f"gs {shape} {nel}: nlocal {nlocal} nglobal {nglobal} shared {nshared} setup {best:.3f} ms", flush=True)
-        for tname, dtype in [("f64", torch.float64)] + ([("f32", torch.float32)] if args.f32 else []):
-            size = torch.finfo(dtype).bits // 8
+        for tname, dtype, size in s.dtypes():
             loc = sf.fill_random(nlocal, 1, dtype=dtype, device=dev)
             glo = sf.fill_random(nglobal, 2, dtype=dtype, device=dev)
             out_l, out_g = torch.empty_like(loc), torch.empty_like(glo)
@@ -85,6 +73,7 @@ def main():
             sign = None
             if args.sign:
                 sign = torch.where(sf.fill_random(nlocal, 3, dtype=dtype, device=dev) < 0, -1.0, 1.0).to(dtype)
+            # not per element, so not in opbench's table: index and value traffic of the map (module docstring)
             nb_l = nlocal * (4 + size) + nglobal * size + (nlocal * size if args.sign else 0)
             nb_g = nb_l + 4 * nglobal
             nb_s = 4 * nglobal + (4 + 2 * size) * nshared
@@ -113,14 +102,12 @@ def main():
             rows = {}
             for name, ours, theirs, nb in cases:
                 work.copy_(loc)                     # gs runs in place over and over: the values overflow, the time is theirs
-                mean_ms, min_ms, g1 = grouped_ms(torch, ours, args.reps)
+                mean_ms, min_ms = timed(ours)
                 work.copy_(loc)
-                t_mean, t_min, g2 = grouped_ms(torch, theirs, args.reps)
-                replayed = replayed and g1 and g2
-                rows[name] = {"ms": round(mean_ms, 5), "ms_min": round(min_ms, 5), "gb_s": round(nb / mean_ms * 1e-6, 1),
-                              "frac_mean": frac(nb, mean_ms), "frac_min": frac(nb, min_ms), "ms_torch": round(t_mean, 5),
-                              "ms_torch_min": round(t_min, 5), "speedup_vs_torch": round(t_mean / mean_ms, 3),
-                              "at_least_as_fast": bool(mean_ms <= t_mean)}
+                t_mean, t_min = timed(theirs)
+                rows[name] = {"ms": ms(mean_ms), "ms_min": ms(min_ms), **roofline(nb, mean_ms, min_ms),
+                              "ms_torch": ms(t_mean), "ms_torch_min": ms(t_min),
+                              "speedup_vs_torch": round(t_mean / mean_ms, 3), "at_least_as_fast": bool(mean_ms <= t_mean)}
                 print(f"gs {shape} {tname} {name}: {rows[name]}", flush=True)
             if args.check:
                 ours_l = sf.global_to_local(gsmap, glo, sign=sign, out=out_l)
@@ -154,27 +141,22 @@ def main():
                     sf.assemble(gsmap, y, sign=sign, out=out_g)
 
                 sf.global_to_local(gsmap, glo, sign=sign, out=out_l)
-                o_mean, o_min, g1 = grouped_ms(torch, operator, args.reps)
-                a_mean, a_min, g2 = grouped_ms(torch, assembled, args.reps)
-                replayed = replayed and g1 and g2
-                rows["helmholtz"] = {"ms_operator": round(o_mean, 5), "ms_operator_min": round(o_min, 5),
-                                     "ms_assembled": round(a_mean, 5), "ms_assembled_min": round(a_min, 5),
+                o_mean, o_min = timed(operator)
+                a_mean, a_min = timed(assembled)
+                rows["helmholtz"] = {"ms_operator": ms(o_mean), "ms_operator_min": ms(o_min),
+                                     "ms_assembled": ms(a_mean), "ms_assembled_min": ms(a_min),
                                      "assembled_over_operator": round(a_mean / o_mean, 3)}
                 print(f"gs {shape} {tname} helmholtz nq {nq}: {rows['helmholtz']}", flush=True)
                 del b, d, g, w, y
             mesh[tname] = rows
             del loc, glo, out_l, out_g, t_l, t_g, tmp, work, sign
-            torch.cuda.empty_cache()
+            s.free()
         res["gs"][shape] = mesh
         del gsmap, l2g, idx64
-        torch.cuda.empty_cache()
-    res["hip_graph_replay"] = replayed
-    line = json.dumps(res)
-    print(line)
-    if args.json:
-        with open(args.json, "w") as fh:
-            fh.write(line + "\n")
+        s.free()
+    s.emit(res)
+    return 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

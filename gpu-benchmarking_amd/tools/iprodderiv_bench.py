@@ -14,20 +14,10 @@ absolute values of every operand (formed on the device): <= 1 says the two agree
     python3 gpu-benchmarking_amd/tools/iprodderiv_bench.py [--chain] [--check] [--json FILE] [--hex 4,6,8]
                                                            [--quad 8,12,16] [--f32]
 """
-import argparse
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from bench import HBM_PEAK_GBS, grouped_ms  # noqa: E402  (the protocol of bench.py extras())
-
-
-def _orders(s):
-    return [int(x) for x in s.split(",") if x]
+import opbench
+from opbench import chain_row, fracs, gdof_s, ms, roofline
 
 
 def make_chain(torch, sf, dim, nq, nelmt, bs, ds, df, w, f, out):
@@ -62,105 +52,65 @@ def make_chain(torch, sf, dim, nq, nelmt, bs, ds, df, w, f, out):
     return chain
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--nelmt3", type=int, default=1 << 18)
-    ap.add_argument("--nelmt2", type=int, default=1 << 20)
-    ap.add_argument("--reps", type=int, default=40)
-    ap.add_argument("--hex", type=_orders, default=[4, 6, 8])
-    ap.add_argument("--quad", type=_orders, default=[8, 12, 16])
-    ap.add_argument("--f32", action="store_true", help="fp32 as well")
-    ap.add_argument("--chain", action="store_true", help="also time torch ops + iproduct on the same buffers")
-    ap.add_argument("--check", action="store_true", help="print max |fused - chain| / (2 gamma_N absref) (needs --chain)")
-    ap.add_argument("--variant", default="auto", help="fp64 route: auto, wave or generic")
-    ap.add_argument("--json", default=None, help="write the result here as well")
-    args = ap.parse_args()
+def case(s, c):
+    torch, args, dim, nelmt, nq = s.torch, s.args, c.dim, c.nelmt, c.nq
+    bs, ds, kw = c.bs, c.ds, c.kw
+    f = c.fill(dim * nelmt * c.npt, 1).view(dim, nelmt * c.npt)
+    df = c.fill(nelmt * dim * dim * c.npt, 5)
+    w = c.fill(nelmt * c.npt, 2)
+    x = c.fill(nelmt * c.nmt, 6)
+    ipd, phys, ipr = c.op("iprodderiv"), c.op("physderiv"), c.op("iproduct")
+    o = torch.empty(nelmt * c.nmt, dtype=c.dtype, device=s.dev)
+    nbytes = c.nbytes("iprodderiv")
+    mean_ms, min_ms = s.timed(lambda: ipd(c.ext, *bs, *ds, df, w, f, out=o, **kw))
+    fused = o.clone() if args.check else None
+    r_mean, r_min = s.timed(lambda: ipd(c.ext, *bs, *ds, None, None, f, out=o, **kw))
+    row = {"t_iprodderiv": ms(mean_ms), "t_iprodderiv_min": ms(min_ms), "gdof_s": gdof_s(nelmt * c.nmt, mean_ms),
+           **roofline(nbytes, mean_ms, min_ms), "t_bothnull": ms(r_mean), "t_bothnull_min": ms(r_min),
+           **fracs("bothnull", c.nbytes("iprodderiv", df=False, w=False), r_mean, r_min)}
+    po = phys(c.ext, *bs, *ds, df, x)
+    p_mean, p_min = s.timed(lambda: phys(c.ext, *bs, *ds, df, x, out=po))
+    i_mean, i_min = s.timed(lambda: ipr(c.ext, *bs, f[0], out=o))
+    row.update({"t_physderiv": ms(p_mean), **fracs("physderiv", c.nbytes("physderiv"), p_mean, p_min),
+                "t_iproduct": ms(i_mean), **fracs("iproduct", c.nbytes("iproduct"), i_mean, i_min)})
+    del po, x
+    if args.chain:
+        o2 = torch.empty_like(o)
+        chain = make_chain(torch, s.sf, dim, nq, nelmt, bs, ds, df, w, f, o2)
+        row.update(chain_row(mean_ms, *s.timed(chain)))
+        del chain
+        if args.check:
+            s.free()
+            diff = (fused - o2).abs_()
+            for t in (bs[0], ds[0], f, df, w):                              # the operands are not needed again
+                t.abs_()
+            absref = ipd(c.ext, *bs, *ds, df, w, f, out=o, **kw)
+            n_ops = dim * nq + nq + 2 * dim
+            u = 2.0 ** (-53 if c.dtype == torch.float64 else -24)
+            gam = n_ops * u / (1 - n_ops * u)
+            excess = float((diff / (2 * gam * absref)).max())
+            row.update({"chain_excess": round(excess, 4), "chain_agrees": excess <= 1.0,
+                        "chain_rel_diff": float(diff.max() / fused.abs().max())})
+    print(f"iprodderiv {c.label}: {row}", flush=True)
+    return row
 
-    import torch
-    import __graft_entry__ as ge
-    sf = ge.load_package()
-    dev = torch.device("cuda:0")
+
+def options(argv=None):
+    ap = opbench.parser(__doc__, chain="also time torch ops + iproduct on the same buffers",
+                        check="print max |fused - chain| / (2 gamma_N absref) (needs --chain)")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = options(argv)
+    s = opbench.Session(args)
     res = {"protocol": f"{args.nelmt3} (3D) / {args.nelmt2} (2D) elements, {args.reps} groups of 8 back-to-back launches "
                        "(bench.py grouped_ms); frac = algorithmic bytes / time / 8 TB/s",
-           "device": sf.device_info()["name"], "iprodderiv": {}}
-    replayed = True
-    dtypes = [("f64", torch.float64)] + ([("f32", torch.float32)] if args.f32 else [])
-    for tname, dtype in dtypes:
-        size = torch.finfo(dtype).bits // 8
-        kw = {"variant": args.variant} if dtype == torch.float64 else {}
-        for dim, orders, nelmt in ((3, args.hex, args.nelmt3), (2, args.quad, args.nelmt2)):
-            for nq in orders:
-                nm, ext = nq - 1, (nq,) * dim
-                nmt, npt = nm ** dim, nq ** dim
-                b = sf.fill_random(nm * nq, 3, dtype=dtype, device=dev)
-                d = sf.fill_random(nq * nq, 4, dtype=dtype, device=dev)
-                bs, ds = (b,) * dim, (d,) * dim
-                f = sf.fill_random(dim * nelmt * npt, 1, dtype=dtype, device=dev).view(dim, nelmt * npt)
-                df = sf.fill_random(nelmt * dim * dim * npt, 5, dtype=dtype, device=dev)
-                w = sf.fill_random(nelmt * npt, 2, dtype=dtype, device=dev)
-                x = sf.fill_random(nelmt * nmt, 6, dtype=dtype, device=dev)
-                ipd, phys, ipr = ((sf.iprodderiv_hex, sf.physderiv_hex, sf.iproduct_hex) if dim == 3 else
-                                  (sf.iprodderiv_quad, sf.physderiv_quad, sf.iproduct_quad))
-                o = torch.empty(nelmt * nmt, dtype=dtype, device=dev)
-
-                def frac(nb, ms):
-                    return round(nb / ms * 1e-6 / HBM_PEAK_GBS, 4)
-
-                nbytes = size * nelmt * ((dim * dim + dim + 1) * npt + nmt)
-                rbytes = size * nelmt * (dim * npt + nmt)
-                mean_ms, min_ms, g0 = grouped_ms(torch, lambda: ipd(ext, *bs, *ds, df, w, f, out=o, **kw), args.reps)
-                fused = o.clone() if args.check else None
-                r_mean, r_min, g1 = grouped_ms(torch, lambda: ipd(ext, *bs, *ds, None, None, f, out=o, **kw), args.reps)
-                replayed = replayed and g0 and g1
-                row = {"t_iprodderiv": round(mean_ms, 5), "t_iprodderiv_min": round(min_ms, 5),
-                       "gdof_s": round(nelmt * nmt / mean_ms * 1e-6, 2), "gb_s": round(nbytes / mean_ms * 1e-6, 1),
-                       "frac_mean": frac(nbytes, mean_ms), "frac_min": frac(nbytes, min_ms),
-                       "t_bothnull": round(r_mean, 5), "t_bothnull_min": round(r_min, 5),
-                       "bothnull_frac_mean": frac(rbytes, r_mean), "bothnull_frac_min": frac(rbytes, r_min)}
-                po = phys(ext, *bs, *ds, df, x)
-                p_mean, p_min, g2 = grouped_ms(torch, lambda: phys(ext, *bs, *ds, df, x, out=po), args.reps)
-                i_mean, i_min, g3 = grouped_ms(torch, lambda: ipr(ext, *bs, f[0], out=o), args.reps)
-                replayed = replayed and g2 and g3
-                pb = size * nelmt * (nmt + (dim * dim + dim) * npt)
-                ib = size * nelmt * (nmt + npt)
-                row.update({"t_physderiv": round(p_mean, 5), "physderiv_frac_mean": frac(pb, p_mean),
-                            "physderiv_frac_min": frac(pb, p_min), "t_iproduct": round(i_mean, 5),
-                            "iproduct_frac_mean": frac(ib, i_mean), "iproduct_frac_min": frac(ib, i_min)})
-                del po, x
-                if args.chain:
-                    o2 = torch.empty_like(o)
-                    chain = make_chain(torch, sf, dim, nq, nelmt, bs, ds, df, w, f, o2)
-                    c_mean, c_min, g4 = grouped_ms(torch, chain, args.reps)
-                    replayed = replayed and g4
-                    row.update({"t_chain": round(c_mean, 5), "t_chain_min": round(c_min, 5),
-                                "speedup_vs_chain": round(c_mean / mean_ms, 3), "not_slower_than_chain": mean_ms <= c_mean})
-                    del chain
-                    if args.check:
-                        torch.cuda.empty_cache()
-                        diff = (fused - o2).abs_()
-                        for t in (b, d, f, df, w):                              # the operands are not needed again
-                            t.abs_()
-                        absref = ipd(ext, *bs, *ds, df, w, f, out=o, **kw)
-                        n_ops = dim * nq + nq + 2 * dim
-                        u = 2.0 ** (-53 if dtype == torch.float64 else -24)
-                        gam = n_ops * u / (1 - n_ops * u)
-                        excess = float((diff / (2 * gam * absref)).max())
-                        row.update({"chain_excess": round(excess, 4), "chain_agrees": excess <= 1.0,
-                                    "chain_rel_diff": float(diff.max() / fused.abs().max())})
-                        del diff
-                    del o2
-                key = f"{'hex' if dim == 3 else 'quad'}_{tname}"
-                res["iprodderiv"].setdefault(key, {})[str(nq)] = row
-                print(f"iprodderiv {dim}D {tname} nq {nq:2d}: {row}", flush=True)
-                del f, df, w, o, fused
-                torch.cuda.empty_cache()
-    res["hip_graph_replay"] = replayed
-    line = json.dumps(res)
-    print(line)
-    if args.json:
-        with open(args.json, "w") as fh:
-            fh.write(line + "\n")
+           "device": s.device_name, "iprodderiv": {}}
+    s.collect(res["iprodderiv"], lambda c: case(s, c))
+    s.emit(res)
+    return 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

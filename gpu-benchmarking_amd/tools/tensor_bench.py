@@ -14,17 +14,11 @@ AUTO at nq 8 / 16 (the flagship's tuned rows), with the compile seconds of each 
     python3 gpu-benchmarking_amd/tools/tensor_bench.py [--chain] [--check] [--f32] [--bwdtrans] [--json FILE]
                                                        [--hex 8>8,4>6,6>9,9>6:t] [--quad 8>8,16>16,10>15] [--repeats 2]
 """
-import argparse
-import json
-import os
 import re
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from bench import HBM_PEAK_GBS, grouped_ms  # noqa: E402  (the protocol of bench.py extras())
+import opbench
+from opbench import chain_row, frac, ms, roofline, scalars
 
 
 def _pairs(s):
@@ -59,48 +53,35 @@ def make_chain(torch, dim, ni, no, trans, nelmt, mats, x, out):
     return chain
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--nelmt3", type=int, default=1 << 18)
-    ap.add_argument("--nelmt2", type=int, default=1 << 20)
-    ap.add_argument("--reps", type=int, default=40)
-    ap.add_argument("--repeats", type=int, default=2)
-    ap.add_argument("--hex", type=_pairs, default=_pairs("8>8,4>6,6>9,9>6:t"))
-    ap.add_argument("--quad", type=_pairs, default=_pairs("8>8,16>16,10>15"))
-    ap.add_argument("--f32", action="store_true", help="fp32 as well")
-    ap.add_argument("--chain", action="store_true", help="also time one torch.matmul per direction on the same buffers")
-    ap.add_argument("--check", action="store_true", help="print max |fused - chain| / max |fused| (needs --chain)")
+def options(argv=None):
+    ap = opbench.parser(__doc__, hex=(_pairs, _pairs("8>8,4>6,6>9,9>6:t")), quad=(_pairs, _pairs("8>8,16>16,10>15")),
+                        repeats=(2, None), chain="also time one torch.matmul per direction on the same buffers",
+                        check="print max |fused - chain| / max |fused| (needs --chain)", variant="auto, wave or generic")
     ap.add_argument("--bwdtrans", action="store_true", help="the specialised (7>8)^3 / (15>16)^2 beside sf_bwdtrans_* AUTO")
-    ap.add_argument("--variant", default="auto", help="auto, wave or generic")
-    ap.add_argument("--json", default=None, help="write the result here as well")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
 
-    import torch
-    import __graft_entry__ as ge
-    sf = ge.load_package()
-    dev = torch.device("cuda:0")
+
+def main(argv=None):
+    args = options(argv)
+    s = opbench.Session(args)
+    torch, sf, dev, timed = s.torch, s.sf, s.dev, s.timed
     res = {"protocol": f"{args.nelmt3} (3D) / {args.nelmt2} (2D) elements, {args.repeats} repeats of {args.reps} groups of 8 "
                        "back-to-back launches (bench.py grouped_ms); frac = algorithmic bytes / time / 8 TB/s",
-           "device": sf.device_info()["name"], "tensor": {}}
-    replayed = True
+           "device": s.device_name, "tensor": {}}
     gen = torch.Generator(device=dev).manual_seed(1)
-    dtypes = [("f64", torch.float64)] + ([("f32", torch.float32)] if args.f32 else [])
 
-    def timed(call):
-        nonlocal replayed
-        mean_ms, min_ms, g = grouped_ms(torch, call, args.reps)
-        replayed = replayed and g
-        return mean_ms, min_ms
+    def rand(n, dtype):
+        return 2 * torch.rand(n, dtype=dtype, device=dev, generator=gen) - 1
 
-    for tname, dtype in dtypes:
-        size = torch.finfo(dtype).bits // 8
+    for tname, dtype, size in s.dtypes():
         for dim, pairs, nelmt in ((3, args.hex, args.nelmt3), (2, args.quad, args.nelmt2)):
-            fn = sf.tensor_hex if dim == 3 else sf.tensor_quad
+            shape = "hex" if dim == 3 else "quad"
+            fn = getattr(sf, f"tensor_{shape}")
             for ni, no, trans in pairs:
-                mats = [2 * torch.rand(ni * no, dtype=dtype, device=dev, generator=gen) - 1 for _ in range(dim)]
-                x = 2 * torch.rand(nelmt * ni ** dim, dtype=dtype, device=dev, generator=gen) - 1
+                mats = [rand(ni * no, dtype) for _ in range(dim)]
+                x = rand(nelmt * ni ** dim, dtype)
                 out = fn((ni,) * dim, (no,) * dim, *mats, x, trans=trans, variant=args.variant)
-                nbytes = size * nelmt * (ni ** dim + no ** dim)
+                nbytes = size * nelmt * scalars("tensor", dim, ni=ni, no=no)
                 row = {"repeats": []}
                 chain = out2 = None
                 if args.chain:
@@ -109,60 +90,49 @@ def main():
                 for _ in range(args.repeats):
                     mean_ms, min_ms = timed(lambda: fn((ni,) * dim, (no,) * dim, *mats, x, trans=trans, out=out,
                                                        variant=args.variant))
-                    rep = {"t_tensor": round(mean_ms, 5), "t_tensor_min": round(min_ms, 5),
-                           "gb_s": round(nbytes / mean_ms * 1e-6, 1),
-                           "frac_mean": round(nbytes / mean_ms * 1e-6 / HBM_PEAK_GBS, 4),
-                           "frac_min": round(nbytes / min_ms * 1e-6 / HBM_PEAK_GBS, 4)}
+                    rep = {"t_tensor": ms(mean_ms), "t_tensor_min": ms(min_ms), **roofline(nbytes, mean_ms, min_ms)}
                     if chain is not None:
-                        c_mean, c_min = timed(chain)
-                        rep.update({"t_chain": round(c_mean, 5), "t_chain_min": round(c_min, 5),
-                                    "speedup_vs_chain": round(c_mean / mean_ms, 3), "not_slower_than_chain": mean_ms <= c_mean})
+                        rep.update(chain_row(mean_ms, *timed(chain)))
                     row["repeats"].append(rep)
                 if chain is not None:
                     row["not_slower_than_chain"] = all(r["not_slower_than_chain"] for r in row["repeats"])
                     if args.check:
                         row["chain_rel_diff"] = float((out - out2).abs().max() / out.abs().max())
                 label = f"{ni}>{no}" + (":t" if trans else "")
-                res["tensor"].setdefault(f"{'hex' if dim == 3 else 'quad'}_{tname}", {})[label] = row
+                res["tensor"].setdefault(f"{shape}_{tname}", {})[label] = row
                 print(f"tensor {dim}D {tname} {label}: {row}", flush=True)
                 del x, out, out2, chain
-                torch.cuda.empty_cache()
+                s.free()
 
         if args.bwdtrans:
             for dim, nq, nelmt in ((3, 8, args.nelmt3), (2, 16, args.nelmt2)):
+                shape = "hex" if dim == 3 else "quad"
                 ni, no = (nq - 1,) * dim, (nq,) * dim
                 rc = sf.specialise_tensor(ni, no, False, dtype)
                 m = re.search(r"compile #\d+, ([\d.]+) s", sf.specialise_log())
                 row = {"specialise_rc": rc, "compile_s": float(m.group(1)) if m else None, "repeats": []}
-                b = 2 * torch.rand((nq - 1) * nq, dtype=dtype, device=dev, generator=gen) - 1
-                x = 2 * torch.rand(nelmt * (nq - 1) ** dim, dtype=dtype, device=dev, generator=gen) - 1
-                fn = sf.tensor_hex if dim == 3 else sf.tensor_quad
-                bwd = sf.bwdtrans_hex if dim == 3 else sf.bwdtrans_quad
+                b = rand((nq - 1) * nq, dtype)
+                x = rand(nelmt * (nq - 1) ** dim, dtype)
+                fn, bwd = getattr(sf, f"tensor_{shape}"), getattr(sf, f"bwdtrans_{shape}")
                 out = fn(ni, no, *(b,) * dim, x)
                 out2 = bwd(no, *(b,) * dim, x)
                 row["launched_specialisation"] = sf.tensor_specialisation_state(ni, no, False, dtype)[1] > 0
                 row["equal_values"] = bool((out == out2).all())
-                nbytes = size * nelmt * ((nq - 1) ** dim + nq ** dim)
+                nbytes = size * nelmt * scalars("bwdtrans", dim, nq)
                 for _ in range(args.repeats):
                     t_mean, t_min = timed(lambda: fn(ni, no, *(b,) * dim, x, out=out))
                     b_mean, b_min = timed(lambda: bwd(no, *(b,) * dim, x, out=out2))
-                    row["repeats"].append({"t_tensor": round(t_mean, 5), "t_bwdtrans": round(b_mean, 5),
-                                           "frac_tensor": round(nbytes / t_mean * 1e-6 / HBM_PEAK_GBS, 4),
-                                           "frac_bwdtrans": round(nbytes / b_mean * 1e-6 / HBM_PEAK_GBS, 4),
+                    row["repeats"].append({"t_tensor": ms(t_mean), "t_bwdtrans": ms(b_mean),
+                                           "frac_tensor": frac(nbytes, t_mean), "frac_bwdtrans": frac(nbytes, b_mean),
                                            "bwdtrans_ahead_by": round(t_mean / b_mean, 3)})
-                label = f"{'hex' if dim == 3 else 'quad'}_{tname}_{nq - 1}>{nq}"
-                res.setdefault("specialised_vs_bwdtrans", {})[label] = row
+                res.setdefault("specialised_vs_bwdtrans", {})[f"{shape}_{tname}_{nq - 1}>{nq}"] = row
                 print(f"specialised tensor vs bwdtrans {dim}D {tname} {nq - 1}>{nq}: {row}", flush=True)
                 del x, out, out2
-                torch.cuda.empty_cache()
+                s.free()
 
-    res["hip_graph_replay"] = replayed
-    line = json.dumps(res)
-    print(line)
-    if args.json:
-        with open(args.json, "w") as fh:
-            fh.write(line + "\n")
+    s.emit(res)
+    return 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
