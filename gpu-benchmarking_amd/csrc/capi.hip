@@ -790,18 +790,49 @@ const char *sf_variant_name(int variant)
     return (variant >= 0 && variant < SF_NUM_VARIANTS) ? names[variant] : "?";
 }
 
-int sf_bwdtrans_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
-                                const double *basis1, const double *basis2, const double *in, double *wsp, double *out,
-                                void *stream)
-{
-    return bwdtrans<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, wsp, out, stream);
-}
+// ---- the operator entry points ---------------------------------------------------------------------------------------
+// Every operator family has six: sf_<stem>_{hex,quad}_f64_variant (the variant first), sf_<stem>_{hex,quad}_f64 and
+// sf_<stem>_{hex,quad}_f32 (both SF_VARIANT_AUTO).  All six forward to the family's one function above, family<DIM, T>,
+// with the per-direction operands in brace groups.  A family spells its parameter list and its forwarding call once, in
+// a macro SF_<FAMILY>(name, D, T, V) -- D: 3 or 2, T: double or float, V: VAR or AUTO -- and SF_ENTRIES stamps the six
+// definitions out of it.  include/sumfact.h declares every one of them by hand: a definition whose type differs from
+// its declaration does not compile.
+// To add a family: write family<DIM, T> above, its macro here from the words below, and one SF_ENTRIES line.
+//   SF_P<D>(q, n)   one parameter `q *n<d>` per direction      SF_A<D>(n)   the group {n0, n1, n2} / {n0, n1, nullptr}
+//   SF_NQ_P<D>      the extents as parameters                  SF_NQ_A<D>   {nq0, nq1, nq2} / {nq0, nq1, 0u}
+//   SF_VP_<V>       `int variant,` / nothing                   SF_VA_<V>    variant / SF_VARIANT_AUTO
+#define SF_P3(q, n) q *n##0, q *n##1, q *n##2
+#define SF_P2(q, n) q *n##0, q *n##1
+#define SF_A3(n) {n##0, n##1, n##2}
+#define SF_A2(n) {n##0, n##1, nullptr}
+#define SF_NQ_P3 unsigned nq0, unsigned nq1, unsigned nq2
+#define SF_NQ_P2 unsigned nq0, unsigned nq1
+#define SF_NQ_A3 {nq0, nq1, nq2}
+#define SF_NQ_A2 {nq0, nq1, 0u}
+#define SF_VP_VAR int variant,
+#define SF_VP_AUTO
+#define SF_VA_VAR variant
+#define SF_VA_AUTO SF_VARIANT_AUTO
+#define SF_ENTRIES(FAMILY, stem)                                                                                       \
+    FAMILY(sf_##stem##_hex_f64_variant, 3, double, VAR)                                                                \
+    FAMILY(sf_##stem##_hex_f64, 3, double, AUTO)                                                                       \
+    FAMILY(sf_##stem##_quad_f64_variant, 2, double, VAR)                                                               \
+    FAMILY(sf_##stem##_quad_f64, 2, double, AUTO)                                                                      \
+    FAMILY(sf_##stem##_hex_f32, 3, float, AUTO)                                                                        \
+    FAMILY(sf_##stem##_quad_f32, 2, float, AUTO)
 
-int sf_bwdtrans_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0, const double *basis1,
-                        const double *basis2, const double *in, double *out, void *stream)
-{
-    return bwdtrans<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, nullptr, out, stream);
-}
+// ---- BwdTrans: the variant form alone takes the caller-owned workspace ---------------------------------------------
+#define SF_WSP_P_VAR(T) T *wsp,
+#define SF_WSP_P_AUTO(T)
+#define SF_WSP_A_VAR wsp
+#define SF_WSP_A_AUTO nullptr
+#define SF_BWDTRANS(name, D, T, V)                                                                                     \
+    int name(SF_VP_##V SF_NQ_P##D, size_t nelmt, SF_P##D(const T, basis), const T *in, SF_WSP_P_##V(T) T *out,         \
+             void *stream)                                                                                             \
+    {                                                                                                                  \
+        return bwdtrans<D, T>(SF_VA_##V, SF_NQ_A##D, nelmt, SF_A##D(basis), in, SF_WSP_A_##V, out, stream);            \
+    }
+SF_ENTRIES(SF_BWDTRANS, bwdtrans)
 
 // SF_VARIANT_MFMA4's leg of bwdtrans<3, double> with the output path named instead of chosen per order
 int sf_bwdtrans_hex_f64_mfma4(int direct, unsigned nq, size_t nelmt, const double *basis0, const double *basis1,
@@ -814,18 +845,6 @@ int sf_bwdtrans_hex_f64_mfma4(int direct, unsigned nq, size_t nelmt, const doubl
         return SF_EALIGN;
     const HexArgs a{basis0, basis1, basis2, in, nullptr, out, (uint64_t)nelmt};
     return launch_hex_mfma4_path(direct != 0, nq, a, (hipStream_t)stream);
-}
-
-int sf_bwdtrans_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
-                                 const double *basis1, const double *in, double *wsp, double *out, void *stream)
-{
-    return bwdtrans<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, wsp, out, stream);
-}
-
-int sf_bwdtrans_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
-                         const double *in, double *out, void *stream)
-{
-    return bwdtrans<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, nullptr, out, stream);
 }
 
 int sf_bwdtrans_hex_f64_interleaved(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
@@ -852,424 +871,82 @@ int sf_interleave64_f64(const double *src, double *dst, size_t nelmt, size_t n, 
     return launch_interleave64(src, dst, nelmt, n, inverse, (hipStream_t)stream);
 }
 
-// ---- fp32 (T = float) ------------------------------------------------------------------------------
-int sf_bwdtrans_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
-                        const float *basis2, const float *in, float *out, void *stream)
-{
-    return bwdtrans<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, nullptr, out, stream);
-}
-
-int sf_bwdtrans_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1, const float *in,
-                         float *out, void *stream)
-{
-    return bwdtrans<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, nullptr, out, stream);
-}
-
 // ---- IProductWRTBase, the transpose of BwdTrans ----------------------------------------------------------------------
-int sf_iproduct_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
-                                const double *basis0, const double *basis1, const double *basis2, const double *in,
-                                double *out, void *stream)
-{
-    return iprod<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, out, stream);
-}
-
-int sf_iproduct_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
-                        const double *basis1, const double *basis2, const double *in, double *out, void *stream)
-{
-    return iprod<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, out, stream);
-}
-
-int sf_iproduct_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
-                                 const double *basis1, const double *in, double *out, void *stream)
-{
-    return iprod<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, out, stream);
-}
-
-int sf_iproduct_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
-                         const double *in, double *out, void *stream)
-{
-    return iprod<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, out, stream);
-}
-
-int sf_iproduct_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
-                        const float *basis1, const float *basis2, const float *in, float *out, void *stream)
-{
-    return iprod<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, in, out,
-                                     stream);
-}
-
-int sf_iproduct_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
-                         const float *in, float *out, void *stream)
-{
-    return iprod<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, in, out,
-                                      stream);
-}
+#define SF_IPRODUCT(name, D, T, V)                                                                                     \
+    int name(SF_VP_##V SF_NQ_P##D, size_t nelmt, SF_P##D(const T, basis), const T *in, T *out, void *stream)           \
+    {                                                                                                                  \
+        return iprod<D, T>(SF_VA_##V, SF_NQ_A##D, nelmt, SF_A##D(basis), in, out, stream);                             \
+    }
+SF_ENTRIES(SF_IPRODUCT, iproduct)
 
 // ---- the fused mass operator: BwdTrans, pointwise weight, IProductWRTBase in one kernel -------------------------------
-int sf_mass_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
-                            const double *basis1, const double *basis2, const double *w, const double *in, double *out,
-                            void *stream)
-{
-    return mass<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, w, in, out, stream);
-}
-
-int sf_mass_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0, const double *basis1,
-                    const double *basis2, const double *w, const double *in, double *out, void *stream)
-{
-    return mass<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, w, in, out, stream);
-}
-
-int sf_mass_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
-                             const double *basis1, const double *w, const double *in, double *out, void *stream)
-{
-    return mass<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, w, in, out, stream);
-}
-
-int sf_mass_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
-                     const double *w, const double *in, double *out, void *stream)
-{
-    return mass<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, w, in, out, stream);
-}
-
-int sf_mass_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
-                    const float *basis2, const float *w, const float *in, float *out, void *stream)
-{
-    return mass<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, w, in, out,
-                                           stream);
-}
-
-int sf_mass_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1, const float *w,
-                     const float *in, float *out, void *stream)
-{
-    return mass<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, w, in, out,
-                                            stream);
-}
+#define SF_MASS(name, D, T, V)                                                                                         \
+    int name(SF_VP_##V SF_NQ_P##D, size_t nelmt, SF_P##D(const T, basis), const T *w, const T *in, T *out,             \
+             void *stream)                                                                                             \
+    {                                                                                                                  \
+        return mass<D, T>(SF_VA_##V, SF_NQ_A##D, nelmt, SF_A##D(basis), w, in, out, stream);                           \
+    }
+SF_ENTRIES(SF_MASS, mass)
 
 // ---- the fused Helmholtz operator: BwdTrans, derivatives, metric, transposed derivatives, IProductWRTBase in one kernel -
-int sf_helmholtz_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
-                                 const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
-                                 const double *deriv2, const double *g, const double *w, double lambda, const double *in,
-                                 double *out, void *stream)
-{
-    return helmholtz<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
-                                         {deriv0, deriv1, deriv2}, g, w, lambda, in, out, stream);
-}
-
-int sf_helmholtz_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
-                         const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
-                         const double *deriv2, const double *g, const double *w, double lambda, const double *in,
-                         double *out, void *stream)
-{
-    return helmholtz<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
-                                         {deriv0, deriv1, deriv2}, g, w, lambda, in, out, stream);
-}
-
-int sf_helmholtz_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
-                                  const double *basis1, const double *deriv0, const double *deriv1, const double *g,
-                                  const double *w, double lambda, const double *in, double *out, void *stream)
-{
-    return helmholtz<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
-                                          {deriv0, deriv1, nullptr}, g, w, lambda, in, out, stream);
-}
-
-int sf_helmholtz_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
-                          const double *deriv0, const double *deriv1, const double *g, const double *w, double lambda,
-                          const double *in, double *out, void *stream)
-{
-    return helmholtz<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
-                                          {deriv0, deriv1, nullptr}, g, w, lambda, in, out, stream);
-}
-
-int sf_helmholtz_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
-                         const float *basis2, const float *deriv0, const float *deriv1, const float *deriv2,
-                         const float *g, const float *w, double lambda, const float *in, float *out, void *stream)
-{
-    return helmholtz<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
-                                                {deriv0, deriv1, deriv2}, g, w, lambda, in, out, stream);
-}
-
-int sf_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
-                          const float *deriv0, const float *deriv1, const float *g, const float *w, double lambda,
-                          const float *in, float *out, void *stream)
-{
-    return helmholtz<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
-                                                 {deriv0, deriv1, nullptr}, g, w, lambda, in, out, stream);
-}
+#define SF_HELMHOLTZ(name, D, T, V)                                                                                    \
+    int name(SF_VP_##V SF_NQ_P##D, size_t nelmt, SF_P##D(const T, basis), SF_P##D(const T, deriv), const T *g,         \
+             const T *w, double lambda, const T *in, T *out, void *stream)                                             \
+    {                                                                                                                  \
+        return helmholtz<D, T>(SF_VA_##V, SF_NQ_A##D, nelmt, SF_A##D(basis), SF_A##D(deriv), g, w, lambda, in, out,    \
+                               stream);                                                                                \
+    }
+SF_ENTRIES(SF_HELMHOLTZ, helmholtz)
 
 // ---- the fused Helmholtz operator on affine elements: a constant metric per element, shared quadrature weights ---------
-int sf_affine_helmholtz_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
-                                        const double *basis0, const double *basis1, const double *basis2,
-                                        const double *deriv0, const double *deriv1, const double *deriv2,
-                                        const double *qw0, const double *qw1, const double *qw2, const double *ge,
-                                        const double *je, double lambda, const double *in, double *out, void *stream)
-{
-    return affine<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
-                             {qw0, qw1, qw2}, ge, je, lambda, in, out, stream);
-}
-
-int sf_affine_helmholtz_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
-                                const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
-                                const double *deriv2, const double *qw0, const double *qw1, const double *qw2,
-                                const double *ge, const double *je, double lambda, const double *in, double *out,
-                                void *stream)
-{
-    return affine<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
-                             {deriv0, deriv1, deriv2}, {qw0, qw1, qw2}, ge, je, lambda, in, out, stream);
-}
-
-int sf_affine_helmholtz_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
-                                         const double *basis1, const double *deriv0, const double *deriv1,
-                                         const double *qw0, const double *qw1, const double *ge, const double *je,
-                                         double lambda, const double *in, double *out, void *stream)
-{
-    return affine<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
-                             {qw0, qw1, nullptr}, ge, je, lambda, in, out, stream);
-}
-
-int sf_affine_helmholtz_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
-                                 const double *deriv0, const double *deriv1, const double *qw0, const double *qw1,
-                                 const double *ge, const double *je, double lambda, const double *in, double *out,
-                                 void *stream)
-{
-    return affine<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
-                             {deriv0, deriv1, nullptr}, {qw0, qw1, nullptr}, ge, je, lambda, in, out, stream);
-}
-
-int sf_affine_helmholtz_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
-                                const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
-                                const float *deriv2, const float *qw0, const float *qw1, const float *qw2,
-                                const float *ge, const float *je, double lambda, const float *in, float *out,
-                                void *stream)
-{
-    return affine<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
-                            {deriv0, deriv1, deriv2}, {qw0, qw1, qw2}, ge, je, lambda, in, out, stream);
-}
-
-int sf_affine_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
-                                 const float *deriv0, const float *deriv1, const float *qw0, const float *qw1,
-                                 const float *ge, const float *je, double lambda, const float *in, float *out,
-                                 void *stream)
-{
-    return affine<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
-                            {deriv0, deriv1, nullptr}, {qw0, qw1, nullptr}, ge, je, lambda, in, out, stream);
-}
+#define SF_AFFINE_HELMHOLTZ(name, D, T, V)                                                                             \
+    int name(SF_VP_##V SF_NQ_P##D, size_t nelmt, SF_P##D(const T, basis), SF_P##D(const T, deriv),                     \
+             SF_P##D(const T, qw), const T *ge, const T *je, double lambda, const T *in, T *out, void *stream)         \
+    {                                                                                                                  \
+        return affine<D, T>(SF_VA_##V, SF_NQ_A##D, nelmt, SF_A##D(basis), SF_A##D(deriv), SF_A##D(qw), ge, je, lambda, \
+                            in, out, stream);                                                                          \
+    }
+SF_ENTRIES(SF_AFFINE_HELMHOLTZ, affine_helmholtz)
 
 // ---- BwdTrans fused with the physical-space gradient: d outputs, no point image in HBM ---------------------------------
-int sf_physderiv_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
-                                 const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
-                                 const double *deriv2, const double *df, const double *in, double *out0, double *out1,
-                                 double *out2, void *stream)
-{
-    return physderiv<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2}, df, in,
-                                {out0, out1, out2}, stream);
-}
-
-int sf_physderiv_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
-                         const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
-                         const double *deriv2, const double *df, const double *in, double *out0, double *out1,
-                         double *out2, void *stream)
-{
-    return physderiv<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
-                                {deriv0, deriv1, deriv2}, df, in, {out0, out1, out2}, stream);
-}
-
-int sf_physderiv_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
-                                  const double *basis1, const double *deriv0, const double *deriv1, const double *df,
-                                  const double *in, double *out0, double *out1, void *stream)
-{
-    return physderiv<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr}, df, in,
-                                {out0, out1, nullptr}, stream);
-}
-
-int sf_physderiv_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
-                          const double *deriv0, const double *deriv1, const double *df, const double *in, double *out0,
-                          double *out1, void *stream)
-{
-    return physderiv<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
-                                {deriv0, deriv1, nullptr}, df, in, {out0, out1, nullptr}, stream);
-}
-
-int sf_physderiv_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
-                         const float *basis2, const float *deriv0, const float *deriv1, const float *deriv2,
-                         const float *df, const float *in, float *out0, float *out1, float *out2, void *stream)
-{
-    return physderiv<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
-                               {deriv0, deriv1, deriv2}, df, in, {out0, out1, out2}, stream);
-}
-
-int sf_physderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
-                          const float *deriv0, const float *deriv1, const float *df, const float *in, float *out0,
-                          float *out1, void *stream)
-{
-    return physderiv<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
-                               {deriv0, deriv1, nullptr}, df, in, {out0, out1, nullptr}, stream);
-}
+#define SF_PHYSDERIV(name, D, T, V)                                                                                    \
+    int name(SF_VP_##V SF_NQ_P##D, size_t nelmt, SF_P##D(const T, basis), SF_P##D(const T, deriv), const T *df,        \
+             const T *in, SF_P##D(T, out), void *stream)                                                               \
+    {                                                                                                                  \
+        return physderiv<D, T>(SF_VA_##V, SF_NQ_A##D, nelmt, SF_A##D(basis), SF_A##D(deriv), df, in, SF_A##D(out),     \
+                               stream);                                                                                \
+    }
+SF_ENTRIES(SF_PHYSDERIV, physderiv)
 
 // ---- IProductWRTDerivBase: d inputs at the points, the weak divergence in modes -----------------------------------------
-int sf_iprodderiv_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
-                                  const double *basis0, const double *basis1, const double *basis2, const double *deriv0,
-                                  const double *deriv1, const double *deriv2, const double *df, const double *w,
-                                  const double *in0, const double *in1, const double *in2, double *out, void *stream)
-{
-    return iprodderiv<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2}, df, w,
-                                 {in0, in1, in2}, out, stream);
-}
-
-int sf_iprodderiv_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
-                          const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
-                          const double *deriv2, const double *df, const double *w, const double *in0, const double *in1,
-                          const double *in2, double *out, void *stream)
-{
-    return iprodderiv<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
-                                 {deriv0, deriv1, deriv2}, df, w, {in0, in1, in2}, out, stream);
-}
-
-int sf_iprodderiv_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
-                                   const double *basis1, const double *deriv0, const double *deriv1, const double *df,
-                                   const double *w, const double *in0, const double *in1, double *out, void *stream)
-{
-    return iprodderiv<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr}, df, w,
-                                 {in0, in1, nullptr}, out, stream);
-}
-
-int sf_iprodderiv_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
-                           const double *deriv0, const double *deriv1, const double *df, const double *w,
-                           const double *in0, const double *in1, double *out, void *stream)
-{
-    return iprodderiv<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
-                                 {deriv0, deriv1, nullptr}, df, w, {in0, in1, nullptr}, out, stream);
-}
-
-int sf_iprodderiv_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
-                          const float *basis2, const float *deriv0, const float *deriv1, const float *deriv2,
-                          const float *df, const float *w, const float *in0, const float *in1, const float *in2,
-                          float *out, void *stream)
-{
-    return iprodderiv<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
-                                {deriv0, deriv1, deriv2}, df, w, {in0, in1, in2}, out, stream);
-}
-
-int sf_iprodderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
-                           const float *deriv0, const float *deriv1, const float *df, const float *w, const float *in0,
-                           const float *in1, float *out, void *stream)
-{
-    return iprodderiv<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
-                                {deriv0, deriv1, nullptr}, df, w, {in0, in1, nullptr}, out, stream);
-}
+#define SF_IPRODDERIV(name, D, T, V)                                                                                   \
+    int name(SF_VP_##V SF_NQ_P##D, size_t nelmt, SF_P##D(const T, basis), SF_P##D(const T, deriv), const T *df,        \
+             const T *w, SF_P##D(const T, in), T *out, void *stream)                                                   \
+    {                                                                                                                  \
+        return iprodderiv<D, T>(SF_VA_##V, SF_NQ_A##D, nelmt, SF_A##D(basis), SF_A##D(deriv), df, w, SF_A##D(in), out, \
+                                stream);                                                                               \
+    }
+SF_ENTRIES(SF_IPRODDERIV, iprodderiv)
 
 // ---- the gradient on affine elements: d*d constants per element in the place of the planes --------------------------------
-int sf_aff_physderiv_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
-                                        const double *basis0, const double *basis1, const double *basis2,
-                                        const double *deriv0, const double *deriv1, const double *deriv2,
-                                        const double *dfe, const double *in, double *out0, double *out1, double *out2,
-                                        void *stream)
-{
-    return affine_physderiv<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
-                                       dfe, in, {out0, out1, out2}, stream);
-}
-
-int sf_aff_physderiv_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
-                                const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
-                                const double *deriv2, const double *dfe, const double *in, double *out0, double *out1,
-                                double *out2, void *stream)
-{
-    return affine_physderiv<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
-                                       {deriv0, deriv1, deriv2}, dfe, in, {out0, out1, out2}, stream);
-}
-
-int sf_aff_physderiv_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
-                                         const double *basis1, const double *deriv0, const double *deriv1,
-                                         const double *dfe, const double *in, double *out0, double *out1, void *stream)
-{
-    return affine_physderiv<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
-                                       dfe, in, {out0, out1, nullptr}, stream);
-}
-
-int sf_aff_physderiv_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
-                                 const double *deriv0, const double *deriv1, const double *dfe, const double *in,
-                                 double *out0, double *out1, void *stream)
-{
-    return affine_physderiv<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
-                                       {deriv0, deriv1, nullptr}, dfe, in, {out0, out1, nullptr}, stream);
-}
-
-int sf_aff_physderiv_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
-                                const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
-                                const float *deriv2, const float *dfe, const float *in, float *out0, float *out1,
-                                float *out2, void *stream)
-{
-    return affine_physderiv<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
-                                      {deriv0, deriv1, deriv2}, dfe, in, {out0, out1, out2}, stream);
-}
-
-int sf_aff_physderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
-                                 const float *deriv0, const float *deriv1, const float *dfe, const float *in, float *out0,
-                                 float *out1, void *stream)
-{
-    return affine_physderiv<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
-                                      {deriv0, deriv1, nullptr}, dfe, in, {out0, out1, nullptr}, stream);
-}
+#define SF_AFF_PHYSDERIV(name, D, T, V)                                                                                \
+    int name(SF_VP_##V SF_NQ_P##D, size_t nelmt, SF_P##D(const T, basis), SF_P##D(const T, deriv), const T *dfe,       \
+             const T *in, SF_P##D(T, out), void *stream)                                                               \
+    {                                                                                                                  \
+        return affine_physderiv<D, T>(SF_VA_##V, SF_NQ_A##D, nelmt, SF_A##D(basis), SF_A##D(deriv), dfe, in,           \
+                                      SF_A##D(out), stream);                                                           \
+    }
+SF_ENTRIES(SF_AFF_PHYSDERIV, aff_physderiv)
 
 // ---- the weak divergence on affine elements: the transpose of the gradient above, weighted by je (x) qw -------------------
-int sf_aff_iprodderiv_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt,
-                                         const double *basis0, const double *basis1, const double *basis2,
-                                         const double *deriv0, const double *deriv1, const double *deriv2,
-                                         const double *qw0, const double *qw1, const double *qw2, const double *dfe,
-                                         const double *je, const double *in0, const double *in1, const double *in2,
-                                         double *out, void *stream)
-{
-    return affine_iprodderiv<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
-                                        {qw0, qw1, qw2}, dfe, je, {in0, in1, in2}, out, stream);
-}
-
-int sf_aff_iprodderiv_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
-                                 const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
-                                 const double *deriv2, const double *qw0, const double *qw1, const double *qw2,
-                                 const double *dfe, const double *je, const double *in0, const double *in1,
-                                 const double *in2, double *out, void *stream)
-{
-    return affine_iprodderiv<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
-                                        {deriv0, deriv1, deriv2}, {qw0, qw1, qw2}, dfe, je, {in0, in1, in2}, out, stream);
-}
-
-int sf_aff_iprodderiv_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
-                                          const double *basis1, const double *deriv0, const double *deriv1,
-                                          const double *qw0, const double *qw1, const double *dfe, const double *je,
-                                          const double *in0, const double *in1, double *out, void *stream)
-{
-    return affine_iprodderiv<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
-                                        {qw0, qw1, nullptr}, dfe, je, {in0, in1, nullptr}, out, stream);
-}
-
-int sf_aff_iprodderiv_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
-                                  const double *deriv0, const double *deriv1, const double *qw0, const double *qw1,
-                                  const double *dfe, const double *je, const double *in0, const double *in1, double *out,
-                                  void *stream)
-{
-    return affine_iprodderiv<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
-                                        {deriv0, deriv1, nullptr}, {qw0, qw1, nullptr}, dfe, je, {in0, in1, nullptr}, out,
-                                        stream);
-}
-
-int sf_aff_iprodderiv_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0,
-                                 const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
-                                 const float *deriv2, const float *qw0, const float *qw1, const float *qw2,
-                                 const float *dfe, const float *je, const float *in0, const float *in1, const float *in2,
-                                 float *out, void *stream)
-{
-    return affine_iprodderiv<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2},
-                                       {deriv0, deriv1, deriv2}, {qw0, qw1, qw2}, dfe, je, {in0, in1, in2}, out, stream);
-}
-
-int sf_aff_iprodderiv_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
-                                  const float *deriv0, const float *deriv1, const float *qw0, const float *qw1,
-                                  const float *dfe, const float *je, const float *in0, const float *in1, float *out,
-                                  void *stream)
-{
-    return affine_iprodderiv<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr},
-                                       {deriv0, deriv1, nullptr}, {qw0, qw1, nullptr}, dfe, je, {in0, in1, nullptr}, out,
-                                       stream);
-}
+#define SF_AFF_IPRODDERIV(name, D, T, V)                                                                               \
+    int name(SF_VP_##V SF_NQ_P##D, size_t nelmt, SF_P##D(const T, basis), SF_P##D(const T, deriv),                     \
+             SF_P##D(const T, qw), const T *dfe, const T *je, SF_P##D(const T, in), T *out, void *stream)              \
+    {                                                                                                                  \
+        return affine_iprodderiv<D, T>(SF_VA_##V, SF_NQ_A##D, nelmt, SF_A##D(basis), SF_A##D(deriv), SF_A##D(qw), dfe, \
+                                       je, SF_A##D(in), out, stream);                                                  \
+    }
+SF_ENTRIES(SF_AFF_IPRODDERIV, aff_iprodderiv)
 
 // ---- the diagonal of the fused Helmholtz operator: Jacobi preconditioner, Chebyshev smoother, diagonal scaling ----------
 int sf_diag_tables_f64(unsigned nq, const double *basis, const double *deriv, double *tab, void *stream)
@@ -1282,310 +959,71 @@ int sf_diag_tables_f32(unsigned nq, const float *basis, const float *deriv, floa
     return diag_tables<float>(nq, basis, deriv, tab, stream);
 }
 
-int sf_diag_helmholtz_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *tab0,
-                                      const double *tab1, const double *tab2, const double *g, const double *w,
-                                      double lambda, double *out, void *stream)
-{
-    return diag<3, double>(variant, {nq0, nq1, nq2}, nelmt, {tab0, tab1, tab2}, g, w, lambda, out, stream);
-}
-
-int sf_diag_helmholtz_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *tab0, const double *tab1,
-                              const double *tab2, const double *g, const double *w, double lambda, double *out,
-                              void *stream)
-{
-    return diag<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {tab0, tab1, tab2}, g, w, lambda, out, stream);
-}
-
-int sf_diag_helmholtz_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *tab0,
-                                       const double *tab1, const double *g, const double *w, double lambda, double *out,
-                                       void *stream)
-{
-    return diag<2, double>(variant, {nq0, nq1, 0u}, nelmt, {tab0, tab1, nullptr}, g, w, lambda, out, stream);
-}
-
-int sf_diag_helmholtz_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *tab0, const double *tab1,
-                               const double *g, const double *w, double lambda, double *out, void *stream)
-{
-    return diag<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {tab0, tab1, nullptr}, g, w, lambda, out, stream);
-}
-
-int sf_diag_helmholtz_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *tab0, const float *tab1,
-                              const float *tab2, const float *g, const float *w, double lambda, float *out, void *stream)
-{
-    return diag<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {tab0, tab1, tab2}, g, w, lambda, out, stream);
-}
-
-int sf_diag_helmholtz_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *tab0, const float *tab1,
-                               const float *g, const float *w, double lambda, float *out, void *stream)
-{
-    return diag<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {tab0, tab1, nullptr}, g, w, lambda, out, stream);
-}
+#define SF_DIAG_HELMHOLTZ(name, D, T, V)                                                                               \
+    int name(SF_VP_##V SF_NQ_P##D, size_t nelmt, SF_P##D(const T, tab), const T *g, const T *w, double lambda, T *out, \
+             void *stream)                                                                                             \
+    {                                                                                                                  \
+        return diag<D, T>(SF_VA_##V, SF_NQ_A##D, nelmt, SF_A##D(tab), g, w, lambda, out, stream);                      \
+    }
+SF_ENTRIES(SF_DIAG_HELMHOLTZ, diag_helmholtz)
 
 // ---- the geometric factors df, w, g, detj from the modal coordinates of every element -----------------------------------
-int sf_geom_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
-                            const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
-                            const double *deriv2, const double *qw0, const double *qw1, const double *qw2, const double *x0,
-                            const double *x1, const double *x2, double *df, double *w, double *g, double *detj, void *stream)
-{
-    return geom<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
-                           {qw0, qw1, qw2}, {x0, x1, x2}, df, w, g, detj, stream);
-}
+#define SF_GEOM(name, D, T, V)                                                                                         \
+    int name(SF_VP_##V SF_NQ_P##D, size_t nelmt, SF_P##D(const T, basis), SF_P##D(const T, deriv),                     \
+             SF_P##D(const T, qw), SF_P##D(const T, x), T *df, T *w, T *g, T *detj, void *stream)                      \
+    {                                                                                                                  \
+        return geom<D, T>(SF_VA_##V, SF_NQ_A##D, nelmt, SF_A##D(basis), SF_A##D(deriv), SF_A##D(qw), SF_A##D(x), df,   \
+                          w, g, detj, stream);                                                                         \
+    }
+SF_ENTRIES(SF_GEOM, geom)
 
-int sf_geom_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0, const double *basis1,
-                    const double *basis2, const double *deriv0, const double *deriv1, const double *deriv2,
-                    const double *qw0, const double *qw1, const double *qw2, const double *x0, const double *x1,
-                    const double *x2, double *df, double *w, double *g, double *detj, void *stream)
-{
-    return geom<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
-                           {qw0, qw1, qw2}, {x0, x1, x2}, df, w, g, detj, stream);
-}
-
-int sf_geom_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
-                             const double *basis1, const double *deriv0, const double *deriv1, const double *qw0,
-                             const double *qw1, const double *x0, const double *x1, double *df, double *w, double *g,
-                             double *detj, void *stream)
-{
-    return geom<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
-                           {qw0, qw1, nullptr}, {x0, x1, nullptr}, df, w, g, detj, stream);
-}
-
-int sf_geom_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
-                     const double *deriv0, const double *deriv1, const double *qw0, const double *qw1, const double *x0,
-                     const double *x1, double *df, double *w, double *g, double *detj, void *stream)
-{
-    return geom<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
-                           {qw0, qw1, nullptr}, {x0, x1, nullptr}, df, w, g, detj, stream);
-}
-
-int sf_geom_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
-                    const float *basis2, const float *deriv0, const float *deriv1, const float *deriv2, const float *qw0,
-                    const float *qw1, const float *qw2, const float *x0, const float *x1, const float *x2, float *df,
-                    float *w, float *g, float *detj, void *stream)
-{
-    return geom<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
-                          {qw0, qw1, qw2}, {x0, x1, x2}, df, w, g, detj, stream);
-}
-
-int sf_geom_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
-                     const float *deriv0, const float *deriv1, const float *qw0, const float *qw1, const float *x0,
-                     const float *x1, float *df, float *w, float *g, float *detj, void *stream)
-{
-    return geom<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
-                          {qw0, qw1, nullptr}, {x0, x1, nullptr}, df, w, g, detj, stream);
-}
-
-int sf_geom_affine_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
-                           const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
-                           const double *deriv2, const double *x0, const double *x1, const double *x2, double *dfe,
-                           double *ge, double *je, void *stream)
-{
-    return geom_affine<3, double>({nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2}, {x0, x1, x2},
-                                  dfe, ge, je, stream);
-}
-
-int sf_geom_affine_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
-                            const double *deriv0, const double *deriv1, const double *x0, const double *x1, double *dfe,
-                            double *ge, double *je, void *stream)
-{
-    return geom_affine<2, double>({nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
-                                  {x0, x1, nullptr}, dfe, ge, je, stream);
-}
-
-int sf_geom_affine_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
-                           const float *basis2, const float *deriv0, const float *deriv1, const float *deriv2,
-                           const float *x0, const float *x1, const float *x2, float *dfe, float *ge, float *je,
-                           void *stream)
-{
-    return geom_affine<3, float>({nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2}, {x0, x1, x2},
-                                 dfe, ge, je, stream);
-}
-
-int sf_geom_affine_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
-                            const float *deriv0, const float *deriv1, const float *x0, const float *x1, float *dfe,
-                            float *ge, float *je, void *stream)
-{
-    return geom_affine<2, float>({nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
-                                 {x0, x1, nullptr}, dfe, ge, je, stream);
-}
+// the affine form has no variant: four entries
+#define SF_GEOM_AFFINE(name, D, T)                                                                                     \
+    int name(SF_NQ_P##D, size_t nelmt, SF_P##D(const T, basis), SF_P##D(const T, deriv), SF_P##D(const T, x), T *dfe,  \
+             T *ge, T *je, void *stream)                                                                               \
+    {                                                                                                                  \
+        return geom_affine<D, T>(SF_NQ_A##D, nelmt, SF_A##D(basis), SF_A##D(deriv), SF_A##D(x), dfe, ge, je, stream);  \
+    }
+SF_GEOM_AFFINE(sf_geom_affine_hex_f64, 3, double)
+SF_GEOM_AFFINE(sf_geom_affine_quad_f64, 2, double)
+SF_GEOM_AFFINE(sf_geom_affine_hex_f32, 3, float)
+SF_GEOM_AFFINE(sf_geom_affine_quad_f32, 2, float)
 
 // ---- the weak advection term out_a = B^T [w (c . grad) B in_a], nf = 1 or d fields ------------------------------------
-int sf_advect_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, unsigned nf,
-                              const double *basis0, const double *basis1, const double *basis2, const double *deriv0,
-                              const double *deriv1, const double *deriv2, const double *df, const double *w,
-                              const double *c0, const double *c1, const double *c2, const double *in0, const double *in1,
-                              const double *in2, double *out0, double *out1, double *out2, void *stream)
-{
-    return advect<3, double>(variant, {nq0, nq1, nq2}, nelmt, nf, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2}, df, w,
-                             {c0, c1, c2}, {in0, in1, in2}, {out0, out1, out2}, stream);
-}
-
-int sf_advect_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, unsigned nf, const double *basis0,
-                      const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
-                      const double *deriv2, const double *df, const double *w, const double *c0, const double *c1,
-                      const double *c2, const double *in0, const double *in1, const double *in2, double *out0,
-                      double *out1, double *out2, void *stream)
-{
-    return advect<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, nf, {basis0, basis1, basis2},
-                             {deriv0, deriv1, deriv2}, df, w, {c0, c1, c2}, {in0, in1, in2}, {out0, out1, out2}, stream);
-}
-
-int sf_advect_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf, const double *basis0,
-                               const double *basis1, const double *deriv0, const double *deriv1, const double *df,
-                               const double *w, const double *c0, const double *c1, const double *in0, const double *in1,
-                               double *out0, double *out1, void *stream)
-{
-    return advect<2, double>(variant, {nq0, nq1, 0u}, nelmt, nf, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr}, df, w,
-                             {c0, c1, nullptr}, {in0, in1, nullptr}, {out0, out1, nullptr}, stream);
-}
-
-int sf_advect_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf, const double *basis0, const double *basis1,
-                       const double *deriv0, const double *deriv1, const double *df, const double *w, const double *c0,
-                       const double *c1, const double *in0, const double *in1, double *out0, double *out1, void *stream)
-{
-    return advect<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, nf, {basis0, basis1, nullptr},
-                             {deriv0, deriv1, nullptr}, df, w, {c0, c1, nullptr}, {in0, in1, nullptr},
-                             {out0, out1, nullptr}, stream);
-}
-
-int sf_advect_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, unsigned nf, const float *basis0,
-                      const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
-                      const float *deriv2, const float *df, const float *w, const float *c0, const float *c1,
-                      const float *c2, const float *in0, const float *in1, const float *in2, float *out0, float *out1,
-                      float *out2, void *stream)
-{
-    return advect<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, nf, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
-                            df, w, {c0, c1, c2}, {in0, in1, in2}, {out0, out1, out2}, stream);
-}
-
-int sf_advect_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf, const float *basis0, const float *basis1,
-                       const float *deriv0, const float *deriv1, const float *df, const float *w, const float *c0,
-                       const float *c1, const float *in0, const float *in1, float *out0, float *out1, void *stream)
-{
-    return advect<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, nf, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
-                            df, w, {c0, c1, nullptr}, {in0, in1, nullptr}, {out0, out1, nullptr}, stream);
-}
+#define SF_ADVECT(name, D, T, V)                                                                                       \
+    int name(SF_VP_##V SF_NQ_P##D, size_t nelmt, unsigned nf, SF_P##D(const T, basis), SF_P##D(const T, deriv),        \
+             const T *df, const T *w, SF_P##D(const T, c), SF_P##D(const T, in), SF_P##D(T, out), void *stream)        \
+    {                                                                                                                  \
+        return advect<D, T>(SF_VA_##V, SF_NQ_A##D, nelmt, nf, SF_A##D(basis), SF_A##D(deriv), df, w, SF_A##D(c),       \
+                            SF_A##D(in), SF_A##D(out), stream);                                                        \
+    }
+SF_ENTRIES(SF_ADVECT, advect)
 
 // ---- the weak advection term on affine elements, out_a = B^T [(je q) (c . grad) B in_a], nf = 1 or d fields ---------
-int sf_aff_advect_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, unsigned nf,
-                                  const double *basis0, const double *basis1, const double *basis2,
-                                  const double *deriv0, const double *deriv1, const double *deriv2, const double *qw0,
-                                  const double *qw1, const double *qw2, const double *dfe, const double *je,
-                                  const double *c0, const double *c1, const double *c2, const double *in0,
-                                  const double *in1, const double *in2, double *out0, double *out1, double *out2,
-                                  void *stream)
-{
-    return affine_advect<3, double>(variant, {nq0, nq1, nq2}, nelmt, nf, {basis0, basis1, basis2},
-                                    {deriv0, deriv1, deriv2}, {qw0, qw1, qw2}, dfe, je, {c0, c1, c2}, {in0, in1, in2},
-                                    {out0, out1, out2}, stream);
-}
-
-int sf_aff_advect_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, unsigned nf, const double *basis0,
-                          const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
-                          const double *deriv2, const double *qw0, const double *qw1, const double *qw2,
-                          const double *dfe, const double *je, const double *c0, const double *c1, const double *c2,
-                          const double *in0, const double *in1, const double *in2, double *out0, double *out1,
-                          double *out2, void *stream)
-{
-    return affine_advect<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, nf, {basis0, basis1, basis2},
-                                    {deriv0, deriv1, deriv2}, {qw0, qw1, qw2}, dfe, je, {c0, c1, c2}, {in0, in1, in2},
-                                    {out0, out1, out2}, stream);
-}
-
-int sf_aff_advect_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf,
-                                   const double *basis0, const double *basis1, const double *deriv0,
-                                   const double *deriv1, const double *qw0, const double *qw1, const double *dfe,
-                                   const double *je, const double *c0, const double *c1, const double *in0,
-                                   const double *in1, double *out0, double *out1, void *stream)
-{
-    return affine_advect<2, double>(variant, {nq0, nq1, 0u}, nelmt, nf, {basis0, basis1, nullptr},
-                                    {deriv0, deriv1, nullptr}, {qw0, qw1, nullptr}, dfe, je, {c0, c1, nullptr},
-                                    {in0, in1, nullptr}, {out0, out1, nullptr}, stream);
-}
-
-int sf_aff_advect_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf, const double *basis0,
-                           const double *basis1, const double *deriv0, const double *deriv1, const double *qw0,
-                           const double *qw1, const double *dfe, const double *je, const double *c0, const double *c1,
-                           const double *in0, const double *in1, double *out0, double *out1, void *stream)
-{
-    return affine_advect<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, nf, {basis0, basis1, nullptr},
-                                    {deriv0, deriv1, nullptr}, {qw0, qw1, nullptr}, dfe, je, {c0, c1, nullptr},
-                                    {in0, in1, nullptr}, {out0, out1, nullptr}, stream);
-}
-
-int sf_aff_advect_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, unsigned nf, const float *basis0,
-                          const float *basis1, const float *basis2, const float *deriv0, const float *deriv1,
-                          const float *deriv2, const float *qw0, const float *qw1, const float *qw2, const float *dfe,
-                          const float *je, const float *c0, const float *c1, const float *c2, const float *in0,
-                          const float *in1, const float *in2, float *out0, float *out1, float *out2, void *stream)
-{
-    return affine_advect<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, nf, {basis0, basis1, basis2},
-                                   {deriv0, deriv1, deriv2}, {qw0, qw1, qw2}, dfe, je, {c0, c1, c2}, {in0, in1, in2},
-                                   {out0, out1, out2}, stream);
-}
-
-int sf_aff_advect_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, unsigned nf, const float *basis0,
-                           const float *basis1, const float *deriv0, const float *deriv1, const float *qw0,
-                           const float *qw1, const float *dfe, const float *je, const float *c0, const float *c1,
-                           const float *in0, const float *in1, float *out0, float *out1, void *stream)
-{
-    return affine_advect<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, nf, {basis0, basis1, nullptr},
-                                   {deriv0, deriv1, nullptr}, {qw0, qw1, nullptr}, dfe, je, {c0, c1, nullptr},
-                                   {in0, in1, nullptr}, {out0, out1, nullptr}, stream);
-}
+#define SF_AFF_ADVECT(name, D, T, V)                                                                                   \
+    int name(SF_VP_##V SF_NQ_P##D, size_t nelmt, unsigned nf, SF_P##D(const T, basis), SF_P##D(const T, deriv),        \
+             SF_P##D(const T, qw), const T *dfe, const T *je, SF_P##D(const T, c), SF_P##D(const T, in),               \
+             SF_P##D(T, out), void *stream)                                                                            \
+    {                                                                                                                  \
+        return affine_advect<D, T>(SF_VA_##V, SF_NQ_A##D, nelmt, nf, SF_A##D(basis), SF_A##D(deriv), SF_A##D(qw), dfe, \
+                                   je, SF_A##D(c), SF_A##D(in), SF_A##D(out), stream);                                 \
+    }
+SF_ENTRIES(SF_AFF_ADVECT, aff_advect)
 
 // ---- the gradient, divergence and curl of a vector field at the quadrature points ---------------------------------------
-int sf_vecgrad_hex_f64_variant(int variant, unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0,
-                               const double *basis1, const double *basis2, const double *deriv0, const double *deriv1,
-                               const double *deriv2, const double *df, const double *in0, const double *in1,
-                               const double *in2, double *grad, double *div, double *curl0, double *curl1, double *curl2,
-                               void *stream)
-{
-    return vecgrad<3, double>(variant, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2}, df,
-                              {in0, in1, in2}, grad, div, {curl0, curl1, curl2}, stream);
-}
-
-int sf_vecgrad_hex_f64(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const double *basis0, const double *basis1,
-                       const double *basis2, const double *deriv0, const double *deriv1, const double *deriv2,
-                       const double *df, const double *in0, const double *in1, const double *in2, double *grad,
-                       double *div, double *curl0, double *curl1, double *curl2, void *stream)
-{
-    return vecgrad<3, double>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
-                              df, {in0, in1, in2}, grad, div, {curl0, curl1, curl2}, stream);
-}
-
-int sf_vecgrad_quad_f64_variant(int variant, unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0,
-                                const double *basis1, const double *deriv0, const double *deriv1, const double *df,
-                                const double *in0, const double *in1, double *grad, double *div, double *curl0,
-                                void *stream)
-{
-    return vecgrad<2, double>(variant, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr}, df,
-                              {in0, in1, nullptr}, grad, div, {curl0, nullptr, nullptr}, stream);
-}
-
-int sf_vecgrad_quad_f64(unsigned nq0, unsigned nq1, size_t nelmt, const double *basis0, const double *basis1,
-                        const double *deriv0, const double *deriv1, const double *df, const double *in0,
-                        const double *in1, double *grad, double *div, double *curl0, void *stream)
-{
-    return vecgrad<2, double>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
-                              df, {in0, in1, nullptr}, grad, div, {curl0, nullptr, nullptr}, stream);
-}
-
-int sf_vecgrad_hex_f32(unsigned nq0, unsigned nq1, unsigned nq2, size_t nelmt, const float *basis0, const float *basis1,
-                       const float *basis2, const float *deriv0, const float *deriv1, const float *deriv2,
-                       const float *df, const float *in0, const float *in1, const float *in2, float *grad, float *div,
-                       float *curl0, float *curl1, float *curl2, void *stream)
-{
-    return vecgrad<3, float>(SF_VARIANT_AUTO, {nq0, nq1, nq2}, nelmt, {basis0, basis1, basis2}, {deriv0, deriv1, deriv2},
-                             df, {in0, in1, in2}, grad, div, {curl0, curl1, curl2}, stream);
-}
-
-int sf_vecgrad_quad_f32(unsigned nq0, unsigned nq1, size_t nelmt, const float *basis0, const float *basis1,
-                        const float *deriv0, const float *deriv1, const float *df, const float *in0, const float *in1,
-                        float *grad, float *div, float *curl0, void *stream)
-{
-    return vecgrad<2, float>(SF_VARIANT_AUTO, {nq0, nq1, 0u}, nelmt, {basis0, basis1, nullptr}, {deriv0, deriv1, nullptr},
-                             df, {in0, in1, nullptr}, grad, div, {curl0, nullptr, nullptr}, stream);
-}
+// the planes of the curl number d(d-1)/2, not d: a parameter list and a group of their own
+#define SF_CURL_P3(q) q *curl0, q *curl1, q *curl2
+#define SF_CURL_P2(q) q *curl0
+#define SF_CURL_A3 {curl0, curl1, curl2}
+#define SF_CURL_A2 {curl0, nullptr, nullptr}
+#define SF_VECGRAD(name, D, T, V)                                                                                      \
+    int name(SF_VP_##V SF_NQ_P##D, size_t nelmt, SF_P##D(const T, basis), SF_P##D(const T, deriv), const T *df,        \
+             SF_P##D(const T, in), T *grad, T *div, SF_CURL_P##D(T), void *stream)                                     \
+    {                                                                                                                  \
+        return vecgrad<D, T>(SF_VA_##V, SF_NQ_A##D, nelmt, SF_A##D(basis), SF_A##D(deriv), df, SF_A##D(in), grad, div, \
+                             SF_CURL_A##D, stream);                                                                    \
+    }
+SF_ENTRIES(SF_VECGRAD, vecgrad)
 
 // ---- gather-scatter: Q, Q^T and Q Q^T of a local-to-global map, and the setup that inverts the map --------------------
 int sf_gs_setup(size_t nlocal, size_t nglobal, const int32_t *l2g, int32_t *rows, int32_t *perm, void *stream)
@@ -1778,57 +1216,19 @@ int sf_device_info(int *num_cu, int *wave_size, char *name, size_t name_len)
 }
 
 // ---- tensor-product apply ----------------------------------------------------------------------------------------
-int sf_tensor_hex_f64_variant(int variant, unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1, unsigned no2,
-                              int trans, size_t nelmt, const double *m0, const double *m1, const double *m2,
-                              const double *in, double *out, void *stream)
-{
-    return tensor<3, double>(variant, {ni0, ni1, ni2}, {no0, no1, no2}, trans, nelmt, {m0, m1, m2}, in, out, stream);
-}
-
-int sf_tensor_hex_f64(unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1, unsigned no2, int trans,
-                      size_t nelmt, const double *m0, const double *m1, const double *m2, const double *in, double *out,
-                      void *stream)
-{
-    return tensor<3, double>(SF_VARIANT_AUTO, {ni0, ni1, ni2}, {no0, no1, no2}, trans, nelmt, {m0, m1, m2}, in, out, stream);
-}
-
-int sf_tensor_quad_f64_variant(int variant, unsigned ni0, unsigned ni1, unsigned no0, unsigned no1, int trans, size_t nelmt,
-                               const double *m0, const double *m1, const double *in, double *out, void *stream)
-{
-    return tensor<2, double>(variant, {ni0, ni1, 1u}, {no0, no1, 1u}, trans, nelmt, {m0, m1, nullptr}, in, out, stream);
-}
-
-int sf_tensor_quad_f64(unsigned ni0, unsigned ni1, unsigned no0, unsigned no1, int trans, size_t nelmt, const double *m0,
-                       const double *m1, const double *in, double *out, void *stream)
-{
-    return tensor<2, double>(SF_VARIANT_AUTO, {ni0, ni1, 1u}, {no0, no1, 1u}, trans, nelmt, {m0, m1, nullptr}, in, out, stream);
-}
-
-int sf_tensor_hex_f32_variant(int variant, unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1, unsigned no2,
-                              int trans, size_t nelmt, const float *m0, const float *m1, const float *m2, const float *in,
-                              float *out, void *stream)
-{
-    return tensor<3, float>(variant, {ni0, ni1, ni2}, {no0, no1, no2}, trans, nelmt, {m0, m1, m2}, in, out, stream);
-}
-
-int sf_tensor_hex_f32(unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1, unsigned no2, int trans,
-                      size_t nelmt, const float *m0, const float *m1, const float *m2, const float *in, float *out,
-                      void *stream)
-{
-    return tensor<3, float>(SF_VARIANT_AUTO, {ni0, ni1, ni2}, {no0, no1, no2}, trans, nelmt, {m0, m1, m2}, in, out, stream);
-}
-
-int sf_tensor_quad_f32_variant(int variant, unsigned ni0, unsigned ni1, unsigned no0, unsigned no1, int trans, size_t nelmt,
-                               const float *m0, const float *m1, const float *in, float *out, void *stream)
-{
-    return tensor<2, float>(variant, {ni0, ni1, 1u}, {no0, no1, 1u}, trans, nelmt, {m0, m1, nullptr}, in, out, stream);
-}
-
-int sf_tensor_quad_f32(unsigned ni0, unsigned ni1, unsigned no0, unsigned no1, int trans, size_t nelmt, const float *m0,
-                       const float *m1, const float *in, float *out, void *stream)
-{
-    return tensor<2, float>(SF_VARIANT_AUTO, {ni0, ni1, 1u}, {no0, no1, 1u}, trans, nelmt, {m0, m1, nullptr}, in, out, stream);
-}
+// two extent triples, padded with 1u in 2D, and an _f32_variant form besides the six
+#define SF_NIO_P3 unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1, unsigned no2
+#define SF_NIO_P2 unsigned ni0, unsigned ni1, unsigned no0, unsigned no1
+#define SF_NIO_A3 {ni0, ni1, ni2}, {no0, no1, no2}
+#define SF_NIO_A2 {ni0, ni1, 1u}, {no0, no1, 1u}
+#define SF_TENSOR(name, D, T, V)                                                                                       \
+    int name(SF_VP_##V SF_NIO_P##D, int trans, size_t nelmt, SF_P##D(const T, m), const T *in, T *out, void *stream)   \
+    {                                                                                                                  \
+        return tensor<D, T>(SF_VA_##V, SF_NIO_A##D, trans, nelmt, SF_A##D(m), in, out, stream);                        \
+    }
+SF_ENTRIES(SF_TENSOR, tensor)
+SF_TENSOR(sf_tensor_hex_f32_variant, 3, float, VAR)
+SF_TENSOR(sf_tensor_quad_f32_variant, 2, float, VAR)
 
 int sf_specialise_tensor(int dim, unsigned ni0, unsigned ni1, unsigned ni2, unsigned no0, unsigned no1, unsigned no2,
                          int trans, int scalar_bytes)
@@ -1881,5 +1281,47 @@ int sf_shutdown(void)
     const int rc = release_workspaces();
     return rc != SF_OK ? rc : rtc;
 }
+
+#undef SF_P3
+#undef SF_P2
+#undef SF_A3
+#undef SF_A2
+#undef SF_NQ_P3
+#undef SF_NQ_P2
+#undef SF_NQ_A3
+#undef SF_NQ_A2
+#undef SF_VP_VAR
+#undef SF_VP_AUTO
+#undef SF_VA_VAR
+#undef SF_VA_AUTO
+#undef SF_ENTRIES
+#undef SF_WSP_P_VAR
+#undef SF_WSP_P_AUTO
+#undef SF_WSP_A_VAR
+#undef SF_WSP_A_AUTO
+#undef SF_CURL_P3
+#undef SF_CURL_P2
+#undef SF_CURL_A3
+#undef SF_CURL_A2
+#undef SF_NIO_P3
+#undef SF_NIO_P2
+#undef SF_NIO_A3
+#undef SF_NIO_A2
+#undef SF_BWDTRANS
+#undef SF_IPRODUCT
+#undef SF_MASS
+#undef SF_HELMHOLTZ
+#undef SF_AFFINE_HELMHOLTZ
+#undef SF_PHYSDERIV
+#undef SF_IPRODDERIV
+#undef SF_AFF_PHYSDERIV
+#undef SF_AFF_IPRODDERIV
+#undef SF_DIAG_HELMHOLTZ
+#undef SF_GEOM
+#undef SF_GEOM_AFFINE
+#undef SF_ADVECT
+#undef SF_AFF_ADVECT
+#undef SF_VECGRAD
+#undef SF_TENSOR
 
 } // extern "C"
